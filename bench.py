@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X accelerate backend (contract: see task brief).
 
-    python bench.py --gpus N --steps K --warmup W [--workload fused|dgemm]
+    python bench.py --gpus N --steps K --warmup W [--workload fused|dgemm|...] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input, through the C ABI:
   fused (default, BASELINE.json configs[1]): D = sin(A).*B + C on 8192x8192 f64 per GPU, i.e. one
@@ -13,9 +13,12 @@ A "step" is one pass of the hot path over one batch of synthetic input, through 
   dgemm (BASELINE.json configs[2]): C = A*B 8192^3 f64 on the fp64 MFMA kernel; with N > 1 the
       matrix is row-block sharded (rank g computes C[rows_g,:] = A[rows_g,:]*B, B replicated, no
       collective in the timed region) -- strong scaling.
-The JSON line carries `roofline` (dominant kernel, HIP-event timed on the library's stream) and,
-on rank 0 at N=1, `cpu_baseline` (the oracle = C port of the reference CPU path, 1 thread, on a
-bounded sample). The secondary workload is reported under "also" at N=1.
+A plain run sets up, warms up, times the K steps and prints the JSON line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+With --full the line also carries `roofline` (dominant kernel, HIP-event timed on the library's stream in a run of its own,
+plus the large-argument sin leg of the fused workload), the other workloads under "also", and, on rank 0 at N=1,
+`cpu_baseline` (the oracle = C port of the reference CPU path, 1 thread, on a bounded sample).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (rank 0; arrays of more than DUMP_SAMPLE
+elements as a fixed, seeded sample of their column-major data), so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -39,9 +42,25 @@ HBM_PEAK_GBS = 8000.0      # HBM3E 8.0 TB/s
 FP64_MFMA_PEAK_TF = 78.6   # 256 CU x 4 SIMD x 32 flop/clk x 2.4 GHz (v_mfma_f64_16x16x4_f64, 64 cyc)
 F32_MFMA_PEAK_TF = 157.3   # 256 CU x 4 SIMD x 64 flop/clk x 2.4 GHz (v_mfma_f32_32x32x2_f32)
 VALU_F64_PEAK_GIPS = 614.4  # wave64 fp64 VALU instructions per second: 1024 SIMDs x 2.4 GHz / 4 cycles (16 lanes per clock)
+# --dump-outputs: an output of more elements is written as this many of them, at indices drawn once from DUMP_SEED
+# (32 MB in float64; one output per workload, so a dump stays under 64 MB)
+DUMP_SAMPLE = 1 << 22
+DUMP_SEED = 20240611
 
 
-def device_peaks(info: dict) -> dict:
+def dump_array(out_dir: Path, name: str, data, dtype=np.float64) -> None:
+    """DIR/<name>.npy: the column-major flat data (complex as interleaved re, im), or a fixed seeded sample of it."""
+    flat = np.asarray(data).reshape(-1, order="F")
+    if flat.dtype.kind == "c":
+        flat = flat.view(np.float64)
+    if flat.size > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.size, DUMP_SAMPLE, replace=False))
+        flat = flat[idx]
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / f"{name}.npy", flat.astype(dtype))
+
+
+def device_peaks(info: dict, query_smi: bool = True) -> dict:
     """Peaks of THIS box from rmhip_device_info (hipDeviceProp_t): compute_units x clock for the matrix / vector pipes, memory bus x
     pin rate for HBM (HBM3E moves 4 bits per pin per reported memory clock: 2000 MHz -> 8 Gb/s per pin).  amd-smi's view of the memory
     clock is recorded beside it when the tool is there."""
@@ -59,6 +78,8 @@ def device_peaks(info: dict) -> dict:
         "spec": {"hbm_gbs": HBM_PEAK_GBS, "mfma_f64_tflops": FP64_MFMA_PEAK_TF, "mfma_f32_tflops": F32_MFMA_PEAK_TF,
                  "valu_f64_ginstr_per_s": VALU_F64_PEAK_GIPS},
     }
+    if not query_smi:
+        return peaks
     try:
         import subprocess
 
@@ -267,7 +288,14 @@ def main() -> None:
     ap.add_argument("--workload", choices=["fused", "dgemm", "mc", "mc_lazy", "mldivide", "chain", "mc_evolved", "image", "fused_f32", "sgemm", "bcast", "fft"], default="fused")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the rooflines (kernel legs of their own), the other workloads (unless --no-also) and the CPU "
+                         "baselines (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", type=Path, default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -347,7 +375,7 @@ def main() -> None:
     # tests/test_gpu_bench_line.py).  The metric strings keep naming the full sizes; `config.shrink` says what ran.  Default 1.
     shrink = max(1, int(os.environ.get("RMHIP_BENCH_SHRINK", "1")))
     n = N_DIM // shrink
-    peaks = device_peaks(prov.device_info_struct())
+    peaks = device_peaks(prov.device_info_struct(), query_smi=args.full)
     # every roofline below divides by the peaks of the box it ran on; the spec values ride along as `peak_spec`
     hbm_peak, mfma_peak, mfma32_peak, valu_peak = peaks["hbm_gbs"], peaks["mfma_f64_tflops"], peaks["mfma_f32_tflops"], peaks["valu_f64_ginstr_per_s"]
 
@@ -408,7 +436,19 @@ def main() -> None:
         if dist is not None:
             dist.barrier()
 
-    def run_fused(steps, warmup, a_range=np.pi):
+    dump_dir = args.dump_outputs if rank == 0 else None  # cleared once the primary workload has run: `also` writes nothing
+
+    def settle(name, p, h, dtype=np.float64):
+        """The last timed step's result handle: written under --dump-outputs, then freed."""
+        if name and dump_dir is not None:
+            dump_array(dump_dir, name, p.download(h), dtype)
+        p.free(h)
+
+    def dump_values(name, values):
+        if dump_dir is not None:
+            dump_array(dump_dir, name, np.asarray(values, dtype=np.float64))
+
+    def run_fused(steps, warmup, a_range=np.pi, dump_name=None):
         plan, out_id = sin_mul_add_plan()
         shader = plan.generate_wgsl_for_output(out_id, "f64")
         base = 100 * rank  # independent matrices per rank
@@ -416,22 +456,29 @@ def main() -> None:
         hb = prov.fill_uniform(2 + base, -1.0, 1.0, (n, n))
         hc = prov.fill_uniform(3 + base, -1.0, 1.0, (n, n))
 
+        def call():
+            return prov.fused_elementwise(shader, [ha, hb, hc], (n, n), n * n)
+
         def step():
-            prov.free(prov.fused_elementwise(shader, [ha, hb, hc], (n, n), n * n))
+            prov.free(call())
 
         for _ in range(warmup):
             step()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        last = call()  # the last timed step: its result is freed (or written) after the clock stops
         barrier()
         wall = time.perf_counter() - t0
-        # roofline leg: HIP events on the library's stream around the same launches
-        prov.timer_begin()
-        for _ in range(steps):
-            step()
-        kern_ms = prov.timer_end() / steps
+        settle(dump_name, prov, last)
+        kern_ms = None
+        if args.full:
+            # roofline leg: HIP events on the library's stream around the same launches
+            prov.timer_begin()
+            for _ in range(steps):
+                step()
+            kern_ms = prov.timer_end() / steps
         for h in (ha, hb, hc):
             prov.free(h)
         return wall, kern_ms
@@ -441,21 +488,28 @@ def main() -> None:
         ha = prov.fill_uniform(11 + 1000 * rank, -1.0, 1.0, (rows, n))
         hb = prov.fill_uniform(12, -1.0, 1.0, (n, n))
 
+        def call():
+            return prov.matmul(ha, hb)
+
         def step():
-            prov.free(prov.matmul(ha, hb))
+            prov.free(call())
 
         for _ in range(warmup):
             step()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        last = call()
         barrier()
         wall = time.perf_counter() - t0
-        prov.timer_begin()
-        for _ in range(steps):
-            step()
-        kern_ms = prov.timer_end() / steps
+        settle("C", prov, last)
+        kern_ms = None
+        if args.full:
+            prov.timer_begin()
+            for _ in range(steps):
+                step()
+            kern_ms = prov.timer_end() / steps
         prov.free(ha)
         prov.free(hb)
         return wall, kern_ms
@@ -471,41 +525,44 @@ def main() -> None:
     dgemm_flops = 2.0 * n ** 3           # whole job per step
 
     def fused_record(steps, warmup):
-        wall, kern_ms = run_fused(steps, warmup)
+        wall, kern_ms = run_fused(steps, warmup, dump_name="D")
         wall = max_over_ranks(wall)
         ms = wall / steps * 1e3
-        achieved = fused_bytes / (kern_ms * 1e-3) / 1e9
-        # SURVEY.md 8(d) config 2's second run: A in [-1e6, 1e6], where sin leaves its small-argument path (Payne-Hanek-style
-        # reduction for most lanes) - same request, same bytes, a short leg of its own; the headline stays the |A| <= pi run.
-        slow_steps = max(5, min(steps, 50))
-        _, slow_ms = run_fused(slow_steps, 3, a_range=1.0e6)
-        slow_ms = max_over_ranks(slow_ms)
-        slow = roofline("hbm", fused_bytes / (slow_ms * 1e-3) / 1e9, kernel="rm_ew_fast, same request with A = U(-1e6, 1e6) (large-argument sin)",
-                        kernel_ms=round(slow_ms, 5), steps=slow_steps)
-        return {
-            "roofline_slow_path": slow,
+        rec = {
             "metric": "fused elementwise GB/s (D = sin(A).*B + C, 8192x8192 f64, per-GPU matrices)",
             "value": round(world * fused_bytes / (ms * 1e-3) / 1e9, 2), "unit": "GB/s",
             "ms_per_step": round(ms, 5), "scaling": "weak", "dtype": "f64",
             "config": {"workload": "fused D=sin(A).*B+C 8192x8192 f64 via rmhip_fused_elementwise (WGSL request)",
                        "bytes_per_step_per_gpu": fused_bytes, "parallelism": f"independent x{world}"},
-            "roofline": roofline("hbm", achieved, traffic=pmc_traffic("fused", "rm_ew_fast"), traffic_source=PMC_TRAFFIC_SOURCE,
-                                 kernel="rm_ew_fast (hipRTC, generated)", kernel_ms=round(kern_ms, 5)),
+            "roofline": None,
         }
+        if args.full:
+            achieved = fused_bytes / (kern_ms * 1e-3) / 1e9
+            # SURVEY.md 8(d) config 2's second run: A in [-1e6, 1e6], where sin leaves its small-argument path (Payne-Hanek-style
+            # reduction for most lanes) - same request, same bytes, a short leg of its own; the headline stays the |A| <= pi run.
+            slow_steps = max(5, min(steps, 50))
+            _, slow_ms = run_fused(slow_steps, 3, a_range=1.0e6)
+            slow_ms = max_over_ranks(slow_ms)
+            rec["roofline_slow_path"] = roofline("hbm", fused_bytes / (slow_ms * 1e-3) / 1e9,
+                                                 kernel="rm_ew_fast, same request with A = U(-1e6, 1e6) (large-argument sin)",
+                                                 kernel_ms=round(slow_ms, 5), steps=slow_steps)
+            rec["roofline"] = roofline("hbm", achieved, traffic=pmc_traffic("fused", "rm_ew_fast"), traffic_source=PMC_TRAFFIC_SOURCE,
+                                       kernel="rm_ew_fast (hipRTC, generated)", kernel_ms=round(kern_ms, 5))
+        return rec
 
     def dgemm_record(steps, warmup):
         wall, kern_ms = run_dgemm(steps, warmup)
         wall = max_over_ranks(wall)
         ms = wall / steps * 1e3
-        achieved = (dgemm_flops / world) / (kern_ms * 1e-3) / 1e12
         return {
             "metric": "fp64 GFLOP/s (8192^3 matmul, row-block sharded across GPUs)",
             "value": round(dgemm_flops / (ms * 1e-3) / 1e9, 1), "unit": "GFLOP/s",
             "ms_per_step": round(ms, 5), "scaling": "strong", "dtype": "f64",
             "config": {"workload": "C=A*B dgemm 8192x8192x8192 f64 via rmhip_matmul", "flops_per_step": dgemm_flops,
                        "parallelism": f"row-block x{world}, B replicated, no collective"},
-            "roofline": roofline("mfma", achieved, 3, traffic=pmc_traffic("dgemm", "k_dgemm_w8"), traffic_source=PMC_TRAFFIC_SOURCE,
-                                 kernel="k_dgemm_w8<false> (eight waves, pipelined k loop; v_mfma_f64_16x16x4_f64)", kernel_ms=round(kern_ms, 5)),
+            "roofline": roofline("mfma", (dgemm_flops / world) / (kern_ms * 1e-3) / 1e12, 3, traffic=pmc_traffic("dgemm", "k_dgemm_w8"),
+                                 traffic_source=PMC_TRAFFIC_SOURCE, kernel="k_dgemm_w8<false> (eight waves, pipelined k loop; v_mfma_f64_16x16x4_f64)",
+                                 kernel_ms=round(kern_ms, 5)) if args.full else None,
         }
 
     def mc_record(steps, warmup, lazy=False):
@@ -530,6 +587,7 @@ def main() -> None:
             wall = max_over_ranks(time.perf_counter() - t0)
         finally:
             prov.set_lazy_random(True)
+        dump_values("price", [price])
         ms = wall / steps * 1e3
         if lazy:
             # bytes the two kernels move per sample: the update writes S (8), the payoff reduction reads it (8).  The update kernel now
@@ -586,6 +644,7 @@ def main() -> None:
             price, _ = sh.monte_carlo_price_evolved(prov, group, M, T, rng_state=0x9E3779B97F4A7C15, payoff_shader=payoff)
         barrier()
         wall = max_over_ranks(time.perf_counter() - t0)
+        dump_values("price", [price])
         ms = wall / steps * 1e3
         # per normal: LCG step + half a Box-Muller (log, sqrt, sincos) + exp + 3 mul/add: ~150 fp64 VALU
         # instructions per sample-step (counted from the ISA); the kernel is VALU bound, not HBM bound
@@ -608,17 +667,22 @@ def main() -> None:
         B, H, W = max(1, 16 // world), 2160 // shrink, 3840 // shrink
         hx = prov.fill_uniform(41 + 100 * rank, 0.0, 1.0, (B, H, W))
 
+        def call():
+            return prov.image_normalize(hx, B, H, W, 1e-6, gain=1.0123, bias=-0.02, gamma=1.8, clamp_zero=True)
+
         def step():
-            prov.free(prov.image_normalize(hx, B, H, W, 1e-6, gain=1.0123, bias=-0.02, gamma=1.8, clamp_zero=True))
+            prov.free(call())
 
         for _ in range(warmup):
             step()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        last = call()
         barrier()
         wall = max_over_ranks(time.perf_counter() - t0)
+        settle("Y", prov, last)
         prov.free(hx)
         ms = wall / steps * 1e3
         nbytes = 24 * B * H * W  # one-pass plane statistics (one read), normalise (one read + one write) per element
@@ -707,7 +771,7 @@ def main() -> None:
         for _ in range(max(1, warmup)):
             hx = solve()
             err = float(np.max(np.abs(prov.download(hx) - 1.0)))
-            if quality is None and not cyclic:
+            if quality is None and not cyclic and args.full:
                 # What the forward error may be for THIS matrix (round-5 review: a flat 1e-7 says little): the normwise backward error
                 # of the computed x, and a lower bound of cond_inf(A) from one more solve - A z = e with e = +-1 gives
                 # ||A^-1||_inf >= ||z||_inf - so that bound ~ cond x backward error.  Device ops outside the timed region.
@@ -733,10 +797,12 @@ def main() -> None:
             prov.free(hx)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             prov.free(solve())
+        last = solve()
         barrier()
         wall = max_over_ranks(time.perf_counter() - t0)
+        settle("x", prov, last)
         ms = wall / steps * 1e3
         flops = (2.0 / 3.0) * nn ** 3 + 2.0 * nn * nn
         for h in (ha, ones, hb):
@@ -777,25 +843,32 @@ def main() -> None:
         hx = prov.upload(np.linspace(0.0, 4.0 * np.pi, m * m), (m, m))
         consts = [prov.upload(np.array([v]), (1, 1)) for v in (10.0, 4.0, 0.25, 2.0, 0.1)]
 
+        def call():
+            return prov.fused_elementwise(shader, [hx] + consts, (m, m), m * m)
+
         def step():
-            prov.free(prov.fused_elementwise(shader, [hx] + consts, (m, m), m * m))
+            prov.free(call())
 
         for _ in range(warmup):
             step()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        last = call()
         barrier()
         wall = max_over_ranks(time.perf_counter() - t0)
+        settle("y", prov, last)
         ms = wall / steps * 1e3
-        # kernel time: HIP events on the library's stream around a back-to-back run (the host issues a call in less time than the kernel
-        # runs, so the stream stays full and elapsed / steps is the launch duration plus the dispatch gap - an upper bound of the former)
-        prov.synchronize()
-        prov.timer_begin()
-        for _ in range(steps):
-            step()
-        kern_ms = max_over_ranks(prov.timer_end() / steps)
+        kern_ms = None
+        if args.full:
+            # kernel time: HIP events on the library's stream around a back-to-back run (the host issues a call in less time than the kernel
+            # runs, so the stream stays full and elapsed / steps is the launch duration plus the dispatch gap - an upper bound of the former)
+            prov.synchronize()
+            prov.timer_begin()
+            for _ in range(steps):
+                step()
+            kern_ms = max_over_ranks(prov.timer_end() / steps)
         for h in [hx] + consts:
             prov.free(h)
         nbytes = 16 * m * m  # fused form: one read + one write per element
@@ -810,7 +883,8 @@ def main() -> None:
             "roofline": valu_roofline("chain", "rm_ew_fast", kern_ms * 1e-3,
                                       kernel="rm_ew_fast (14-op chain, 1024 x 1024: fp64 VALU bound)", kernel_ms=round(kern_ms, 5),
                                       hbm_frac_for_completeness=round(nbytes / (kern_ms * 1e-3) / 1e9 / hbm_peak, 4),
-                                      host_ms_per_call=round(ms, 5), traffic=pmc_traffic("chain", "rm_ew_fast"), traffic_source=PMC_TRAFFIC_SOURCE),
+                                      host_ms_per_call=round(ms, 5), traffic=pmc_traffic("chain", "rm_ew_fast"),
+                                      traffic_source=PMC_TRAFFIC_SOURCE) if args.full else None,
         }
 
     def bcast_record(steps, warmup):
@@ -819,27 +893,34 @@ def main() -> None:
         expansions.  `repmat` is a zero-copy view here and elem_mul reads it in place, so a step must move one 512 MiB write."""
         ha, hb = prov.fill_uniform(31 + rank, -1.0, 1.0, (n, 1)), prov.fill_uniform(32 + rank, -1.0, 1.0, (1, n))
 
-        def step():
+        def call():
             le, re = prov.repmat(ha, [1, n]), prov.repmat(hb, [n, 1])
             h = prov.elem_mul(le, re)
             prov.free(le)
             prov.free(re)
-            prov.free(h)
+            return h
+
+        def step():
+            prov.free(call())
 
         for _ in range(warmup):
             step()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        last = call()
         barrier()
         wall = max_over_ranks(time.perf_counter() - t0)
+        settle("P", prov, last)
         ms = wall / steps * 1e3
-        prov.synchronize()
-        prov.timer_begin()
-        for _ in range(steps):
-            step()
-        kern_ms = max_over_ranks(prov.timer_end() / steps)
+        kern_ms = None
+        if args.full:
+            prov.synchronize()
+            prov.timer_begin()
+            for _ in range(steps):
+                step()
+            kern_ms = max_over_ranks(prov.timer_end() / steps)
         prov.free(ha)
         prov.free(hb)
         nbytes = 8 * n * n + 16 * n  # the product written once, the two vectors read once
@@ -849,7 +930,8 @@ def main() -> None:
             "config": {"workload": "times builtin's unfused broadcast sequence on resident operands (repmat views + rmhip_binary)",
                        "bytes_per_step_per_gpu": nbytes, "parallelism": f"independent x{world}"},
             "roofline": roofline("hbm", nbytes / (kern_ms * 1e-3) / 1e9, traffic=pmc_traffic("bcast", "k_bcast2"), traffic_source=PMC_TRAFFIC_SOURCE,
-                                 kernel="k_bcast2<double, mul> (both operands stride-0 views: write-only traffic)", kernel_ms=round(kern_ms, 5)),
+                                 kernel="k_bcast2<double, mul> (both operands stride-0 views: write-only traffic)",
+                                 kernel_ms=round(kern_ms, 5)) if args.full else None,
         }
 
     def fft_record(steps, warmup):
@@ -857,24 +939,31 @@ def main() -> None:
         the 8 B/element input read once, the 16 B/element complex result written once."""
         h = prov.fill_uniform(41 + rank, -1.0, 1.0, (n, n))
 
+        def call():
+            return prov.fft_dim(h, None, 0)
+
         def step():
-            prov.free(prov.fft_dim(h, None, 0))
+            prov.free(call())
 
         for _ in range(warmup):
             step()
         prov.synchronize()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        last = call()
         prov.synchronize()
         barrier()
         wall = max_over_ranks(time.perf_counter() - t0)
+        settle("X", prov, last)
         ms = wall / steps * 1e3
-        prov.timer_begin()
-        for _ in range(steps):
-            step()
-        kern_ms = max_over_ranks(prov.timer_end() / steps)
+        kern_ms = None
+        if args.full:
+            prov.timer_begin()
+            for _ in range(steps):
+                step()
+            kern_ms = max_over_ranks(prov.timer_end() / steps)
         prov.free(h)
         nbytes = 24 * n * n
         return {
@@ -884,7 +973,7 @@ def main() -> None:
                        "flops_per_step": 5.0 * n * n * 13, "parallelism": f"independent x{world}"},
             "roofline": roofline("hbm", nbytes / (kern_ms * 1e-3) / 1e9, traffic=pmc_traffic("fft", "k_fft_tile"), traffic_source=PMC_TRAFFIC_SOURCE,
                                  kernel="k_fft_tile<1024> (Stockham radix-8 passes in LDS; first pass loads, last pass stores)",
-                                 kernel_ms=round(kern_ms, 5)),
+                                 kernel_ms=round(kern_ms, 5)) if args.full else None,
         }
 
     def fused_f32_record(steps, warmup):
@@ -895,27 +984,33 @@ def main() -> None:
         base = 100 * rank
         hs = [p32.fill_uniform(s + base, lo, hi, (n, n)) for s, lo, hi in ((1, -np.pi, np.pi), (2, -1.0, 1.0), (3, -1.0, 1.0))]
 
+        def call():
+            return p32.fused_elementwise(shader, hs, (n, n), n * n)
+
         def step():
-            p32.free(p32.fused_elementwise(shader, hs, (n, n), n * n))
+            p32.free(call())
 
         for _ in range(warmup):
             step()
         p32.synchronize()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        last = call()
         p32.synchronize()
         barrier()
         wall = max_over_ranks(time.perf_counter() - t0)
-        p32.timer_begin()
-        for _ in range(steps):
-            step()
-        kern_ms = p32.timer_end() / steps
+        settle("D", p32, last, np.float32)
+        kern_ms = None
+        if args.full:
+            p32.timer_begin()
+            for _ in range(steps):
+                step()
+            kern_ms = p32.timer_end() / steps
         p32.close()
         ms = wall / steps * 1e3
         nbytes = 4 * 4 * n * n
-        achieved = nbytes / (kern_ms * 1e-3) / 1e9
         return {
             "metric": "fused elementwise GB/s (D = sin(A).*B + C, 8192x8192, f32 storage on a precision-32 provider)",
             "value": round(world * nbytes / (ms * 1e-3) / 1e9, 2), "unit": "GB/s", "ms_per_step": round(ms, 5),
@@ -923,8 +1018,9 @@ def main() -> None:
             "config": {"workload": "fused D=sin(A).*B+C 8192x8192 via rmhip_fused_elementwise (f32 WGSL request)",
                        "bytes_per_step_per_gpu": nbytes, "elements_per_s": round(world * n * n / (ms * 1e-3), 1),
                        "parallelism": f"independent x{world}"},
-            "roofline": roofline("hbm", achieved, traffic=pmc_traffic("fused_f32", "rm_ew_fast"), traffic_source=PMC_TRAFFIC_SOURCE,
-                                 kernel="rm_ew_fast (f32 variant: 16-byte vectors of four, body in f64)", kernel_ms=round(kern_ms, 5)),
+            "roofline": roofline("hbm", nbytes / (kern_ms * 1e-3) / 1e9, traffic=pmc_traffic("fused_f32", "rm_ew_fast"), traffic_source=PMC_TRAFFIC_SOURCE,
+                                 kernel="rm_ew_fast (f32 variant: 16-byte vectors of four, body in f64)",
+                                 kernel_ms=round(kern_ms, 5)) if args.full else None,
         }
 
     def sgemm_record(steps, warmup):
@@ -934,34 +1030,41 @@ def main() -> None:
         ha = p32.fill_uniform(11 + 1000 * rank, -1.0, 1.0, (rows, n))
         hb = p32.fill_uniform(12, -1.0, 1.0, (n, n))
 
+        def call():
+            return p32.matmul(ha, hb)
+
         def step():
-            p32.free(p32.matmul(ha, hb))
+            p32.free(call())
 
         for _ in range(warmup):
             step()
         p32.synchronize()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        last = call()
         p32.synchronize()
         barrier()
         wall = max_over_ranks(time.perf_counter() - t0)
-        p32.timer_begin()
-        for _ in range(steps):
-            step()
-        kern_ms = p32.timer_end() / steps
+        settle("C", p32, last, np.float32)
+        kern_ms = None
+        if args.full:
+            p32.timer_begin()
+            for _ in range(steps):
+                step()
+            kern_ms = p32.timer_end() / steps
         p32.close()
         ms = wall / steps * 1e3
-        achieved = (dgemm_flops / world) / (kern_ms * 1e-3) / 1e12
         return {
             "metric": "fp32 GFLOP/s (8192^3 matmul on a precision-32 provider, row-block sharded across GPUs)",
             "value": round(dgemm_flops / (ms * 1e-3) / 1e9, 1), "unit": "GFLOP/s", "ms_per_step": round(ms, 5),
             "scaling": "strong", "dtype": "f32 (f32 MFMA accumulation)",
             "config": {"workload": "C=A*B 8192x8192x8192 f32 storage via rmhip_matmul", "flops_per_step": dgemm_flops,
                        "parallelism": f"row-block x{world}, B replicated, no collective"},
-            "roofline": roofline("mfma_f32", achieved, 3, traffic=pmc_traffic("sgemm", "k_sgemm_w8"), traffic_source=PMC_TRAFFIC_SOURCE,
-                                 kernel="k_sgemm_w8 (eight waves, pipelined k loop; v_mfma_f32_16x16x4_f32)", kernel_ms=round(kern_ms, 5)),
+            "roofline": roofline("mfma_f32", (dgemm_flops / world) / (kern_ms * 1e-3) / 1e12, 3, traffic=pmc_traffic("sgemm", "k_sgemm_w8"),
+                                 traffic_source=PMC_TRAFFIC_SOURCE, kernel="k_sgemm_w8 (eight waves, pipelined k loop; v_mfma_f32_16x16x4_f32)",
+                                 kernel_ms=round(kern_ms, 5)) if args.full else None,
         }
 
     def agreed(ok: bool) -> bool:
@@ -994,6 +1097,7 @@ def main() -> None:
                "chain": chain_record, "mc_evolved": mc_evolved_record, "image": image_record, "bcast": bcast_record, "fft": fft_record}
     primary = records[args.workload]
     rec = safe_record(args.workload, primary, args.steps, args.warmup)
+    dump_dir = None
     # Developer knob, OFF by default (round-5 advisor finding: an untimed loop that exists to move an external utilisation signal
     # measures nothing): RMHIP_BENCH_BUSY_S=<seconds> keeps the device busy with untimed headline launches, e.g. while watching clocks.
     busy_s = float(os.environ.get("RMHIP_BENCH_BUSY_S", "0"))
@@ -1044,7 +1148,7 @@ def main() -> None:
         except Exception as e:  # noqa: BLE001
             comm = {"transport": "unknown", "error": str(e)[:200]}
     out["comm"] = comm
-    if not args.no_also:
+    if args.full and not args.no_also:
         # the other configs of BASELINE.json, short runs; every rank takes part (collectives inside)
         # Order matters: the driver keeps the TAIL of this line, so the extras come first and BASELINE.json's own configs - the 1024^2
         # chain, the 1e8-sample Monte-Carlo, the 8192^3 dgemm, the 16384^2 solve - last (tests/test_bench_contract.py pins that they
@@ -1064,7 +1168,7 @@ def main() -> None:
                 also.append({**{k: sec[k] for k in ("metric", "value", "unit", "ms_per_step", "scaling", "config", "roofline", "roofline_slow_path") if k in sec},
                              "steps": steps, "warmup": 5 if w != "mldivide" else 1})
         out["also"] = also
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = {"fused": cpu_baseline_fused, "dgemm": cpu_baseline_dgemm, "mc": cpu_baseline_mc,
                                "mldivide": cpu_baseline_mldivide, "chain": cpu_baseline_chain,
                                "mc_evolved": cpu_baseline_mc, "mc_lazy": cpu_baseline_mc, "image": cpu_baseline_fused,
@@ -1090,7 +1194,8 @@ def main() -> None:
                      "hbm_bytes": info["total_memory_bytes"]}
     # LAST key of the line: BASELINE.json's five configs in compact form, so that whatever keeps only the end of the line (the driver's
     # `tail` is 2 000 characters) still holds the dgemm half of BASELINE's metric.  tests/test_bench_contract.py pins <= 1 800 characters.
-    out["baseline_configs"] = baseline_configs(out)
+    if args.full:
+        out["baseline_configs"] = baseline_configs(out)
     prov.close()
     if dist is not None:
         dist.barrier()

@@ -15,6 +15,6 @@ python $ROOT/scripts/gemm_variants.py > "$OUT/gemm_variants.txt" 2>&1
 python $ROOT/scripts/rng_accuracy.py 2000000 > "$OUT/rng_accuracy.txt" 2>&1
 for n in 1024 2048 4096 6144 8192 12288 16384; do python $ROOT/scripts/lu_trace.py $n 4 2>&1 | grep "rep=" | tail -1; done > "$OUT/solve_sizes.txt"
 cd $ROOT
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 timeout 600 tests/tools/offload_calibrate > "$OUT/offload_calibration.json" 2> "$OUT/calib.err"
 tail -3 "$OUT/solve_sizes.txt"; tail -2 "$OUT/tier2_rates.txt"; head -c 300 "$OUT/bench_default.json"

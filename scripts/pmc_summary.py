@@ -102,7 +102,7 @@ json.dump({"_method": "rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE
           open(f"{out}/pmc_valu.json", "w"), indent=1)
 json.dump(summary, open(f"{out}/pmc_summary.json", "w"), indent=1)
 traffic = {"_method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in SEPARATE passes (plus a --kernel-trace --stats pass for the durations) over "
-                      "`bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-also --workload <w>` (mldivide: --steps 2 --warmup 1; reductions: scripts/red_driver.py) - "
+                      "`bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-also --workload <w>` (mldivide: --steps 2 --warmup 1; reductions: scripts/red_driver.py) - "
                       "scripts/profile_r03.sh.  bytes per launch = (2*FETCH_SIZE + WRITE_SIZE)*1024: both counters are in KiB and on gfx950 FETCH_SIZE reports half of a wide "
                       "(16 B/lane) coalesced streaming read (MI355X_MICROARCH.md, HBM section); WRITE_SIZE calibrates exactly (524288 KiB = a 512 MiB output).  For the GEMMs the "
                       "fetch figure is memory-side (fabric) traffic including Infinity-Cache hits, not DRAM bytes.  `_bytes_per_step` = all kernels of the run except set-up "

@@ -10,7 +10,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline"
+BENCH="python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $BENCH > "$OUT/trace_bench.json" 2> "$OUT/trace.err"
 for W in fused dgemm; do
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$W" -o trace -- $BENCH --no-also --workload $W > "$OUT/trace_${W}_bench.json" 2> "$OUT/trace_$W.err"
@@ -20,7 +20,7 @@ done
 # matrix-pipe evidence for the dgemm kernel (own pass: SQ + GRBM counters only)
 timeout 400 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OUT/pmc_mfma_dgemm" -o mfma -- $BENCH --no-also --workload dgemm > "$OUT/mfma_dgemm_bench.json" 2> "$OUT/mfma_dgemm.err"
 # kernel mix of the LU solve (kernel trace only)
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_mldivide" -o trace -- python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-also --workload mldivide > "$OUT/trace_mldivide_bench.json" 2> "$OUT/trace_mldivide.err"
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_mldivide" -o trace -- python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-also --workload mldivide > "$OUT/trace_mldivide_bench.json" 2> "$OUT/trace_mldivide.err"
 for f in $(find "$OUT/trace" -name "*kernel_stats.csv"); do echo "== $f"; head -14 "$f" | cut -c1-170; done
 python - "$OUT" <<'PY'
 import csv, glob, sys, collections, json

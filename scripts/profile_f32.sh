@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-also"
+BENCH="python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-also"
 for W in fused_f32 sgemm; do
   STEPS=20; [ $W = fused_f32 ] && STEPS=200   # 200 back-to-back dispatches: the per-dispatch trace below shows drift, if any
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$W" -o trace -- ${BENCH/--steps 20/--steps $STEPS} --workload $W > "$OUT/trace_${W}_bench.json" 2> "$OUT/trace_$W.err"

@@ -15,8 +15,8 @@ WORKLOADS=${*:-fused dgemm mc mc_evolved image chain bcast fft fused_f32 sgemm m
 for W in $WORKLOADS; do
   case $W in
     reductions) CMD="python $ROOT/scripts/red_driver.py 6" ;;
-    mldivide)   CMD="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-also --workload mldivide" ;;
-    *)          CMD="python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-also --workload $W" ;;
+    mldivide)   CMD="python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-also --workload mldivide" ;;
+    *)          CMD="python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-also --workload $W" ;;
   esac
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$W" -o trace -- $CMD > "$OUT/trace_${W}_bench.json" 2> "$OUT/trace_$W.err"
   timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch_$W" -o fetch -- $CMD > "$OUT/fetch_${W}_bench.json" 2> "$OUT/fetch_$W.err"

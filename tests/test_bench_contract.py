@@ -1,7 +1,7 @@
 """The default bench line must keep BASELINE.json's own configs where the driver can see them: it records the TAIL of the line
 (8 081 characters in rounds 1-4), and in round 4 a longer `also` list pushed the dgemm and Monte-Carlo entries out of it.
 Checked here without a GPU: the order bench.py emits the secondary workloads in, and - on the committed default line of the
-round (profiles/r06_bench_default.json, written on the GPU box by `python bench.py > ...`) - that the last 8 000 characters still
+round (profiles/r06_bench_default.json, written on the GPU box by `python bench.py --full > ...`) - that the last 8 000 characters still
 hold the dgemm, Monte-Carlo (1e8 samples) and mldivide entries with their ms_per_step and the last 2 000 the compact `baseline_configs`."""
 import json
 import re
@@ -30,7 +30,7 @@ def _entry_span(line: str, needle: str):
 
 
 def test_committed_default_line_keeps_the_baseline_configs_in_its_tail():
-    """profiles/r06_bench_default.json is the line `python bench.py` printed on the GPU box this round: its `also` list still ends with
+    """profiles/r06_bench_default.json is the line `python bench.py --full` prints (the default line of round 6): its `also` list still ends with
     BASELINE's configs inside the last 8 000 characters (the driver's long tail), and - round 6 - its LAST 2 000 characters (the driver's
     short `tail`) hold the compact `baseline_configs` object with all five configs."""
     f = ROOT / "profiles" / "r06_bench_default.json"
@@ -112,3 +112,32 @@ def test_cpu_baselines_are_bounded_and_the_busy_loop_is_opt_in():
     src = (ROOT / "bench.py").read_text()
     assert 'os.environ.get("RMHIP_BENCH_BUSY_S", "0")' in src          # advisor r5 (medium): no default busy loop
     assert "n, cols = 2048, 256" in src and "np.log(t1_ / t0_)" not in src  # dgemm: measured rate on a bounded sample, no fitted exponent
+
+
+def test_full_and_dump_outputs_are_options_and_steps_must_be_positive():
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stdout + r.stderr
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_array_writes_small_outputs_whole_and_a_fixed_sample_of_large_ones(tmp_path):
+    import numpy as np
+
+    import bench
+
+    small = np.arange(12.0).reshape(3, 4)
+    bench.dump_array(tmp_path, "small", small)
+    got = np.load(tmp_path / "small.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small.reshape(-1, order="F"))  # column-major, like the library's data
+    big = np.arange(bench.DUMP_SAMPLE + 12345, dtype=np.float64)
+    bench.dump_array(tmp_path, "a", big)
+    bench.dump_array(tmp_path, "b", big, np.float32)
+    a, b = np.load(tmp_path / "a.npy"), np.load(tmp_path / "b.npy")
+    assert a.shape == (bench.DUMP_SAMPLE,) and a.nbytes <= 32 << 20 and b.dtype == np.float32
+    assert np.all(np.diff(a) > 0) and np.array_equal(a.astype(np.float32), b)  # distinct indices, in order; the same ones every time
+    bench.dump_array(tmp_path, "c", np.array([1 + 2j, 3 - 4j]))
+    assert np.array_equal(np.load(tmp_path / "c.npy"), [1.0, 2.0, 3.0, -4.0])  # complex as interleaved re, im

@@ -9,6 +9,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -46,7 +47,7 @@ def _check_roofline(rf):
 
 
 def test_two_rank_line_has_every_config_and_a_communicator():
-    out = _run_bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline"], {})
+    out = _run_bench(["--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], {})
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "comm", "also"):
         assert k in out, k
@@ -79,7 +80,7 @@ def test_eight_rank_line_on_one_gpu():
     """The line the driver launches on an 8-GPU node (`--gpus 8`), with all eight ranks sharing cuda:0 over the host shared-memory
     transport and every linear size divided by four (RMHIP_BENCH_SHRINK): the row-sharded dgemm, the sample-sharded Monte-Carlo and the
     row-partitioned solve all run with world = 8 - shard arithmetic, skip-ahead, eight-way exchanges - and the line keeps its schema."""
-    out = _run_bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {"RMHIP_BENCH_SHRINK": "4", "RMHIP_BENCH_BUSY_S": "0"}, nproc=8,
+    out = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {"RMHIP_BENCH_SHRINK": "4", "RMHIP_BENCH_BUSY_S": "0"}, nproc=8,
                      timeout=1500)
     assert out["n_gpus"] == 8 and out["config"]["shrink"] == 4 and out["value"] > 0
     assert out["comm"] == {"transport": "host-shm", "world_seen": 8, "rank_seen": 0}
@@ -122,3 +123,32 @@ def test_a_failing_torch_process_group_does_not_cost_the_line():
     assert out["n_gpus"] == 2 and out["value"] > 0
     assert "gloo" in out["config"]["control_plane"] and "forced by RMHIP_BENCH_TEST_PG_FAIL" in out["config"]["control_plane"]
     assert out["comm"]["transport"] == "host-shm"
+
+
+def test_plain_line_is_lean_and_dumps_what_the_last_step_computed(prov, oracle, tmp_path):
+    """`bench.py --gpus 1` without --full: the headline fields, nothing measured beside them (no `also`, no CPU baseline, no roofline
+    leg), and --dump-outputs writes the last step's D = sin(A).*B + C - the same array on a second run, and the one the inputs give."""
+    n = 8192 // 8
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        env = dict(os.environ, RMHIP_BENCH_SHRINK="8", RMHIP_BENCH_BUSY_S="0")
+        env.pop("RMHIP_BENCH_BACKEND", None)
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-1500:]
+        out = json.loads(lines[0])
+        assert out["metric"].startswith("fused elementwise GB/s") and out["unit"] == "GB/s" and out["higher_is_better"] is True
+        assert out["dtype"] == "f64" and out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+        assert out["roofline"] is None and not {"also", "cpu_baseline", "baseline_configs", "roofline_slow_path"} & set(out)
+        assert sorted(p.name for p in d.iterdir()) == ["D.npy"]
+        outs.append(np.load(d / "D.npy"))
+    assert outs[0].dtype == np.float64 and outs[0].shape == (n * n,)
+    assert np.array_equal(outs[0].view(np.uint64), outs[1].view(np.uint64))
+    hs = [prov.fill_uniform(s, lo, hi, (n, n)) for s, lo, hi in ((1, -np.pi, np.pi), (2, -1.0, 1.0), (3, -1.0, 1.0))]
+    A, B, C = (prov.download(h) for h in hs)
+    for h in hs:
+        prov.free(h)
+    assert np.max(np.abs(outs[0] - oracle.sin_mul_add(A, B, C))) <= 4e-16 * 2.0  # smoke()'s bound against the reference CPU path
