@@ -669,6 +669,15 @@ RMHIP_API int rmhip_mrdivide(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf
  * RMHIP_ERR_UNSUPPORTED: the builtin falls back (chol.rs:331-342) and its host code produces `info` and the partial factor. */
 /* @serves chol */
 RMHIP_API int rmhip_chol(rmhip_ctx* ctx, rmhip_buf a, int lower, rmhip_buf* factor, unsigned* info);
+/* `qr(a, options)` (lib.rs:2509-2515 -> ProviderQrResult { q, r, perm_matrix, perm_vector } :665-670) with the CPU builtin's contract
+ * (qr.rs:576-870): column pivoting always on (squared norms recomputed before every step, ties to the last index), the builtin's
+ * reflector quirks, Q and R cleaned at |x| <= 1e-12.  economy != 0 with rows >= cols: Q is rows x cols and R cols x cols; otherwise Q is
+ * rows x rows and R rows x cols.  `pivot_vector` (ProviderQrOptions.pivot == Vector) only selects which output the builtin shows: both
+ * are returned.  out4 order: Q, R, perm_matrix (cols x cols, E(perm[c], c) = 1), perm_vector (cols x 1, 1-based).
+ * RMHIP_ERR_UNSUPPORTED (the builtin's host path answers): more than two dimensions, a non-finite entry, max |a| >= 1e150, a full Q that
+ * does not fit in device memory. */
+/* @serves qr */
+RMHIP_API int rmhip_qr(rmhip_ctx* ctx, rmhip_buf a, int economy, int pivot_vector, rmhip_buf out4[4]);
 /* `inv(matrix, options)` (lib.rs:2430-2436, ProviderInvOptions {} :716; CPU inv.rs:209-230, 258-280: nalgebra 0.32.6 `try_inverse`, an LU
  * with partial pivoting and substitutions on the identity - absent from /root/reference, parity by residual as for mldivide): X = A \ I on
  * the LU path.  Scalars, [n, n] and [n, n, 1, ...] operands (the shape is kept); a non-square or higher-rank operand is

@@ -60,6 +60,16 @@ struct ProviderLuResult {
     GpuTensorHandle combined, lower, upper, perm_matrix, perm_vector;
 };
 
+// lib.rs:665-670, 794-812
+enum class ProviderQrPivot { Matrix, Vector };
+struct ProviderQrOptions {
+    bool economy = false;
+    ProviderQrPivot pivot = ProviderQrPivot::Matrix;
+};
+struct ProviderQrResult {
+    GpuTensorHandle q, r, perm_matrix, perm_vector;
+};
+
 class HipProvider {
 public:
     // precision_bits: 64 or 32 (ProviderPrecision, lib.rs:815-818), fixed for the provider's lifetime
@@ -460,6 +470,13 @@ public:
         unsigned info = 0;
         check(rmhip_chol(ctx_, own(a), lower ? 1 : 0, &out, &info));
         return {with_shape(out), info};
+    }
+    // lib.rs:2509-2515: column-pivoted QR with the CPU builtin's contract; both permutations are returned whatever options.pivot says.
+    // Throws for what the host path must answer (non-finite input, max |a| >= 1e150, more than two dimensions, a full Q that does not fit)
+    ProviderQrResult qr(const GpuTensorHandle& a, const ProviderQrOptions& options = ProviderQrOptions()) const {
+        uint64_t ids[4] = {0, 0, 0, 0};
+        check(rmhip_qr(ctx_, own(a), options.economy ? 1 : 0, options.pivot == ProviderQrPivot::Vector ? 1 : 0, ids));
+        return {with_shape(ids[0]), with_shape(ids[1]), with_shape(ids[2]), with_shape(ids[3])};
     }
     // lib.rs:2430-2436 (ProviderInvOptions is empty)
     GpuTensorHandle inv(const GpuTensorHandle& matrix) const {

@@ -111,6 +111,36 @@ class ProviderLuResult:
     perm_vector: GpuTensorHandle
 
 
+@dataclass(frozen=True)
+class ProviderQrPivot:
+    """`ProviderQrPivot` (lib.rs:794-798): which permutation output the builtin shows."""
+    kind: str  # "matrix" | "vector"
+
+    @staticmethod
+    def Matrix() -> "ProviderQrPivot":
+        return ProviderQrPivot("matrix")
+
+    @staticmethod
+    def Vector() -> "ProviderQrPivot":
+        return ProviderQrPivot("vector")
+
+
+@dataclass
+class ProviderQrOptions:
+    """`ProviderQrOptions` (lib.rs:800-812); the default is full mode with the permutation matrix."""
+    economy: bool = False
+    pivot: ProviderQrPivot = ProviderQrPivot("matrix")
+
+
+@dataclass
+class ProviderQrResult:
+    """`ProviderQrResult` (lib.rs:665-670)."""
+    q: GpuTensorHandle
+    r: GpuTensorHandle
+    perm_matrix: GpuTensorHandle
+    perm_vector: GpuTensorHandle
+
+
 @dataclass
 class ProviderLinsolveOptions:
     """lib.rs:679-690"""
@@ -686,6 +716,15 @@ class HipProvider:
         self._check(self._lib.rmhip_lu(self._ctx, self._id(a), outs))
         hs = [self._handle(outs[i]) for i in range(5)]
         return ProviderLuResult(*hs)
+
+    def qr(self, a: GpuTensorHandle, options: Optional[ProviderQrOptions] = None) -> ProviderQrResult:
+        """`qr(a, options)` (lib.rs:2509-2515): column-pivoted Householder QR with the CPU builtin's contract (qr.rs:576-870).  Both
+        permutation outputs are always returned; `options.pivot` only says which one the caller shows.  Non-finite input, max |a| >= 1e150,
+        more than two dimensions or a full Q that does not fit raise (UNSUPPORTED) and the builtin takes its host path."""
+        opts = options or ProviderQrOptions()
+        outs = (C.c_uint64 * 4)()
+        self._check(self._lib.rmhip_qr(self._ctx, self._id(a), 1 if opts.economy else 0, 1 if opts.pivot.kind == "vector" else 0, outs))
+        return ProviderQrResult(*[self._handle(outs[i]) for i in range(4)])
 
     def mldivide(self, lhs: GpuTensorHandle, rhs: GpuTensorHandle) -> GpuTensorHandle:
         out = C.c_uint64()

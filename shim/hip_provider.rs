@@ -17,7 +17,7 @@ use runmat_accelerate_api::{
     AccelProvider, AccelProviderFuture, ApiDeviceInfo, CorrcoefNormalization, CorrcoefOptions, CorrcoefRows, CovNormalization, CovRows, CovarianceOptions, FindDirection, GpuTensorHandle, GpuTensorStorage,
     HostLogicalOwned, HostTensorOwned, HostTensorView, IsMemberOptions, IsMemberResult, SetdiffOptions, SetdiffOrder, SetdiffResult, UnionOptions, UnionOrder, UnionResult, UniqueOccurrence, UniqueOptions, UniqueOrder, UniqueResult, ImageNormalizeDescriptor, ImfilterMode, ImfilterOptions, ImfilterPadding, ImfilterShape, KernelAttrTelemetry, MeshgridAxisView, ProviderMeshgridResult, ProviderPolyderQuotient, ProviderPolyvalOptions, KernelLaunchTelemetry, MatmulEpilogue,
     PowerStepEpilogue, ProviderBandwidth, ProviderCovarianceToCorrelationResult, ProviderHilbertRequest, ProviderCondNorm, ProviderPinvOptions, ProviderIirFilterOptions, ProviderIirFilterResult, ProviderInterp1Extrapolation, ProviderInterp1Method, ProviderInterp1Request, ProviderConv1dOptions, ProviderConvMode, ProviderConvOrientation, ProviderCholResult, ProviderCummaxResult, ProviderCumminResult, ProviderDispatchStats, ProviderInvOptions, ProviderFallbackStat, ProviderFindResult, ProviderHermitianKind, ProviderLinsolveOptions,
-    ProviderLinsolveResult, ProviderLuResult, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
+    ProviderLinsolveResult, ProviderLuResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
     ProviderStdNormalization, ProviderSymmetryKind, ProviderTelemetry, ProviderTrapezoidSpacing, ReduceDimResult, ReductionFlavor, ScaleOp, SortComparison, SortOrder, SortResult, SortRowsColumnSpec,
 };
 use std::ffi::{c_char, c_int, c_void, CStr, CString};
@@ -605,6 +605,17 @@ impl AccelProvider for HipProvider {
             check(unsafe { rmhip_lu(self.ctx, self.own(a)?, ids.as_mut_ptr()) })?;
             Ok(ProviderLuResult { combined: self.handle(ids[0])?, lower: self.handle(ids[1])?, upper: self.handle(ids[2])?,
                 perm_matrix: self.handle(ids[3])?, perm_vector: self.handle(ids[4])? })
+        })
+    }
+    // qr: column-pivoted Householder QR with the CPU builtin's contract (qr.rs:576-870); Err (non-finite input, max |a| >= 1e150, more than
+    // two dimensions, a full Q that does not fit) -> qr.rs:458-469 host path.  Both permutations are returned whatever `pivot` says.
+    fn qr<'a>(&'a self, _a: &'a GpuTensorHandle, _options: ProviderQrOptions) -> AccelProviderFuture<'a, ProviderQrResult> {
+        Box::pin(async move {
+            let mut ids = [0u64; 4];
+            let vector = matches!(_options.pivot, ProviderQrPivot::Vector);
+            check(unsafe { rmhip_qr(self.ctx, self.own(_a)?, _options.economy as c_int, vector as c_int, ids.as_mut_ptr()) })?;
+            Ok(ProviderQrResult { q: self.handle(ids[0])?, r: self.handle(ids[1])?, perm_matrix: self.handle(ids[2])?,
+                perm_vector: self.handle(ids[3])? })
         })
     }
     fn stochastic_evolution(&self, state: &GpuTensorHandle, drift: f64, scale: f64, steps: u32) -> Result<GpuTensorHandle> {
