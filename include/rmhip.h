@@ -678,6 +678,20 @@ RMHIP_API int rmhip_chol(rmhip_ctx* ctx, rmhip_buf a, int lower, rmhip_buf* fact
  * does not fit in device memory. */
 /* @serves qr */
 RMHIP_API int rmhip_qr(rmhip_ctx* ctx, rmhip_buf a, int economy, int pivot_vector, rmhip_buf out4[4]);
+/* `pagefun(request)` (lib.rs:2386; PagefunRequest { op, inputs, output_shape, page_dims, input_page_dims } :603-614, built by
+ * build_pagefun_request, builtins/acceleration/gpu/pagefun.rs:450-530).  op RMHIP_PAGEFUN_MTIMES: output page p (column-major over
+ * page_dims) = A(:, :, a(p)) * B(:, :, b(p)), where an operand takes index 0 along every page dimension of extent 1 in its row of
+ * input_page_dims (n_inputs x page_rank, row-major).  Arithmetic is the host loop's (pagefun.rs:330-384 over matmul_real,
+ * common/linalg.rs:6-32): bit-exact for pages of at most 32 on a side, k eps sum|a||b| on the matrix-core tiers.  The output has exactly
+ * output_shape ([m, n, page_dims...]); a zero m, n or page extent gives an empty tensor, k == 0 zeros.  At most 2 launches, no
+ * device -> host read.  RMHIP_ERR_INVALID: n_inputs != 2, a missing input_page_dims, an output_shape that is not [m, n, page_dims...],
+ * an operand whose element count is not rows x cols x its page volume; RMHIP_ERR_SHAPE: inner dimensions or page extents (neither
+ * equal nor 1) that disagree; RMHIP_ERR_UNSUPPORTED: complex operands, another op, more than 8 page dimensions that do not collapse.
+ * The builtin takes its host path on any error. */
+enum rmhip_pagefun_op { RMHIP_PAGEFUN_MTIMES = 0 };
+/* @serves pagefun */
+RMHIP_API int rmhip_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inputs, const size_t* page_dims, size_t page_rank,
+                            const size_t* input_page_dims, const size_t* output_shape, size_t out_rank, rmhip_buf* out);
 /* `inv(matrix, options)` (lib.rs:2430-2436, ProviderInvOptions {} :716; CPU inv.rs:209-230, 258-280: nalgebra 0.32.6 `try_inverse`, an LU
  * with partial pivoting and substitutions on the identity - absent from /root/reference, parity by residual as for mldivide): X = A \ I on
  * the LU path.  Scalars, [n, n] and [n, n, 1, ...] operands (the shape is kept); a non-square or higher-rank operand is

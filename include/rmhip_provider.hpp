@@ -70,6 +70,16 @@ struct ProviderQrResult {
     GpuTensorHandle q, r, perm_matrix, perm_vector;
 };
 
+// lib.rs:601-613
+enum class PagefunOp { Mtimes };
+struct PagefunRequest {
+    PagefunOp op = PagefunOp::Mtimes;
+    std::vector<GpuTensorHandle> inputs;
+    std::vector<size_t> output_shape;
+    std::vector<size_t> page_dims;
+    std::vector<std::vector<size_t>> input_page_dims;
+};
+
 class HipProvider {
 public:
     // precision_bits: 64 or 32 (ProviderPrecision, lib.rs:815-818), fixed for the provider's lifetime
@@ -477,6 +487,23 @@ public:
         uint64_t ids[4] = {0, 0, 0, 0};
         check(rmhip_qr(ctx_, own(a), options.economy ? 1 : 0, options.pivot == ProviderQrPivot::Vector ? 1 : 0, ids));
         return {with_shape(ids[0]), with_shape(ids[1]), with_shape(ids[2]), with_shape(ids[3])};
+    }
+    // lib.rs:2386: batched page products (Mtimes); throws for what the host loop must answer (malformed request, complex input)
+    GpuTensorHandle pagefun(const PagefunRequest& request) const {
+        const size_t rank = request.page_dims.size();
+        if (request.input_page_dims.size() != request.inputs.size())
+            throw std::runtime_error("pagefun: input_page_dims must hold one row per input");
+        std::vector<uint64_t> ids;
+        std::vector<size_t> ipd;
+        for (size_t i = 0; i < request.inputs.size(); ++i) {
+            if (request.input_page_dims[i].size() != rank) throw std::runtime_error("pagefun: an input_page_dims row is not page_dims long");
+            ids.push_back(own(request.inputs[i]));
+            ipd.insert(ipd.end(), request.input_page_dims[i].begin(), request.input_page_dims[i].end());
+        }
+        uint64_t out = 0;
+        check(rmhip_pagefun(ctx_, RMHIP_PAGEFUN_MTIMES, ids.data(), ids.size(), request.page_dims.data(), rank, ipd.data(),
+                            request.output_shape.data(), request.output_shape.size(), &out));
+        return with_shape(out);
     }
     // lib.rs:2430-2436 (ProviderInvOptions is empty)
     GpuTensorHandle inv(const GpuTensorHandle& matrix) const {

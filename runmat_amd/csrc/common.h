@@ -378,6 +378,39 @@ int launch_sgemm_trans(Context* c, bool ta, bool tb, size_t m, size_t n, size_t 
 int launch_dgemm_epilogue(Context* c, size_t m, size_t n, size_t k, const double* A, size_t lda, const double* B,
                           size_t ldb, double* C, size_t ldc, const GemmEpilogue& ep);
 
+// Batched page products (pagefun.hip, dgemm.hip k_pgemm_w8): C page p = A page a(p) * B page b(p), C pages dense.  Page p is
+// decomposed column-major over dims[0..rank); an operand's page offset (in elements) is sum_d idx_d * s?[d], with s?[d] = 0 along a
+// dimension the operand broadcasts.  The host collapses mergeable dimensions first, so rank is small and usually 1.
+static constexpr int kPageRankMax = 8;
+struct PageMap {
+    int rank;
+    unsigned long long dims[kPageRankMax], sa[kPageRankMax], sb[kPageRankMax];
+    // element offsets of output page p's operands.  Constant indices only (the loop is unrolled against kPageRankMax): a
+    // dynamically indexed by-value kernel argument would be copied to scratch.
+    __device__ __forceinline__ void offsets(unsigned long long p, unsigned long long& oa, unsigned long long& ob) const {
+        oa = 0;
+        ob = 0;
+#pragma unroll
+        for (int d = 0; d < kPageRankMax; ++d) {
+            if (d >= rank) break;
+            unsigned long long i = p;
+            if (d + 1 < rank) {
+                const unsigned long long q = p / dims[d];
+                i = p - q * dims[d];
+                p = q;
+            }
+            oa += i * sa[d];
+            ob += i * sb[d];
+        }
+    }
+};
+int launch_pagefun_tiny(Context* c, const double* A, const double* B, double* C, unsigned m, unsigned n, unsigned k,
+                        unsigned long long pages, const PageMap& pm, bool a_dense, bool b_dense, unsigned* pages_per_block);
+int launch_pagefun_mfma(Context* c, const double* A, const double* B, double* C, unsigned m, unsigned n, unsigned k,
+                        unsigned long long pages, const PageMap& pm);
+int launch_pgemm_w8(Context* c, const double* A, const double* B, double* C, unsigned m, unsigned n, unsigned k,
+                    unsigned long long pages, const PageMap& pm);
+
 // rng (rng.hip)
 int launch_rng_uniform(Context* c, uint64_t state, double* out, size_t n);
 void lcg_jump_host(unsigned long long delta, unsigned long long* mult, unsigned long long* plus);  // s -> mult * s + plus advances `delta` steps

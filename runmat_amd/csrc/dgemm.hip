@@ -872,6 +872,28 @@ __global__ void __launch_bounds__(512) k_dgemm_w8p(const GemmArgs g) {
     }
 }
 
+// pagefun's large-page tier (pagefun.hip, rmhip_ops.cpp rmhip_pagefun): the guarded eight-wave tile over (page, tile) work items, page
+// bases from PageMap in 64 bits, tiles of a page in column-major order (neighbouring blocks share B's columns).  A grid-stride loop
+// takes page counts beyond the grid; the LDS is reused between work items.  Two waves per SIMD (one block per CU): the page loop's
+// bookkeeping pushes the tile past the 128 registers four waves allow, where it spilled 88 bytes per lane; at 151 it has no scratch.
+__global__ void __launch_bounds__(512, 2) k_pgemm_w8(const GemmArgs g0, const PageMap pm, const unsigned long long pages) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const unsigned long long tpp = (unsigned long long)g0.tiles_m * g0.tiles_n, work = pages * tpp;
+    const unsigned long long mn = (unsigned long long)g0.m * g0.n;
+    for (unsigned long long w = blockIdx.x; w < work; w += gridDim.x) {
+        const unsigned long long p = w / tpp;
+        const unsigned tt = (unsigned)(w - p * tpp);
+        unsigned long long oa, ob;
+        pm.offsets(p, oa, ob);
+        GemmArgs g = g0;
+        g.A += oa;
+        g.B += ob;
+        g.C += p * mn;
+        w8_tile<false, false, false, 0, true>(g, tt % g0.tiles_m, tt / g0.tiles_m, lds, lds + 2 * A_TILE);
+        __syncthreads();
+    }
+}
+
 static int g_rowmap = -1;
 
 static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double alpha, const double* A, size_t lda,
@@ -1177,6 +1199,34 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
     }
+    return RMHIP_OK;
+}
+
+int launch_pgemm_w8(Context* c, const double* A, const double* B, double* C, unsigned m, unsigned n, unsigned k, unsigned long long pages,
+                    const PageMap& pm) {
+    if (m == 0 || n == 0 || k == 0 || pages == 0) return fail(RMHIP_ERR_INVALID, "pgemm: empty product");
+    GemmArgs g{};
+    g.A = A;
+    g.B = B;
+    g.C = C;
+    g.lda = m;
+    g.ldb = k;
+    g.ldc = m;
+    g.m = m;
+    g.n = n;
+    g.k = k;
+    g.tiles_m = (m + BM - 1) / BM;
+    g.tiles_n = (n + BN - 1) / BN;
+    g.alpha = 1.0;
+    g.beta = 0.0;
+    g.k_chunk = k;
+    const size_t lds_bytes = (size_t)(2 * A_TILE + 2 * B_TILE) * sizeof(double);
+    const unsigned long long work = pages * g.tiles_m * g.tiles_n;
+    const unsigned grid = (unsigned)(work < (1ull << 20) ? work : (1ull << 20));
+    c->ensure_max_lds((const void*)k_pgemm_w8, lds_bytes);
+    hipLaunchKernelGGL(k_pgemm_w8, dim3(grid), dim3(512), lds_bytes, c->stream, g, pm, pages);
+    c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
     return RMHIP_OK;
 }
 

@@ -2113,4 +2113,110 @@ int rmhip_stochastic_evolution_sharded(rmhip_ctx* ctx, rmhip_buf state, double d
     return rc;
 }
 
+// pagefun(@mtimes) (include/rmhip.h; kernels pagefun.hip and dgemm.hip k_pgemm_w8).  Validation restates
+// build_pagefun_request (pagefun.rs:450-530) so that a malformed request never reaches a kernel; the tier is chosen here from
+// (m, n, k, page count, broadcast pattern) and recorded as record_launch("pagefun", {m, n, k, pages}, {tier, ...}).
+int rmhip_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inputs, const size_t* page_dims, size_t page_rank,
+                  const size_t* input_page_dims, const size_t* output_shape, size_t out_rank, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "pagefun: null out");
+    *out = 0;
+    if (op != RMHIP_PAGEFUN_MTIMES) return fail(RMHIP_ERR_UNSUPPORTED, "pagefun: unknown op %d", op);
+    if (n_inputs != 2 || !inputs) return fail(RMHIP_ERR_INVALID, "pagefun: @mtimes takes exactly two inputs (got %zu)", n_inputs);
+    if (page_rank && (!page_dims || !input_page_dims)) return fail(RMHIP_ERR_INVALID, "pagefun: page dimensions missing");
+    if (!output_shape && out_rank) return fail(RMHIP_ERR_INVALID, "pagefun: null output shape");
+    Buffer raw[2];
+    size_t rows[2], cols[2], vol[2] = {1, 1};
+    for (int i = 0; i < 2; ++i) {
+        RMHIP_TRY(c->lookup(inputs[i], &raw[i]));
+        if (raw[i].cplx) return fail(RMHIP_ERR_UNSUPPORTED, "pagefun: complex input; the host path answers");
+        const std::vector<size_t>& s = raw[i].shape;  // canonical_matrix_shape (pagefun.rs:899-911)
+        rows[i] = s.empty() ? 1 : (s.size() == 1 ? 1 : s[0]);
+        cols[i] = s.empty() ? 1 : (s.size() == 1 ? s[0] : s[1]);
+        for (size_t d = 0; d < page_rank; ++d) vol[i] *= input_page_dims[i * page_rank + d];
+        if (raw[i].numel != rows[i] * cols[i] * vol[i])
+            return fail(RMHIP_ERR_INVALID, "pagefun: input %d holds %zu elements, not %zu x %zu x %zu", i, raw[i].numel, rows[i], cols[i], vol[i]);
+    }
+    const size_t m = rows[0], k = cols[0], n = cols[1];
+    if (k != rows[1]) return fail(RMHIP_ERR_SHAPE, "pagefun: inner matrix dimensions must agree (%zux%zu * %zux%zu)", m, k, rows[1], n);
+    size_t pages = 1;
+    for (size_t d = 0; d < page_rank; ++d) {
+        const size_t ea = input_page_dims[d], eb = input_page_dims[page_rank + d];
+        size_t want;  // the builtin's rule: a zero extent wins, then equal extents or 1
+        if (ea == 0 || eb == 0) want = 0;
+        else if (ea == 1 || ea == eb) want = eb;
+        else if (eb == 1) want = ea;
+        else return fail(RMHIP_ERR_SHAPE, "pagefun: page dimension %zu mismatch (%zu vs %zu)", d + 3, ea, eb);
+        if (page_dims[d] != want) return fail(RMHIP_ERR_INVALID, "pagefun: page_dims[%zu] = %zu, the inputs give %zu", d, page_dims[d], want);
+        pages *= want;
+    }
+    if (out_rank != page_rank + 2 || output_shape[0] != m || output_shape[1] != n)
+        return fail(RMHIP_ERR_INVALID, "pagefun: output shape must be [m, n, page_dims...]");
+    for (size_t d = 0; d < page_rank; ++d)
+        if (output_shape[2 + d] != page_dims[d]) return fail(RMHIP_ERR_INVALID, "pagefun: output shape must be [m, n, page_dims...]");
+    if (m > 0xffffffffULL || n > 0xffffffffULL || k > 0xffffffffULL)
+        return fail(RMHIP_ERR_UNSUPPORTED, "pagefun: a page side exceeds 2^32");
+    // page strides in elements (0 along a broadcast dimension); dimensions of extent 1 dropped, neighbours whose strides continue each
+    // other merged (a dense operand collapses to one dimension)
+    PageMap pm{};
+    std::vector<unsigned long long> dims, sa, sb;
+    unsigned long long cur[2] = {(unsigned long long)m * k, (unsigned long long)k * n};
+    for (size_t d = 0; d < page_rank; ++d) {
+        const size_t e[2] = {input_page_dims[d], input_page_dims[page_rank + d]};
+        const unsigned long long s0 = e[0] == 1 ? 0 : cur[0], s1 = e[1] == 1 ? 0 : cur[1];
+        cur[0] *= e[0];
+        cur[1] *= e[1];
+        if (page_dims[d] == 1) continue;
+        if (!dims.empty() && s0 == sa.back() * dims.back() && s1 == sb.back() * dims.back()) {
+            dims.back() *= page_dims[d];
+            continue;
+        }
+        dims.push_back(page_dims[d]);
+        sa.push_back(s0);
+        sb.push_back(s1);
+    }
+    if (m != 0 && n != 0 && pages != 0 && dims.size() > (size_t)kPageRankMax)
+        return fail(RMHIP_ERR_UNSUPPORTED, "pagefun: %zu page dimensions after collapsing (at most %d)", dims.size(), kPageRankMax);
+    pm.rank = (int)dims.size();
+    for (size_t d = 0; d < dims.size() && d < (size_t)kPageRankMax; ++d) {
+        pm.dims[d] = dims[d];
+        pm.sa[d] = sa[d];
+        pm.sb[d] = sb[d];
+    }
+    const bool dense[2] = {vol[0] == pages, vol[1] == pages};  // not broadcast: the operand's page of output page p is page p
+    Buffer ob;
+    RMHIP_TRY(c->new_buffer(output_shape, out_rank, out, &ob));
+    if (ob.numel == 0) return RMHIP_OK;
+    // settle lazy operands (transpose / repmat views, lazy random_normal) and widen f32 storage: f64 data in plain layout
+    Buffer ab, bb;
+    int rc = c->get(inputs[0], &ab);
+    if (!rc) rc = c->get(inputs[1], &bb);
+    int tier = 0;
+    unsigned tuning = 0;
+    if (rc) {
+    } else if (k == 0) {
+        rc = launch_fill(c, ob.data(), ob.numel, 0.0);  // matmul_real's empty sum
+    } else if (vol[0] == 1 && dense[1] && n * pages <= 0xffffffffULL) {
+        tier = 1;  // C(m, n P) = A(m, k) B(k, n P): bit for bit the 2-D matmul of the reshaped B
+        rc = launch_dgemm(c, m, n * pages, k, 1.0, ab.data(), m, bb.data(), k, 0.0, ob.data(), m);
+    } else if (m <= 32 && n <= 32 && k <= 32) {
+        tier = 2;
+        rc = launch_pagefun_tiny(c, ab.data(), bb.data(), ob.data(), (unsigned)m, (unsigned)n, (unsigned)k, pages, pm, dense[0], dense[1], &tuning);
+    } else if (m >= 256 && n >= 256) {
+        tier = 4;
+        rc = launch_pgemm_w8(c, ab.data(), bb.data(), ob.data(), (unsigned)m, (unsigned)n, (unsigned)k, pages, pm);
+    } else {
+        tier = 3;
+        rc = launch_pagefun_mfma(c, ab.data(), bb.data(), ob.data(), (unsigned)m, (unsigned)n, (unsigned)k, pages, pm);
+    }
+    if (rc) {
+        rmhip_free(ctx, *out);
+        *out = 0;
+        return rc;
+    }
+    c->record_launch("pagefun", {{"m", m}, {"n", n}, {"k", k}, {"pages", pages}},
+                     {{"tier", (uint64_t)tier}, {"page_rank", (uint64_t)pm.rank}, {"pages_per_block", tuning}});
+    return RMHIP_OK;
+}
+
 }  // extern "C"

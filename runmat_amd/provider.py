@@ -141,6 +141,22 @@ class ProviderQrResult:
     perm_vector: GpuTensorHandle
 
 
+class PagefunOp:
+    """`PagefunOp` (lib.rs:601-604): the page operation.  Only `Mtimes` exists."""
+    Mtimes = "mtimes"
+
+
+@dataclass
+class PagefunRequest:
+    """`PagefunRequest` (lib.rs:606-613), as `build_pagefun_request` (pagefun.rs:450-530) fills it: `input_page_dims[i]` is input i's
+    page extents padded with 1s to len(page_dims), `output_shape` is [m, n, *page_dims]."""
+    op: str
+    inputs: List[GpuTensorHandle]
+    output_shape: List[int]
+    page_dims: List[int]
+    input_page_dims: List[List[int]]
+
+
 @dataclass
 class ProviderLinsolveOptions:
     """lib.rs:679-690"""
@@ -725,6 +741,25 @@ class HipProvider:
         outs = (C.c_uint64 * 4)()
         self._check(self._lib.rmhip_qr(self._ctx, self._id(a), 1 if opts.economy else 0, 1 if opts.pivot.kind == "vector" else 0, outs))
         return ProviderQrResult(*[self._handle(outs[i]) for i in range(4)])
+
+    def pagefun(self, request: PagefunRequest) -> GpuTensorHandle:
+        """`pagefun(request)` (lib.rs:2386): for `PagefunOp.Mtimes` every output page is the product of the inputs' pages, an input of
+        page extent 1 broadcasting along that dimension; the host loop's arithmetic (pagefun.rs:330-384 over matmul_real).  Malformed
+        requests raise INVALID / SHAPE, complex inputs UNSUPPORTED, and the builtin takes its host path."""
+        if request.op != PagefunOp.Mtimes:
+            raise ProviderError(_lib.ERR_UNSUPPORTED, f"pagefun: unsupported op {request.op!r}")
+        rank = len(request.page_dims)
+        if len(request.input_page_dims) != len(request.inputs) or any(len(d) != rank for d in request.input_page_dims):
+            raise ProviderError(_lib.ERR_INVALID, "pagefun: input_page_dims must hold one row of len(page_dims) extents per input")
+        ids = (C.c_uint64 * max(len(request.inputs), 1))(*[self._id(h) for h in request.inputs])
+        pd = (C.c_size_t * max(rank, 1))(*[int(d) for d in request.page_dims])
+        ipd = (C.c_size_t * max(rank * len(request.inputs), 1))(*[int(d) for row in request.input_page_dims for d in row])
+        osh = (C.c_size_t * max(len(request.output_shape), 1))(*[int(d) for d in request.output_shape])
+        out = C.c_uint64()
+        op = _lib.ENUMS["rmhip_pagefun_op"]["RMHIP_PAGEFUN_MTIMES"]
+        self._check(self._lib.rmhip_pagefun(self._ctx, op, ids, len(request.inputs), pd, rank, ipd, osh, len(request.output_shape),
+                                            C.byref(out)))
+        return self._handle(out.value, request.output_shape)
 
     def mldivide(self, lhs: GpuTensorHandle, rhs: GpuTensorHandle) -> GpuTensorHandle:
         out = C.c_uint64()

@@ -17,7 +17,7 @@ use runmat_accelerate_api::{
     AccelProvider, AccelProviderFuture, ApiDeviceInfo, CorrcoefNormalization, CorrcoefOptions, CorrcoefRows, CovNormalization, CovRows, CovarianceOptions, FindDirection, GpuTensorHandle, GpuTensorStorage,
     HostLogicalOwned, HostTensorOwned, HostTensorView, IsMemberOptions, IsMemberResult, SetdiffOptions, SetdiffOrder, SetdiffResult, UnionOptions, UnionOrder, UnionResult, UniqueOccurrence, UniqueOptions, UniqueOrder, UniqueResult, ImageNormalizeDescriptor, ImfilterMode, ImfilterOptions, ImfilterPadding, ImfilterShape, KernelAttrTelemetry, MeshgridAxisView, ProviderMeshgridResult, ProviderPolyderQuotient, ProviderPolyvalOptions, KernelLaunchTelemetry, MatmulEpilogue,
     PowerStepEpilogue, ProviderBandwidth, ProviderCovarianceToCorrelationResult, ProviderHilbertRequest, ProviderCondNorm, ProviderPinvOptions, ProviderIirFilterOptions, ProviderIirFilterResult, ProviderInterp1Extrapolation, ProviderInterp1Method, ProviderInterp1Request, ProviderConv1dOptions, ProviderConvMode, ProviderConvOrientation, ProviderCholResult, ProviderCummaxResult, ProviderCumminResult, ProviderDispatchStats, ProviderInvOptions, ProviderFallbackStat, ProviderFindResult, ProviderHermitianKind, ProviderLinsolveOptions,
-    ProviderLinsolveResult, ProviderLuResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
+    ProviderLinsolveResult, ProviderLuResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
     ProviderStdNormalization, ProviderSymmetryKind, ProviderTelemetry, ProviderTrapezoidSpacing, ReduceDimResult, ReductionFlavor, ScaleOp, SortComparison, SortOrder, SortResult, SortRowsColumnSpec,
 };
 use std::ffi::{c_char, c_int, c_void, CStr, CString};
@@ -594,6 +594,25 @@ impl AccelProvider for HipProvider {
     }
     // The library keeps the transpose lazily (a view consumed in place by matmul / syrk); nothing to record on
     // the Rust side, so `handle_transpose_info` stays empty for these handles and callers treat them as plain.
+    // pagefun(@mtimes): batched page products on the device (rmhip_pagefun); Err (malformed request, complex input) -> the builtin's
+    // host loop, pagefun.rs:413-448.  `input_page_dims` goes over row by row (n_inputs x page_rank).
+    fn pagefun(&self, request: &PagefunRequest) -> Result<GpuTensorHandle> {
+        let op = match request.op {
+            PagefunOp::Mtimes => RMHIP_PAGEFUN_MTIMES,
+        };
+        let rank = request.page_dims.len();
+        if request.input_page_dims.len() != request.inputs.len() || request.input_page_dims.iter().any(|d| d.len() != rank) {
+            return Err(anyhow!("pagefun: input_page_dims must hold one row of page_dims.len() extents per input"));
+        }
+        let ids = request.inputs.iter().map(|h| self.own(h)).collect::<Result<Vec<u64>>>()?;
+        let ipd: Vec<usize> = request.input_page_dims.iter().flatten().copied().collect();
+        let mut out = 0u64;
+        check(unsafe {
+            rmhip_pagefun(self.ctx, op, ids.as_ptr(), ids.len(), request.page_dims.as_ptr(), rank, ipd.as_ptr(),
+                request.output_shape.as_ptr(), request.output_shape.len(), &mut out)
+        })?;
+        self.handle(out)
+    }
     fn transpose(&self, a: &GpuTensorHandle) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
         check(unsafe { rmhip_transpose(self.ctx, self.own(a)?, &mut out) })?;
