@@ -197,22 +197,14 @@ struct Context {
     std::vector<unsigned char>* lu_linv_ok = nullptr;  // host: block q has its inverse queued (a base panel of another width leaves none)
     const double* lu_work = nullptr;
     size_t lu_work_ld = 0;
-    bool gemm_chain_prio = false;  // the look-ahead LU's main-stream dgemm launches raise their wave priority (RMHIP_LU_GEMM_PRIO=0 disables)
-    unsigned* gemm_announce_tab = nullptr;  // the table itself while a two-level factorisation runs (k_trsm_lower_mfma on the main stream)
-    bool lu_yield_trsm = false;
-    unsigned* gemm_announce = nullptr;  // two-level LU: the yield table for the main stream's dgemm blocks to count themselves into (RMHIP_LU_YIELD_ALL)
+    bool gemm_chain_prio = false;  // the two-level LU's main-stream dgemm launches raise their wave priority
     unsigned* ext_yield_tab = nullptr;  // a yield table (kYieldSlots counters) owned by a driver outside lu.hip for the panels it factors (sharded.cpp), or nullptr
     const unsigned* gemm_yield_word = nullptr;  // two-level LU: the CU (key) whose update blocks pause while k_rp_top runs there (device word; 0: none)
-    double* gemm_split_ws = nullptr;  // caller-owned workspace for split-K partial products (per stream; see launch_dgemm)
-    size_t gemm_split_ws_elems = 0;
-    size_t gemm_split_min_k = 0;  // != 0: launch_dgemm splits the inner dimension of few-tile products from this k on (the LU's products with inverted L11 blocks)
-    double lu_last_minv = 0.0;    // largest |entry| of the inverted L11 blocks of the last solve-path factorisation (0: none were formed)
     bool in_lookahead = false;  // inside the LU's look-ahead driver: main-stream dgemm blocks must fit beside the update stream's
     // set after a persistent-panel factorisation found its workgroups not co-resident (device shared with
     // another context): from then on LU uses the one-launch-per-column panels on a single stream
     double rp_phase_ms[4] = {0, 0, 0, 0};  // rmhip_rp_phase_ms: panel / broadcast wait / update / exchange device time of the last row-partitioned solve
     hipStream_t lu_side_stream = nullptr;  // update stream of the look-ahead LU (low priority), created on first use
-    hipStream_t lu_aux_stream = nullptr;   // solve path: the full-height kernels' rows below the band of the panel in flight (lu.hip, LuState::aux)
     hipStream_t lu_prep_stream = nullptr;  // interchanges + triangular solves of one half of the trailing columns under the other half's dgemm
     hipStream_t lu_far_stream = nullptr;   // two-level driver (solve path): the deep rank-W updates of the columns beyond the next super-panel
     hipStream_t lu_mid_stream = nullptr;   // two-level driver: the updates inside the super-panel in flight (normal priority)
@@ -234,7 +226,6 @@ struct Context {
     // runs its f64 kernel on widened temporaries and the entry point narrows what it created on return (NarrowScope).
     int precision = 64;
     std::vector<uint64_t> narrow_pending;  // buffers created by new_buffer since the enclosing entry point began
-    int trsm_base = 128;  // base width of the triangular-solve recursion (64 on the main stream under LU look-ahead)
     Comm* comm = nullptr;  // communicator of the multi-GPU entry points (rmhip_comm_init), owned by the context
 
     // ---- helpers (rmhip_core.cpp) ----
@@ -464,6 +455,36 @@ int lu_solve_device(Context* c, const double* LU, size_t n, size_t lda, const in
                     const double* B, size_t nrhs, size_t ldb, double* X, size_t ldx);
 int lu_extract_device(Context* c, const double* LU, size_t rows, size_t cols, const int* perm_dev,
                       double* L, double* U, double* P, double* piv);
+// The RMHIP_LU_* environment knobs (docs/KNOBS.md), each read by one of the two functions below (lu.hip) and nowhere else.
+struct LuKnobs {  // read on every call: tests flip these inside one process
+    bool fast = true;             // RMHIP_LU_FAST=0: the grid-wide pivot rule on the solve path too
+    double tau = 8.0;             // RMHIP_LU_TAU: the solve path's multiplier bound
+    bool pad = true;              // RMHIP_LU_PAD=0: the solves factor at the order they were given
+    int lookahead = -1;           // RMHIP_LU_LOOKAHEAD: 1 forces the look-ahead driver, 0 disables it, -1 (unset) by order
+    long nb = -1;                 // RMHIP_LU_NB: panel width of the one-level look-ahead driver (-1: by order)
+    bool panel_columns = false;   // RMHIP_LU_PANEL=columns: the one-launch-per-column panels
+    bool panel_debug = false;     // RMHIP_LU_PANEL_DEBUG=1: phase ticks of the panel kernels on stderr
+    bool subst_pair = false;      // RMHIP_LU_SUBST=pair: launch-per-block substitution instead of k_subst_chain
+    bool verbose = false;         // RMHIP_LU_VERBOSE
+    bool timeline = false;        // RMHIP_LU_TIMELINE
+    bool test_retry = false;      // RMHIP_LU_TEST_RETRY (test hook)
+    bool test_growth = false;     // RMHIP_LU_TEST_GROWTH (test hook)
+    bool test_subst_retry = false;  // RMHIP_LU_TEST_SUBST_RETRY (test hook)
+};
+LuKnobs lu_knobs();
+struct LuProcessKnobs {  // read once per process: tests set these in a fresh subprocess
+    bool super = true;            // RMHIP_LU_SUPER=0: the one-level driver on the solve path
+    std::vector<std::pair<size_t, size_t>> super_seq;  // RMHIP_LU_SUPER_SEQ: super-panel plan (W, nb) (empty: by order)
+    std::pair<size_t, size_t> super_late{128, 128};    // RMHIP_LU_SUPER_LATE
+    long super_rows = -1;         // RMHIP_LU_SUPER_ROWS (-1: by order)
+    int iprep = -1;               // RMHIP_LU_IPREP (-1: by order)
+    bool iprep_split = true;      // RMHIP_LU_IPREP_SPLIT
+    long small_upd = 1024;        // RMHIP_LU_SMALL_UPD (dgemm.hip)
+    bool rb_mfma = true;          // RMHIP_LU_RB_MFMA
+    bool trsm_mfma = true;        // RMHIP_LU_TRSM_MFMA
+    int skip = 0;                 // RMHIP_LU_SKIP: phase bit mask (results are garbage)
+};
+const LuProcessKnobs& lu_process_knobs();
 
 // svdsolve.hip: minimum-norm least squares by a one-sided Jacobi SVD with the reference's tolerance rule (mldivide.rs:380-404) - what the
 // LU / Gram paths refuse (rank deficient, ill conditioned, singular), for min(rows, cols) <= svd_max_cols() (RMHIP_SVD_MAX_COLS)
@@ -486,8 +507,8 @@ void comm_destroy(Context* c);  // comm.cpp
 
 
 // ---- cooperative yield table (two-level LU) -----------------------------------------------------------------------------------------
-// One counter per CU (index: XCC id << 8 | the cu / sh / se byte of HW_ID; kYieldSlots entries).  A workgroup of the LU's critical chain
-// (k_rp_top, the main stream's dgemm / trsm / rows-below kernels) counts itself in while it runs; the update streams' eight-wave dgemm
+// One counter per CU (index: XCC id << 8 | the cu / sh / se byte of HW_ID; kYieldSlots entries).  The top-block kernel of the LU's
+// critical chain (k_rp_top) counts itself in while it runs; the update streams' eight-wave dgemm
 // blocks read their CU's counter once per k tile and sleep while it is non-zero (dgemm.hip w8_tile<YIELD>): the fp64 VALU and the matrix
 // pipe are one datapath per SIMD, and every instruction of a chain kernel otherwise queues behind the update block's MFMAs.
 static constexpr unsigned kYieldSlots = 4096;

@@ -81,7 +81,6 @@ struct GemmArgs {
     // eight-wave tile on the LU's update streams: a device word naming the CU (key: bit 31 | XCC id << 8 | HW_ID cu/sh/se byte) on which
     // k_rp_top is running right now; a block on that CU pauses until the word changes (nullptr: no check)
     const unsigned* yield_word;
-    unsigned* announce;  // the same table, for a block of the LU's main stream: it counts itself in on its CU while it runs (CuAnnounce), or nullptr
     int prio;  // nonzero: raise the wave priority (s_setprio 3) - the LU's main-stream updates, which share SIMDs with the update streams' blocks
 };
 
@@ -144,7 +143,6 @@ template <bool EDGE, bool EPI, bool TA, bool TB, bool PRE = false>
 __global__ void __launch_bounds__(256, 2) k_dgemm(const GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (g.prio) __builtin_amdgcn_s_setprio(3);
-    const CuAnnounce on_cu(g.announce);
     double* As = lds;                    // [2][A_TILE]
     double* Bs = lds + 2 * A_TILE;       // [2][B_TILE]   (A_TILE == B_TILE)
 
@@ -421,7 +419,6 @@ __global__ void __launch_bounds__(256, 2) k_dgemm(const GemmArgs g) {
             }
         }
     }
-    on_cu.done();
 }
 
 
@@ -444,7 +441,6 @@ static constexpr int S_B_TILE = SN * SB;     // 1152 doubles
 template <bool PRE, bool GUARD = false>  // PRE: C <- C - A*B with the C tile preloaded into the accumulators (see k_dgemm)
 __global__ void __launch_bounds__(256) k_dgemm_small(const GemmArgs g) {
     if (g.prio) __builtin_amdgcn_s_setprio(3);
-    const CuAnnounce on_cu(g.announce);
     __shared__ __attribute__((aligned(16))) double As[2][S_A_TILE];
     __shared__ __attribute__((aligned(16))) double Bs[2][S_B_TILE];
     const unsigned tm = blockIdx.x % g.tiles_m, tn = blockIdx.x / g.tiles_m;  // column-major tile order: neighbours share B
@@ -565,7 +561,6 @@ __global__ void __launch_bounds__(256) k_dgemm_small(const GemmArgs g) {
                 }
                 if (ok[e]) *dst[e] = v;
             }
-    on_cu.done();
 }
 
 
@@ -987,12 +982,11 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
     g.avoid_xcc = nullptr;
     g.yield_word = (c->gemm_lds_pad != 0) ? c->gemm_yield_word : nullptr;  // update streams of the two-level LU only
     g.prio = (c->in_lookahead && c->gemm_lds_pad == 0 && c->gemm_chain_prio) ? 1 : 0;  // the look-ahead LU's main stream
-    g.announce = (c->in_lookahead && c->gemm_lds_pad == 0) ? c->gemm_announce : nullptr;     // ... whose blocks ask the update blocks on their CU to pause
     std::shared_ptr<Allocation> partials;
     // (round 3: from k = 1024 - slices of multiples of 128 - outside the LU.  A block walks its k range at about 1 us per 16 columns
     // - one memory latency per tile with nothing else resident - so few blocks with a long k are latency bound whatever the tile:
     // 4096 x 100 with k = 4096 (32 tiles) 547 -> 97 us, 32 x 512 with k = 8192 on one slice 1100 us.)
-    const size_t split_min_k = c->gemm_split_min_k ? c->gemm_split_min_k : (c->in_lookahead ? 8192 : 1024);
+    const size_t split_min_k = c->in_lookahead ? 8192 : 1024;
     if (!ep && blocks * 4 <= (unsigned)c->num_cus && k >= split_min_k) {
         const size_t want = (2 * (size_t)c->num_cus + blocks - 1) / blocks;
         size_t chunk = (k + want - 1) / want;
@@ -1000,13 +994,9 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
         chunk = ((chunk + gran - 1) / gran) * gran;
         splits = (unsigned)((k + chunk - 1) / chunk);
         if (splits > 1) {
-            // a caller that runs several streams (the two-level LU) lends a workspace per stream: a pooled block released at the end of
-            // this call could be handed to another stream's call while this one's kernels are still queued
-            double* ws = nullptr;
-            if (c->gemm_split_ws && c->gemm_split_ws_elems >= (size_t)splits * m * n) ws = c->gemm_split_ws;
-            else RMHIP_TRY(c->alloc_device((size_t)splits * m * n, &partials));
+            RMHIP_TRY(c->alloc_device((size_t)splits * m * n, &partials));
             g.k_chunk = (unsigned)chunk;
-            g.C = ws ? ws : partials->ptr;
+            g.C = partials->ptr;
             g.ldc = m;
             g.c_split_stride = (unsigned long long)m * n;
             g.alpha = 1.0;
@@ -1047,10 +1037,10 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
     const bool skinny = (m <= (size_t)SM || n <= (size_t)SN) && k < 1024 && !c->in_lookahead;  // (longer k: split-K above)
     // The look-ahead LU's update streams run their few-tile products - the dgemm steps of the W-wide triangular solves, 14-112 tiles of
     // 128 x 128 for 0.1-0.2 ms each - on the 64 x 64 tiles as well: four times the blocks, 16384 69.1 -> 67.6 ms, 8192 20.6 -> 20.2
-    // (RMHIP_LU_SMALL_UPD = largest k, 0 = off; _BLOCKS = most 128 x 128 tiles)
-    static const long small_upd = std::getenv("RMHIP_LU_SMALL_UPD") ? std::atol(std::getenv("RMHIP_LU_SMALL_UPD")) : 1024;
-    static const long small_upd_blocks = std::getenv("RMHIP_LU_SMALL_UPD_BLOCKS") ? std::atol(std::getenv("RMHIP_LU_SMALL_UPD_BLOCKS")) : 128;
-    const bool upd_small = small_upd > 0 && c->gemm_lds_pad != 0 && c->in_lookahead && (long)k <= small_upd && (long)blocks <= small_upd_blocks;
+    // (RMHIP_LU_SMALL_UPD = largest k, 0 = off; at most kSmallUpdBlocks 128 x 128 tiles)
+    constexpr long kSmallUpdBlocks = 128;
+    const long small_upd = lu_process_knobs().small_upd;
+    const bool upd_small = small_upd > 0 && c->gemm_lds_pad != 0 && c->in_lookahead && (long)k <= small_upd && (long)blocks <= kSmallUpdBlocks;
     const bool small_shape = !ep && !ta && !tb && splits == 1 && (c->gemm_lds_pad == 0 || small_force || upd_small) && k > 0 &&
                              ((k <= 1024 && (size_t)blocks * 2 <= (size_t)c->num_cus) || skinny || small_force || upd_small);
     const bool small_whole = (m % SM == 0) && (n % SN == 0) && (k % BK == 0) && vec_ok;

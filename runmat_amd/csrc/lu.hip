@@ -25,9 +25,9 @@
 namespace rmhip {
 
 // Wave priority of the panel chain's kernels (s_setprio): they share CUs with the update stream's dgemm blocks, and every
-// instruction they wait to issue is on the critical path.  Set once per process (lu_factor_device); RMHIP_LU_CHAIN_PRIO=0 turns it
-// off.  Measured at n = 16384: 74.0-74.1 ms with, 74.6-75.2 without; with the panel block sharing its CU (no LDS padding) 75.1
-// against 77.4 - the priority recovers most of what sharing costs, a CU of its own is still better.
+// instruction they wait to issue is on the critical path.  Measured at n = 16384: 74.0-74.1 ms with, 74.6-75.2 without; with the
+// panel block sharing its CU (no LDS padding) 75.1 against 77.4 - the priority recovers most of what sharing costs, a CU of its own
+// is still better.
 // (XCC id, HW_ID cu / sh / se byte) of the CU this wave runs on, bit 31 set: never 0
 __device__ __forceinline__ unsigned cu_key() {
     unsigned xcc, hw;
@@ -35,10 +35,7 @@ __device__ __forceinline__ unsigned cu_key() {
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
     return 0x80000000u | ((xcc & 0xfu) << 8) | ((hw >> 8) & 0xffu);
 }
-__device__ int d_chain_prio = 0;
-__device__ __forceinline__ void chain_prio() {
-    if (d_chain_prio) __builtin_amdgcn_s_setprio(3);
-}
+__device__ __forceinline__ void chain_prio() { __builtin_amdgcn_s_setprio(3); }
 
 
 static constexpr double LU_EPS = 1.0e-12;  // host_lu.rs:3
@@ -74,18 +71,10 @@ struct LuState {
     double* ucomp = nullptr;              // device [BASE_W][BASE_W]: the pivot rows of the panel in flight
     unsigned long long* growth = nullptr; // device: bits of the largest multiplier below the top block so far
     bool screened = false;                // the first panel's multipliers were checked on the host (early way out)
-    // band split (look-ahead driver, solve path): rows below band_end of the panel in flight are nobody's dependency until the NEXT
-    // panel's look-ahead update, so their share of the full-height kernels (k_rp_below, the in-panel dgemm) runs on `aux` and the main
-    // stream - the critical chain of k_rp_top launches - only touches rows [j, band_end)
-    hipStream_t aux = nullptr;
-    size_t band_end = 0;                  // 0: no split
     size_t ev_used = 0;                   // events drawn from the context's pool by this factorisation
-    unsigned ucomp_slot = 0;              // ring of compact U copies: k_rp_below on `aux` may still read panel p's while k_rp_top writes p + 1's
-    hipEvent_t aux_tail = nullptr;        // last event recorded on aux (what the main stream's next look-ahead update has to wait for)
+    unsigned ucomp_slot = 0;              // next slot of the ring of compact U copies (kUcompSlots)
     double* linv = nullptr;               // solve path: inverted 16 x 16 diagonal blocks of L, block q at 256 q (k_trsm_lower_mfma)
-    unsigned* yield_word = nullptr;       // two-level driver: the yield table (common.h CuAnnounce) through which chain kernels ask the update blocks on their CU to pause
-    int yield_all = 0;                    // which chain kernels besides k_rp_top count themselves in: 1 main-stream dgemm, 2 k_rp_below_mfma, 4 k_trsm_lower_mfma
-    unsigned long long* minv_max = nullptr;  // two-level driver: bits of the largest |entry| of the super-panels' inverted L11 blocks (guard, see getrf_super)
+    unsigned* yield_word = nullptr;       // two-level driver: the yield table (common.h CuAnnounce) through which k_rp_top asks the update blocks on its CU to pause
 };
 static constexpr unsigned kUcompSlots = 16;  // >= base panels per look-ahead panel (512 / 64) with room to spare
 // one slot: the 64 x 64 compact U of k_rp_top, then the inverses of its four 16 x 16 diagonal blocks (row-major [k][i], zero below the
@@ -1193,12 +1182,11 @@ __global__ void __launch_bounds__(RT_ROWS) k_rp_top(const RtArgs g, pk_u64* dbg)
 // ~ cond(U_bb) eps per block instead of eps per step); the multiplier bound is checked exactly as before.
 static constexpr int RBM_JT = 2;  // 16-row tiles per wave (32 rows: 64 accumulator registers - the wave must fit beside an update block's two waves per SIMD)
 __global__ void __launch_bounds__(64) k_rp_below_mfma(double* __restrict__ A, const size_t lda, const size_t rows, const size_t r0, const int j0,
-                                                      const double* __restrict__ ut, pk_u64* __restrict__ growth, unsigned* yield_tab) {
+                                                      const double* __restrict__ ut, pk_u64* __restrict__ growth) {
     typedef double v4d __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) double Ub[10 * 256];  // block id(b, c), b <= c: diagonal = inv(U_bb), off-diagonal = -U_bc; [k][i] row-major
     const int t = threadIdx.x, l15 = t & 15, lq = t >> 4;
     chain_prio();
-    const CuAnnounce on_cu(yield_tab);
     {
         constexpr int BB[10] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3}, CC[10] = {0, 1, 2, 3, 1, 2, 3, 2, 3, 3};
 #pragma unroll
@@ -1262,13 +1250,13 @@ __global__ void __launch_bounds__(64) k_rp_below_mfma(double* __restrict__ A, co
     }
     mx = wave_max_u64(mx);
     if (t == 0 && mx != 0) atomicMax(growth, mx > 0x7ff0000000000000ull ? 0x7ff8000000000000ull : mx);
-    on_cu.done();
 }
 
 // Rows below the top block: l = a U11^-1, one thread per row, U (transposed, as k_rp_top left it) staged in LDS.  One wave per
 // workgroup: every FMA takes an 8-byte operand from LDS, so a CU's LDS feeds about one wave at the rate its SIMD multiplies, and the
 // rows should spread over as many CUs as there are.
-template <int RB_THREADS, bool DBG>
+static constexpr int RB_THREADS = 64;
+template <bool DBG>
 __global__ void __launch_bounds__(RB_THREADS) k_rp_below(double* __restrict__ A, const size_t lda, const size_t rows, const size_t r0,
                                                          const int j0, const int w, const double* __restrict__ ut,
                                                          pk_u64* __restrict__ growth, const double /*tau: the host compares*/, pk_u64* dbg) {
@@ -1755,7 +1743,7 @@ __global__ void __launch_bounds__(TRSM_THREADS) k_trsm_lower_2p(const double* __
 // L2 hits), no LDS.  Rounding: products with an inverted 16 x 16 block instead of 16 substitution steps.
 template <int NB>  // 16 x 16 blocks of L: 4 (w = 64) or 8 (w = 128)
 __global__ void __launch_bounds__(64) k_trsm_lower_mfma(const double* __restrict__ T, const size_t ldt, const double* __restrict__ linv,
-                                                        double* __restrict__ B, const size_t ldb, const size_t nc, unsigned* yield_tab) {
+                                                        double* __restrict__ B, const size_t ldb, const size_t nc) {
     typedef double v4d __attribute__((ext_vector_type(4)));
     typedef double v2d __attribute__((ext_vector_type(2)));
     constexpr int W = 16 * NB;
@@ -1763,7 +1751,6 @@ __global__ void __launch_bounds__(64) k_trsm_lower_mfma(const double* __restrict
     __shared__ __attribute__((aligned(16))) double tile[16 * CS];  // this wave's 16 right-hand sides, [column][row]
     const int t = threadIdx.x, l15 = t & 15, lq = t >> 4;
     chain_prio();
-    const CuAnnounce on_cu(yield_tab);
     const size_t col0 = (size_t)blockIdx.x * 16;
     // coalesced load: one right-hand side per step, W rows as W / 2 lanes x 16 bytes (the rows of a column are contiguous in memory)
 #pragma unroll
@@ -1803,21 +1790,19 @@ __global__ void __launch_bounds__(64) k_trsm_lower_mfma(const double* __restrict
 #pragma unroll
     for (int cc = 0; cc < 16; ++cc)
         if (2 * t < W && col0 + cc < nc) *(v2d*)(B + (col0 + cc) * ldb + 2 * t) = *(const v2d*)(tile + cc * CS + 2 * t);
-    on_cu.done();
 }
 
 static int launch_check(Context* c);
 template <int MODE, int NC, int TRSM_THREADS>
 static int launch_trsm_fused_nc(Context* c, const double* T, size_t ldt, size_t w, double* B, size_t ldb, size_t nc) {
     // inside the look-ahead LU a 65..128-wide unit-lower solve takes the two-pass kernel (66 KiB: it shares CUs with the update
-    // stream's dgemm blocks; RMHIP_LU_TRSM_2P=0: the 132 KiB one-pass kernel everywhere)
-    static const int two_pass = std::getenv("RMHIP_LU_TRSM_2P") ? std::atoi(std::getenv("RMHIP_LU_TRSM_2P")) : 1;
-    if (MODE == 0 && w > 64 && c->in_lookahead && two_pass) {
+    // stream's dgemm blocks, where the 132 KiB one-pass kernel waits for a whole CU)
+    if (MODE == 0 && w > 64 && c->in_lookahead) {
         const size_t lds2 = (size_t)64 * TRSM_SW * sizeof(double);
         c->ensure_max_lds((const void*)k_trsm_lower_2p<NC, TRSM_THREADS>, lds2);
         const size_t per_block2 = (size_t)(TRSM_THREADS / 64) * NC;
         size_t want2 = (nc + per_block2 - 1) / per_block2;
-        const size_t cap2 = (size_t)c->num_cus * (two_pass > 1 ? (size_t)two_pass : 1);
+        const size_t cap2 = (size_t)c->num_cus;
         if (want2 < 1) want2 = 1;
         hipLaunchKernelGGL((k_trsm_lower_2p<NC, TRSM_THREADS>), dim3((unsigned)(want2 < cap2 ? want2 : cap2)), dim3(TRSM_THREADS), lds2,
                            c->stream, T, ldt, (int)w, B, ldb, nc);
@@ -1848,9 +1833,8 @@ static int launch_trsm_fused(Context* c, const double* T, size_t ldt, size_t w, 
         if (have) {
             const double* linv = c->lu_linv + (j / 16) * 256;
             const unsigned grid = (unsigned)((nc + 15) / 16);
-            unsigned* const ytab = (c->in_lookahead && c->gemm_lds_pad == 0 && c->lu_yield_trsm) ? c->gemm_announce_tab : nullptr;  // main stream of the two-level driver
-            if (w == 64) hipLaunchKernelGGL(k_trsm_lower_mfma<4>, dim3(grid), dim3(64), 0, c->stream, T, ldt, linv, B, ldb, nc, ytab);
-            else hipLaunchKernelGGL(k_trsm_lower_mfma<8>, dim3(grid), dim3(64), 0, c->stream, T, ldt, linv, B, ldb, nc, ytab);
+            if (w == 64) hipLaunchKernelGGL(k_trsm_lower_mfma<4>, dim3(grid), dim3(64), 0, c->stream, T, ldt, linv, B, ldb, nc);
+            else hipLaunchKernelGGL(k_trsm_lower_mfma<8>, dim3(grid), dim3(64), 0, c->stream, T, ldt, linv, B, ldb, nc);
             return launch_check(c);
         }
     }
@@ -1859,30 +1843,66 @@ static int launch_trsm_fused(Context* c, const double* T, size_t ldt, size_t w, 
                                   : launch_trsm_fused_nc<MODE, 1, 256>(c, T, ldt, w, B, ldb, nc);
 }
 
-// Developer knob: RMHIP_LU_SKIP bitmask drops whole phases (results are then garbage) so wall-clock
-// differences attribute time to phases without a profiler: 1 column kernels, 2 dgemm, 4 trsm base
-// kernels, 8 row interchanges.
-static int lu_skip_mask() {
-    static int mask = -1;
-    if (mask < 0) {
-        const char* v = std::getenv("RMHIP_LU_SKIP");
-        mask = v ? std::atoi(v) : 0;
+// ---- environment knobs (docs/KNOBS.md): every RMHIP_LU_* variable is read here and nowhere else -----------------------------------
+static std::vector<std::pair<size_t, size_t>> parse_super_seq(const char* v) {
+    std::vector<std::pair<size_t, size_t>> out;  // (W, nb)
+    while (v && *v) {
+        char* end = nullptr;
+        const size_t W = (size_t)std::strtoull(v, &end, 10);
+        size_t nb = W;
+        if (end && *end == ':') nb = (size_t)std::strtoull(end + 1, &end, 10);
+        if (W >= 64) out.emplace_back((W / 64) * 64, nb < 64 ? 64 : (nb / 64) * 64);
+        v = end;
+        while (v && (*v == ',' || *v == '/' || *v == ' ')) ++v;
+        if (!end) break;
     }
-    return mask;
+    return out;
 }
+
+LuKnobs lu_knobs() {
+    LuKnobs k;
+    const char* v = nullptr;
+    if ((v = std::getenv("RMHIP_LU_FAST"))) k.fast = v[0] != '0';
+    if ((v = std::getenv("RMHIP_LU_TAU"))) k.tau = std::atof(v);
+    if ((v = std::getenv("RMHIP_LU_PAD"))) k.pad = v[0] != '0';
+    if ((v = std::getenv("RMHIP_LU_LOOKAHEAD"))) k.lookahead = v[0] == '1' ? 1 : 0;
+    if ((v = std::getenv("RMHIP_LU_NB"))) k.nb = std::atol(v);
+    if ((v = std::getenv("RMHIP_LU_PANEL"))) k.panel_columns = v[0] == 'c';
+    if ((v = std::getenv("RMHIP_LU_PANEL_DEBUG"))) k.panel_debug = v[0] == '1';
+    if ((v = std::getenv("RMHIP_LU_SUBST"))) k.subst_pair = v[0] == 'p';
+    k.verbose = std::getenv("RMHIP_LU_VERBOSE") != nullptr;
+    k.timeline = std::getenv("RMHIP_LU_TIMELINE") != nullptr;
+    k.test_retry = std::getenv("RMHIP_LU_TEST_RETRY") != nullptr;
+    k.test_growth = std::getenv("RMHIP_LU_TEST_GROWTH") != nullptr;
+    k.test_subst_retry = std::getenv("RMHIP_LU_TEST_SUBST_RETRY") != nullptr;
+    return k;
+}
+
+const LuProcessKnobs& lu_process_knobs() {
+    static const LuProcessKnobs knobs = [] {
+        LuProcessKnobs k;
+        const char* v = nullptr;
+        if ((v = std::getenv("RMHIP_LU_SUPER"))) k.super = std::atoi(v) != 0;
+        k.super_seq = parse_super_seq(std::getenv("RMHIP_LU_SUPER_SEQ"));
+        const auto late = parse_super_seq(std::getenv("RMHIP_LU_SUPER_LATE"));
+        if (!late.empty()) k.super_late = late[0];
+        if ((v = std::getenv("RMHIP_LU_SUPER_ROWS"))) k.super_rows = std::atol(v);
+        if ((v = std::getenv("RMHIP_LU_IPREP"))) k.iprep = std::atoi(v);
+        if ((v = std::getenv("RMHIP_LU_IPREP_SPLIT"))) k.iprep_split = std::atoi(v) != 0;
+        if ((v = std::getenv("RMHIP_LU_SMALL_UPD"))) k.small_upd = std::atol(v);
+        if ((v = std::getenv("RMHIP_LU_RB_MFMA"))) k.rb_mfma = std::atoi(v) != 0;
+        if ((v = std::getenv("RMHIP_LU_TRSM_MFMA"))) k.trsm_mfma = std::atoi(v) != 0;
+        if ((v = std::getenv("RMHIP_LU_SKIP"))) k.skip = std::atoi(v);
+        return k;
+    }();
+    return knobs;
+}
+
+// RMHIP_LU_SKIP bit mask drops whole phases (results are then garbage) so wall-clock differences attribute time to phases without a
+// profiler: 1 column kernels, 2 dgemm, 4 trsm base kernels, 8 row interchanges (16: lu_solve_device's few-right-hand-side form).
 static int lu_dgemm(Context* c, size_t m, size_t n, size_t k, double alpha, const double* A, size_t lda, const double* B,
                     size_t ldb, double beta, double* C, size_t ldc) {
-    if (lu_skip_mask() & 2) return RMHIP_OK;
-    static long kmin = -1, mmax = -1;
-    if (kmin < 0) {
-        const char* v = std::getenv("RMHIP_LU_SKIP_K_BELOW");
-        kmin = v ? std::atol(v) : 0;
-        v = std::getenv("RMHIP_LU_SKIP_M_BELOW");
-        mmax = v ? std::atol(v) : 0;
-    }
-    if ((long)k < kmin || (long)m < mmax) return RMHIP_OK;
-    static const bool log_shapes = std::getenv("RMHIP_LU_GEMM_LOG") != nullptr;  // developer aid: every update's shape and stream, in launch order (stderr)
-    if (log_shapes) std::fprintf(stderr, "[lu_dgemm] stream %p m %zu n %zu k %zu pad %zu\n", (void*)c->stream, m, n, k, c->gemm_lds_pad);
+    if (lu_process_knobs().skip & 2) return RMHIP_OK;
     return launch_dgemm(c, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
 }
 
@@ -1892,13 +1912,9 @@ static int launch_check(Context* c) {
     return RMHIP_OK;
 }
 
-// Base size of the recursion: TRSM_W, or 64 when Context::trsm_base says so (under look-ahead a 64-wide solve's
-// 33 KiB of LDS fits beside an update dgemm block, a 128-wide one needs a whole CU and waits for one to drain).
-static size_t trsm_base(const Context* c) { return c->trsm_base == 64 ? 64 : (size_t)TRSM_W; }
-
-// split point of a triangular solve wider than the base: whole base blocks on the left
-static size_t trsm_split(size_t w, size_t base) {
-    size_t h = ((w / 2 + base - 1) / base) * base;
+// split point of a triangular solve wider than the base TRSM_W: whole base blocks on the left
+static size_t trsm_split(size_t w) {
+    size_t h = ((w / 2 + TRSM_W - 1) / TRSM_W) * TRSM_W;
     if (h >= w) h = w / 2;
     return h;
 }
@@ -1907,11 +1923,11 @@ static size_t trsm_split(size_t w, size_t base) {
 static int trsm_lower_rec(Context* c, const double* T, size_t ldt, size_t w, double* B, size_t ldb, size_t nc,
                           bool unit = true) {
     if (w == 0 || nc == 0) return RMHIP_OK;
-    if (w <= trsm_base(c)) {
-        if (lu_skip_mask() & 4) return RMHIP_OK;
+    if (w <= (size_t)TRSM_W) {
+        if (lu_process_knobs().skip & 4) return RMHIP_OK;
         return unit ? launch_trsm_fused<0>(c, T, ldt, w, B, ldb, nc) : launch_trsm_fused<1>(c, T, ldt, w, B, ldb, nc);
     }
-    const size_t h = trsm_split(w, trsm_base(c));
+    const size_t h = trsm_split(w);
     RMHIP_TRY(trsm_lower_rec(c, T, ldt, h, B, ldb, nc, unit));
     RMHIP_TRY(lu_dgemm(c, w - h, nc, h, -1.0, T + h, ldt, B, ldb, 1.0, B + h, ldb));
     return trsm_lower_rec(c, T + h + h * ldt, ldt, w - h, B + h, ldb, nc, unit);
@@ -1919,11 +1935,11 @@ static int trsm_lower_rec(Context* c, const double* T, size_t ldt, size_t w, dou
 
 static int trsm_upper_rec(Context* c, const double* T, size_t ldt, size_t w, double* B, size_t ldb, size_t nc) {
     if (w == 0 || nc == 0) return RMHIP_OK;
-    if (w <= trsm_base(c)) {
-        if (lu_skip_mask() & 4) return RMHIP_OK;
+    if (w <= (size_t)TRSM_W) {
+        if (lu_process_knobs().skip & 4) return RMHIP_OK;
         return launch_trsm_fused<2>(c, T, ldt, w, B, ldb, nc);
     }
-    const size_t h = trsm_split(w, trsm_base(c));
+    const size_t h = trsm_split(w);
     RMHIP_TRY(trsm_upper_rec(c, T + h + h * ldt, ldt, w - h, B + h, ldb, nc));
     RMHIP_TRY(lu_dgemm(c, h, nc, w - h, -1.0, T + h * ldt, ldt, B + h, ldb, 1.0, B, ldb));
     return trsm_upper_rec(c, T, ldt, h, B, ldb, nc);
@@ -1940,7 +1956,7 @@ static int laswp(LuState& s, size_t c0, size_t c1, size_t k0, size_t k1) {
             p1 = (int)i + 1;
         }
     }
-    if (p0 < 0 || (lu_skip_mask() & 8)) return RMHIP_OK;
+    if (p0 < 0 || (lu_process_knobs().skip & 8)) return RMHIP_OK;
     const size_t ncols = c1 - c0;
     Context* c = s.c;
     unsigned* counter = nullptr;
@@ -1950,39 +1966,29 @@ static int laswp(LuState& s, size_t c0, size_t c1, size_t k0, size_t k1) {
     return launch_check(s.c);
 }
 
-// Most blocks a base panel may have and still sit on ONE XCD, one per CU (getrf_rec's placement rule; 0: never;
-// RMHIP_LU_ONE_XCD=0 disables).
+// Most blocks a base panel may have and still sit on ONE XCD, one per CU (getrf_rec's placement rule; 0: never - after such a
+// panel timed out once, see lu_factor_device).
 // (Tried: twice as many - tall panels, two blocks per CU in a 256-register build of the kernel - so that the update stream's
 // persistent dgemm has the other seven XCDs to itself in the first half too: 124 ms against 102 at n = 16384.  A panel block
 // that needs a whole SIMD's registers waits for every small kernel of the other streams to leave its CU; the panels then
 // average 450 us instead of 210 and the main stream becomes the critical path from the start.)
-static size_t one_xcd_block_limit(const Context* c) {
-    static int one_xcd = -1;
-    if (one_xcd < 0) {
-        const char* v = std::getenv("RMHIP_LU_ONE_XCD");
-        one_xcd = (v && *v == '0') ? 0 : 1;
-    }
-    return (one_xcd && c->one_xcd_ok) ? (size_t)c->num_cus / 8 : 0;
-}
+static size_t one_xcd_block_limit(const Context* c) { return c->one_xcd_ok ? (size_t)c->num_cus / 8 : 0; }
 
-// retarget the context's stream (and the LDS pad / triangular-solve base that go with it) for a scope
+// retarget the context's stream (and the LDS pad that goes with it) for a scope
 struct StreamScope {
     Context* c;
     hipStream_t saved;
     size_t saved_pad;
-    int saved_base;
     bool saved_prio;
-    StreamScope(Context* ctx, hipStream_t s, size_t gemm_lds_pad, int base = 128)
-        : c(ctx), saved(ctx->stream), saved_pad(ctx->gemm_lds_pad), saved_base(ctx->trsm_base), saved_prio(ctx->gemm_chain_prio) {
+    StreamScope(Context* ctx, hipStream_t s, size_t gemm_lds_pad)
+        : c(ctx), saved(ctx->stream), saved_pad(ctx->gemm_lds_pad), saved_prio(ctx->gemm_chain_prio) {
         c->stream = s;
         c->gemm_lds_pad = gemm_lds_pad;
-        c->trsm_base = base;  // (128: the update stream owns whole CUs between its dgemm blocks anyway)
         c->gemm_chain_prio = false;  // only the main stream's dgemm launches raise their wave priority
     }
     ~StreamScope() {
         c->stream = saved;
         c->gemm_lds_pad = saved_pad;
-        c->trsm_base = saved_base;
         c->gemm_chain_prio = saved_prio;
     }
 };
@@ -1997,7 +2003,7 @@ static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller =
     if (w <= (size_t)BASE_W) {
         const size_t c1 = j0 + w;  // j0 + w <= min(rows, cols) always holds (see lu_factor_device)
         const size_t nbp = (s.rows - j0 + P2_ROWS - 1) / P2_ROWS;
-        if (s.fast && !(lu_skip_mask() & 1)) {
+        if (s.fast && !(lu_process_knobs().skip & 1)) {
             // solve path: ONE workgroup factors the top P2_ROWS rows with partial pivoting (no exchange), k_rp_below turns every row
             // below into multipliers and records the largest one
             const size_t pid = s.panel_start->size();
@@ -2015,22 +2021,15 @@ static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller =
             g.ucomp = ucomp;
             g.xcc_out = s.panel_xcc;
             g.yield_word = s.yield_word;
-            static const int rb_mfma = std::getenv("RMHIP_LU_RB_MFMA") ? std::atoi(std::getenv("RMHIP_LU_RB_MFMA")) : 1;
-            const bool below_mfma = rb_mfma && w == (size_t)BASE_W && !s.xdbg;
+            const bool below_mfma = lu_process_knobs().rb_mfma && w == (size_t)BASE_W && !s.xdbg;
             g.uinv_on = below_mfma ? 1 : 0;
             g.linv = (below_mfma && s.linv) ? s.linv + (j0 / 16) * 256 : nullptr;
             if (g.linv && s.c->lu_linv_ok)
                 for (size_t q = j0 / 16; q < (j0 + BASE_W) / 16 && q < s.c->lu_linv_ok->size(); ++q) (*s.c->lu_linv_ok)[q] = 1;
             // like k_lu_panel2 the block ASKS for more LDS than it uses (48.6 KiB static) so that it does not share its CU with an
-            // update-stream dgemm block: every column step would run slower beside one (RMHIP_LU_PANEL_PAD_KB; the phase-dependent
-            // values of getrf_blocked apply)
-            static long pad_kb_top = -1;
-            if (pad_kb_top < 0) {
-                const char* v = std::getenv("RMHIP_LU_PANEL_PAD_KB");
-                pad_kb_top = v ? std::atol(v) : 96;  // (96: the workgroup has its CU to itself; 32: 78.3 -> 77.3 ms at n = 16384)
-                if (pad_kb_top > 96) pad_kb_top = 96;
-            }
-            const size_t pad_bytes = (size_t)(s.panel_pad_kb >= 0 ? (s.panel_pad_kb > 96 ? 96 : s.panel_pad_kb) : pad_kb_top) * 1024;
+            // update-stream dgemm block: every column step would run slower beside one (the phase-dependent values of the drivers apply)
+            constexpr long kTopPadKb = 96;  // (96: the workgroup has its CU to itself; 32: 78.3 -> 77.3 ms at n = 16384)
+            const size_t pad_bytes = (size_t)(s.panel_pad_kb >= 0 ? (s.panel_pad_kb > kTopPadKb ? kTopPadKb : s.panel_pad_kb) : kTopPadKb) * 1024;
             if (pad_bytes) {
                 s.c->ensure_max_lds((const void*)k_rp_top<false>, 96 * 1024);
                 s.c->ensure_max_lds((const void*)k_rp_top<true>, 96 * 1024);
@@ -2039,33 +2038,17 @@ static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller =
             else hipLaunchKernelGGL(k_rp_top<false>, dim3(1), dim3(RT_ROWS), pad_bytes, s.c->stream, g, (pk_u64*)nullptr);
             RMHIP_TRY(launch_check(s.c));
             if (g.rows < s.rows) {
-                static const int rb_threads = std::getenv("RMHIP_LU_RB_THREADS") ? std::atoi(std::getenv("RMHIP_LU_RB_THREADS")) : 64;  // developer knob (A/B)
-                const size_t rbt = rb_threads == 256 ? 256 : (rb_threads == 128 ? 128 : 64);
-                void (*kern)(double*, size_t, size_t, size_t, int, int, const double*, pk_u64*, double, pk_u64*) =
-                    s.xdbg ? (rbt == 256 ? k_rp_below<256, true> : (rbt == 128 ? k_rp_below<128, true> : k_rp_below<64, true>))
-                           : (rbt == 256 ? k_rp_below<256, false> : (rbt == 128 ? k_rp_below<128, false> : k_rp_below<64, false>));
-                auto below = [&](hipStream_t st, size_t r0, size_t r1) {  // rows [r0, r1)
-                    if (r1 <= r0) return;
-                    if (below_mfma) {
-                        hipLaunchKernelGGL(k_rp_below_mfma, dim3((unsigned)((r1 - r0 + 16 * RBM_JT - 1) / (16 * RBM_JT))), dim3(64), 0, st, s.A, s.lda, r1, r0, (int)j0,
-                                           (const double*)ucomp, (pk_u64*)s.growth, (s.yield_all & 2) ? s.yield_word : (unsigned*)nullptr);
-                        s.c->tel.kernel_launches++;
-                        return;
-                    }
-                    hipLaunchKernelGGL(kern, dim3((unsigned)((r1 - r0 + rbt - 1) / rbt)), dim3((unsigned)rbt), 0, st, s.A, s.lda, r1, r0, (int)j0, (int)w,
-                                       (const double*)ucomp, (pk_u64*)s.growth, s.tau, (pk_u64*)s.xdbg);
-                    s.c->tel.kernel_launches++;
-                };
-                const size_t split = (s.aux && s.band_end > (size_t)g.rows && s.band_end < s.rows) ? s.band_end : s.rows;
-                below(s.c->stream, g.rows, split);
-                if (split < s.rows) {  // the rest of the rows: off the critical chain
-                    hipEvent_t top_done = lu_new_event(s);
-                    (void)hipEventRecord(top_done, s.c->stream);  // (recorded behind the band's k_rp_below: same stream order as the top block)
-                    (void)hipStreamWaitEvent(s.aux, top_done, 0);
-                    below(s.aux, split, s.rows);
-                    s.aux_tail = lu_new_event(s);
-                    (void)hipEventRecord(s.aux_tail, s.aux);
-                }
+                const size_t r0 = g.rows, nrows = s.rows - r0;
+                if (below_mfma)
+                    hipLaunchKernelGGL(k_rp_below_mfma, dim3((unsigned)((nrows + 16 * RBM_JT - 1) / (16 * RBM_JT))), dim3(64), 0, s.c->stream, s.A, s.lda,
+                                       s.rows, r0, (int)j0, (const double*)ucomp, (pk_u64*)s.growth);
+                else if (s.xdbg)
+                    hipLaunchKernelGGL(k_rp_below<true>, dim3((unsigned)((nrows + RB_THREADS - 1) / RB_THREADS)), dim3(RB_THREADS), 0,
+                                       s.c->stream, s.A, s.lda, s.rows, r0, (int)j0, (int)w, (const double*)ucomp, (pk_u64*)s.growth, s.tau, (pk_u64*)s.xdbg);
+                else
+                    hipLaunchKernelGGL(k_rp_below<false>, dim3((unsigned)((nrows + RB_THREADS - 1) / RB_THREADS)), dim3(RB_THREADS), 0,
+                                       s.c->stream, s.A, s.lda, s.rows, r0, (int)j0, (int)w, (const double*)ucomp, (pk_u64*)s.growth, s.tau, (pk_u64*)s.xdbg);
+                s.c->tel.kernel_launches++;
                 RMHIP_HIP_CHECK(hipGetLastError());
             }
             s.xbase += (unsigned)w;
@@ -2075,7 +2058,6 @@ static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller =
                 // fails at its first panel; one small read here instead of a whole factorisation of wasted work.
                 s.screened = true;
                 unsigned long long bits = 0;
-                if (s.aux) RMHIP_HIP_CHECK(hipStreamSynchronize(s.aux));  // its rows of the first panel count too
                 RMHIP_HIP_CHECK(hipMemcpyAsync(&bits, s.growth, sizeof(bits), hipMemcpyDeviceToHost, s.c->stream));
                 RMHIP_HIP_CHECK(hipStreamSynchronize(s.c->stream));
                 double gmax;
@@ -2091,7 +2073,7 @@ static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller =
             }
             return laswp(s, j0, c1, j0, c1);  // the panel's own interchange
         }
-        if (s.persistent && nbp <= (size_t)PK_MAXB && nbp <= (size_t)s.c->num_cus && !(lu_skip_mask() & 1)) {
+        if (s.persistent && nbp <= (size_t)PK_MAXB && nbp <= (size_t)s.c->num_cus && !(lu_process_knobs().skip & 1)) {
             // one launch factors the panel, interchanges its own columns and leaves the row-move list for the others
             const size_t pid = s.panel_start->size();
             P2Args g;
@@ -2101,16 +2083,10 @@ static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller =
             g.j0 = (int)j0;
             g.w = (int)w;
             g.nblocks = (int)nbp;
-            static int onehop_max = -1;  // developer knob
-            if (onehop_max < 0) {
-                const char* v = std::getenv("RMHIP_LU_ONEHOP");
-                onehop_max = v ? std::atoi(v) : P2_ONEHOP_MAXB;
-                if (onehop_max > P2_ONEHOP_MAXB) onehop_max = P2_ONEHOP_MAXB;
-            }
-            g.onehop_max = onehop_max;
+            g.onehop_max = P2_ONEHOP_MAXB;
             // One-XCD placement when every block finds a CU of its own on one XCD (<= num_cus / 8 blocks): the exchange hop
             // drops from a write-through + a miss in another XCD's L2 to two accesses of one L2 (scripts/micro/
-            // xcd_exchange.hip: 2.1-2.5 -> 1.45 us per step).  RMHIP_LU_ONE_XCD=0 disables.
+            // xcd_exchange.hip: 2.1-2.5 -> 1.45 us per step).
             g.bstride = nbp <= one_xcd_block_limit(s.c) ? 8 : 1;
             if (g.bstride > 1) s.c->lu_used_one_xcd = true;
             g.seq0 = s.xbase;
@@ -2126,14 +2102,9 @@ static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller =
             // The block needs 18.5 KiB of LDS but ASKS for 82.5: it then does not fit beside an update-stream dgemm block
             // (84 KiB) and waits for a CU of its own.  Sharing a CU costs more than the wait: with the panel waves on the
             // same SIMDs as a dgemm wave every column step slows down, and the column chain is the critical path
-            // (n = 16384: 135 ms sharing, 123 ms exclusive; RMHIP_LU_PANEL_PAD_KB).
-            static long pad_kb = -1;
-            if (pad_kb < 0) {
-                const char* v = std::getenv("RMHIP_LU_PANEL_PAD_KB");
-                pad_kb = v ? std::atol(v) : 64;
-                if (pad_kb > 128) pad_kb = 128;
-            }
-            const size_t lds_bytes = P2_LDS_DOUBLES * sizeof(double) + (size_t)(s.panel_pad_kb >= 0 ? s.panel_pad_kb : pad_kb) * 1024;
+            // (n = 16384: 135 ms sharing, 123 ms exclusive).
+            constexpr long kPanelPadKb = 64;
+            const size_t lds_bytes = P2_LDS_DOUBLES * sizeof(double) + (size_t)(s.panel_pad_kb >= 0 ? s.panel_pad_kb : kPanelPadKb) * 1024;
             if (lds_bytes > 65536) {
                 s.c->ensure_max_lds((const void*)k_lu_panel2<false>, lds_bytes);
                 s.c->ensure_max_lds((const void*)k_lu_panel2<true>, lds_bytes);
@@ -2157,7 +2128,7 @@ static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller =
         hipLaunchKernelGGL(k_lu_col, dim3((unsigned)nb), dim3(PANEL_THREADS), 0, s.c->stream, s.A, s.lda, s.rows, (int)j0,
                            (int)j0 - 1, (int)c1, 1, (int)nb, s.pos_of, s.row_at, s.prow, s.ipiv, s.info, s.cand_abs, s.cand_pos, s.cand_row);
         RMHIP_TRY(launch_check(s.c));
-        for (size_t k = j0; k < c1 && !(lu_skip_mask() & 1); ++k) {
+        for (size_t k = j0; k < c1 && !(lu_process_knobs().skip & 1); ++k) {
             hipLaunchKernelGGL(k_lu_col, dim3((unsigned)nb), dim3(PANEL_THREADS), 0, s.c->stream, s.A, s.lda, s.rows,
                                (int)j0, (int)k, (int)c1, 0, (int)nb, s.pos_of, s.row_at, s.prow, s.ipiv, s.info,
                                s.cand_abs, s.cand_pos, s.cand_row);
@@ -2183,22 +2154,7 @@ static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller =
     if (j0 + h < s.rows) {
         double* A21 = s.A + (j0 + h) + j0 * s.lda;
         double* A22 = s.A + (j0 + h) + (j0 + h) * s.lda;
-        const size_t r0 = j0 + h;
-        const size_t split = (s.fast && s.aux && s.band_end > r0 && s.band_end < s.rows) ? s.band_end : s.rows;
-        RMHIP_TRY(lu_dgemm(s.c, split - r0, w - h, h, -1.0, A21, s.lda, A12, s.lda, 1.0, A22, s.lda));
-        if (split < s.rows) {
-            // rows below the band: their multipliers come from aux's own k_rp_below launches (stream order), the U block row from the
-            // triangular solve the main stream just enqueued
-            hipEvent_t u_ready = lu_new_event(s);
-            (void)hipEventRecord(u_ready, s.c->stream);
-            (void)hipStreamWaitEvent(s.aux, u_ready, 0);
-            {
-                StreamScope scope(s.c, s.aux, s.c->gemm_lds_pad, s.c->trsm_base);
-                RMHIP_TRY(lu_dgemm(s.c, s.rows - split, w - h, h, -1.0, A21 + (split - r0), s.lda, A12, s.lda, 1.0, A22 + (split - r0), s.lda));
-            }
-            s.aux_tail = lu_new_event(s);
-            (void)hipEventRecord(s.aux_tail, s.aux);
-        }
+        RMHIP_TRY(lu_dgemm(s.c, s.rows - (j0 + h), w - h, h, -1.0, A21, s.lda, A12, s.lda, 1.0, A22, s.lda));
         RMHIP_TRY(getrf_rec(s, j0 + h, w - h, true, &right_deferred));
         const size_t k1 = (j0 + w <= s.rows) ? (j0 + w) : s.rows;
         RMHIP_TRY(laswp(s, j0, right_deferred ? j0 + w : j0 + h, j0 + h, k1));
@@ -2248,6 +2204,10 @@ static int iprep_columns(LuState& s, size_t S0, size_t j, size_t w, size_t c0, s
     return trsm_lower_rec(s.c, s.A + j + j * s.lda, s.lda, w, A12, s.lda, c1 - c0);
 }
 
+// update-stream dgemm blocks ask for 84 KiB of LDS (73.7 needed): one per CU, leaving 76 KiB for a panel
+// block (66 KiB) or a main-stream dgemm block (73.7 KiB)
+static constexpr size_t kSidePad = 84 * 1024 - 73728;
+
 static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
     Context* c = s.c;
     hipStream_t main_stream = c->stream;
@@ -2265,45 +2225,28 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
     // with the usual padded blocks: 370 ms against 112.  Work submitted through a CU-masked queue is slow here for
     // reasons beyond the CU count.)
     auto new_event = [&]() { return lu_new_event(s); };
-    // solve path: the band split (LuState::aux).  Off by default: measured 75.0 / 42.6 / 21.7 ms with it against 74.4 / 42.0 / 20.8
-    // without (n = 16384 / 12288 / 8192) - the update stream is the busy one for the first 60 ms and the extra stream only takes CUs
-    // from it (profiles/r03_mldivide_timeline.txt).  RMHIP_LU_BAND=1 turns it on for A/B runs.
-    static const int band_on = std::getenv("RMHIP_LU_BAND") ? std::atoi(std::getenv("RMHIP_LU_BAND")) : 0;
-    static const long band_extra = std::getenv("RMHIP_LU_BAND_ROWS") ? std::atol(std::getenv("RMHIP_LU_BAND_ROWS")) : 320;  // rows of a top block (256) + one base panel
-    if (s.fast && band_on) {
-        if (!c->lu_aux_stream) RMHIP_HIP_CHECK(hipStreamCreateWithFlags(&c->lu_aux_stream, hipStreamNonBlocking));
-        s.aux = c->lu_aux_stream;
-    }
-    // update-stream dgemm blocks ask for 84 KiB of LDS (73.7 needed): one per CU, leaving 76 KiB for a panel
-    // block (66 KiB) or a main-stream dgemm block (73.7 KiB)
-    size_t side_pad = 84 * 1024 - 73728;
-    if (const char* v = std::getenv("RMHIP_LU_LA_PAD")) side_pad = (size_t)std::atoll(v);
-    // main-stream triangular solves keep the 128-wide base: a 64-wide one (33 KiB of LDS) would fit beside an update
-    // dgemm block instead of waiting for a CU to drain, but the extra launches cost more (140.7 vs 129.6 ms at
-    // n = 16384; RMHIP_LU_LA_TRSM=64 selects it)
+    // (Tried, solve path: the band split - the rows below a band of the panel in flight on a fourth stream, off the chain of k_rp_top
+    // launches: 75.0 / 42.6 / 21.7 ms with it against 74.4 / 42.0 / 20.8 without (n = 16384 / 12288 / 8192); the update stream is the
+    // busy one for the first 60 ms and the extra stream only takes CUs from it (profiles/r03_mldivide_timeline.txt; docs/EXPERIMENTS.md).)
+    // (Main-stream triangular solves keep the 128-wide base: a 64-wide one (33 KiB of LDS) would fit beside an update dgemm block
+    // instead of waiting for a CU to drain, but the extra launches cost more: 140.7 vs 129.6 ms at n = 16384.)
     std::shared_ptr<Allocation> late_ctl;  // tile counters of the persistent kernels (outlives the guard below)
     // the context fields this driver borrows go back on EVERY way out (an allocation or stream-creation failure below returns early),
     // and nothing of this factorisation is still running when they do
     struct Restore {
         Context* c;
         LuState* s;
-        int trsm_base;
         ~Restore() {
             if (c->lu_prep_stream) (void)hipStreamSynchronize(c->lu_prep_stream);
             if (c->lu_side_stream) (void)hipStreamSynchronize(c->lu_side_stream);
-            if (c->lu_aux_stream) (void)hipStreamSynchronize(c->lu_aux_stream);
-            s->aux = nullptr;
-            s->band_end = 0;
             c->gemm_tile_counters = nullptr;
             c->gemm_avoid_xcc = nullptr;
             c->gemm_counter_cap = 0;
             s->panel_xcc = nullptr;
             s->panel_pad_kb = -1;
             c->in_lookahead = false;
-            c->trsm_base = trsm_base;
         }
-    } restore{c, &s, c->trsm_base};
-    if (const char* v = std::getenv("RMHIP_LU_LA_TRSM")) c->trsm_base = std::atoi(v) == 64 ? 64 : 128;
+    } restore{c, &s};
     c->in_lookahead = true;
     int rc = RMHIP_OK;
     // Late phase (the next panel fits one XCD, getrf_rec places it there): the update stream's dgemm runs as a persistent
@@ -2311,11 +2254,9 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
     // such a placeholder can always be scheduled beside them.  The panel chain is the critical path there and everything
     // the update stream does disturbs it (without ANY update work in that phase the solve takes 95.7 instead of 108.4 ms):
     // this keeps the panel's CUs free (no drain before a panel or a 132 KiB triangular solve starts) and its L2 quiet.
-    // RMHIP_LU_LATE_XCD=0 disables.
-    // (solve path: off by default - its panel is one workgroup and k_rp_below's workgroups fit beside a dgemm block, so there is no XCD to
-    // keep free; n = 16384: 78.8 -> 76.4 ms without the persistent form)
-    static const int late_xcd_env = std::getenv("RMHIP_LU_LATE_XCD") ? std::atoi(std::getenv("RMHIP_LU_LATE_XCD")) : -1;  // 2: persistent dgemm in every phase (A/B)
-    const int late_xcd_on = late_xcd_env >= 0 ? late_xcd_env : (s.fast ? 0 : 1);
+    // (Not on the solve path: its panel is one workgroup and k_rp_below's workgroups fit beside a dgemm block, so there is no XCD to
+    // keep free; n = 16384: 78.8 -> 76.4 ms without the persistent form.)
+    const bool late_xcd_on = !s.fast;
     constexpr size_t kCounters = 4096;
     unsigned* late_counters = nullptr;
     if (late_xcd_on && c->one_xcd_ok) {
@@ -2328,8 +2269,8 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
         c->gemm_counter_cap = kCounters;
         c->gemm_avoid_xcc = s.panel_xcc;
     }
-    // Split update (RMHIP_LU_SPLIT=0 disables): on the update stream the interchanges and triangular solves are 14 % of the
-    // throughput-bound first half, and the matrix cores idle meanwhile.  While more than split_rows rows remain (6144: into the
+    // Split update: on the update stream the interchanges and triangular solves are 14 % of the
+    // throughput-bound first half, and the matrix cores idle meanwhile.  While more than kSplitRows rows remain (6144: into the
     // beginning of the late phase; 8192 measured 0.5 ms slower at n = 16384 and 8192) the trailing
     // columns are cut at a fixed column csplit into A | B; a third stream prepares (interchange + solve) one part while the
     // update stream's dgemm runs on the other:
@@ -2338,14 +2279,9 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
     // csplit stays put (so A_j lies inside A_{j-1}) until A has shrunk below a fifth of the range, then it moves to the
     // middle again (that one step waits for all of step j-1).  The main stream waits for dgemm_{j-1}(A) only - the next
     // panel's columns are its first ones - in either mode.  Same kernels on the same columns: bit-identical factors.
-    static const int split_on = std::getenv("RMHIP_LU_SPLIT") ? std::atoi(std::getenv("RMHIP_LU_SPLIT")) : 1;
-    static const long split_rows_env = std::getenv("RMHIP_LU_SPLIT_ROWS") ? std::atol(std::getenv("RMHIP_LU_SPLIT_ROWS")) : 6144;
-    static const int prep_base = std::getenv("RMHIP_LU_PREP_TRSM") ? std::atoi(std::getenv("RMHIP_LU_PREP_TRSM")) : 128;
-    hipStream_t prep = nullptr;
-    if (split_on) {
-        if (!c->lu_prep_stream) RMHIP_HIP_CHECK(hipStreamCreateWithPriority(&c->lu_prep_stream, hipStreamNonBlocking, prio_low));
-        prep = c->lu_prep_stream;
-    }
+    constexpr size_t kSplitRows = 6144;
+    if (!c->lu_prep_stream) RMHIP_HIP_CHECK(hipStreamCreateWithPriority(&c->lu_prep_stream, hipStreamNonBlocking, prio_low));
+    hipStream_t prep = c->lu_prep_stream;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;  // dgemm of the previous step finished on [.., a_end) / everything of that step finished
     size_t a_end = s.cols;                      // right edge of the previous step's part A
     size_t csplit = 0;
@@ -2353,7 +2289,7 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
         hipEvent_t e0 = new_event();  // side starts after whatever main already has queued (the copy of A)
         (void)hipEventRecord(e0, main_stream);
         (void)hipStreamWaitEvent(side, e0, 0);
-        if (prep) (void)hipStreamWaitEvent(prep, e0, 0);
+        (void)hipStreamWaitEvent(prep, e0, 0);
     }
     // Panel width by phase.  While the trailing matrix is large the update stream is the bottleneck and the main stream
     // idles a third of the time: wider panels there (fewer, deeper rank-k updates: the dgemm runs 53 instead of 47
@@ -2361,49 +2297,37 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
     // columns) the narrower panel wins.  n = 16384: 128.3 -> 125.2 ms (interleaved, scripts/lu_env_ab.sh); giving the
     // main stream a share of the trailing columns as well (its dgemm blocks fit beside the update stream's) measured
     // nothing (127.3 vs 127.9).
-    size_t nb_early = 512, early_rows = 10240;  // (10240 since the update stream's eight-wave dgemm: 113.7 -> 112.7 ms; 8192 before)
-    if (const char* v = std::getenv("RMHIP_LU_NB_EARLY")) nb_early = (size_t)std::atoll(v);
-    if (const char* v = std::getenv("RMHIP_LU_EARLY_ROWS")) early_rows = (size_t)std::atoll(v);
-    nb_early = nb_early < 64 ? 64 : (nb_early / 64) * 64;
-    if (nb_early < nb) nb_early = nb;
-    // third tier (RMHIP_LU_NB_LATE / RMHIP_LU_LATE_ROWS): once the panel chain is the critical path, a narrower panel
-    // moves more of each update from the main stream (look-ahead columns) to the idle update stream
+    constexpr size_t kNbEarly = 512, kEarlyRows = 10240;  // (10240 since the update stream's eight-wave dgemm: 113.7 -> 112.7 ms; 8192 before)
+    const size_t nb_early = kNbEarly < nb ? nb : kNbEarly;
+    // third tier: once the panel chain is the critical path, a narrower panel moves more of each update from the main stream
+    // (look-ahead columns) to the idle update stream
     // (n = 16384, interleaved: 123.1 / 124.2 ms without, 120.8 / 120.6 with 128 below 6144 rows; 64 below 3072: 122.9 / 121.6)
-    size_t nb_late = 128, late_rows = 8192;  // (8192 since the two-pass solve and the third stream: 98.4 vs 99.1 ms at n = 16384; 6144 before)
-    if (const char* v = std::getenv("RMHIP_LU_NB_LATE")) nb_late = (size_t)std::atoll(v);
-    if (const char* v = std::getenv("RMHIP_LU_LATE_ROWS")) late_rows = (size_t)std::atoll(v);
-    nb_late = nb_late < 64 ? 64 : (nb_late / 64) * 64;
-    if (nb_late > nb) nb_late = nb;
+    constexpr size_t kNbLate = 128, kLateRows = 8192;  // (8192 since the two-pass solve and the third stream: 98.4 vs 99.1 ms at n = 16384; 6144 before)
+    const size_t nb_late = kNbLate > nb ? nb : kNbLate;
     // the very first panel is narrower (the update stream has nothing to do until it is factored: 128 columns instead of
     // 512 start it 1.5 ms earlier; n = 16384: 108.9 -> 107.9 ms); the second one realigns to multiples of the wide width
-    // (RMHIP_LU_NB_FIRST, 0 = off)
-    size_t nb_first = 128;
-    if (const char* v = std::getenv("RMHIP_LU_NB_FIRST")) nb_first = ((size_t)std::atoll(v) / 64) * 64;
+    constexpr size_t kNbFirst = 128;
     auto width_at = [&](size_t j) {
-        if (nb_first && nb_first < nb_early && early_rows && kmin > early_rows + nb_early) {
-            if (j == 0) return nb_first;
-            if (j == nb_first) return nb_early - nb_first;
+        if (kNbFirst < nb_early && kmin > kEarlyRows + nb_early) {
+            if (j == 0) return kNbFirst;
+            if (j == kNbFirst) return nb_early - kNbFirst;
         }
-        if (early_rows && kmin - j > early_rows) return nb_early;
-        if (late_rows && kmin - j <= late_rows) return nb_late;
+        if (kmin - j > kEarlyRows) return nb_early;
+        if (kmin - j <= kLateRows) return nb_late;
         return nb;
     };
     // While the trailing matrix is large the machine is throughput bound on the update dgemm (one block per CU: ~50 TFLOP/s
     // in place, 56 alone) and the main stream has slack, so the panel blocks drop their LDS pad there and start beside a
     // dgemm block instead of waiting for a CU to drain (n = 16384: 119.9 -> 118.8 ms).  Letting the update stream drop ITS
     // pad there as well (two dgemm blocks per CU) starves the main stream: a retiring block's slot goes to the next block
-    // of the same kernel, stream priority or not (138 ms).  Developer knobs: RMHIP_LU_EARLY_SIDE_PAD (bytes),
-    // RMHIP_LU_EARLY_PANEL_PAD_KB.
+    // of the same kernel, stream priority or not (138 ms).  In the late phase (panel on one XCD) the panel blocks drop their pad
+    // too, see above.
     // (Also tried: the interchanges of the finished left columns on a third low-priority stream - they only depend on their panel and
     // on the previous update - instead of behind the update: 109.25 vs 108.6 ms, 8192: 40.4 vs 39.7 ms.)
     // (Also tried: the first quarter / half of the trailing columns on a second update stream, so that its dgemm covers the
     // row interchange and triangular solve of the rest - 125-130 ms against 119.)
     // (With the eight-wave update kernel trimmed to 128 VGPRs and the panel to 256 the two do share a CU again - and the solve
     // takes 119 ms instead of 108: a panel wave beside TWO MFMA waves per SIMD crawls.  Exclusive CUs for the panel it is.)
-    size_t early_side_pad = side_pad;
-    long early_panel_pad = 0;
-    if (const char* v = std::getenv("RMHIP_LU_EARLY_SIDE_PAD")) early_side_pad = (size_t)std::atoll(v);
-    if (const char* v = std::getenv("RMHIP_LU_EARLY_PANEL_PAD_KB")) early_panel_pad = std::atol(v);
     // (Tried: DEFERRED update of the far columns.  While the chain is left of column far_c every step updates only [next panel,
     // far_c) and the columns right of it collect their panels - applied later, range by range, with one interchange pass
     // (F may see later interchanges early: Pi (F - L U) = Pi F - (Pi L) U), one triangular solve and one rank-(b - a) update,
@@ -2413,23 +2337,15 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
     // panel chain - exchange latency under load, CUs that must drain before a panel or a triangular solve starts.)
     for (size_t j = 0; j < kmin && rc == RMHIP_OK;) {
         const size_t nbj = width_at(j);
-        const bool early = early_rows && kmin - j > early_rows;
+        const bool early = kmin - j > kEarlyRows;
         // this panel on one XCD?  (the condition getrf_rec applies to its first base panel)
         const bool late_xcd = late_counters && (s.rows - j + P2_ROWS - 1) / P2_ROWS <= one_xcd_block_limit(c);
-        static const long late_panel_pad = std::getenv("RMHIP_LU_LATE_PANEL_PAD_KB") ? std::atol(std::getenv("RMHIP_LU_LATE_PANEL_PAD_KB")) : 0;
-        s.panel_pad_kb = late_xcd ? late_panel_pad : (early ? early_panel_pad : -1);
+        s.panel_pad_kb = (late_xcd || early) ? 0 : -1;  // unpadded panel blocks in the early and the late phase (-1: getrf_rec's default)
         const size_t w = (kmin - j) < nbj ? (kmin - j) : nbj;
-        if (s.aux) {
-            const size_t be = j + w + (size_t)band_extra;
-            s.band_end = be < s.rows ? be : 0;  // nothing below the band: no split
-            s.aux_tail = nullptr;
-        }
-        rc = getrf_rec(s, j, w);  // P_j on main (and, below the band, on aux)
+        rc = getrf_rec(s, j, w);  // P_j on main
         if (rc != RMHIP_OK) break;
         hipEvent_t panel_done = new_event();
         (void)hipEventRecord(panel_done, main_stream);
-        hipEvent_t aux_done = s.aux_tail;  // aux's share of P_j (nullptr: it had none)
-        const size_t panel_band_end = s.band_end;
         const size_t next = j + w;
         size_t la_w = 0;
         if (next < kmin) {  // there is a next panel: the main stream updates its columns right away
@@ -2438,7 +2354,7 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
         }
         const size_t t0 = next + la_w;  // trailing columns [t0, cols)
         const bool next_late = late_counters && next < s.rows && (s.rows - next + P2_ROWS - 1) / P2_ROWS <= one_xcd_block_limit(c);
-        bool split = prep && kmin - j > (size_t)split_rows_env && s.cols > t0 && s.cols - t0 >= 2048;
+        bool split = kmin - j > kSplitRows && s.cols > t0 && s.cols - t0 >= 2048;
         bool moved = false;
         if (split) {
             if (csplit < t0 + 256 || csplit >= s.cols || (csplit - t0) * 5 < (s.cols - t0)) {
@@ -2452,47 +2368,15 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
         if (la_w) {
             if (ev_a) (void)hipStreamWaitEvent(main_stream, ev_a, 0);
             if (ev_b && next + la_w > a_end) (void)hipStreamWaitEvent(main_stream, ev_b, 0);
-            if (s.aux && panel_band_end) {
-                // Band split of the look-ahead update: the next panel's chain needs rows [next, next + la_w + band) of its columns;
-                // of those, rows beyond THIS panel's band got their multipliers on aux (one wait per look-ahead panel).  Everything below
-                // goes to aux, behind its share of P_j.
-                rc = prep_columns(s, j, w, next, next + la_w);  // interchange + U block row: top rows only
-                if (rc != RMHIP_OK) break;
-                hipEvent_t u_ready = new_event();
-                (void)hipEventRecord(u_ready, main_stream);
-                size_t be_next = next + la_w + (size_t)band_extra;
-                if (be_next > s.rows) be_next = s.rows;
-                const size_t r0 = j + w;
-                double* A12 = s.A + j + next * s.lda;
-                double* A21 = s.A + r0 + j * s.lda;
-                double* A22 = s.A + r0 + next * s.lda;
-                if (aux_done) (void)hipStreamWaitEvent(main_stream, aux_done, 0);
-                if (be_next > r0) rc = lu_dgemm(c, be_next - r0, la_w, w, -1.0, A21, s.lda, A12, s.lda, 1.0, A22, s.lda);
-                if (rc != RMHIP_OK) break;
-                if (be_next < s.rows) {
-                    (void)hipStreamWaitEvent(s.aux, u_ready, 0);
-                    if (ev_a) (void)hipStreamWaitEvent(s.aux, ev_a, 0);
-                    if (ev_b && next + la_w > a_end) (void)hipStreamWaitEvent(s.aux, ev_b, 0);
-                    {
-                        StreamScope scope(c, s.aux, c->gemm_lds_pad, c->trsm_base);
-                        rc = lu_dgemm(c, s.rows - be_next, la_w, w, -1.0, A21 + (be_next - r0), s.lda, A12, s.lda, 1.0, A22 + (be_next - r0), s.lda);
-                    }
-                    if (rc != RMHIP_OK) break;
-                    s.aux_tail = new_event();
-                    (void)hipEventRecord(s.aux_tail, s.aux);
-                }
-            } else {
-                rc = update_columns(s, j, w, next, next + la_w);
-                if (rc != RMHIP_OK) break;
-            }
+            rc = update_columns(s, j, w, next, next + la_w);
+            if (rc != RMHIP_OK) break;
         }
         if (split) {
             c->gemm_tile_counters = next_late ? late_counters : nullptr;  // persistent, XCD-avoiding kernels if the next panel sits on one XCD
             hipEvent_t ra = new_event(), rb = new_event();
             (void)hipStreamWaitEvent(prep, panel_done, 0);
-            if (aux_done) (void)hipStreamWaitEvent(side, aux_done, 0);  // the Schur update reads every row of L(P_j)
             {
-                StreamScope scope(c, prep, 0, prep_base);  // unpadded small blocks: they run beside the update stream's dgemm
+                StreamScope scope(c, prep, 0);  // unpadded small blocks: they run beside the update stream's dgemm
                 if (ev_a) (void)hipStreamWaitEvent(prep, ev_a, 0);
                 if (ev_b && (moved || csplit > a_end)) (void)hipStreamWaitEvent(prep, ev_b, 0);
                 rc = prep_columns(s, j, w, t0, csplit);
@@ -2501,7 +2385,7 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
                 if (rc == RMHIP_OK) rc = prep_columns(s, j, w, csplit, s.cols);
                 (void)hipEventRecord(rb, prep);
             }
-            StreamScope scope(c, side, early ? early_side_pad : side_pad);
+            StreamScope scope(c, side, kSidePad);
             (void)hipStreamWaitEvent(side, ra, 0);
             if (rc == RMHIP_OK) rc = gemm_columns(s, j, w, t0, csplit);
             ev_a = new_event();
@@ -2513,18 +2397,16 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
             a_end = csplit;
         } else {
             (void)hipStreamWaitEvent(side, panel_done, 0);
-            if (aux_done) (void)hipStreamWaitEvent(side, aux_done, 0);
-            StreamScope scope(c, side, early ? early_side_pad : side_pad);
+            StreamScope scope(c, side, kSidePad);
             // S_j overlaps panel j+1: persistent, XCD-avoiding dgemm if that panel sits on one XCD
-            c->gemm_tile_counters = (next_late || (late_xcd_on == 2 && late_counters)) ? late_counters : nullptr;
+            c->gemm_tile_counters = next_late ? late_counters : nullptr;
             // (Attribution, n = 16384 at 100.9 ms: dropping the update stream's work of this phase altogether - knob below, results
             // are garbage - gives 100.3: with the XCD partition it no longer disturbs the chain.  But the phase has no room to
             // spare either: repeating its dgemm into a scratch copy k more times, on this stream before or behind the event the main
             // stream waits for or on the third stream, costs 6 ms per repeat (12 ms of kernel time each); repeats only below 6144 /
             // 4096 remaining rows cost what the work takes at 55-75 TFLOP/s.  Each step's update just fits the time of the next
             // panel, so deferring first-half work into this phase buys (1/43 - 1/60 TFLOP/s) per flop at best.)
-            static const int late_skip = std::getenv("RMHIP_LU_LATE_SKIP") ? std::atoi(std::getenv("RMHIP_LU_LATE_SKIP")) : 0;
-            if (!(next_late && late_skip)) rc = update_columns(s, j, w, t0, s.cols);      // S_j
+            rc = update_columns(s, j, w, t0, s.cols);      // S_j
             ev_a = new_event();
             (void)hipEventRecord(ev_a, side);
             if (rc == RMHIP_OK && j > 0) rc = laswp(s, 0, j, j, j + w);  // finished left columns
@@ -2537,9 +2419,8 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
     }
     s.panel_pad_kb = -1;
     if (ev_b) (void)hipStreamWaitEvent(main_stream, ev_b, 0);
-    if (prep) (void)hipStreamSynchronize(prep);
+    (void)hipStreamSynchronize(prep);
     (void)hipStreamSynchronize(side);
-    if (s.aux) (void)hipStreamSynchronize(s.aux);
     (void)hipStreamSynchronize(main_stream);
     return rc;
 }
@@ -2560,57 +2441,13 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
 // A super-panel of ONE panel is the one-level scheme (far = the update stream above), which is what the plan ends with once the
 // panel chain is the critical path.  Same kernels, same per-element operation order inside a panel; the trailing updates sum in
 // super-panel-sized groups (results agree with the one-level driver to rounding, pivots are identical).
-// ---- round 6: the W-wide unit-lower solves of the two-level driver as products with the explicit inverse ----------------------------
-// At a super-panel boundary every column right of it needs U12 = L11^-1 A12 with L11 the W x W unit-lower block of the super-panel
-// (W = 1024 / 2048) before the deep rank-W update.  As a recursive solve that is 31 launches of 128-wide solves and few-tile products
-// at low fill: 17 of the far stream's 58 ms, 1.2 of the 2 ms the main stream spends at every boundary, and the mid stream's 3 ms
-// before every second inner panel (round 5's timeline).  Instead the mid stream builds M = L11^-1 row block by row block while the
-// super-panel's inner panels are being factored (row block p as soon as panel p's interchanges have reached the columns left of it:
-// M_pp = L_pp^-1 by the 256-wide solve on an identity, M_p,0:p = -M_pp (L_p,0:p M_0:p,0:p), two small products), and the boundary
-// computes T = M A12 as ONE deep product per column chunk (twice the flops of the substitution, all of them at the deep-product rate),
-// updates with T as the B operand and copies T into A12 afterwards.
-// Error: |T - U12| <= c W eps |M| |L11| |U12|-like, i.e. the condition of L11 enters where substitution is backward stable.  The
-// solve path already bounds every multiplier by tau = 8; here the largest |M_ij| of every super-panel is recorded as well (k_absmax_word)
-// and a value above RMHIP_LU_MINV_MAX (default 1e6) sends the factorisation to the caller's fall-back like a multiplier above tau.
-// RMHIP_LU_MINV=0 restores the recursive solves.
-__global__ void __launch_bounds__(256) k_set_identity(double* __restrict__ M, size_t ld, unsigned w) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (size_t)w * w) return;
-    const unsigned r = (unsigned)(idx % w), cidx = (unsigned)(idx / w);
-    M[r + (size_t)cidx * ld] = r == cidx ? 1.0 : 0.0;
-}
-__global__ void __launch_bounds__(256) k_absmax_word(const double* __restrict__ M, size_t ld, unsigned rows, unsigned cols, pk_u64* __restrict__ word) {
-    pk_u64 mx = 0;
-    const size_t total = (size_t)rows * cols;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const pk_u64 b = (pk_u64)__double_as_longlong(M[idx % rows + (idx / rows) * ld]) & 0x7fffffffffffffffull;  // |x| (NaN sorts above Inf)
-        mx = b > mx ? b : mx;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const pk_u64 o = __shfl_down(mx, off);
-        mx = o > mx ? o : mx;
-    }
-    if ((threadIdx.x & 63) == 0 && mx != 0) atomicMax(word, mx > 0x7ff0000000000000ull ? 0x7ff8000000000000ull : mx);
-}
-
+// (Tried, round 6: the W-wide unit-lower solves at the super-panel boundaries as products with the explicitly inverted L11 block, built
+// row block by row block on the mid stream while the inner panels are factored - twice the flops of the substitution, all at the
+// deep-product rate, with a guard on the inverse's largest entry: measured slower.  Also tried: the main stream's dgemm blocks,
+// k_rp_below_mfma and k_trsm_lower_mfma counting themselves into the yield table as k_rp_top does: neutral.  docs/EXPERIMENTS.md R6.)
 struct SuperPanel {
     size_t s0, s1, nb;
 };
-
-static std::vector<std::pair<size_t, size_t>> parse_super_seq(const char* v) {
-    std::vector<std::pair<size_t, size_t>> out;  // (W, nb)
-    while (v && *v) {
-        char* end = nullptr;
-        const size_t W = (size_t)std::strtoull(v, &end, 10);
-        size_t nb = W;
-        if (end && *end == ':') nb = (size_t)std::strtoull(end + 1, &end, 10);
-        if (W >= 64) out.emplace_back((W / 64) * 64, nb < 64 ? 64 : (nb / 64) * 64);
-        v = end;
-        while (v && (*v == ',' || *v == '/' || *v == ' ')) ++v;
-        if (!end) break;
-    }
-    return out;
-}
 
 static int getrf_super(LuState& s, size_t kmin) {
     Context* c = s.c;
@@ -2625,46 +2462,35 @@ static int getrf_super(LuState& s, size_t kmin) {
     // and seat-holder experiments of round 5.  With far at the default priority a fourth stream costs 2 ms, not 47 (docs/EXPERIMENTS.md R5).
     if (!c->lu_far_stream) RMHIP_HIP_CHECK(hipStreamCreateWithPriority(&c->lu_far_stream, hipStreamNonBlocking, (prio_low + prio_high) / 2));
     hipStream_t mid = c->lu_mid_stream, far = c->lu_far_stream;
-    std::shared_ptr<Allocation> yield_ctl;  // the yield word (outlives the guard below)
+    std::shared_ptr<Allocation> yield_ctl;  // the yield table (outlives the guard below)
     struct Restore {
         Context* c;
         LuState* s;
-        int trsm_base;
-        bool clear_yield = false;
         ~Restore() {
             s->yield_word = nullptr;
             c->gemm_chain_prio = false;
             if (c->lu_mid_stream) (void)hipStreamSynchronize(c->lu_mid_stream);
             if (c->lu_far_stream) (void)hipStreamSynchronize(c->lu_far_stream);
             c->gemm_yield_word = nullptr;
-            c->gemm_announce = nullptr;
-            c->gemm_announce_tab = nullptr;
-            c->lu_yield_trsm = false;
             s->panel_pad_kb = -1;
             c->in_lookahead = false;
-            c->trsm_base = trsm_base;
         }
-    } restore{c, &s, c->trsm_base};
-    if (const char* v = std::getenv("RMHIP_LU_LA_TRSM")) c->trsm_base = std::atoi(v) == 64 ? 64 : 128;
+    } restore{c, &s};
     c->in_lookahead = true;
-    static const int gemm_prio_on = std::getenv("RMHIP_LU_GEMM_PRIO") ? std::atoi(std::getenv("RMHIP_LU_GEMM_PRIO")) : 1;
-    c->gemm_chain_prio = gemm_prio_on != 0;
+    c->gemm_chain_prio = true;  // the main stream's dgemm launches raise their wave priority (GemmArgs::prio)
+    const LuKnobs knobs = lu_knobs();
+    const LuProcessKnobs& pknobs = lu_process_knobs();
     // ---- the plan: super-panels (W, nb) while more than super_rows rows remain, single panels afterwards
     // (defaults by order, interleaved runs of scripts/lu_super_ab.sh: n = 16384 69.7-69.9 ms with 256 / 1024 / 2048-column super-panels of
     // 256-column panels down to 4096 remaining rows against 71.6-72.7 with the plan below; 12288 41.0-41.5 against 40.9, 8192 22.1 against 20.8:
     // the shorter plan stays below 14336)
-    static const std::vector<std::pair<size_t, size_t>> seq_env = parse_super_seq(std::getenv("RMHIP_LU_SUPER_SEQ"));
     const bool large = kmin >= 14336;
     const std::vector<std::pair<size_t, size_t>> seq =
-        !seq_env.empty() ? seq_env
-                         : (large ? std::vector<std::pair<size_t, size_t>>{{256, 256}, {1024, 256}, {2048, 256}}
-                                  : std::vector<std::pair<size_t, size_t>>{{512, 512}, {1024, 512}, {2048, 512}});
-    static const std::pair<size_t, size_t> late = [] {
-        auto q = parse_super_seq(std::getenv("RMHIP_LU_SUPER_LATE"));
-        return q.empty() ? std::pair<size_t, size_t>{128, 128} : q[0];
-    }();
-    static const long super_rows_env = std::getenv("RMHIP_LU_SUPER_ROWS") ? std::atol(std::getenv("RMHIP_LU_SUPER_ROWS")) : -1;
-    const size_t super_rows = super_rows_env >= 0 ? (size_t)super_rows_env : (large ? 4096 : 6144);
+        !pknobs.super_seq.empty() ? pknobs.super_seq
+                                  : (large ? std::vector<std::pair<size_t, size_t>>{{256, 256}, {1024, 256}, {2048, 256}}
+                                           : std::vector<std::pair<size_t, size_t>>{{512, 512}, {1024, 512}, {2048, 512}});
+    const std::pair<size_t, size_t> late = pknobs.super_late;
+    const size_t super_rows = pknobs.super_rows >= 0 ? (size_t)pknobs.super_rows : (large ? 4096 : 6144);
     std::vector<SuperPanel> plan;
     for (size_t s0 = 0, i = 0; s0 < kmin;) {
         const size_t rem = kmin - s0;
@@ -2678,56 +2504,16 @@ static int getrf_super(LuState& s, size_t kmin) {
         plan.push_back({s0, s1, e.second < e.first ? e.second : e.first});
         s0 = s1;
     }
-    // LDS asked for by the update streams' dgemm blocks (see getrf_blocked: 84 KiB = one eight-wave block per CU with room beside it)
-    const size_t pad_default = 84 * 1024 - 73728;
-    static const long mid_pad_env = std::getenv("RMHIP_LU_MID_PAD") ? std::atol(std::getenv("RMHIP_LU_MID_PAD")) : -1;
-    static const long far_pad_env = std::getenv("RMHIP_LU_FAR_PAD") ? std::atol(std::getenv("RMHIP_LU_FAR_PAD")) : -1;
-    static const long super_panel_pad = std::getenv("RMHIP_LU_SUPER_PANEL_PAD_KB") ? std::atol(std::getenv("RMHIP_LU_SUPER_PANEL_PAD_KB")) : 0;
-    const size_t mid_pad = mid_pad_env >= 0 ? (size_t)mid_pad_env : pad_default;
-    const size_t far_pad = far_pad_env >= 0 ? (size_t)far_pad_env : pad_default;
-    // cooperative yield of the update blocks on k_rp_top's CU (RMHIP_LU_YIELD=0 disables)
-    static const int yield_on = std::getenv("RMHIP_LU_YIELD") ? std::atoi(std::getenv("RMHIP_LU_YIELD")) : 1;
-    static const long top_pad_env = std::getenv("RMHIP_LU_TOP_PAD_KB") ? std::atol(std::getenv("RMHIP_LU_TOP_PAD_KB")) : (yield_on ? 0 : -1);
-    if (yield_on) {
-        RMHIP_TRY(c->alloc_device(kYieldSlots / 2, &yield_ctl));
-        RMHIP_HIP_CHECK(hipMemsetAsync(yield_ctl->ptr, 0, sizeof(unsigned) * kYieldSlots, main_stream));
-        s.yield_word = (unsigned*)yield_ctl->ptr;
-        c->gemm_yield_word = s.yield_word;
-        restore.clear_yield = true;
-        // round 6: other chain kernels count themselves in as well (RMHIP_LU_YIELD_ALL bit mask: 1 the main stream's dgemm blocks,
-        // 2 k_rp_below_mfma, 4 k_trsm_lower_mfma; 0 = k_rp_top alone as in round 5)
-        static const int yield_all = std::getenv("RMHIP_LU_YIELD_ALL") ? std::atoi(std::getenv("RMHIP_LU_YIELD_ALL")) : 0;
-        s.yield_all = yield_all;
-        c->gemm_announce = (yield_all & 1) ? s.yield_word : nullptr;
-        c->gemm_announce_tab = s.yield_word;
-        c->lu_yield_trsm = (yield_all & 4) != 0;
-    }
-    // ---- explicit inverses of the super-panels' L11 blocks (see the note above k_set_identity)
-    const int minv_env = std::getenv("RMHIP_LU_MINV") ? std::atoi(std::getenv("RMHIP_LU_MINV")) : 0;  // (read per call: the tests run both forms; default off, see docs/EXPERIMENTS.md R6 1)
-    static const int minv_who = std::getenv("RMHIP_LU_MINV_WHO") ? std::atoi(std::getenv("RMHIP_LU_MINV_WHO")) : 7;   // dev: 1 main, 2 mid, 4 far use the inverse
-    static const int minv_ext_far = std::getenv("RMHIP_LU_MINV_EXT") ? std::atoi(std::getenv("RMHIP_LU_MINV_EXT")) : 0;  // dev: the inverse is built on the far stream
-    static const size_t far_chunk = std::getenv("RMHIP_LU_MINV_CHUNK") ? (size_t)std::atol(std::getenv("RMHIP_LU_MINV_CHUNK")) / 128 * 128 : 4096;
-    size_t Wmax = 0, nbmax = 0;
-    for (const SuperPanel& sp : plan)
-        if (sp.s1 - sp.s0 > sp.nb) {
-            Wmax = sp.s1 - sp.s0 > Wmax ? sp.s1 - sp.s0 : Wmax;
-            nbmax = sp.nb > nbmax ? sp.nb : nbmax;
-        }
-    std::shared_ptr<Allocation> minv_mem[2], mtmp_mem, t_main_mem, t_mid_mem, t_far_mem, split_ws[3];  // (split-K partials: one per stream)
-    const size_t kSplitWsElems = (size_t)8 << 20;  // at most 64 output tiles x 8 slices
-    const bool minv_on = minv_env != 0 && Wmax > 0 && s.minv_max != nullptr && far_chunk >= 128;
-    if (minv_on) {
-        const size_t far_cols = far_chunk > Wmax ? far_chunk : Wmax;
-        RMHIP_TRY(c->alloc_device(Wmax * Wmax, &minv_mem[0]));
-        RMHIP_TRY(c->alloc_device(Wmax * Wmax, &minv_mem[1]));
-        RMHIP_TRY(c->alloc_device(nbmax * Wmax, &mtmp_mem));
-        RMHIP_TRY(c->alloc_device(Wmax * 512, &t_main_mem));
-        RMHIP_TRY(c->alloc_device(Wmax * Wmax, &t_mid_mem));
-        RMHIP_TRY(c->alloc_device(Wmax * far_cols, &t_far_mem));
-        for (auto& w : split_ws) RMHIP_TRY(c->alloc_device(kSplitWsElems, &w));
-    }
-    hipEvent_t ev_minv = nullptr;                      // the inverse of the super-panel in flight is complete (mid stream)
-    hipEvent_t ev_minv_read[2] = {nullptr, nullptr};   // the far stream's last product with inverse buffer 0 / 1
+    // the mid and far streams' dgemm blocks ask for kSidePad of LDS like the update stream of getrf_blocked: one eight-wave block per CU
+    // with room beside it
+    // cooperative yield of the update blocks on k_rp_top's CU: k_rp_top names its CU in the table, the update streams' eight-wave dgemm
+    // block on that CU sleeps until it leaves (k_rp_top 120-250 us instead of 60-70 beside a deep update)
+    RMHIP_TRY(c->alloc_device(kYieldSlots / 2, &yield_ctl));
+    RMHIP_HIP_CHECK(hipMemsetAsync(yield_ctl->ptr, 0, sizeof(unsigned) * kYieldSlots, main_stream));
+    s.yield_word = (unsigned*)yield_ctl->ptr;
+    c->gemm_yield_word = s.yield_word;
+    // with the yield k_rp_top asks for no LDS pad in any phase: it may start beside an update block, which then pauses
+    s.panel_pad_kb = 0;
     auto new_event = [&]() { return lu_new_event(s); };
     auto record = [&](hipStream_t st) {
         hipEvent_t e = new_event();
@@ -2738,7 +2524,6 @@ static int getrf_super(LuState& s, size_t kmin) {
         hipEvent_t e0 = record(main_stream);  // the update streams start after whatever main already has queued (the copy of A)
         (void)hipStreamWaitEvent(mid, e0, 0);
         (void)hipStreamWaitEvent(far, e0, 0);
-        if (s.aux) (void)hipStreamWaitEvent(s.aux, e0, 0);
     }
     hipEvent_t ev_mid = nullptr;       // everything the mid stream was given so far
     hipEvent_t ev_far_next = nullptr;  // far finished the columns of the super-panel after the one in flight
@@ -2747,13 +2532,10 @@ static int getrf_super(LuState& s, size_t kmin) {
     // incremental block rows of U for the next super-panel's columns (iprep_columns): 12288 40.4-40.8 -> 39.3-39.9 ms with the 512-column
     // plan; with the large-order plan the far stream delivers those columns too late - the mid stream stalls behind the wait and
     // 16384 goes 69.4 -> 73 ms (docs/EXPERIMENTS.md R5 22)
-    static const int iprep_env = std::getenv("RMHIP_LU_IPREP") ? std::atoi(std::getenv("RMHIP_LU_IPREP")) : -1;
-    const bool iprep = iprep_env >= 0 ? iprep_env != 0 : !large;
-    static const int iprep_split = std::getenv("RMHIP_LU_IPREP_SPLIT") ? std::atoi(std::getenv("RMHIP_LU_IPREP_SPLIT")) : 1;
+    const bool iprep = pknobs.iprep >= 0 ? pknobs.iprep != 0 : !large;
     int rc = RMHIP_OK;
-    const bool verbose = std::getenv("RMHIP_LU_VERBOSE") != nullptr;
     // developer aid (RMHIP_LU_TIMELINE=1): timed events on the main stream around every super-panel boundary, printed after the factorisation
-    const bool tl_on = std::getenv("RMHIP_LU_TIMELINE") != nullptr;
+    const bool tl_on = knobs.timeline;
     std::vector<std::pair<std::string, hipEvent_t>> tl;
     auto tl_mark = [&](const std::string& what) {
         if (!tl_on) return;
@@ -2765,72 +2547,12 @@ static int getrf_super(LuState& s, size_t kmin) {
     tl_mark("start");
     const auto host_t0 = std::chrono::steady_clock::now();
     auto host_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count(); };
-    // columns [c0, c1) right of the complete super-panel [S0, S1) (M = its inverted L11, leading dimension W): its interchanges (unless the
-    // caller applied them), T = M A12, the rank-W update with T as the B operand, then T into A12 (U's block row) - on the stream in scope
-    auto minv_update_sp = [&](size_t S0, size_t S1, size_t W, const double* M, double* T, size_t c0, size_t c1, bool swaps) -> int {
-        if (c1 <= c0) return RMHIP_OK;
-        struct WsScope {
-            Context* c;
-            ~WsScope() {
-                c->gemm_split_ws = nullptr;
-                c->gemm_split_ws_elems = 0;
-            }
-        } ws_scope{c};
-        c->gemm_split_ws = split_ws[c->stream == main_stream ? 0 : (c->stream == mid ? 1 : 2)]->ptr;
-        c->gemm_split_ws_elems = kSplitWsElems;
-        if (swaps) RMHIP_TRY(laswp(s, c0, c1, S0, S1));
-        const size_t nc = c1 - c0;
-        double* A12 = s.A + S0 + c0 * s.lda;
-        const size_t keep = c->gemm_split_min_k;
-        c->gemm_split_min_k = 1024;  // few output tiles and k = W: split the inner dimension (one block alone walks 16 k per us)
-        int r;
-        const size_t h = (W / 2 / 128) * 128;
-        if (nc >= 1024 && h >= 256) {  // M is lower triangular: the upper half of T only needs the leading h x h block
-            r = lu_dgemm(c, h, nc, h, 1.0, M, W, A12, s.lda, 0.0, T, W);
-            if (r == RMHIP_OK) r = lu_dgemm(c, W - h, nc, W, 1.0, M + h, W, A12, s.lda, 0.0, T + h, W);
-        } else {
-            r = lu_dgemm(c, W, nc, W, 1.0, M, W, A12, s.lda, 0.0, T, W);
-        }
-        c->gemm_split_min_k = keep;
-        RMHIP_TRY(r);
-        if (S1 < s.rows) RMHIP_TRY(lu_dgemm(c, s.rows - S1, nc, W, -1.0, s.A + S1 + S0 * s.lda, s.lda, T, W, 1.0, s.A + S1 + c0 * s.lda, s.lda));
-        RMHIP_HIP_CHECK(hipMemcpy2DAsync(A12, s.lda * sizeof(double), T, W * sizeof(double), W * sizeof(double), nc, hipMemcpyDeviceToDevice, c->stream));
-        return RMHIP_OK;
-    };
-    // The mid stream's share of a boundary beyond the next super-panel's first two inner panels is issued LATER - behind that
-    // super-panel's first inner update of its second panel's columns (see the boundary code): the main stream's look-ahead after the
-    // second inner panel then waits for two small launches instead of the deep update of 1280 columns (round 5: 1-4 ms per super-panel)
-    std::function<int()> mid_deferred;
     for (size_t J = 0; J < plan.size() && rc == RMHIP_OK; ++J) {
         const size_t S0 = plan[J].s0, S1 = plan[J].s1, nbJ = plan[J].nb, W = S1 - S0;
-        if (verbose && (W > nbJ || J + 1 == plan.size())) std::fprintf(stderr, "[lu] host %.2f ms: super-panel %zu [%zu, %zu) nb %zu queued so far %llu launches\n", host_ms(), J, S0, S1, nbJ, (unsigned long long)c->tel.kernel_launches);
+        if (knobs.verbose && (W > nbJ || J + 1 == plan.size())) std::fprintf(stderr, "[lu] host %.2f ms: super-panel %zu [%zu, %zu) nb %zu queued so far %llu launches\n", host_ms(), J, S0, S1, nbJ, (unsigned long long)c->tel.kernel_launches);
         const size_t S1n = J + 1 < plan.size() ? plan[J + 1].s1 : S1;
         const size_t S1nn = J + 2 < plan.size() ? plan[J + 2].s1 : S1n;
         const bool multi = W > nbJ;
-        const bool use_minv = minv_on && multi && !iprep && W <= Wmax;
-        double* const minv = use_minv ? minv_mem[J & 1]->ptr : nullptr;
-        const size_t ldm = W;
-        // row block [j - S0, j - S0 + w) of M = L11^-1, on the stream in scope (mid), once panel [j, j + w)'s interchanges are in columns [S0, j)
-        auto minv_extend = [&](size_t j, size_t w) -> int {
-            const size_t off = j - S0;
-            double* Mpp = minv + off + off * ldm;
-            if (off == 0) {
-                if (ev_minv_read[J & 1]) (void)hipStreamWaitEvent(c->stream, ev_minv_read[J & 1], 0);  // far may still read this buffer (boundary J - 2)
-                RMHIP_HIP_CHECK(hipMemsetAsync(minv, 0, sizeof(double) * W * W, c->stream));
-            }
-            hipLaunchKernelGGL(k_set_identity, dim3((unsigned)((w * w + 255) / 256)), dim3(256), 0, c->stream, Mpp, ldm, (unsigned)w);
-            RMHIP_TRY(launch_check(c));
-            RMHIP_TRY(trsm_lower_rec(c, s.A + j + j * s.lda, s.lda, w, Mpp, ldm, w));
-            if (off) {
-                RMHIP_TRY(lu_dgemm(c, w, off, off, 1.0, s.A + j + S0 * s.lda, s.lda, minv, ldm, 0.0, mtmp_mem->ptr, w));
-                RMHIP_TRY(lu_dgemm(c, w, off, w, -1.0, Mpp, ldm, mtmp_mem->ptr, w, 0.0, minv + off, ldm));
-            }
-            return RMHIP_OK;
-        };
-        auto minv_update = [&, S0, S1, W, minv](double* T, size_t c0, size_t c1, bool swaps) -> int {
-            return minv_update_sp(S0, S1, W, minv, T, c0, c1, swaps);
-        };
-        s.panel_pad_kb = top_pad_env >= 0 ? top_pad_env : ((kmin - S0 > super_rows) ? super_panel_pad : -1);
         for (size_t j = S0; j < S1 && rc == RMHIP_OK;) {
             const size_t w = (S1 - j) < nbJ ? (S1 - j) : nbJ;
             rc = getrf_rec(s, j, w);  // P_j on main
@@ -2851,27 +2573,10 @@ static int getrf_super(LuState& s, size_t kmin) {
                 if (rc != RMHIP_OK) break;
                 (void)hipStreamWaitEvent(mid, panel_done, 0);
                 {
-                    StreamScope scope(c, mid, mid_pad);
-                    if (mid_deferred) {
-                        // first inner panel after a boundary: the next panel's columns first (what the main stream's next look-ahead
-                        // needs), then the boundary's remaining columns, then this panel's update of those
-                        const size_t ts = t0 + nbJ < S1 ? t0 + nbJ : S1;
-                        rc = update_columns(s, j, w, t0, ts);
-                        ev_mid = record(mid);
-                        if (rc == RMHIP_OK) rc = mid_deferred();
-                        mid_deferred = nullptr;
-                        if (rc == RMHIP_OK) rc = update_columns(s, j, w, ts, S1);
-                    } else {
-                        rc = update_columns(s, j, w, t0, S1);
-                        if (rc == RMHIP_OK && j > S0) rc = laswp(s, S0, j, j, j + w);  // the super-panel's own left columns
-                        ev_mid = record(mid);
-                    }
-                    if (rc == RMHIP_OK && use_minv && !minv_ext_far) rc = minv_extend(j, w);  // (behind the event: the main stream does not wait for it)
-                }
-                if (rc == RMHIP_OK && use_minv && minv_ext_far) {
-                    (void)hipStreamWaitEvent(far, ev_mid, 0);  // (this panel's interchanges are in the columns left of it)
-                    StreamScope scope(c, far, far_pad);
-                    rc = minv_extend(j, w);
+                    StreamScope scope(c, mid, kSidePad);
+                    rc = update_columns(s, j, w, t0, S1);
+                    if (rc == RMHIP_OK && j > S0) rc = laswp(s, S0, j, j, j + w);  // the super-panel's own left columns
+                    ev_mid = record(mid);
                 }
                 if (rc != RMHIP_OK) break;
                 if (iprep && S1 < S1n) {
@@ -2880,7 +2585,7 @@ static int getrf_super(LuState& s, size_t kmin) {
                     // (on a stream of their own instead: 76-79 ms at n = 16384)
                     if (ev_far_next) (void)hipStreamWaitEvent(mid, ev_far_next, 0);
                     {
-                        StreamScope scope(c, mid, mid_pad);
+                        StreamScope scope(c, mid, kSidePad);
                         rc = iprep_columns(s, S0, j, w, S1, S1n);
                     }
                     if (rc != RMHIP_OK) break;
@@ -2890,40 +2595,15 @@ static int getrf_super(LuState& s, size_t kmin) {
                 // the super-panel is complete: its last panel's interchanges reach its left columns first - everything below reads L21
                 // of the whole super-panel
                 hipEvent_t ev_left = panel_done;
-                if (mid_deferred) {  // (a super-panel of a single panel: nobody consumed the previous boundary's second piece)
-                    StreamScope scope(c, mid, mid_pad);
-                    rc = mid_deferred();
-                    mid_deferred = nullptr;
-                    if (rc != RMHIP_OK) break;
-                    ev_mid = record(mid);
-                }
                 if (multi && j > S0) {
                     (void)hipStreamWaitEvent(mid, panel_done, 0);
                     {
-                        StreamScope scope(c, mid, mid_pad);
+                        StreamScope scope(c, mid, kSidePad);
                         rc = laswp(s, S0, j, j, j + w);
                         if (rc == RMHIP_OK) {
                             ev_left = record(mid);
                             ev_mid = ev_left;
                         }
-                        if (rc == RMHIP_OK && use_minv && !minv_ext_far) {  // the last row block of the inverse, then its largest entry for the guard
-                            rc = minv_extend(j, w);
-                            if (rc == RMHIP_OK) {
-                                hipLaunchKernelGGL(k_absmax_word, dim3(256), dim3(256), 0, mid, (const double*)minv, ldm, (unsigned)W, (unsigned)W, (pk_u64*)s.minv_max);
-                                rc = launch_check(c);
-                            }
-                            ev_minv = record(mid);
-                        }
-                    }
-                    if (rc == RMHIP_OK && use_minv && minv_ext_far) {
-                        (void)hipStreamWaitEvent(far, ev_left, 0);
-                        StreamScope scope(c, far, far_pad);
-                        rc = minv_extend(j, w);
-                        if (rc == RMHIP_OK) {
-                            hipLaunchKernelGGL(k_absmax_word, dim3(256), dim3(256), 0, far, (const double*)minv, ldm, (unsigned)W, (unsigned)W, (pk_u64*)s.minv_max);
-                            rc = launch_check(c);
-                        }
-                        ev_minv = record(far);
                     }
                     if (rc != RMHIP_OK) break;
                 }
@@ -2933,10 +2613,7 @@ static int getrf_super(LuState& s, size_t kmin) {
                     tl_mark("J" + std::to_string(J) + " mid ready");
                     if (ev_far_next) (void)hipStreamWaitEvent(main_stream, ev_far_next, 0);
                     tl_mark("J" + std::to_string(J) + " far ready");
-                    if (use_minv && (minv_who & 1)) {
-                        (void)hipStreamWaitEvent(main_stream, ev_minv, 0);
-                        rc = minv_update(t_main_mem->ptr, next, t0, true);
-                    } else if (iprep && multi) {
+                    if (iprep && multi) {
                         // the columns hold every block row of U but the last panel's: that one, then the deep update alone
                         if (ev_iprep) (void)hipStreamWaitEvent(main_stream, ev_iprep, 0);
                         rc = iprep_columns(s, S0, j, w, next, t0);
@@ -2951,27 +2628,11 @@ static int getrf_super(LuState& s, size_t kmin) {
                     (void)hipStreamWaitEvent(mid, panel_done, 0);
                     if (ev_far_next) (void)hipStreamWaitEvent(mid, ev_far_next, 0);
                     {
-                        StreamScope scope(c, mid, mid_pad);
-                        if (use_minv && (minv_who & 2)) {
-                            (void)hipStreamWaitEvent(mid, ev_minv, 0);
-                            // The second inner panel's columns first: the main stream's next look-ahead
-                            // update waits for these only
-                            static const int defer_on = std::getenv("RMHIP_LU_MINV_DEFER") ? std::atoi(std::getenv("RMHIP_LU_MINV_DEFER")) : 1;
-                            const size_t nbn = plan[J + 1].nb, t1 = t0 + 2 * nbn < S1n ? t0 + 2 * nbn : S1n;
-                            rc = minv_update(t_mid_mem->ptr, t0, t1, true);  // the second and third inner panels' columns now
-                            if (rc == RMHIP_OK) ev_mid = record(mid);
-                            if (rc == RMHIP_OK && t1 < S1n) {
-                                double* const Tm = t_mid_mem->ptr;
-                                const double* const Mc = minv;
-                                const size_t S0c = S0, S1c = S1, Wc = W, c1c = S1n;
-                                auto rest = [&minv_update_sp, S0c, S1c, Wc, Mc, Tm, t1, c1c]() { return minv_update_sp(S0c, S1c, Wc, Mc, Tm, t1, c1c, true); };
-                                if (defer_on && plan[J + 1].s1 - plan[J + 1].s0 > plan[J + 1].nb) mid_deferred = rest;  // the rest behind the next panel's first update
-                                else rc = rest();
-                            }
-                        } else if (iprep && multi) {
+                        StreamScope scope(c, mid, kSidePad);
+                        if (iprep && multi) {
                             rc = iprep_columns(s, S0, j, w, t0, S1n);
                             // the second panel's columns first: the main stream's next look-ahead update waits for these only
-                            const size_t nbn = plan[J + 1].nb, t1 = (iprep_split && t0 + nbn < S1n) ? t0 + nbn : S1n;
+                            const size_t nbn = plan[J + 1].nb, t1 = (pknobs.iprep_split && t0 + nbn < S1n) ? t0 + nbn : S1n;
                             if (rc == RMHIP_OK) rc = gemm_columns(s, S0, W, t0, t1);
                             if (rc == RMHIP_OK && t1 < S1n) {
                                 ev_mid = record(mid);
@@ -2995,32 +2656,18 @@ static int getrf_super(LuState& s, size_t kmin) {
                 // factors - 84.5 / 75.4 / 73.3 ms at budgets of 1 / 2 / 3 chain times against 73.4 eager.  docs/EXPERIMENTS.md.)
                 (void)hipStreamWaitEvent(far, ev_left, 0);
                 {
-                    StreamScope scope(c, far, far_pad);
+                    StreamScope scope(c, far, kSidePad);
                     ev_far_next = nullptr;
                     if (S1n < s.cols) {
                         const size_t cn = S1nn < s.cols ? S1nn : s.cols;
                         // (tried: interchange + solve + update of the next super-panel's columns first, then the rest's - a second
                         // 31-launch solve per boundary on this stream: 69.4 -> 73.8 ms; the far stream is the bottleneck of the first phase)
-                        if (use_minv && (minv_who & 4)) {
-                            // one interchange pass, then per column chunk T = M A12, the deep update, T -> A12; the next super-panel's
-                            // columns are the first chunk (the event no longer waits for the solve of ALL columns)
-                            (void)hipStreamWaitEvent(far, ev_minv, 0);
-                            rc = laswp(s, S1n, s.cols, S0, S1);
-                            if (rc == RMHIP_OK && cn > S1n) {
-                                rc = minv_update(t_far_mem->ptr, S1n, cn, false);
-                                ev_far_next = record(far);
-                            }
-                            for (size_t q0 = cn; q0 < s.cols && rc == RMHIP_OK; q0 += far_chunk)
-                                rc = minv_update(t_far_mem->ptr, q0, q0 + far_chunk < s.cols ? q0 + far_chunk : s.cols, false);
-                            ev_minv_read[J & 1] = record(far);
-                        } else {
                         rc = prep_columns(s, S0, W, S1n, s.cols);
                         if (rc == RMHIP_OK && cn > S1n) {
                             rc = gemm_columns(s, S0, W, S1n, cn);
                             ev_far_next = record(far);
                         }
                         if (rc == RMHIP_OK) rc = gemm_columns(s, S0, W, cn, s.cols);
-                        }
                     }
                     if (rc == RMHIP_OK && S0 > 0) rc = laswp(s, 0, S0, S0, S1);  // columns left of the super-panel: all of its interchanges at once
                 }
@@ -3042,7 +2689,7 @@ static int getrf_super(LuState& s, size_t kmin) {
         }
         for (auto& kv : tl) (void)hipEventDestroy(kv.second);
     }
-    if (verbose) std::fprintf(stderr, "[lu] host %.2f ms: everything queued (%llu launches)\n", host_ms(), (unsigned long long)c->tel.kernel_launches);
+    if (knobs.verbose) std::fprintf(stderr, "[lu] host %.2f ms: everything queued (%llu launches)\n", host_ms(), (unsigned long long)c->tel.kernel_launches);
     (void)hipStreamSynchronize(mid);
     (void)hipStreamSynchronize(far);
     (void)hipStreamSynchronize(main_stream);
@@ -3076,13 +2723,7 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
     const size_t kmin = rows < cols ? rows : cols;
     if (rows > 0x7fffffffULL || cols > 0x7fffffffULL) return fail(RMHIP_ERR_UNSUPPORTED, "lu: dimension exceeds 2^31");
     c->lu_used_one_xcd = false;
-    {
-        static std::once_flag prio_once;  // (one device per process: rmhip_init binds the context to its device)
-        std::call_once(prio_once, [] {
-            const int p = std::getenv("RMHIP_LU_CHAIN_PRIO") ? std::atoi(std::getenv("RMHIP_LU_CHAIN_PRIO")) : 1;
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(d_chain_prio), &p, sizeof(int));
-        });
-    }
+    const LuKnobs knobs = lu_knobs();
     // one device block: ipiv[rows] | info | pos_of | row_at | prow | panel lists | cand_abs[2*MAXB] | cand_pos | cand_row
     const size_t n_int = rows + 4;
     const size_t isz = (rows * sizeof(int) + 15) & ~(size_t)15;
@@ -3117,26 +2758,21 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
     {
         // persistent panels need all their blocks co-resident (18.5 KiB of LDS and 270 VGPRs per 4-wave block: at most one
         // per CU beside a dgemm block, so up to num_cus blocks)
-        const char* pm = std::getenv("RMHIP_LU_PANEL");  // "columns" selects the one-launch-per-column kernels
-        if ((pm && pm[0] == 'c') || c->lu_conservative) s.persistent = false;
-        const char* dbgenv = std::getenv("RMHIP_LU_PANEL_DEBUG");
-        if (dbgenv && dbgenv[0] == '1') s.xdbg = (unsigned long long*)(blk + off_xctl + 64);
-        // solve path: RMHIP_LU_FAST=0 keeps the grid-wide pivot rule everywhere; RMHIP_LU_TAU sets the multiplier bound (read per call: tests)
-        const char* fe = std::getenv("RMHIP_LU_FAST");
-        s.fast = mode == 1 && !(fe && fe[0] == '0') && s.persistent;
+        if (knobs.panel_columns || c->lu_conservative) s.persistent = false;  // RMHIP_LU_PANEL=columns: the one-launch-per-column kernels
+        if (knobs.panel_debug) s.xdbg = (unsigned long long*)(blk + off_xctl + 64);
+        // solve path: RMHIP_LU_FAST=0 keeps the grid-wide pivot rule everywhere; RMHIP_LU_TAU sets the multiplier bound
+        s.fast = mode == 1 && knobs.fast && s.persistent;
         c->lu_last_fast = s.fast;  // the caller counts solve-path factorisations on what actually ran (rmhip_lu_stats)
-        if (const char* tv = std::getenv("RMHIP_LU_TAU")) s.tau = std::atof(tv);
+        s.tau = knobs.tau;
         c->lu_tau = s.tau;
         s.ucomp = (double*)(blk + off_ucomp);
         s.growth = (unsigned long long*)(blk + off_xctl + 32);
-        s.minv_max = (unsigned long long*)(blk + off_xctl + 40);
         if (deferred_guard) s.screened = true;  // no early read of the first panel's multipliers: the caller's guard sees them at the end
         // a driver that runs updates on a stream of its own beside this factorisation (csrc/sharded.cpp) lends its yield table: k_rp_top
         // counts itself in and that stream's eight-wave blocks on its CU pause (the two-level driver below installs its own)
         if (c->ext_yield_tab) s.yield_word = c->ext_yield_tab;
         // matrix-core triangular solves with k_rp_top's inverted diagonal blocks: every base panel must be 64 columns wide
-        static const int trsm_mfma = std::getenv("RMHIP_LU_TRSM_MFMA") ? std::atoi(std::getenv("RMHIP_LU_TRSM_MFMA")) : 1;
-        if (s.fast && trsm_mfma && !s.xdbg) s.linv = (double*)(blk + off_linv);
+        if (s.fast && lu_process_knobs().trsm_mfma && !s.xdbg) s.linv = (double*)(blk + off_linv);
     }
     std::vector<unsigned char> linv_ok(rows / 16 + 8, 0);
     struct LinvScope {  // the solves find the inverses through the context while this factorisation runs
@@ -3158,8 +2794,7 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
     // x = A\b): n = 6144: 38.7 without look-ahead, 33.6 with nb 128, 34.9 with 256, 36.8 with 512; 8192: 51.2 (nb 512)
     // / 48.4 (256) / 47.2 (128); 10240: 67.3 / 63.4 / 62.2; 12288: 84.7 / 80.6 / 81.2; 16384: 130.8 / 130.7 / -;
     // 5120: 31.6 without, 27.9 with; 4096: 22.2 without, 22.6-24 with.
-    size_t nb = kmin < 12288 ? 128 : 256;
-    if (const char* v = std::getenv("RMHIP_LU_NB")) nb = (size_t)std::atoll(v);
+    size_t nb = knobs.nb >= 0 ? (size_t)knobs.nb : (kmin < 12288 ? 128 : 256);
     nb = nb < 64 ? 64 : (nb / 64) * 64;
     // Look-ahead (second stream): default from kmin = 5120; RMHIP_LU_LOOKAHEAD=1 forces it for every kmin > nb, =0
     // disables it.  It needs the persistent panels: with one launch per column the panel kernels wait behind the
@@ -3167,20 +2802,17 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
     // Solve path (one-workgroup panels: nothing has to be co-resident, and the chain is all there is at these sizes): from 1152 -
     // n = 1280 3.30 -> 2.52 ms, 1536 3.63 -> 2.95, 2048 4.30 -> 3.91, 3072 8.06 -> 5.98, 4096 9.92 -> 8.17 (5120: 16.9 without,
     // 10.6 with; 1024: 2.03 / 2.00).
-    const char* la = std::getenv("RMHIP_LU_LOOKAHEAD");
     bool blocked = kmin >= (s.fast ? 1152u : 5120u) && kmin > nb;
-    if (la) blocked = kmin > nb && la[0] == '1';
+    if (knobs.lookahead >= 0) blocked = kmin > nb && knobs.lookahead == 1;
     if (!s.persistent) blocked = false;
     // Under look-ahead the panels keep 256-row blocks (132 KiB of LDS: a whole CU).  The update stream's dgemm runs one
     // block per CU (84 KiB) at low priority, so a CU is empty whenever its dgemm block retires and the waiting panel
     // block (main stream, higher priority) takes it: all blocks are resident after about one dgemm-block time
     // (~55 us) and the bounded spins absorb that.  128-row blocks (66 KiB) fit BESIDE a dgemm block and start at
-    // once, but twice as many blocks make every exchange slower: measured 145.8 ms against 129.0 ms at n = 16384
-    // (RMHIP_LU_PANEL_ROWS=128 selects them).
-    // two-level driver (super-panels) on the solve path from kmin = 8192 (RMHIP_LU_SUPER=0: the one-level driver; RMHIP_LU_SUPER_MIN)
-    static const int super_on = std::getenv("RMHIP_LU_SUPER") ? std::atoi(std::getenv("RMHIP_LU_SUPER")) : 1;
-    static const size_t super_min = std::getenv("RMHIP_LU_SUPER_MIN") ? (size_t)std::atoll(std::getenv("RMHIP_LU_SUPER_MIN")) : 8192;
-    const bool super = blocked && s.fast && super_on && kmin >= super_min;
+    // once, but twice as many blocks make every exchange slower: measured 145.8 ms against 129.0 ms at n = 16384.
+    // two-level driver (super-panels) on the solve path from kmin = 8192 (RMHIP_LU_SUPER=0: the one-level driver)
+    constexpr size_t kSuperMin = 8192;
+    const bool super = blocked && s.fast && lu_process_knobs().super && kmin >= kSuperMin;
     int rc = super ? getrf_super(s, kmin) : (blocked ? getrf_blocked(s, kmin, nb) : getrf_rec(s, 0, kmin));
     if (rc == RMHIP_OK && cols > rows && !blocked) {  // wide: finish U's right block (the blocked driver covers it)
         rc = laswp(s, rows, cols, 0, rows);
@@ -3202,11 +2834,10 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
     std::vector<int> h_ipiv(rows + 1, 0);
     if (rc == RMHIP_OK) {
         int h_xerr = 0;
-        unsigned long long h_growth = 0, h_minv = 0;
+        unsigned long long h_growth = 0;
         e = hipMemcpyAsync(h_ipiv.data(), ipiv, sizeof(int) * (rows + 1), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&h_xerr, s.xerr, sizeof(int), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess && s.fast) e = hipMemcpyAsync(&h_growth, s.growth, sizeof(h_growth), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && s.fast) e = hipMemcpyAsync(&h_minv, s.minv_max, sizeof(h_minv), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(RMHIP_ERR_HIP, "lu: reading pivots: %s", hipGetErrorString(e));
         if (e == hipSuccess && s.fast) {
@@ -3214,23 +2845,14 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
             std::memcpy(&gmax, &h_growth, sizeof(gmax));
             c->lu_last_growth = gmax;
             // a multiplier beyond tau, a NaN, or a pivot at the singular cut-off inside a top block (a larger entry may lie below it)
-            double minv_abs;
-            std::memcpy(&minv_abs, &h_minv, sizeof(minv_abs));
-            c->lu_last_minv = minv_abs;
-            static const double minv_limit = std::getenv("RMHIP_LU_MINV_MAX") ? std::atof(std::getenv("RMHIP_LU_MINV_MAX")) : 1.0e6;
-            if (!(minv_abs <= minv_limit)) {  // an ill-conditioned L11: the products with its inverse are not to be trusted (also NaN)
-                if (std::getenv("RMHIP_LU_VERBOSE"))
-                    std::fprintf(stderr, "[lu] solve path: largest entry of an inverted L11 block %.3g (limit %.3g): refactoring with the grid-wide rule\n", minv_abs, minv_limit);
-                return RMHIP_LU_GROWTH;
-            }
-            if (!(gmax <= s.tau) || h_ipiv[rows] > 0 || std::getenv("RMHIP_LU_TEST_GROWTH")) {
-                if (std::getenv("RMHIP_LU_VERBOSE"))
+            if (!(gmax <= s.tau) || h_ipiv[rows] > 0 || knobs.test_growth) {
+                if (knobs.verbose)
                     std::fprintf(stderr, "[lu] solve path: max multiplier %.3g (tau %.3g), %d small pivot(s): refactoring with the grid-wide rule\n", gmax,
                                  s.tau, h_ipiv[rows]);
                 return RMHIP_LU_GROWTH;
             }
         }
-        if (!h_xerr && s.persistent && std::getenv("RMHIP_LU_TEST_RETRY")) h_xerr = 1;  // test hook for the retry path
+        if (!h_xerr && s.persistent && knobs.test_retry) h_xerr = 1;  // test hook for the retry path
         if (e == hipSuccess && h_xerr) {
             c->lu_exchange_timeouts++;
             // bounded spins expired: the panel workgroups were not co-resident (device shared with another
@@ -3238,10 +2860,10 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
             // A factorisation that placed panels on one XCD first gives that up (if the workgroup -> XCD assignment is not
             // the expected round robin the plain stores of the exchange are never seen); only a failure of the spread
             // placement makes the context conservative.
-            if (std::getenv("RMHIP_LU_VERBOSE"))
+            if (knobs.verbose)
                 std::fprintf(stderr, "[lu] panel exchange timed out (one-XCD placement used: %d, allowed: %d)\n", (int)c->lu_used_one_xcd,
                              (int)c->one_xcd_ok);
-            if (c->lu_used_one_xcd && c->one_xcd_ok && !std::getenv("RMHIP_LU_TEST_RETRY")) c->one_xcd_ok = false;
+            if (c->lu_used_one_xcd && c->one_xcd_ok && !knobs.test_retry) c->one_xcd_ok = false;
             else c->lu_conservative = true;
             (void)fail(RMHIP_ERR_HIP, "lu: panel workgroups were not co-resident (device shared?)");
             rc = RMHIP_LU_RETRY;
@@ -3851,8 +3473,8 @@ static int launch_subst_chain(Context* c, const double* LU, size_t lda, size_t n
 static int substitute_few_rhs(Context* c, const double* LU, size_t n, size_t lda, double* X, size_t ldx, size_t nrhs) {
     // One launch per direction (k_subst_chain) when the system is big enough for the launches to matter and the chain's
     // workgroups (one per 128 rows) fit the chip; RMHIP_LU_SUBST=pair keeps the launch-per-block form.
-    const char* subst_env = std::getenv("RMHIP_LU_SUBST");  // read per call (tests switch it)
-    const int chain = (subst_env && subst_env[0] == 'p') ? 0 : 1;
+    const LuKnobs knobs = lu_knobs();
+    const int chain = knobs.subst_pair ? 0 : 1;
     const size_t nblk_chain = (n + TRSM_W - 1) / TRSM_W;
     if (chain && nblk_chain >= 4 && nblk_chain <= (size_t)c->num_cus && !c->subst_chain_failed) {
         std::shared_ptr<Allocation> ctl;  // flags of both directions + the error word, pooled
@@ -3869,7 +3491,7 @@ static int substitute_few_rhs(Context* c, const double* LU, size_t n, size_t lda
         int h_err = 0;
         RMHIP_HIP_CHECK(hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (!h_err && std::getenv("RMHIP_LU_TEST_SUBST_RETRY")) h_err = 1;  // test hook for the fallback below
+        if (!h_err && knobs.test_subst_retry) h_err = 1;  // test hook for the fallback below
         if (!h_err) return RMHIP_OK;
         c->lu_subst_timeouts++;
         c->subst_chain_failed = true;  // a spin timed out: X is clobbered, the caller gathers the right-hand side again
@@ -3923,7 +3545,7 @@ int lu_solve_device(Context* c, const double* LU, size_t n, size_t lda, const in
     hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n + 255) / 256), (unsigned)nrhs), dim3(256), 0, c->stream, B, ldb,
                        perm_dev, n, nrhs, X, ldx);
     RMHIP_TRY(launch_check(c));
-    if (nrhs <= (size_t)RU_MAX_RHS && !(lu_skip_mask() & 16)) {
+    if (nrhs <= (size_t)RU_MAX_RHS && !(lu_process_knobs().skip & 16)) {
         int rc = substitute_few_rhs(c, LU, n, lda, X, ldx, nrhs);
         if (rc == RMHIP_SUBST_RETRY) {  // the chain kernel timed out (never seen; context flag now selects the pair form)
             hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n + 255) / 256), (unsigned)nrhs), dim3(256), 0, c->stream, B, ldb,

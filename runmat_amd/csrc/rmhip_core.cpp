@@ -479,7 +479,6 @@ int rmhip_shutdown(rmhip_ctx* ctx) {
         if (e) (void)hipEventDestroy(e);
     if (c->lu_side_stream) (void)hipStreamDestroy(c->lu_side_stream);
     if (c->lu_prep_stream) (void)hipStreamDestroy(c->lu_prep_stream);
-    if (c->lu_aux_stream) (void)hipStreamDestroy(c->lu_aux_stream);
     if (c->lu_far_stream) (void)hipStreamDestroy(c->lu_far_stream);
     if (c->lu_mid_stream) (void)hipStreamDestroy(c->lu_mid_stream);
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);

@@ -59,7 +59,7 @@ static int lu_copy_and_factor(Context* c, const double* src, size_t rows, size_t
             c->lu_growth_fallbacks++;
             // telemetry.solve_fallbacks names it when a multiplier actually exceeded the bound; a pivot at the singular cut-off inside a
             // top block also lands here (the grid-wide rule has to confirm it), and is then reported as what it turns out to be
-            if (!(c->lu_last_growth <= c->lu_tau) || std::getenv("RMHIP_LU_TEST_GROWTH")) c->record_solve_fallback("lu:pivot_growth");
+            if (!(c->lu_last_growth <= c->lu_tau) || lu_knobs().test_growth) c->record_solve_fallback("lu:pivot_growth");
             continue;
         }
         if (rc == RMHIP_OK && mode == 1 && c->lu_last_fast) c->lu_fast_count++;  // RMHIP_LU_FAST=0 / conservative panels: the grid-wide rule ran
@@ -74,11 +74,10 @@ size_t lu_padded_ld(size_t rows) { return rows >= 256 ? ((rows + 1) & ~(size_t)1
 // 128; otherwise EVERY update of the factorisation runs a guarded kernel (n = 10000: 37.0 ms against 31.7 at 10240, n = 13001: 55.6
 // against 47.2 at 13056).  The solves therefore factor [A 0; 0 I] at the next multiple of 128 - 2-4 % more flops, all of them on
 // the fast kernels - and drop the padded unknowns (zero).  `lu` itself returns factors of the order it was given.
-// RMHIP_LU_PAD=0 disables.
+// RMHIP_LU_PAD=0 disables (read per call: the tests compare both forms).
 static size_t lu_pad_rows(size_t n) {
-    const char* v = std::getenv("RMHIP_LU_PAD");  // read per call: the tests compare both forms
-    static const size_t min_n = std::getenv("RMHIP_LU_PAD_MIN") ? (size_t)std::atol(std::getenv("RMHIP_LU_PAD_MIN")) : 2048;  // dev knob
-    if ((v && *v == '0') || n < min_n || n % 128 == 0) return n;
+    constexpr size_t kPadMin = 2048;
+    if (!lu_knobs().pad || n < kPadMin || n % 128 == 0) return n;
     const size_t np = (n + 127) / 128 * 128;
     return np <= 65535 ? np : n;
 }
@@ -1520,8 +1519,7 @@ static int mldivide_impl(rmhip_ctx* ctx, Context* c, rmhip_buf a, rmhip_buf b, r
         // path below is a dozen launches and two read-backs whatever the order.  Same decisions: a pivot <= 1e-12 is SINGULAR (-> the SVD
         // path), a pivot ratio below 1e3 n eps lets the SVD decide.  RMHIP_LU_FAST=0 (the grid-wide rule everywhere) and
         // RMHIP_NO_SMALL_SOLVE=1 keep the blocked path.
-        const char* fe = std::getenv("RMHIP_LU_FAST");
-        if (small_solve_applies(n, nrhs) && !(fe && fe[0] == '0') && !std::getenv("RMHIP_NO_SMALL_SOLVE")) {
+        if (small_solve_applies(n, nrhs) && lu_knobs().fast && !std::getenv("RMHIP_NO_SMALL_SOLVE")) {
             Buffer sb;
             rmhip_buf sid = 0;
             const size_t sshape[2] = {n, nrhs};
@@ -1689,8 +1687,7 @@ static int linsolve_impl(rmhip_ctx* ctx, Context* c, rmhip_buf a, rmhip_buf b, c
         std::shared_ptr<Allocation> perm_mem;
         int* perm = nullptr;
         int info = 0;
-        const char* fe = std::getenv("RMHIP_LU_FAST");
-        const bool small = small_solve_applies(n, nrhs) && !(fe && fe[0] == '0') && !std::getenv("RMHIP_NO_SMALL_SOLVE");
+        const bool small = small_solve_applies(n, nrhs) && lu_knobs().fast && !std::getenv("RMHIP_NO_SMALL_SOLVE");
         if (small) {  // one launch (small_solve.hip), the same kernel and therefore the same bits as mldivide's
             rc = c->new_buffer(oshape, 2, &oid, &ob);
             double mn = 0.0, mx = 0.0;

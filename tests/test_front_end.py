@@ -399,3 +399,44 @@ def test_every_environment_knob_is_documented():
     docs = (ROOT / "INTEGRATION.md").read_text() + (ROOT / "DESIGN.md").read_text() + "".join(f.read_text() for f in sorted((ROOT / "docs").glob("*.md")))
     missing = sorted(k for k in knobs if k not in docs)
     assert not missing, f"undocumented environment variables: {missing}"
+
+
+def _function_body(text: str, signature: str) -> str:
+    start = text.index(signature)
+    i = text.index("{", start)
+    depth = 0
+    for j in range(i, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[j], 0)
+        if depth == 0:
+            return text[i:j + 1]
+    raise AssertionError(f"unbalanced braces after {signature!r}")
+
+
+def test_lu_knobs_are_read_in_one_place_and_match_the_knob_table():
+    """The RMHIP_LU_* variables are read by lu_knobs() (per call) and lu_process_knobs() (per process) in lu.hip and nowhere else, and
+    the LU table of docs/KNOBS.md names exactly those variables, each with the group that reads it."""
+    import re
+
+    pat = re.compile(r'getenv\("(RMHIP_LU_[A-Z0-9_]+)"\)')
+    src = ROOT / "runmat_amd" / "csrc"
+    everywhere = []
+    for f in sorted(list(src.glob("*.cpp")) + list(src.glob("*.hip")) + list(src.glob("*.h"))):
+        everywhere += pat.findall(f.read_text())
+    lu = (src / "lu.hip").read_text()
+    per_call = pat.findall(_function_body(lu, "LuKnobs lu_knobs()"))
+    per_process = pat.findall(_function_body(lu, "const LuProcessKnobs& lu_process_knobs()"))
+    assert sorted(everywhere) == sorted(per_call + per_process), "RMHIP_LU_* read outside lu_knobs() / lu_process_knobs()"
+    assert not set(per_call) & set(per_process), set(per_call) & set(per_process)
+
+    doc = (ROOT / "docs" / "KNOBS.md").read_text()
+    section = doc[doc.index("## LU and solves"):]
+    section = section[:section.index("\n## ", 1)] if "\n## " in section[1:] else section
+    table = {}
+    for row in section.splitlines():
+        m = re.match(r"\| `(RMHIP_LU_[A-Z0-9_]+)` \|[^|]*\| ([^|]*) \|", row)
+        if m:
+            assert m.group(1) not in table, f"{m.group(1)} has two rows"
+            table[m.group(1)] = m.group(2).strip()
+    assert set(table.values()) <= {"per call", "per process"}, table
+    assert {k for k, v in table.items() if v == "per call"} == set(per_call)
+    assert {k for k, v in table.items() if v == "per process"} == set(per_process)

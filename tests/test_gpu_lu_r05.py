@@ -49,7 +49,6 @@ SWITCHES = [
     {"RMHIP_LU_SUPER": "0"},                                     # one-level driver
     {"RMHIP_LU_RB_MFMA": "0", "RMHIP_LU_TRSM_MFMA": "0"},         # fp64-VALU rows-below kernel and triangular solves
     {"RMHIP_LU_TRSM_MFMA": "0"},
-    {"RMHIP_LU_YIELD": "0", "RMHIP_LU_GEMM_PRIO": "0"},
     {"RMHIP_LU_SUPER_SEQ": "512:256/1024:256", "RMHIP_LU_SUPER_ROWS": "2048", "RMHIP_LU_SUPER_LATE": "512:128"},  # another plan
     {"RMHIP_LU_IPREP": "0", "RMHIP_LU_SMALL_UPD": "0"},           # W-wide solve at the boundary, 128 x 128 tiles only on the update streams
     {"RMHIP_LU_IPREP": "1", "RMHIP_LU_IPREP_SPLIT": "0", "RMHIP_LU_SUPER_SEQ": "256:256/1024:256/2048:256", "RMHIP_LU_SUPER_ROWS": "4096"},  # the large-order plan with incremental block rows
