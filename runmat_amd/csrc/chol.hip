@@ -13,13 +13,6 @@
 
 using namespace rmhip;
 
-#define CTX_OR_FAIL(ctx)                                            \
-    if (!(ctx)) return fail(RMHIP_ERR_INVALID, "null context");     \
-    Context* c = context_of(ctx);                                   \
-    std::lock_guard<std::recursive_mutex> _call(c->call_mu);        \
-    DeviceGuard _dg(c);                                             \
-    NarrowScope _ns(c)
-
 namespace rmhip {
 namespace {
 

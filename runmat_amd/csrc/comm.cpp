@@ -269,12 +269,6 @@ void comm_destroy(Context* c) {
 
 using namespace rmhip;
 
-#define CTX_OR_FAIL(ctx)                                            \
-    if (!(ctx)) return fail(RMHIP_ERR_INVALID, "null context");     \
-    Context* c = context_of(ctx);                                   \
-    std::lock_guard<std::recursive_mutex> _call(c->call_mu);        \
-    DeviceGuard _dg(c)
-
 extern "C" {
 
 int rmhip_comm_unique_id(int transport, void* id_out) {
@@ -299,7 +293,7 @@ int rmhip_comm_unique_id(int transport, void* id_out) {
 }
 
 int rmhip_comm_init(rmhip_ctx* ctx, const void* unique_id, int rank, int world) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     if (!unique_id || world < 1 || rank < 0 || rank >= world) return fail(RMHIP_ERR_INVALID, "comm_init: bad id / rank %d / world %d", rank, world);
     if (c->comm) return fail(RMHIP_ERR_INVALID, "comm_init: this context already has a communicator");
     Comm* cm = new Comm();
@@ -448,7 +442,7 @@ int rmhip_comm_init(rmhip_ctx* ctx, const void* unique_id, int rank, int world) 
 }
 
 int rmhip_comm_destroy(rmhip_ctx* ctx) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     if (c->comm && c->comm->pending) (void)hipStreamSynchronize(c->comm->stream);
     (void)hipStreamSynchronize(c->stream);
     comm_destroy(c);
@@ -456,7 +450,7 @@ int rmhip_comm_destroy(rmhip_ctx* ctx) {
 }
 
 int rmhip_comm_abort(rmhip_ctx* ctx) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     Comm* cm = c->comm;
     if (!cm || cm->aborted) return RMHIP_OK;
     cm->aborted = true;
@@ -470,7 +464,7 @@ int rmhip_comm_abort(rmhip_ctx* ctx) {
 }
 
 int rmhip_comm_wait_bounded(rmhip_ctx* ctx, double timeout_s) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     Comm* cm = c->comm;
     if (!cm || cm->aborted || cm->world <= 1) {
         RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -522,14 +516,14 @@ int rmhip_comm_wait_bounded(rmhip_ctx* ctx, double timeout_s) {
 }
 
 int rmhip_comm_rank(rmhip_ctx* ctx, int* rank, int* world) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     if (rank) *rank = c->comm ? c->comm->rank : 0;
     if (world) *world = c->comm ? c->comm->world : 1;
     return RMHIP_OK;
 }
 
 int rmhip_comm_wait(rmhip_ctx* ctx) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     Comm* cm;
     if (c->comm && c->comm->aborted) return RMHIP_OK;  // nothing of it is in flight any more
     RMHIP_TRY(require_comm(c, &cm));
@@ -541,7 +535,7 @@ int rmhip_comm_wait(rmhip_ctx* ctx) {
 }
 
 int rmhip_comm_bcast(rmhip_ctx* ctx, const rmhip_view_t* v, int root, int async) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     Comm* cm;
     RMHIP_TRY(require_comm(c, &cm));
     if (!v) return fail(RMHIP_ERR_INVALID, "null view");
@@ -592,7 +586,7 @@ int rmhip_comm_bcast(rmhip_ctx* ctx, const rmhip_view_t* v, int root, int async)
 }
 
 int rmhip_comm_allgather_f64(rmhip_ctx* ctx, rmhip_buf local, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     Comm* cm;
     RMHIP_TRY(require_comm(c, &cm));
     RMHIP_TRY(join_pending(c, cm));
@@ -632,7 +626,7 @@ int rmhip_comm_allgather_f64(rmhip_ctx* ctx, rmhip_buf local, rmhip_buf* out) {
 }
 
 int rmhip_comm_allgather_rows(rmhip_ctx* ctx, rmhip_buf local, size_t rows_total, size_t granule, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     Comm* cm;
     RMHIP_TRY(require_comm(c, &cm));
     RMHIP_TRY(join_pending(c, cm));
@@ -700,7 +694,7 @@ int rmhip_comm_allgather_rows(rmhip_ctx* ctx, rmhip_buf local, size_t rows_total
 }
 
 int rmhip_comm_barrier(rmhip_ctx* ctx) {
-    CTX_OR_FAIL(ctx);
+    COMM_CTX_OR_FAIL(ctx);
     Comm* cm;
     RMHIP_TRY(require_comm(c, &cm));
     RMHIP_TRY(join_pending(c, cm));

@@ -214,7 +214,6 @@ struct Context {
     bool one_xcd_ok = true;  // LU panels may place their blocks on one XCD (cleared when such a panel timed out once)
     bool lu_used_one_xcd = false;
     bool lu_last_fast = false;  // the last lu_factor_device call restricted pivoting to the panels' top blocks (mode 1 taken, not merely asked for)
-    bool solve_strict = false;  // a refused square solve stays refused (inv): no SVD answer for a singular matrix
     double lu_last_growth = 0.0;       // largest multiplier the last solve-path factorisation saw below its top blocks
     uint64_t lu_fast_count = 0, lu_growth_fallbacks = 0;  // solve-path factorisations accepted / refactored with the grid-wide rule
     uint64_t lu_exchange_timeouts = 0, lu_subst_timeouts = 0;
@@ -277,6 +276,24 @@ struct NarrowScope {
         else c->narrow_pending.resize(mark);
     }
 };
+
+// First statement of every C-ABI entry point that takes a context: the null check, the per-context call lock, the context's device and
+// the narrowing scope.  Leaves `Context* c` in scope.
+#define CTX_OR_FAIL(ctx)                                            \
+    if (!(ctx)) return fail(RMHIP_ERR_INVALID, "null context");     \
+    Context* c = context_of(ctx);                                   \
+    std::lock_guard<std::recursive_mutex> _call(c->call_mu);        \
+    DeviceGuard _dg(c);                                             \
+    NarrowScope _ns(c)
+// The collectives (comm.cpp) take the context without a NarrowScope.  They work in place on f64 storage or register their f64 result
+// themselves (allgather_f64: partial sums stay f64 whatever the provider precision); the one result made through new_buffer
+// (allgather_rows) is made only after f32 storage has been refused.  At precision 64 a scope would change nothing; at precision 32 it
+// would round that one result to f32.
+#define COMM_CTX_OR_FAIL(ctx)                                       \
+    if (!(ctx)) return fail(RMHIP_ERR_INVALID, "null context");     \
+    Context* c = context_of(ctx);                                   \
+    std::lock_guard<std::recursive_mutex> _call(c->call_mu);        \
+    DeviceGuard _dg(c)
 
 struct ScopedTimer {
     std::atomic<uint64_t>* count;
@@ -496,6 +513,14 @@ int svd_solve_device(Context* c, const double* A, size_t m, size_t n, const doub
 int svd_values_host(Context* c, const char* who, const double* A, size_t m, size_t n, std::vector<double>* values);
 double svd_default_tolerance(const std::vector<double>& values, size_t m, size_t n);
 int svd_pinv_device(Context* c, const double* A, size_t m, size_t n, double tol, double* X);
+
+// The switches of the solve dispatch (docs/KNOBS.md), read by solve_knobs() (solve.cpp) and nowhere else.
+struct SolveKnobs {  // read on every call: tests flip these inside one process
+    bool svd_path = true;     // cleared by RMHIP_NO_SVD_PATH: what the LU / Gram paths refuse goes back to the caller
+    bool small_solve = true;  // cleared by RMHIP_NO_SMALL_SOLVE: small square systems take the blocked kernels
+    bool gram_skinny = true;  // cleared by RMHIP_NO_GRAM_SKINNY: covariance / syrk / least squares of a few columns take the MFMA route
+};
+SolveKnobs solve_knobs();
 
 // small_solve.hip: x = A \ B for small n (policy: <= 64), nrhs <= 16 in one launch (the augmented matrix in the LDS of one CU) + the pivot statistics
 bool small_solve_applies(size_t n, size_t nrhs);

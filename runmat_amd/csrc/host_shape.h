@@ -9,6 +9,13 @@
 
 namespace rmhip {
 
+// A MATLAB shape as a matrix: a scalar is 1 x 1, a rank-1 shape a column; anything of rank >= 2 is kept
+inline std::vector<size_t> normalize_matrix_shape(const std::vector<size_t>& s) {
+    if (s.empty()) return {1, 1};
+    if (s.size() == 1) return {s[0], 1};
+    return s;
+}
+
 // Front-pad `shape` to `rank` (broadcast.rs:108-115, elementwise.rs:1681-1687) and derive strides
 // with 0 on broadcast (extent 1) dims.  Returns false if the shape cannot broadcast to `out`.
 inline bool padded_strides(const std::vector<size_t>& shape_in, const size_t* out, size_t rank, std::vector<uint64_t>* strides) {

@@ -3516,7 +3516,7 @@ static int substitute_few_rhs(Context* c, const double* LU, size_t n, size_t lda
 
 // W (np x np, ld ldw) holds an n x n matrix in its top-left corner: make the rest [0; 0 I] - the padded system [A 0; 0 I] has the
 // factors of A in its leading block, the padded rows are never chosen as pivots for A's columns (zeros there) and the padded
-// unknowns come out zero.  Used by the solves for n that is not a multiple of 128 (rmhip_ops.cpp: lu_pad_rows).
+// unknowns come out zero.  Used by the solves for n that is not a multiple of 128 (solve.cpp: lu_pad_rows).
 __global__ void __launch_bounds__(256) k_lu_pad_identity(double* __restrict__ W, size_t ldw, size_t n, size_t np) {
     const size_t pad = np - n;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;  // row 0 .. np-1

@@ -362,13 +362,6 @@ struct rmhip_ctx {
     Context c;
 };
 
-#define CTX_OR_FAIL(ctx)                                                  \
-    if (!(ctx)) return fail(RMHIP_ERR_INVALID, "null context");           \
-    Context* c = &(ctx)->c;                                               \
-    std::lock_guard<std::recursive_mutex> _call(c->call_mu);              \
-    DeviceGuard _dg(c);                                                   \
-    NarrowScope _ns(c)
-
 // Which XCD does workgroup b of a launch run on?  The LU places small panels on ONE XCD by launching 8x the grid and keeping
 // workgroups b % 8 == 0, and its late-phase update kernels leave the panel's XCD: both assume eight dies and a round-robin
 // dispatcher.  A CPX partition (one die, 32 CUs) passes the gfx950 check and breaks both - every update workgroup would leave.

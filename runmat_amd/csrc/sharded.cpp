@@ -18,13 +18,6 @@
 
 using namespace rmhip;
 
-#define CTX_OR_FAIL(ctx)                                            \
-    if (!(ctx)) return fail(RMHIP_ERR_INVALID, "null context");     \
-    Context* c = context_of(ctx);                                   \
-    std::lock_guard<std::recursive_mutex> _call(c->call_mu);        \
-    DeviceGuard _dg(c);                                             \
-    NarrowScope _ns(c)
-
 namespace {
 
 rmhip_view_t view(rmhip_buf buf, size_t r0, size_t c0, size_t rows, size_t cols) { return rmhip_view_t{buf, r0, c0, rows, cols}; }

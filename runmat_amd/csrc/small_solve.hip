@@ -1,12 +1,12 @@
 // small_solve.hip -- x = A \ B for a small square system in ONE launch.
 //
-// The blocked solve path (lu.hip + rmhip_ops.cpp) spends a dozen launches and two host read-backs on any system: 0.15 ms at n = 8,
+// The blocked solve path (lu.hip + solve.cpp) spends a dozen launches and two host read-backs on any system: 0.15 ms at n = 8,
 // 0.20 ms at n = 64 (scripts/solve_small.py), of which the elimination itself is a fraction.  A small augmented matrix [A | B] (the
 // kernel: n <= 128 and 16 right-hand sides; used up to n = 64) fits the LDS of one CU: one workgroup loads it, eliminates with partial pivoting (largest |a| of the
 // column, first occurrence - the rule of host_lu.rs:37-59; pivots never leave the provider on this path, mldivide.rs:380-404 defines the
 // answer, not the factorisation), substitutes back one wave per right-hand side with the finished component broadcast by v_readlane
 // (no barrier inside the substitution), and leaves the pivot statistics the caller's singular / nearly-singular tests need
-// (rmhip_ops.cpp: a pivot <= 1e-12 -> SINGULAR -> the SVD path; a tiny pivot ratio -> the SVD decides) next to the solution: one launch,
+// (solve.cpp: a pivot <= 1e-12 -> SINGULAR -> the SVD path; a tiny pivot ratio -> the SVD decides) next to the solution: one launch,
 // one read-back.  Deterministic: fixed reduction order, no atomics.
 #include "common.h"
 

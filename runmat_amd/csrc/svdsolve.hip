@@ -3,7 +3,7 @@
 // The CPU builtin answers EVERY shape with the minimum-norm least-squares solution of an SVD,
 //   x = V diag(1/s_i, s_i > tol) U' b,   tol = eps * max(m, n) * max(s_max, 1)
 // (crates/runmat-runtime/src/builtins/math/linalg/ops/mldivide.rs:380-404; nalgebra `SVD::solve`).  The LU solve and the
-// Gram-matrix least squares (rmhip_ops.cpp) reproduce that answer only for full-rank, reasonably conditioned systems and hand
+// Gram-matrix least squares (solve.cpp) reproduce that answer only for full-rank, reasonably conditioned systems and hand
 // everything else back to the caller (RMHIP_ERR_SINGULAR / UNSUPPORTED).  For systems whose smaller dimension is at most
 // svd_max_cols() (4096, RMHIP_SVD_MAX_COLS) this file computes the same thing the reference computes: a one-sided Jacobi SVD of the tall orientation W (p x q,
 // p >= q) - rotations of column pairs until every pair is orthogonal to 1e-15, singular values = column norms, right vectors

@@ -1,4 +1,4 @@
-"""Developer tool (GPU box): rectangular `A\\b` (least squares through the Gram matrix, rmhip_ops.cpp lstsq_full_rank) on tall and wide
+"""Developer tool (GPU box): rectangular `A\\b` (least squares through the Gram matrix, solve.cpp lstsq_full_rank) on tall and wide
 shapes - ms per solve and the residual check against numpy's lstsq on the smaller ones."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

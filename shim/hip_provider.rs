@@ -36,7 +36,7 @@ pub struct HipProvider {
 }
 // `AccelProvider: Send + Sync` (lib.rs:1386).  The context pointer is only ever handed to librmhip entry points, and
 // every entry point takes the context's call mutex first (`Context::call_mu`, taken by CTX_OR_FAIL in
-// runmat_amd/csrc/rmhip_core.cpp / rmhip_ops.cpp): overlapping calls from several host threads serialise inside the
+// runmat_amd/csrc/rmhip_core.cpp / rmhip_ops.cpp / solve.cpp): overlapping calls from several host threads serialise inside the
 // library instead of interleaving on its per-context state (scratch, RNG state, the look-ahead LU's stream
 // retargeting).  tests/test_gpu_threads.py hammers one context from two threads.
 unsafe impl Send for HipProvider {}

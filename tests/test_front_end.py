@@ -440,3 +440,50 @@ def test_lu_knobs_are_read_in_one_place_and_match_the_knob_table():
     assert set(table.values()) <= {"per call", "per process"}, table
     assert {k for k, v in table.items() if v == "per call"} == set(per_call)
     assert {k for k, v in table.items() if v == "per process"} == set(per_process)
+
+
+def test_solve_knobs_are_read_in_one_place_and_match_the_knob_table():
+    """RMHIP_NO_SVD_PATH, RMHIP_NO_SMALL_SOLVE and RMHIP_NO_GRAM_SKINNY are read by solve_knobs() (per call) in solve.cpp and nowhere else,
+    and the "Solve dispatch" table of docs/KNOBS.md names exactly those three as read per call, plus RMHIP_SVD_MAX_COLS, which
+    svd_max_cols() reads once per process."""
+    import re
+
+    pat = re.compile(r'getenv\("(RMHIP_NO_[A-Z0-9_]+)"\)')
+    src = ROOT / "runmat_amd" / "csrc"
+    everywhere = []
+    for f in sorted(list(src.glob("*.cpp")) + list(src.glob("*.hip")) + list(src.glob("*.h"))):
+        everywhere += pat.findall(f.read_text())
+    in_knobs = pat.findall(_function_body((src / "solve.cpp").read_text(), "SolveKnobs solve_knobs()"))
+    assert sorted(in_knobs) == ["RMHIP_NO_GRAM_SKINNY", "RMHIP_NO_SMALL_SOLVE", "RMHIP_NO_SVD_PATH"]
+    assert sorted(everywhere) == sorted(in_knobs), "RMHIP_NO_* read outside solve_knobs()"
+    max_cols = [f.name for f in sorted(list(src.glob("*.cpp")) + list(src.glob("*.hip")) + list(src.glob("*.h")))
+                for _ in re.findall(r'getenv\("RMHIP_SVD_MAX_COLS"\)', f.read_text())]
+    assert max_cols == ["svdsolve.hip"], max_cols
+    assert "solve_strict" not in "".join(f.read_text() for f in src.iterdir() if f.suffix in (".cpp", ".hip", ".h"))
+
+    doc = (ROOT / "docs" / "KNOBS.md").read_text()
+    section = doc[doc.index("## Solve dispatch"):]
+    section = section[:section.index("\n## ", 1)]
+    table = {}
+    for row in section.splitlines():
+        m = re.match(r"\| `(RMHIP_[A-Z0-9_]+)` \|[^|]*\| ([^|]*) \|", row)
+        if m:
+            assert m.group(1) not in table, f"{m.group(1)} has two rows"
+            table[m.group(1)] = m.group(2).strip()
+    assert {k for k, v in table.items() if v == "per call"} == set(in_knobs)
+    assert {k for k, v in table.items() if v == "per process"} == {"RMHIP_SVD_MAX_COLS"}
+
+
+def test_ctx_or_fail_is_defined_once():
+    """The entry-point prologue CTX_OR_FAIL is one macro in common.h; no translation unit carries a copy of its own (the collectives'
+    variant without a NarrowScope has a name of its own, next to it)."""
+    import re
+
+    src = ROOT / "runmat_amd" / "csrc"
+    where = [f.name for f in sorted(src.iterdir()) if f.suffix in (".cpp", ".hip", ".h")
+             for _ in re.findall(r"#\s*define\s+CTX_OR_FAIL\b", f.read_text())]
+    assert where == ["common.h"], where
+    common = (src / "common.h").read_text()
+    assert len(re.findall(r"#\s*define\s+COMM_CTX_OR_FAIL\b", common)) == 1
+    comm = (src / "comm.cpp").read_text()
+    assert "COMM_CTX_OR_FAIL(ctx);" in comm and not re.search(r"(?<!COMM_)CTX_OR_FAIL\(ctx\);", comm)

@@ -89,7 +89,7 @@ def test_solve_path_matches_partial_pivoting_quality(prov, kind, n):
 @pytest.mark.parametrize("n,nrhs", [(2100, 1), (4100, 3), (5001, 2)])
 def test_ragged_orders_factor_at_the_padded_order(prov, n, nrhs):
     """n >= 2048 that is not a multiple of 128: the solves factor [A 0; 0 I] at the next multiple (every trailing update a whole
-    tile; rmhip_ops.cpp: lu_pad_rows).  The padded rows hold zeros in A's columns and are never chosen as pivots; the solution agrees
+    tile; solve.cpp: lu_pad_rows).  The padded rows hold zeros in A's columns and are never chosen as pivots; the solution agrees
     with the unpadded factorisation's (RMHIP_LU_PAD=0) to rounding - the panel boundaries, hence the grouping of the updates, depend
     on the order - and has the same backward error; linsolve and mrdivide take the same route."""
     rng = np.random.default_rng(n)
