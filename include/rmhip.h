@@ -636,6 +636,48 @@ RMHIP_API int rmhip_covariance_to_correlation(rmhip_ctx* ctx, rmhip_buf matrix, 
  * exponentials per point: within 2e-14 absolute of the oracle (terms of magnitude up to ~8). */
 /* @serves peaks peaks_xy */
 RMHIP_API int rmhip_peaks(rmhip_ctx* ctx, size_t n, rmhip_buf x_or_0, rmhip_buf y_or_0, rmhip_buf* out);
+/* `black_scholes_price(request)` (lib.rs:1572-1579; ProviderBlackScholesPriceRequest { inputs, output_shape, len } :3409-3424, built by
+ * blsprice, builtins/finance/black_scholes.rs:568-592; CPU contract simple_provider.rs:800-883, 2855-2920): European call and put
+ * prices, one pair per output element.  inputs: Price, Strike, Rate, Time, Volatility, Yield; row k of input_shapes / input_strides
+ * (6 x rank, row-major) is input k's shape aligned to output_shape's rank and its column-major strides.  Element `linear` of the output
+ * reads input k at provider_broadcast_index: the sum over dimensions of coordinate x stride, a dimension of input extent 1 mapping to
+ * offset 0.  Per element: an input that is not finite, price < 0, strike <= 0, time < 0 or volatility < 0 prices to (NaN, NaN) - a
+ * value, not an error; time == 0 or volatility == 0 to the intrinsic pair max(fp - ds, 0), max(ds - fp, 0); otherwise d1, d2 and
+ * N(x) = 0.5 (1 + erf(x / SQRT_2)) in the CPU's operation order.  Parity by tolerance: the device's log / exp / erf are within 2 ulp
+ * of the CPU's libm, which leaves |error| <= 8 eps (S e^{-qT} + K e^{-rT}).  Both outputs have exactly output_shape; len == 0 gives two
+ * empty tensors.  One launch, no device -> host read: requests whose inputs are all output-shaped and contiguous or single elements
+ * take a 16-byte streaming kernel, everything else the strided one over dimensions collapsed on the host.  RMHIP_ERR_INVALID:
+ * len != prod(output_shape), an input whose element count is not prod(its shape), an extent that is neither 1 nor the output's,
+ * strides that reach beyond the input, more than 8 dimensions after collapsing; RMHIP_ERR_UNSUPPORTED: a complex operand.  The
+ * builtin takes its host path on any error (black_scholes.rs:598-605). */
+/* @serves black_scholes_price */
+RMHIP_API int rmhip_black_scholes_price(rmhip_ctx* ctx, const rmhip_buf inputs[6], const size_t* input_shapes, const size_t* input_strides,
+                                        const size_t* output_shape, size_t rank, size_t len, rmhip_buf* call, rmhip_buf* put);
+/* `adam_update(request)` (lib.rs:1582-1587; ProviderAdamUpdateRequest :3443-3453, called by adamupdate, deep_learning/training.rs:961;
+ * CPU contract simple_provider.rs:985-1064, 2922-3009): m = b1 m0 + (1 - b1) g, v = b2 v0 + ((1 - b2) g) g,
+ * p = p0 - (lr (m / gc)) / (sqrt(v / sc) + eps) with gc = 1 - b1^iteration, sc = 1 - b2^iteration computed on the host: true divisions,
+ * a correctly rounded square root, the CPU's operation order - bit-exact.  An absent moment (0) is zeros and is not read.  out3 order:
+ * parameters, average_grad, average_sq_grad, each in parameters' shape.  RMHIP_ERR_INVALID with the CPU's messages, in its order:
+ * iteration == 0, a learn rate or epsilon that is not finite and positive, a decay factor outside [0, 1), empty parameters, operands of
+ * another shape, gc <= 0 or sc <= 0; complex operands are RMHIP_ERR_UNSUPPORTED.  The data is validated by the kernel that computes:
+ * a non-finite input element ("inputs must contain finite values") wins over a non-finite p, m or v ("update produced a non-finite
+ * value"); either is RMHIP_ERR_INVALID and the three outputs are freed.  One launch; synchronises the stream once (the verdict). */
+/* @serves adam_update */
+RMHIP_API int rmhip_adam_update(rmhip_ctx* ctx, rmhip_buf parameters, rmhip_buf gradient, rmhip_buf average_grad_or_0, rmhip_buf average_sq_grad_or_0,
+                                unsigned long long iteration, double learn_rate, double gradient_decay, double sq_gradient_decay, double epsilon,
+                                rmhip_buf out3[3]);
+/* `crossentropy_terms(request)` (lib.rs:1590-1597; ProviderCrossentropyRequest :3472-3478, called by crossentropy,
+ * deep_learning/losses.rs:189; CPU contract simple_provider.rs:1066-1137, 3011-3095): per-element loss terms in predictions' shape.
+ * c = clamp(prediction, 1e-12, 1 - 1e-12); multi_label == 0: (-t) ln(c); else (-t) ln(c) - (1 - t) ln(1 - c); then times the weight,
+ * then times the mask (an absent one, 0, is 1 and is not read).  Parity by tolerance (the device logarithm: 2 ulp).
+ * RMHIP_ERR_INVALID with the CPU's messages: empty predictions, operands of another shape, and - found by the kernel, the output freed -
+ * in this priority when several occur: a non-finite prediction or target, a weight that is not finite or negative, a mask value other
+ * than 0 or 1, a target outside [0, 1], a non-finite loss.  The CPU orders the last two by element index (whichever element fails
+ * first); one pass over the data does not reproduce that, so a request holding both reports the target.  Complex operands:
+ * RMHIP_ERR_UNSUPPORTED.  One launch; synchronises the stream once (the verdict). */
+/* @serves crossentropy_terms */
+RMHIP_API int rmhip_crossentropy_terms(rmhip_ctx* ctx, rmhip_buf predictions, rmhip_buf targets, rmhip_buf weights_or_0, rmhip_buf mask_or_0,
+                                       int multi_label, rmhip_buf* losses);
 /* `corrcoef(matrix, options)` (lib.rs:1867-1874; `CorrcoefOptions { normalization, rows }`, :906-911; corrcoef.rs:720-787, 895-926) for
  * rows == All (rows_mode 0; Complete / Pairwise: RMHIP_ERR_UNSUPPORTED): the covariance path above, then r = cov / (sd_i sd_j) with the CPU's
  * NaN rules (a variance that is not finite and positive), its 1e-12 clamp onto [-1, 1] and an exact unit diagonal.  Sums of products:

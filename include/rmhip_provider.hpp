@@ -578,6 +578,47 @@ public:
         check(rmhip_peaks(ctx_, 0, own(x), own(y), &out));
         return with_shape(out);
     }
+    // lib.rs:1572-1579: one input of ProviderBlackScholesPriceRequest (:3409-3415) - the handle, its shape aligned to the output's rank and
+    // the column-major strides of that shape, as blsprice prepares them (black_scholes.rs:568-578).  Returns (call, put).
+    struct BlackScholesInput {
+        GpuTensorHandle handle;
+        std::vector<size_t> shape, strides;
+    };
+    std::pair<GpuTensorHandle, GpuTensorHandle> black_scholes_price(const std::vector<BlackScholesInput>& inputs,
+                                                                    const std::vector<size_t>& output_shape, size_t len) const {
+        if (inputs.size() != 6) throw std::runtime_error("black_scholes_price: expected six inputs");
+        const size_t rank = output_shape.size();
+        std::vector<uint64_t> ids;
+        std::vector<size_t> shapes, strides;
+        for (const auto& in : inputs) {
+            if (in.shape.size() != rank || in.strides.size() != rank)
+                throw std::runtime_error("black_scholes_price: input broadcast metadata rank mismatch");
+            ids.push_back(own(in.handle));
+            shapes.insert(shapes.end(), in.shape.begin(), in.shape.end());
+            strides.insert(strides.end(), in.strides.begin(), in.strides.end());
+        }
+        uint64_t call = 0, put = 0;
+        check(rmhip_black_scholes_price(ctx_, ids.data(), shapes.data(), strides.data(), output_shape.data(), rank, len, &call, &put));
+        return {with_shape(call), with_shape(put)};
+    }
+    // lib.rs:1582-1587 (ProviderAdamUpdateRequest, :3443-3453): nullptr moments are zeros.  Returns {parameters, average_grad, average_sq_grad}.
+    std::array<GpuTensorHandle, 3> adam_update(const GpuTensorHandle& parameters, const GpuTensorHandle& gradient, const GpuTensorHandle* average_grad,
+                                               const GpuTensorHandle* average_sq_grad, size_t iteration, double learn_rate,
+                                               double gradient_decay_factor, double squared_gradient_decay_factor, double epsilon) const {
+        uint64_t out[3] = {0, 0, 0};
+        check(rmhip_adam_update(ctx_, own(parameters), own(gradient), average_grad ? own(*average_grad) : 0,
+                                average_sq_grad ? own(*average_sq_grad) : 0, iteration, learn_rate, gradient_decay_factor,
+                                squared_gradient_decay_factor, epsilon, out));
+        return {with_shape(out[0]), with_shape(out[1]), with_shape(out[2])};
+    }
+    // lib.rs:1590-1597 (ProviderCrossentropyRequest, :3472-3478): nullptr weights / mask are 1; multi_label selects ProviderCrossentropyMode::MultiLabel
+    GpuTensorHandle crossentropy_terms(const GpuTensorHandle& predictions, const GpuTensorHandle& targets, const GpuTensorHandle* weights,
+                                       const GpuTensorHandle* mask, bool multi_label) const {
+        uint64_t out = 0;
+        check(rmhip_crossentropy_terms(ctx_, own(predictions), own(targets), weights ? own(*weights) : 0, mask ? own(*mask) : 0,
+                                       multi_label ? 1 : 0, &out));
+        return with_shape(out);
+    }
     GpuTensorHandle corrcoef(const GpuTensorHandle& matrix, bool biased, int rows_mode = 0) const {  // lib.rs:1867 (rows_mode: 0 All, 1 Complete, 2 Pairwise)
         uint64_t out = 0;
         check(rmhip_corrcoef(ctx_, own(matrix), biased ? 1 : 0, rows_mode, &out));

@@ -170,6 +170,9 @@ struct Context {
     // scratch for reductions / LU (grown on demand, reused)
     double* scratch = nullptr;
     size_t scratch_bytes = 0;
+    // device-side validation (workload_ops.hip): failing lanes lower this word to their priority code with atomicMin; the entry point
+    // resets it on the stream before its launch and reads it back once after.  Allocated on first use.
+    unsigned* verdict_word = nullptr;
 
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     Telemetry tel;
@@ -528,6 +531,9 @@ int small_solve_device(Context* c, const double* A, const double* B, size_t n, s
 
 // opaque handle -> Context (rmhip_core.cpp)
 Context* context_of(rmhip_ctx* h);
+// Precision-32 contexts: fetch an operand for a kernel that has an f32-storage variant (rmhip_ops.cpp).  `*native` stays true while
+// every operand so far is plain f32 storage; otherwise the caller falls back to widened f64 copies (Context::get).
+int get_operand(Context* c, rmhip_buf id, Buffer* out, bool* native);
 void comm_destroy(Context* c);  // comm.cpp
 
 

@@ -468,6 +468,7 @@ int rmhip_shutdown(rmhip_ctx* ctx) {
     for (auto& kv : c->pool) (void)hipFree(kv.second);
     c->pool.clear();
     if (c->scratch) (void)hipFree(c->scratch);
+    if (c->verdict_word) (void)hipFree(c->verdict_word);
     for (hipEvent_t e : c->lu_events)
         if (e) (void)hipEventDestroy(e);
     if (c->lu_side_stream) (void)hipStreamDestroy(c->lu_side_stream);

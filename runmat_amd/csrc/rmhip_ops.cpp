@@ -24,13 +24,8 @@
 
 using namespace rmhip;
 
-namespace {
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// Precision-32 contexts: fetch an operand for a kernel that has an f32-storage variant.  `*native` stays true while
-// every operand so far is plain f32 storage; otherwise the caller falls back to widened f64 copies (Context::get).
-int get_operand(Context* c, rmhip_buf id, Buffer* out, bool* native) {
+// (declared in common.h: workload_ops.hip fetches its operands the same way)
+int rmhip::get_operand(Context* c, rmhip_buf id, Buffer* out, bool* native) {
     if (*native) {
         RMHIP_TRY(c->get_raw(id, out));
         if (out->dtype == DT_F32 && out->lazy()) {  // materialise the view once, as f32
@@ -42,6 +37,10 @@ int get_operand(Context* c, rmhip_buf id, Buffer* out, bool* native) {
     }
     return c->get(id, out);
 }
+
+namespace {
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Operand of a broadcasting elementwise launch (rmhip_binary, rmhip_fused_elementwise): as get_operand, but a repmat view
 // stays a view - the launch indexes its base with stride 0 (host_shape.h refined_strides).

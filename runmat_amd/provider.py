@@ -881,6 +881,85 @@ class HipProvider:
         self._check(self._lib.rmhip_peaks(self._ctx, 0, self._id(x), self._id(y), C.byref(out)))
         return self._handle(out.value)
 
+    @staticmethod
+    def black_scholes_request_layout(shapes: Sequence[Sequence[int]]):
+        """What blsprice hands the provider (black_scholes.rs:568-578): the broadcast of the six canonical shapes, front-padded with
+        ones (broadcast.rs:8-46), each shape aligned to that rank (`align_shape`) and its column-major strides (`compute_strides`: a
+        zero extent counts as one).  Returns (output_shape, aligned_shapes, strides)."""
+        canon = [tuple(int(e) for e in s) for s in shapes]
+        canon = [(1, 1) if len(s) == 0 else (s[0], 1) if len(s) == 1 else s for s in canon]  # canonical_shape
+        out = (1, 1)
+        for s in canon:
+            rank = max(len(out), len(s))
+            a, b = (1,) * (rank - len(out)) + out, (1,) * (rank - len(s)) + s
+            merged = []
+            for d, (x, y) in enumerate(zip(a, b)):
+                if x == y or y == 1:
+                    merged.append(x)
+                elif x == 1:
+                    merged.append(y)
+                elif x == 0 or y == 0:
+                    merged.append(0)
+                else:
+                    raise ProviderError(_lib.ERR_SHAPE, f"blsprice: size mismatch between inputs (dimension {d + 1} has lengths {x} and {y})")
+            out = tuple(merged)
+        aligned = [(1,) * (len(out) - len(s)) + s for s in canon]
+        strides = []
+        for s in aligned:
+            row, step = [], 1
+            for e in s:
+                row.append(step)
+                step *= max(e, 1)
+            strides.append(tuple(row))
+        return out, aligned, strides
+
+    def black_scholes_price(self, inputs: Sequence[GpuTensorHandle], output_shape: Optional[Sequence[int]] = None):
+        """`black_scholes_price` (lib.rs:1572-1579) -> (call, put).  `inputs`: Price, Strike, Rate, Time, Volatility, Yield, which
+        broadcast against each other as in blsprice; `output_shape`, when given, must be what they broadcast to."""
+        if len(inputs) != 6:
+            raise ProviderError(_lib.ERR_INVALID, "black_scholes_price: expected six inputs")
+        out_shape, aligned, strides = self.black_scholes_request_layout([h.shape for h in inputs])
+        if output_shape is not None and tuple(int(e) for e in output_shape) != out_shape:
+            raise ProviderError(_lib.ERR_SHAPE, f"black_scholes_price: inputs broadcast to {out_shape}, not {tuple(output_shape)}")
+        rank = len(out_shape)
+        ids = (C.c_uint64 * 6)(*[self._id(h) for h in inputs])
+        shp = (C.c_size_t * (6 * rank))(*[e for s in aligned for e in s])
+        std = (C.c_size_t * (6 * rank))(*[e for s in strides for e in s])
+        osh = (C.c_size_t * rank)(*out_shape)
+        call, put = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.rmhip_black_scholes_price(self._ctx, ids, shp, std, osh, rank, int(np.prod(out_shape, dtype=np.int64)),
+                                                        C.byref(call), C.byref(put)))
+        return self._handle(call.value, out_shape), self._handle(put.value, out_shape)
+
+    def adam_update(self, parameters: GpuTensorHandle, gradient: GpuTensorHandle, average_grad: Optional[GpuTensorHandle] = None,
+                    average_sq_grad: Optional[GpuTensorHandle] = None, iteration: int = 1, learn_rate: float = 0.001,
+                    gradient_decay_factor: float = 0.9, squared_gradient_decay_factor: float = 0.999, epsilon: float = 1e-8):
+        """`adam_update` (lib.rs:1582-1587; the fields of ProviderAdamUpdateRequest, :3443-3453; adamupdate's defaults) ->
+        (parameters, average_grad, average_sq_grad).  An absent moment is zeros.  Invalid scalars and non-finite data raise INVALID
+        with the CPU provider's messages."""
+        if iteration < 0:
+            raise ProviderError(_lib.ERR_INVALID, "adam_update: iteration must be positive")
+        outs = (C.c_uint64 * 3)()
+        self._check(self._lib.rmhip_adam_update(self._ctx, self._id(parameters), self._id(gradient),
+                                                self._id(average_grad) if average_grad is not None else 0,
+                                                self._id(average_sq_grad) if average_sq_grad is not None else 0, int(iteration),
+                                                float(learn_rate), float(gradient_decay_factor), float(squared_gradient_decay_factor),
+                                                float(epsilon), outs))
+        return tuple(self._handle(outs[i], parameters.shape) for i in range(3))
+
+    def crossentropy_terms(self, predictions: GpuTensorHandle, targets: GpuTensorHandle, weights: Optional[GpuTensorHandle] = None,
+                           mask: Optional[GpuTensorHandle] = None, mode: str = "single-label") -> GpuTensorHandle:
+        """`crossentropy_terms` (lib.rs:1590-1597; `ProviderCrossentropyMode::{SingleLabel, MultiLabel}`, :3465-3468): the per-element
+        loss terms in predictions' shape; an absent weight or mask is 1."""
+        if mode not in ("single-label", "multi-label"):
+            raise ProviderError(_lib.ERR_INVALID, f"crossentropy_terms: mode {mode!r}")
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_crossentropy_terms(self._ctx, self._id(predictions), self._id(targets),
+                                                       self._id(weights) if weights is not None else 0,
+                                                       self._id(mask) if mask is not None else 0, 1 if mode == "multi-label" else 0,
+                                                       C.byref(out)))
+        return self._handle(out.value, predictions.shape)
+
     def corrcoef(self, matrix: GpuTensorHandle, normalization: str = "unbiased", rows: str = "all") -> GpuTensorHandle:
         """lib.rs:1867-1874 (`CorrcoefOptions`, :906-911): only rows == "all" is offloaded (what corrcoef_try_gpu issues, corrcoef.rs:480-483)."""
         if normalization not in ("unbiased", "biased") or rows not in ("all", "complete", "pairwise"):

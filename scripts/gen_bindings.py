@@ -90,7 +90,7 @@ def parse(text: str):
 
 # ---- ctypes ------------------------------------------------------------------------------------------------------------
 PY_SCALAR = {"int": "C.c_int", "unsigned": "C.c_uint", "uint32_t": "C.c_uint32", "uint64_t": "C.c_uint64", "rmhip_buf": "C.c_uint64",
-             "size_t": "C.c_size_t", "double": "C.c_double", "long long": "C.c_longlong", "char": "C.c_char", "unsigned char": "C.c_ubyte"}
+             "size_t": "C.c_size_t", "double": "C.c_double", "long long": "C.c_longlong", "unsigned long long": "C.c_ulonglong", "char": "C.c_char", "unsigned char": "C.c_ubyte"}
 
 
 def py_type(ty: str, structs) -> str:
@@ -158,7 +158,7 @@ def emit_python(serves, defines, enums, structs, funcs) -> str:
 
 # ---- Rust --------------------------------------------------------------------------------------------------------------
 RS_SCALAR = {"int": "c_int", "unsigned": "c_uint", "uint32_t": "u32", "uint64_t": "u64", "rmhip_buf": "u64", "size_t": "usize",
-             "double": "c_double", "long long": "c_longlong", "char": "c_char", "unsigned char": "u8"}
+             "double": "c_double", "long long": "c_longlong", "unsigned long long": "c_ulonglong", "char": "c_char", "unsigned char": "u8"}
 RS_KEYWORDS = {"async", "in", "type", "ref", "move", "box", "loop", "match", "fn", "use", "mod", "self"}
 
 
@@ -185,7 +185,7 @@ def emit_rust(serves, defines, enums, structs, funcs) -> str:
            "// The raw FFI surface of librmhip.so: `#[repr(C)]` structs, constants and the `extern \"C\"` block.  shim/hip_provider.rs",
            "// (`impl AccelProvider for HipProvider`) is the hand-written half and `include!`s this file.",
            "#![allow(non_upper_case_globals, dead_code)]",
-           "use std::ffi::{c_char, c_double, c_int, c_longlong, c_uint, c_void};", "",
+           "use std::ffi::{c_char, c_double, c_int, c_longlong, c_uint, c_ulonglong, c_void};", "",
            "#[repr(C)]", "pub struct RmhipCtx {", "    _private: [u8; 0],", "}", ""]
     for name, fields in structs.items():
         out.append(f"/// `{name}`")

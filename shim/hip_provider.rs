@@ -18,6 +18,7 @@ use runmat_accelerate_api::{
     HostLogicalOwned, HostTensorOwned, HostTensorView, IsMemberOptions, IsMemberResult, SetdiffOptions, SetdiffOrder, SetdiffResult, UnionOptions, UnionOrder, UnionResult, UniqueOccurrence, UniqueOptions, UniqueOrder, UniqueResult, ImageNormalizeDescriptor, ImfilterMode, ImfilterOptions, ImfilterPadding, ImfilterShape, KernelAttrTelemetry, MeshgridAxisView, ProviderMeshgridResult, ProviderPolyderQuotient, ProviderPolyvalOptions, KernelLaunchTelemetry, MatmulEpilogue,
     PowerStepEpilogue, ProviderBandwidth, ProviderCovarianceToCorrelationResult, ProviderHilbertRequest, ProviderCondNorm, ProviderPinvOptions, ProviderIirFilterOptions, ProviderIirFilterResult, ProviderInterp1Extrapolation, ProviderInterp1Method, ProviderInterp1Request, ProviderConv1dOptions, ProviderConvMode, ProviderConvOrientation, ProviderCholResult, ProviderCummaxResult, ProviderCumminResult, ProviderDispatchStats, ProviderInvOptions, ProviderFallbackStat, ProviderFindResult, ProviderHermitianKind, ProviderLinsolveOptions,
     ProviderLinsolveResult, ProviderLuResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
+    ProviderAdamUpdateRequest, ProviderAdamUpdateResult, ProviderBlackScholesPriceRequest, ProviderBlackScholesPriceResult, ProviderCrossentropyMode, ProviderCrossentropyRequest, ProviderCrossentropyResult,
     ProviderStdNormalization, ProviderSymmetryKind, ProviderTelemetry, ProviderTrapezoidSpacing, ReduceDimResult, ReductionFlavor, ScaleOp, SortComparison, SortOrder, SortResult, SortRowsColumnSpec,
 };
 use std::ffi::{c_char, c_int, c_void, CStr, CString};
@@ -572,6 +573,44 @@ impl AccelProvider for HipProvider {
         let mut out = 0u64;
         check(unsafe { rmhip_peaks(self.ctx, 0, self.own(x)?, self.own(y)?, &mut out) })?;
         self.handle(out)
+    }
+    // black_scholes_price: the request's aligned shapes and strides go over row by row (6 x rank); Err -> blsprice's host path (black_scholes.rs:598-605)
+    fn black_scholes_price(&self, request: &ProviderBlackScholesPriceRequest<'_>) -> Result<ProviderBlackScholesPriceResult> {
+        let rank = request.output_shape.len();
+        if request.inputs.len() != 6 {
+            return Err(anyhow!("black_scholes_price: expected six inputs"));
+        }
+        if request.inputs.iter().any(|i| i.shape.len() != rank || i.strides.len() != rank) {
+            return Err(anyhow!("black_scholes_price: input broadcast metadata rank mismatch"));
+        }
+        let ids = request.inputs.iter().map(|i| self.own(i.handle)).collect::<Result<Vec<u64>>>()?;
+        let shapes: Vec<usize> = request.inputs.iter().flat_map(|i| i.shape.iter().copied()).collect();
+        let strides: Vec<usize> = request.inputs.iter().flat_map(|i| i.strides.iter().copied()).collect();
+        let (mut call, mut put) = (0u64, 0u64);
+        check(unsafe {
+            rmhip_black_scholes_price(self.ctx, ids.as_ptr(), shapes.as_ptr(), strides.as_ptr(), request.output_shape.as_ptr(), rank,
+                request.len, &mut call, &mut put)
+        })?;
+        Ok(ProviderBlackScholesPriceResult { call: self.handle(call)?, put: self.handle(put)? })
+    }
+    // adam_update: an absent moment goes over as 0 (zeros, never allocated); scalar and data validation with the CPU provider's messages
+    fn adam_update(&self, request: &ProviderAdamUpdateRequest<'_>) -> Result<ProviderAdamUpdateResult> {
+        let m = match request.average_grad { Some(h) => self.own(h)?, None => 0 };
+        let v = match request.average_sq_grad { Some(h) => self.own(h)?, None => 0 };
+        let mut ids = [0u64; 3];
+        check(unsafe {
+            rmhip_adam_update(self.ctx, self.own(request.parameters)?, self.own(request.gradient)?, m, v, request.iteration as u64,
+                request.learn_rate, request.gradient_decay_factor, request.squared_gradient_decay_factor, request.epsilon, ids.as_mut_ptr())
+        })?;
+        Ok(ProviderAdamUpdateResult { parameters: self.handle(ids[0])?, average_grad: self.handle(ids[1])?, average_sq_grad: self.handle(ids[2])? })
+    }
+    fn crossentropy_terms(&self, request: &ProviderCrossentropyRequest<'_>) -> Result<ProviderCrossentropyResult> {
+        let w = match request.weights { Some(h) => self.own(h)?, None => 0 };
+        let k = match request.mask { Some(h) => self.own(h)?, None => 0 };
+        let multi = matches!(request.mode, ProviderCrossentropyMode::MultiLabel) as c_int;
+        let mut out = 0u64;
+        check(unsafe { rmhip_crossentropy_terms(self.ctx, self.own(request.predictions)?, self.own(request.targets)?, w, k, multi, &mut out) })?;
+        Ok(ProviderCrossentropyResult { losses: self.handle(out)? })
     }
     fn corrcoef<'a>(&'a self, matrix: &'a GpuTensorHandle, options: &'a CorrcoefOptions) -> AccelProviderFuture<'a, GpuTensorHandle> {
         Box::pin(async move {
