@@ -720,6 +720,18 @@ RMHIP_API int rmhip_chol(rmhip_ctx* ctx, rmhip_buf a, int lower, rmhip_buf* fact
  * does not fit in device memory. */
 /* @serves qr */
 RMHIP_API int rmhip_qr(rmhip_ctx* ctx, rmhip_buf a, int economy, int pivot_vector, rmhip_buf out4[4]);
+/* `eig(a, compute_left)` (lib.rs:2491-2497 -> ProviderEigResult { eigenvalues, diagonal, right, left } :786-791) for a REAL, BITWISE
+ * SYMMETRIC matrix (a(i,j) == a(j,i) for every pair, what rmhip_issymmetric(a, 0, 0) answers) of order n <= 4096, finite in every entry;
+ * at most two non-unit dimensions.  out4 order: eigenvalues [n, 1] ASCENDING (the reference's Schur order is unpinned, eig.rs:1196-1207),
+ * diagonal [n, n] (zero off the diagonal), right [n, n] with orthonormal columns (right(:, k) belongs to eigenvalues(k)), left [n, n].
+ * `left` is a handle of its own with right's values - inv(V)' normalised to left_k . right_k = 1 (eig.rs:890-940) is V for an
+ * orthonormal V - and 0 when compute_left == 0.  n == 0 gives [0, 0] tensors (eig.rs:534-557).  The input is not modified.  Two-sided
+ * Jacobi in one launch up to n = 64, blocked one-sided Jacobi on the shifted matrix above (eig.hip); absolute accuracy ~ n eps ||A||.
+ * RMHIP_ERR_UNSUPPORTED (the builtin's host path answers, eig.rs:436-461): not bitwise symmetric, a non-finite entry, n > 4096, a
+ * complex-interleaved buffer, no convergence within the sweep cap.  RMHIP_ERR_INVALID: not square, more than two non-unit dimensions, a
+ * null pointer.  A refused call leaves no buffer behind. */
+/* @serves eig */
+RMHIP_API int rmhip_eig(rmhip_ctx* ctx, rmhip_buf a, int compute_left, rmhip_buf out4[4]);
 /* `pagefun(request)` (lib.rs:2386; PagefunRequest { op, inputs, output_shape, page_dims, input_page_dims } :603-614, built by
  * build_pagefun_request, builtins/acceleration/gpu/pagefun.rs:450-530).  op RMHIP_PAGEFUN_MTIMES: output page p (column-major over
  * page_dims) = A(:, :, a(p)) * B(:, :, b(p)), where an operand takes index 0 along every page dimension of extent 1 in its row of

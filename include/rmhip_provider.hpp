@@ -80,6 +80,12 @@ struct PagefunRequest {
     std::vector<std::vector<size_t>> input_page_dims;
 };
 
+// lib.rs:786-791: `left` is a null handle (buffer_id 0) when it was not asked for (the trait's Option::None)
+struct ProviderEigResult {
+    GpuTensorHandle eigenvalues, diagonal, right, left;
+    bool has_left = false;
+};
+
 class HipProvider {
 public:
     // precision_bits: 64 or 32 (ProviderPrecision, lib.rs:815-818), fixed for the provider's lifetime
@@ -504,6 +510,16 @@ public:
         check(rmhip_pagefun(ctx_, RMHIP_PAGEFUN_MTIMES, ids.data(), ids.size(), request.page_dims.data(), rank, ipd.data(),
                             request.output_shape.data(), request.output_shape.size(), &out));
         return with_shape(out);
+    }
+    // lib.rs:2491-2497: real, bitwise symmetric matrices of order <= 4096 - eigenvalues ascending, orthonormal right vectors, `left` a copy
+    // of `right` in a buffer of its own.  Throws for what the host path must answer (not symmetric, non-finite, larger, complex, no
+    // convergence) and for a non-square or higher-rank operand
+    ProviderEigResult eig(const GpuTensorHandle& a, bool compute_left = false) const {
+        uint64_t ids[4] = {0, 0, 0, 0};
+        check(rmhip_eig(ctx_, own(a), compute_left ? 1 : 0, ids));
+        ProviderEigResult r{with_shape(ids[0]), with_shape(ids[1]), with_shape(ids[2]), GpuTensorHandle(), compute_left};
+        if (compute_left) r.left = with_shape(ids[3]);
+        return r;
     }
     // lib.rs:2430-2436 (ProviderInvOptions is empty)
     GpuTensorHandle inv(const GpuTensorHandle& matrix) const {

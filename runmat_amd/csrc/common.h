@@ -544,6 +544,19 @@ void comm_destroy(Context* c);  // comm.cpp
 // pipe are one datapath per SIMD, and every instruction of a chain kernel otherwise queues behind the update block's MFMAs.
 static constexpr unsigned kYieldSlots = 4096;
 #if defined(__HIPCC__)
+// Jacobi tournaments (svdsolve.hip, eig.hip)
+// pair `b` of step `t` in the round-robin tournament over Q (even) players: player Q-1 stays, the others rotate
+__device__ __forceinline__ void jac_pair(int Q, int t, int b, int* x, int* y) {
+    const int m = Q - 1;
+    if (b == 0) {
+        *x = m;
+        *y = t % m;
+    } else {
+        *x = (t + b) % m;
+        *y = (t - b + m) % m;
+    }
+}
+
 __device__ __forceinline__ unsigned cu_slot() {
     unsigned xcc, hw;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));

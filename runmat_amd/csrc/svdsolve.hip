@@ -43,18 +43,6 @@ __device__ __forceinline__ double jac_block_sum(double v, double* lds) {
     return ((lds[0] + lds[1]) + lds[2]) + lds[3];  // every thread, fixed order
 }
 
-// pair `b` of step `t` in the round-robin tournament over Q (even) players: player Q-1 stays, the others rotate
-__device__ __forceinline__ void jac_pair(int Q, int t, int b, int* x, int* y) {
-    const int m = Q - 1;
-    if (b == 0) {
-        *x = m;
-        *y = t % m;
-    } else {
-        *x = (t + b) % m;
-        *y = (t - b + m) % m;
-    }
-}
-
 __global__ void __launch_bounds__(JAC_THREADS) k_jacobi_step(double* __restrict__ W, size_t p, int q, int Q, double* __restrict__ V, int step,
                                                              unsigned long long* __restrict__ off_bits) {
     __shared__ double lds[4];

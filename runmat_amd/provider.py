@@ -158,6 +158,15 @@ class PagefunRequest:
 
 
 @dataclass
+class ProviderEigResult:
+    """`ProviderEigResult` (lib.rs:786-791); `left` is None unless it was asked for."""
+    eigenvalues: GpuTensorHandle
+    diagonal: GpuTensorHandle
+    right: GpuTensorHandle
+    left: Optional[GpuTensorHandle] = None
+
+
+@dataclass
 class ProviderLinsolveOptions:
     """lib.rs:679-690"""
     lower: bool = False
@@ -760,6 +769,15 @@ class HipProvider:
         self._check(self._lib.rmhip_pagefun(self._ctx, op, ids, len(request.inputs), pd, rank, ipd, osh, len(request.output_shape),
                                             C.byref(out)))
         return self._handle(out.value, request.output_shape)
+
+    def eig(self, a: GpuTensorHandle, compute_left: bool = False) -> ProviderEigResult:
+        """`eig(a, compute_left)` (lib.rs:2491-2497) for real, bitwise symmetric matrices of order <= 4096: eigenvalues [n, 1] ascending,
+        `diagonal` = diag(eigenvalues), `right` with orthonormal columns, `left` (on request) a buffer of its own with the same values.
+        Not symmetric, non-finite, larger or complex input and a missed sweep cap raise (UNSUPPORTED): the builtin takes its host path."""
+        outs = (C.c_uint64 * 4)()
+        self._check(self._lib.rmhip_eig(self._ctx, self._id(a), 1 if compute_left else 0, outs))
+        hs = [self._handle(outs[i]) for i in range(3)]
+        return ProviderEigResult(*hs, self._handle(outs[3]) if compute_left else None)
 
     def mldivide(self, lhs: GpuTensorHandle, rhs: GpuTensorHandle) -> GpuTensorHandle:
         out = C.c_uint64()

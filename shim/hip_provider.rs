@@ -17,7 +17,7 @@ use runmat_accelerate_api::{
     AccelProvider, AccelProviderFuture, ApiDeviceInfo, CorrcoefNormalization, CorrcoefOptions, CorrcoefRows, CovNormalization, CovRows, CovarianceOptions, FindDirection, GpuTensorHandle, GpuTensorStorage,
     HostLogicalOwned, HostTensorOwned, HostTensorView, IsMemberOptions, IsMemberResult, SetdiffOptions, SetdiffOrder, SetdiffResult, UnionOptions, UnionOrder, UnionResult, UniqueOccurrence, UniqueOptions, UniqueOrder, UniqueResult, ImageNormalizeDescriptor, ImfilterMode, ImfilterOptions, ImfilterPadding, ImfilterShape, KernelAttrTelemetry, MeshgridAxisView, ProviderMeshgridResult, ProviderPolyderQuotient, ProviderPolyvalOptions, KernelLaunchTelemetry, MatmulEpilogue,
     PowerStepEpilogue, ProviderBandwidth, ProviderCovarianceToCorrelationResult, ProviderHilbertRequest, ProviderCondNorm, ProviderPinvOptions, ProviderIirFilterOptions, ProviderIirFilterResult, ProviderInterp1Extrapolation, ProviderInterp1Method, ProviderInterp1Request, ProviderConv1dOptions, ProviderConvMode, ProviderConvOrientation, ProviderCholResult, ProviderCummaxResult, ProviderCumminResult, ProviderDispatchStats, ProviderInvOptions, ProviderFallbackStat, ProviderFindResult, ProviderHermitianKind, ProviderLinsolveOptions,
-    ProviderLinsolveResult, ProviderLuResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
+    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
     ProviderAdamUpdateRequest, ProviderAdamUpdateResult, ProviderBlackScholesPriceRequest, ProviderBlackScholesPriceResult, ProviderCrossentropyMode, ProviderCrossentropyRequest, ProviderCrossentropyResult,
     ProviderStdNormalization, ProviderSymmetryKind, ProviderTelemetry, ProviderTrapezoidSpacing, ReduceDimResult, ReductionFlavor, ScaleOp, SortComparison, SortOrder, SortResult, SortRowsColumnSpec,
 };
@@ -674,6 +674,16 @@ impl AccelProvider for HipProvider {
             check(unsafe { rmhip_qr(self.ctx, self.own(_a)?, _options.economy as c_int, vector as c_int, ids.as_mut_ptr()) })?;
             Ok(ProviderQrResult { q: self.handle(ids[0])?, r: self.handle(ids[1])?, perm_matrix: self.handle(ids[2])?,
                 perm_vector: self.handle(ids[3])? })
+        })
+    }
+    // eig: real, bitwise symmetric matrices of order <= 4096 (ascending eigenvalues, orthonormal right vectors, `left` a copy of `right`);
+    // Err (not symmetric, non-finite, larger, complex, no convergence) -> eig.rs:436-461 host path
+    fn eig<'a>(&'a self, _a: &'a GpuTensorHandle, _compute_left: bool) -> AccelProviderFuture<'a, ProviderEigResult> {
+        Box::pin(async move {
+            let mut ids = [0u64; 4];
+            check(unsafe { rmhip_eig(self.ctx, self.own(_a)?, _compute_left as c_int, ids.as_mut_ptr()) })?;
+            let left = if _compute_left { Some(self.handle(ids[3])?) } else { None };
+            Ok(ProviderEigResult { eigenvalues: self.handle(ids[0])?, diagonal: self.handle(ids[1])?, right: self.handle(ids[2])?, left })
         })
     }
     fn stochastic_evolution(&self, state: &GpuTensorHandle, drift: f64, scale: f64, steps: u32) -> Result<GpuTensorHandle> {
