@@ -80,6 +80,25 @@ int main() {
                  eq(p.download(p.not_nan_mask(p.upload({1, nan, 3}, {3, 1}))).data, {1, 0, 1});
         }
         {
+            // uniform_spectral_estimate (lib.rs:2560-2565): two sliding frames of [1 2 3 4 5 6] under a unit window, nfft 4, hop 2, one-sided:
+            // fft([1 2 3 4]) = [10, -2+2i, -2, ..], fft([3 4 5 6]) = [18, -2+2i, -2, ..]; ps = |s|^2 * (1, 2, 1) / 2
+            rmhip::ProviderSpectralRequest q;
+            q.input = p.upload({1, 2, 3, 4, 5, 6}, {6, 1});
+            q.input_len = 6, q.window = {1, 1, 1, 1}, q.nfft = 4, q.frame_count = 2, q.denominator = 2.0;
+            q.frame_mode.kind = rmhip::ProviderSpectralFrameMode::Sliding, q.frame_mode.hop = 2;
+            auto sp = p.uniform_spectral_estimate(q);
+            auto sv = p.download(sp.s);
+            ok = ok && sp.rows == 3 && sp.cols == 2 && sv.complex_interleaved && sp.s.shape == std::vector<size_t>{3, 2} &&
+                 near(sv.data, {10, 0, -2, 2, -2, 0, 18, 0, -2, 2, -2, 0}, 1e-14) && near(p.download(sp.ps).data, {50, 8, 2, 162, 8, 2}, 1e-13);
+            q.frame_count = 3;  // the third frame would need x[4 .. 7]: refused by the coverage rule
+            try {
+                p.uniform_spectral_estimate(q);
+                ok = false;
+            } catch (const rmhip::ProviderError& e) {
+                ok = ok && e.code == RMHIP_ERR_INVALID;
+            }
+        }
+        {
             // ProviderPrecision::F32 (lib.rs:815-818): host views stay f64, storage is f32, results round once
             rmhip::HipProvider q(0, 32);
             ok = ok && std::string(q.precision()) == "F32";

@@ -546,6 +546,38 @@ RMHIP_API int rmhip_fft_dim(rmhip_ctx* ctx, rmhip_buf a, long long len_or_neg, i
  * transforms'. */
 /* @serves signal_hilbert */
 RMHIP_API int rmhip_hilbert(rmhip_ctx* ctx, rmhip_buf a, long long len_or_neg, int dim, rmhip_buf* out);
+/* `uniform_spectral_estimate(request)` (lib.rs:2560-2565; `ProviderSpectralRequest { input, input_len, input_complex, window, nfft, frame_count,
+ * frame_mode, range, denominator }` -> `ProviderSpectralResult { s, ps, rows, cols }`, lib.rs:266-307): the hook behind spectrogram
+ * (Sliding), pwelch (ColumnSliding) and periodogram (FoldedColumns).  Semantics of the wgpu provider's executor (ops/signal.rs:274-397)
+ * and its three shaders (shaders/signal.rs:35-260); `window` is `window_len` host doubles, x the input's first `input_len` elements.
+ * Frame: point r < nfft of frame c < frame_count is
+ *   mode 0 (Sliding)        x[c*hop + r] * w[r] if r < window_len, else 0;
+ *   mode 1 (ColumnSliding)  the same with source index (c / fpc)*input_rows + (c % fpc)*hop + r, fpc = frames_per_column (frame_count need
+ *                           not be a multiple of fpc);
+ *   mode 2 (FoldedColumns)  the sum over r' = r, r + nfft, ... < window_len of x[c*input_rows + r'] * w[r'], added in ascending r'.
+ * A source index >= input_len contributes 0.  In modes 0 and 1 a window longer than nfft is truncated; only mode 2 folds.  Complex
+ * input multiplies both parts by the real window.
+ * Spectrum: S is the forward DFT (exp(-2 pi i jk / nfft)) of each frame.
+ * `s`: complex-interleaved [rows, frame_count].  Onesided: rows = nfft/2 + 1, the first rows of S.  Twosided: rows = nfft, all of S.
+ * Centered: rows = nfft and row r is S[(r + shift) % nfft] with shift = nfft/2 + 1 for even nfft and (nfft + 1)/2 for odd nfft
+ * (common.rs:221-227 - this is the provider's rotation, NOT the host rotation pwelch applies to its own output).
+ * `ps`: real [rows, frame_count], ps = (re^2 + im^2) * scale / denominator, multiplied by scale first and divided after, as the shader
+ * does; scale = 2 on Onesided rows other than row 0 and other than the last row when nfft is even, 1 everywhere else.
+ * `rows` / `cols` are returned as in ProviderSpectralResult (cols = frame_count).
+ * RMHIP_ERR_INVALID: everything `validate_uniform_spectral_request` refuses (lib.rs:368-424: an empty window, nfft == 0, frame_count == 0,
+ * hop == 0 in modes 0 and 1, the coverage rule of each mode - which looks at the LAST frame and the whole window -, a non-finite or
+ * non-positive denominator); input_len greater than the tensor's element count; input_complex disagreeing with the handle's storage;
+ * an unknown mode or range.  RMHIP_ERR_UNSUPPORTED: an nfft beyond what `rmhip_fft_dim` transforms along dimension 0; an index product
+ * that overflows.  Nothing is allocated or left behind on any error path.
+ * Precision-32 context: the input is read as `rmhip_fft_dim` reads it, `s` follows the rule for complex results (values rounded
+ * through f32, taken from the unrounded spectrum as `ps` is), `ps` is an ordinary real tensor of that context.
+ * Power-of-two nfft <= 8192 in modes 0 and 1 load their frames straight from the signal inside the transform (no framed buffer) unless
+ * some frame reaches past input_len; every other request writes the frames out first.  One kernel then selects / rotates `s` and
+ * forms `ps` (Twosided: the transform writes `s` itself).  Accuracy of `s` as `rmhip_fft_dim`'s (tests/test_gpu_spectral.py). */
+/* @serves uniform_spectral_estimate */
+RMHIP_API int rmhip_spectral_estimate(rmhip_ctx* ctx, rmhip_buf input, size_t input_len, int input_complex, const double* window, size_t window_len, size_t nfft,
+                                      size_t frame_count, int frame_mode, size_t hop, size_t input_rows, size_t frames_per_column, int range, double denominator,
+                                      rmhip_buf* s, rmhip_buf* ps, size_t* rows, size_t* cols);
 /* `complex_from_real(real)` (imag_or_0 == 0) / `complex_from_real_imag(real, imag)` (lib.rs:1940-1959): equal shapes, or either
  * operand a one-element tensor that expands. */
 /* @serves complex_from_real complex_from_real_imag */

@@ -86,6 +86,27 @@ struct ProviderEigResult {
     bool has_left = false;
 };
 
+// lib.rs:266-307: the request of uniform_spectral_estimate and its result
+enum class ProviderSpectralRange { Onesided = 0, Twosided = 1, Centered = 2 };
+struct ProviderSpectralFrameMode {
+    enum Kind { Sliding = 0, ColumnSliding = 1, FoldedColumns = 2 } kind = Sliding;
+    size_t hop = 0, input_rows = 0, frames_per_column = 0;  // Sliding: hop; ColumnSliding: all three; FoldedColumns: input_rows
+};
+struct ProviderSpectralRequest {
+    GpuTensorHandle input;
+    size_t input_len = 0;
+    bool input_complex = false;
+    std::vector<double> window;
+    size_t nfft = 0, frame_count = 0;
+    ProviderSpectralFrameMode frame_mode;
+    ProviderSpectralRange range = ProviderSpectralRange::Onesided;
+    double denominator = 1.0;
+};
+struct ProviderSpectralResult {
+    GpuTensorHandle s, ps;  // complex-interleaved [rows, cols]; real [rows, cols]
+    size_t rows = 0, cols = 0;
+};
+
 class HipProvider {
 public:
     // precision_bits: 64 or 32 (ProviderPrecision, lib.rs:815-818), fixed for the provider's lifetime
@@ -957,6 +978,16 @@ public:
         uint64_t out = 0;
         check(rmhip_hilbert(ctx_, own(a), len, (int)dim, &out));
         return with_shape(out);
+    }
+    // lib.rs:2560-2565: framed, windowed spectra and their scaled powers (rmhip.h states the rules); throws INVALID for what
+    // validate_uniform_spectral_request refuses
+    ProviderSpectralResult uniform_spectral_estimate(const ProviderSpectralRequest& q) const {
+        uint64_t s = 0, ps = 0;
+        size_t rows = 0, cols = 0;
+        check(rmhip_spectral_estimate(ctx_, own(q.input), q.input_len, q.input_complex ? 1 : 0, q.window.data(), q.window.size(), q.nfft, q.frame_count,
+                                      (int)q.frame_mode.kind, q.frame_mode.hop, q.frame_mode.input_rows, q.frame_mode.frames_per_column, (int)q.range, q.denominator,
+                                      &s, &ps, &rows, &cols));
+        return ProviderSpectralResult{with_shape(s), with_shape(ps), rows, cols};
     }
     GpuTensorHandle fft_extract_real(const GpuTensorHandle& a) const {
         uint64_t out = 0;

@@ -56,6 +56,8 @@ struct FftPass {
     int log2m, log2b;
     int in_complex, mode, step_by_i, conj_in, conj_out, round32;  // mode: see k_fft_tile
     int nrad, rad[5];
+    // k_fft_tile<NT, true> only (the spectral estimate's frames):
+    const double* win;        // a REAL per-point factor on load, indexed like mul_in (the window)
 };
 
 __device__ __forceinline__ void cmul(double& xr, double& xi, double wr, double wi) {
@@ -141,8 +143,8 @@ struct RadixLog {
 };
 
 // one pass: K = 8 / R butterflies per thread.  FIRST: inputs come from global memory (unless STAGED: from LDS, like a later pass);
-// LAST: results go to global memory.
-template <int NT, int R, bool first_from_global, bool last>
+// LAST: results go to global memory.  WIN: the load multiplies by the real table P.win instead of the complex P.mul_in.
+template <int NT, int R, bool first_from_global, bool last, bool WIN = false>
 __device__ __forceinline__ void stockham_pass(const FftPass& P, const TileCtx<NT>& T, int log2ns) {
     constexpr int LR = RadixLog<R>::v, K = 8 / R;
     const int log2m = T.log2m, log2b = T.log2b;
@@ -177,9 +179,14 @@ __device__ __forceinline__ void stockham_pass(const FftPass& P, const TileCtx<NT
                         vr = P.in[off];
                     }
                     if (P.conj_in) vi = -vi;
-                    if (P.mul_in) {
-                        const double2 f = P.mul_in[pos];
-                        cmul(vr, vi, f.x, f.y);
+                    if constexpr (WIN) {
+                        const double f = P.win[pos];
+                        vr *= f, vi *= f;
+                    } else {
+                        if (P.mul_in) {
+                            const double2 f = P.mul_in[pos];
+                            cmul(vr, vi, f.x, f.y);
+                        }
                     }
                 }
                 xr[kk][q] = vr, xi[kk][q] = vi;
@@ -270,17 +277,19 @@ __device__ __forceinline__ void stockham_pass(const FftPass& P, const TileCtx<NT
     }
 }
 
-template <int NT, int R>
+template <int NT, int R, bool WIN>
 __device__ __forceinline__ void run_pass(int variant, const FftPass& P, const TileCtx<NT>& T, int log2ns) {
     switch (variant) {
         case 0: stockham_pass<NT, R, false, false>(P, T, log2ns); break;
         case 1: stockham_pass<NT, R, false, true>(P, T, log2ns); break;
-        case 2: stockham_pass<NT, R, true, false>(P, T, log2ns); break;
-        default: stockham_pass<NT, R, true, true>(P, T, log2ns); break;
+        case 2: stockham_pass<NT, R, true, false, WIN>(P, T, log2ns); break;
+        default: stockham_pass<NT, R, true, true, WIN>(P, T, log2ns); break;
     }
 }
 
-template <int NT>
+// WIN = true is the instantiation of the spectral estimate's fused path (rmhip_spectral_estimate): frames are read straight from the
+// signal through Side's strides and multiplied by the real window table; the transforms' own instantiation carries none of it.
+template <int NT, bool WIN = false>
 __global__ void __launch_bounds__(NT, 4) k_fft_tile(const FftPass P) {
     extern __shared__ __attribute__((aligned(16))) double fft_lds[];
     const int t = threadIdx.x;
@@ -331,9 +340,14 @@ __global__ void __launch_bounds__(NT, 4) k_fft_tile(const FftPass P) {
                     vr = P.in[off];
                 }
                 if (P.conj_in) vi = -vi;
-                if (P.mul_in) {
-                    const double2 f = P.mul_in[pos];
-                    cmul(vr, vi, f.x, f.y);
+                if constexpr (WIN) {
+                    const double f = P.win[pos];
+                    vr *= f, vi *= f;
+                } else {
+                    if (P.mul_in) {
+                        const double2 f = P.mul_in[pos];
+                        cmul(vr, vi, f.x, f.y);
+                    }
                 }
             }
             const int a = T.lidx(b, pt);
@@ -362,9 +376,9 @@ __global__ void __launch_bounds__(NT, 4) k_fft_tile(const FftPass P) {
     const bool only = P.nrad == 1;
     const int variant = (from_global ? 2 : 0) | (only ? 1 : 0);
     int log2ns;
-    if (P.rad[0] == 8) run_pass<NT, 8>(variant, P, T, 0), log2ns = 3;
-    else if (P.rad[0] == 4) run_pass<NT, 4>(variant, P, T, 0), log2ns = 2;
-    else run_pass<NT, 2>(variant, P, T, 0), log2ns = 1;
+    if (P.rad[0] == 8) run_pass<NT, 8, WIN>(variant, P, T, 0), log2ns = 3;
+    else if (P.rad[0] == 4) run_pass<NT, 4, WIN>(variant, P, T, 0), log2ns = 2;
+    else run_pass<NT, 2, WIN>(variant, P, T, 0), log2ns = 1;
     if (only) return;
     for (int s = 1; s + 1 < P.nrad; ++s, log2ns += 3) stockham_pass<NT, 8, false, false>(P, T, log2ns);
     stockham_pass<NT, 8, false, true>(P, T, log2ns);
@@ -439,7 +453,11 @@ int launch_pass(Context* c, FftPass& P) {
     const u64 blocks = (P.nlines + (1ull << lb) - 1) >> lb;
     if (blocks > 0x7fffffffull) return fail(RMHIP_ERR_UNSUPPORTED, "fft: %llu lines", P.nlines);
     const size_t tile = (size_t)m << lb, lds = (2 * (tile + (tile >> 3) + 1) + 2 * ((size_t)1 << lb)) * sizeof(double) + 2 * ((size_t)1 << lb) * sizeof(unsigned);
-    if (tile > (size_t)TILE) hipLaunchKernelGGL(k_fft_tile<1024>, dim3((unsigned)blocks), dim3(1024), lds, c->stream, P);
+    if (P.win) {
+        if (tile > (size_t)TILE) hipLaunchKernelGGL((k_fft_tile<1024, true>), dim3((unsigned)blocks), dim3(1024), lds, c->stream, P);
+        else if (tile <= (size_t)TILE_SMALL) hipLaunchKernelGGL((k_fft_tile<256, true>), dim3((unsigned)blocks), dim3(256), lds, c->stream, P);
+        else hipLaunchKernelGGL((k_fft_tile<512, true>), dim3((unsigned)blocks), dim3(512), lds, c->stream, P);
+    } else if (tile > (size_t)TILE) hipLaunchKernelGGL(k_fft_tile<1024>, dim3((unsigned)blocks), dim3(1024), lds, c->stream, P);
     else if (tile <= (size_t)TILE_SMALL) hipLaunchKernelGGL(k_fft_tile<256>, dim3((unsigned)blocks), dim3(256), lds, c->stream, P);
     else hipLaunchKernelGGL(k_fft_tile<512>, dim3((unsigned)blocks), dim3(512), lds, c->stream, P);
     c->tel.kernel_launches++;
@@ -714,6 +732,187 @@ int fft_entry(Context* c, rmhip_buf a, long long len_or_neg, int dim, bool inver
     return rc;
 }
 
+// ---- framed spectra: uniform_spectral_estimate (lib.rs:266-307, :2560-2565) ---------------------------------------------------------------
+// spectrogram / pwelch / periodogram hand over a signal, a window and a framing rule (rmhip.h states it) and take back the selected
+// rows of every frame's spectrum, `s`, and their scaled powers, `ps`.  The wgpu provider runs four passes over a materialised
+// [nfft, frames] complex buffer (frame, transform, select, power).  Here a power-of-two frame that one tile holds is loaded by
+// k_fft_tile straight from the signal - a hop-strided, windowed, zero-padded line is what Side, `win` and `in_len` address - and
+// one kernel reads the spectrum once for the selection / rotation and the power.  Folded frames, Bluestein lengths, lengths of
+// several passes and frames that reach past input_len are written out by k_spectral_frame first.
+struct SpectralFrames {
+    u64 input_len, window_len, nfft, hop, input_rows, fpc;
+    int mode, x_complex;
+};
+
+// frame c, point r of the [nfft, frames] complex frame buffer; a source index >= input_len contributes zero
+__global__ void __launch_bounds__(FT) k_spectral_frame(const double* __restrict__ x, const double* __restrict__ w, const SpectralFrames F, u64 total, double2* __restrict__ out) {
+    const u64 e = (u64)blockIdx.x * FT + threadIdx.x;
+    if (e >= total) return;
+    const u64 r = e % F.nfft, c = e / F.nfft;
+    const u64 base = F.mode == 0 ? c * F.hop : (F.mode == 1 ? (c / F.fpc) * F.input_rows + (c % F.fpc) * F.hop : c * F.input_rows);
+    // modes 0 and 1 truncate the window at nfft (one term); mode 2 folds it: r, r + nfft, ... in ascending order
+    const u64 end = F.mode == 2 ? F.window_len : (r < F.window_len ? r + 1 : 0);
+    double vr = 0.0, vi = 0.0;
+    for (u64 rr = r; rr < end; rr += F.nfft) {
+        const u64 src = base + rr;
+        if (src >= F.input_len) break;  // (src grows with rr)
+        const double f = w[rr];
+        if (F.x_complex) {
+            const double2 v = reinterpret_cast<const double2*>(x)[src];
+            vr += v.x * f, vi += v.y * f;
+        } else {
+            vr += x[src] * f;
+        }
+    }
+    double2 v;
+    v.x = vr, v.y = vi;
+    out[e] = v;
+}
+
+// row r of frame c: s = S[src(r)] (src = r, or (r + shift) mod nfft for the centered range), ps = |s|^2 * scale / denominator with
+// scale = 2 on the one-sided rows that stand for two frequencies.  `s_out` is null when the transform wrote `s` itself (two-sided) and
+// equals `spec` when only its values are to be rounded (two-sided on a precision-32 context): every thread then rewrites the element it read.
+__global__ void __launch_bounds__(FT) k_spectral_finish(const double2* spec, u64 nfft, u64 rows, u64 total, int range, u64 shift, double denominator, int round32,
+                                                        double2* s_out, double* __restrict__ ps) {
+    const u64 e = (u64)blockIdx.x * FT + threadIdx.x;
+    if (e >= total) return;
+    const u64 r = e % rows, c = e / rows;
+    u64 src = r;
+    if (range == 2) {
+        src = r + shift;
+        if (src >= nfft) src -= nfft;
+    }
+    double2 v = spec[c * nfft + src];
+    const double scale = range == 0 && r != 0 && !(nfft % 2 == 0 && r == rows - 1) ? 2.0 : 1.0;
+    ps[e] = (v.x * v.x + v.y * v.y) * scale / denominator;
+    if (s_out) {
+        if (round32) v.x = (double)(float)v.x, v.y = (double)(float)v.y;
+        s_out[e] = v;
+    }
+}
+
+inline bool mul_ovf(u64 a, u64 b, u64* out) { return __builtin_mul_overflow(a, b, out); }
+inline bool add_ovf(u64 a, u64 b, u64* out) { return __builtin_add_overflow(a, b, out); }
+
+struct SpectralArgs {
+    size_t input_len, window_len, nfft, frame_count, hop, input_rows, fpc;
+    int input_complex, mode, range;
+    double denominator;
+    const double* window;
+};
+
+// validate_uniform_spectral_request (lib.rs:368-424): true when the request is refused
+bool spectral_invalid(const SpectralArgs& a) {
+    if (!a.window || a.window_len == 0 || a.nfft == 0 || a.frame_count == 0) return true;
+    if (!std::isfinite(a.denominator) || a.denominator <= 0.0) return true;
+    u64 req = 0;
+    if (a.mode == 0) {
+        if (a.hop == 0) return true;
+        return mul_ovf(a.frame_count - 1, a.hop, &req) || add_ovf(req, a.window_len, &req) || req > a.input_len;
+    }
+    if (a.mode == 1) {
+        if (a.hop == 0 || a.input_rows == 0 || a.fpc == 0) return true;
+        const u64 last = a.frame_count - 1;
+        u64 step = 0;
+        return mul_ovf(last / a.fpc, a.input_rows, &req) || mul_ovf(last % a.fpc, a.hop, &step) || add_ovf(req, step, &req) || add_ovf(req, a.window_len, &req) ||
+               req > a.input_len;
+    }
+    return a.input_rows == 0 || mul_ovf(a.input_rows, a.frame_count, &req) || req > a.input_len;
+}
+
+int spectral_entry(Context* c, rmhip_buf input, const SpectralArgs& a, rmhip_buf* s, rmhip_buf* ps, size_t* rows_out, size_t* cols_out) {
+    if (!s || !ps || !rows_out || !cols_out) return fail(RMHIP_ERR_INVALID, "uniform_spectral_estimate: null output");
+    *s = 0, *ps = 0;
+    if (a.mode < 0 || a.mode > 2 || a.range < 0 || a.range > 2) return fail(RMHIP_ERR_INVALID, "uniform_spectral_estimate: unknown frame mode or range");
+    if (spectral_invalid(a)) return fail(RMHIP_ERR_INVALID, "uniform_spectral_estimate: invalid request");
+    Buffer xb;
+    RMHIP_TRY(c->get_any(input, &xb));
+    if (a.input_len > xb.numel) return fail(RMHIP_ERR_INVALID, "uniform_spectral_estimate: input_len %zu exceeds the tensor's %zu elements", a.input_len, xb.numel);
+    if ((a.input_complex != 0) != xb.cplx) return fail(RMHIP_ERR_INVALID, "uniform_spectral_estimate: input_complex disagrees with the handle's storage");
+    const u64 nfft = a.nfft, fc = a.frame_count;
+    // what fft_pow2 / fft_bluestein transform along dimension 0
+    const bool pow2 = is_pow2(nfft);
+    if (pow2 ? nfft > (1ull << 27) : nfft > (1ull << 23)) return fail(RMHIP_ERR_UNSUPPORTED, "uniform_spectral_estimate: nfft %zu", a.nfft);
+    u64 total = 0, bytes = 0, top = 0;
+    if (mul_ovf(nfft, fc, &total) || mul_ovf(total, 2 * sizeof(double), &bytes) || (total + FT - 1) / FT > 0x7fffffffull)
+        return fail(RMHIP_ERR_UNSUPPORTED, "uniform_spectral_estimate: %zu frames of %zu points", a.frame_count, a.nfft);
+    // `top`: one past the largest source index any frame forms - the coverage rule above only looks at the last frame
+    const u64 wl = a.mode == 2 ? a.window_len : std::min<u64>(a.window_len, nfft);  // window points a frame reads
+    bool ovf = false;
+    if (a.mode == 0) ovf = mul_ovf(fc - 1, a.hop, &top);
+    else if (a.mode == 2) ovf = mul_ovf(fc - 1, a.input_rows, &top);
+    else {
+        const u64 full = fc / a.fpc, rem = fc % a.fpc;  // whole columns, and the frames of a partial last one
+        u64 base = 0, step = 0;
+        if (full) ovf = mul_ovf(full - 1, a.input_rows, &base) || mul_ovf(a.fpc - 1, a.hop, &step) || add_ovf(base, step, &top);
+        if (rem && !ovf) {
+            ovf = mul_ovf(full, a.input_rows, &base) || mul_ovf(rem - 1, a.hop, &step) || add_ovf(base, step, &base);
+            top = std::max(top, base);
+        }
+    }
+    if (ovf || add_ovf(top, wl, &top)) return fail(RMHIP_ERR_UNSUPPORTED, "uniform_spectral_estimate: index overflow");
+    const bool fused = pow2 && nfft >= 2 && nfft <= (u64)TILE_BIG && a.mode != 2 && top <= a.input_len;
+    const u64 rows = a.range == 0 ? nfft / 2 + 1 : nfft;
+    const u64 shift = nfft % 2 == 0 ? nfft / 2 + 1 : (nfft + 1) / 2;  // common.rs:221-227
+    const bool r32 = c->precision == 32;
+    const bool direct = a.range == 1;  // two-sided: the transform's output IS `s`
+
+    Table win, frames, spec;
+    RMHIP_TRY(c->alloc_device(a.window_len, &win));
+    RMHIP_HIP_CHECK(hipMemcpyAsync(win->ptr, a.window, a.window_len * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const bool own_spectrum = nfft == 1 && !fused;  // a one-point frame is its own spectrum: the frame kernel writes what the finish kernel reads
+    if (!fused && !(own_spectrum && direct)) RMHIP_TRY(c->alloc_device(2 * total, &frames));
+    if (!direct && !own_spectrum) RMHIP_TRY(c->alloc_device(2 * total, &spec));
+    const size_t oshape[2] = {(size_t)rows, (size_t)fc};
+    Buffer sb, pb;
+    RMHIP_TRY(c->new_buffer_complex(oshape, 2, s, &sb));
+    int rc = c->new_buffer(oshape, 2, ps, &pb);
+    double* const spec_ptr = direct ? sb.data() : (spec ? spec->ptr : frames->ptr);
+    if (rc == RMHIP_OK && fused) {
+        FftPass P{};
+        P.nlines = fc, P.inner = 1, P.qcnt = a.mode == 1 ? a.fpc : 1;
+        P.in = xb.data(), P.out = spec_ptr, P.in_complex = xb.cplx ? 1 : 0;
+        P.a = a.mode == 1 ? Side{0, a.hop, a.input_rows, 1} : Side{0, 0, a.hop, 1};
+        P.b = Side{0, nfft, nfft * P.qcnt, 1};
+        P.in_pk = 1, P.in_qk = 0, P.in_len = wl;
+        P.win = win->ptr;
+        P.scale = 1.0, P.log2m = ilog2(nfft), P.mode = 0;
+        rc = launch_pass(c, P);
+    } else if (rc == RMHIP_OK) {
+        const SpectralFrames F{a.input_len, a.window_len, nfft, a.hop, a.input_rows, a.fpc ? a.fpc : 1, a.mode, xb.cplx ? 1 : 0};
+        double* const fout = nfft == 1 ? spec_ptr : frames->ptr;
+        hipLaunchKernelGGL(k_spectral_frame, dim3((unsigned)((total + FT - 1) / FT)), dim3(FT), 0, c->stream, xb.data(), win->ptr, F, total, reinterpret_cast<double2*>(fout));
+        c->tel.kernel_launches++;
+        if (hipGetLastError() != hipSuccess) rc = fail(RMHIP_ERR_HIP, "uniform_spectral_estimate: launch failed");
+        if (rc == RMHIP_OK && nfft > 1) {
+            const Lines L{frames->ptr, 1, 1, fc, nfft, spec_ptr};
+            rc = pow2 ? fft_pow2(c, L, nfft, false, false, 1.0, false) : fft_bluestein(c, L, nfft, false, 1.0, false);
+        }
+    }
+    if (rc == RMHIP_OK) {
+        const u64 otot = rows * fc;
+        double2* const s_out = direct ? (r32 ? reinterpret_cast<double2*>(sb.data()) : nullptr) : reinterpret_cast<double2*>(sb.data());
+        hipLaunchKernelGGL(k_spectral_finish, dim3((unsigned)((otot + FT - 1) / FT)), dim3(FT), 0, c->stream, reinterpret_cast<const double2*>(spec_ptr), nfft, rows, otot,
+                           a.range, shift, a.denominator, r32 ? 1 : 0, s_out, pb.data());
+        c->tel.kernel_launches++;
+        if (hipGetLastError() != hipSuccess) rc = fail(RMHIP_ERR_HIP, "uniform_spectral_estimate: launch failed");
+    }
+    if (rc != RMHIP_OK) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        for (rmhip_buf* id : {s, ps}) {
+            Buffer victim;
+            auto it = c->table.find(*id);
+            if (*id && it != c->table.end()) victim = std::move(it->second), c->table.erase(it);
+            *id = 0;
+        }
+        return rc;
+    }
+    if (fused) c->record_launch("spectral", {{"rows", rows}, {"frames", fc}}, {{"fused", 1}});
+    else c->record_launch("spectral", {{"rows", rows}, {"frames", fc}}, {{"framed", 1}});
+    *rows_out = rows, *cols_out = fc;
+    return RMHIP_OK;
+}
+
 // the analytic-signal mask of hilbert (builtins/math/signal/hilbert.rs:349-412): the spectrum times 1 at frequency 0 (and at n / 2 for even n),
 // 2 on the positive half, 0 on the negative half - in place, tensor layout [inner, n, outer]
 __global__ void __launch_bounds__(FT) k_hilbert_mask(double2* __restrict__ a, u64 inner, u64 n, u64 total) {
@@ -753,6 +952,14 @@ extern "C" {
 int rmhip_fft_dim(rmhip_ctx* ctx, rmhip_buf a, long long len_or_neg, int dim, int inverse, rmhip_buf* out) {
     CTX_OR_FAIL(ctx);
     return fft_entry(c, a, len_or_neg, dim, inverse != 0, out);
+}
+
+int rmhip_spectral_estimate(rmhip_ctx* ctx, rmhip_buf input, size_t input_len, int input_complex, const double* window, size_t window_len, size_t nfft, size_t frame_count,
+                            int frame_mode, size_t hop, size_t input_rows, size_t frames_per_column, int range, double denominator, rmhip_buf* s, rmhip_buf* ps, size_t* rows,
+                            size_t* cols) {
+    CTX_OR_FAIL(ctx);
+    const SpectralArgs a{input_len, window_len, nfft, frame_count, hop, input_rows, frames_per_column, input_complex, frame_mode, range, denominator, window};
+    return spectral_entry(c, input, a, s, ps, rows, cols);
 }
 
 int rmhip_hilbert(rmhip_ctx* ctx, rmhip_buf a, long long len_or_neg, int dim, rmhip_buf* out) {

@@ -166,6 +166,57 @@ class ProviderEigResult:
     left: Optional[GpuTensorHandle] = None
 
 
+class ProviderSpectralRange:
+    """`ProviderSpectralRange` (lib.rs:266-271); the values are rmhip_spectral_estimate's `range` codes."""
+    Onesided = 0
+    Twosided = 1
+    Centered = 2
+
+
+@dataclass(frozen=True)
+class ProviderSpectralFrameMode:
+    """`ProviderSpectralFrameMode` (lib.rs:273-286): how frame c is cut from the signal; `code` is rmhip_spectral_estimate's `frame_mode`."""
+    code: int
+    hop: int = 0
+    input_rows: int = 0
+    frames_per_column: int = 0
+
+    @staticmethod
+    def Sliding(hop: int) -> "ProviderSpectralFrameMode":
+        return ProviderSpectralFrameMode(0, hop=int(hop))
+
+    @staticmethod
+    def ColumnSliding(hop: int, input_rows: int, frames_per_column: int) -> "ProviderSpectralFrameMode":
+        return ProviderSpectralFrameMode(1, int(hop), int(input_rows), int(frames_per_column))
+
+    @staticmethod
+    def FoldedColumns(input_rows: int) -> "ProviderSpectralFrameMode":
+        return ProviderSpectralFrameMode(2, input_rows=int(input_rows))
+
+
+@dataclass
+class ProviderSpectralRequest:
+    """`ProviderSpectralRequest` (lib.rs:288-299); `window` is host data."""
+    input: GpuTensorHandle
+    input_len: int
+    input_complex: bool
+    window: Sequence[float]
+    nfft: int
+    frame_count: int
+    frame_mode: ProviderSpectralFrameMode
+    range: int
+    denominator: float
+
+
+@dataclass
+class ProviderSpectralResult:
+    """`ProviderSpectralResult` (lib.rs:301-307): `s` complex-interleaved [rows, cols], `ps` real [rows, cols]."""
+    s: GpuTensorHandle
+    ps: GpuTensorHandle
+    rows: int
+    cols: int
+
+
 @dataclass
 class ProviderLinsolveOptions:
     """lib.rs:679-690"""
@@ -1500,6 +1551,20 @@ class HipProvider:
         out = C.c_uint64()
         self._check(self._lib.rmhip_hilbert(self._ctx, self._id(input), -1 if length is None else int(length), int(dim), C.byref(out)))
         return self._handle(out.value)
+
+    def uniform_spectral_estimate(self, request: ProviderSpectralRequest) -> ProviderSpectralResult:
+        """lib.rs:2560-2565: the framed, windowed spectra behind spectrogram / pwelch / periodogram - `s` (the selected rows of every
+        frame's DFT) and `ps` (their scaled powers); rmhip.h states the framing, selection and scaling rules.  An invalid request
+        raises with code INVALID (what `validate_uniform_spectral_request` refuses) and leaves nothing behind."""
+        w = np.ascontiguousarray(np.asarray(request.window, dtype=np.float64).reshape(-1))
+        m = request.frame_mode
+        s, ps, rows, cols = C.c_uint64(), C.c_uint64(), C.c_size_t(), C.c_size_t()
+        self._check(self._lib.rmhip_spectral_estimate(self._ctx, self._id(request.input), int(request.input_len), 1 if request.input_complex else 0,
+                                                      w.ctypes.data_as(C.POINTER(C.c_double)), w.size, int(request.nfft), int(request.frame_count), int(m.code),
+                                                      int(m.hop), int(m.input_rows), int(m.frames_per_column), int(request.range), float(request.denominator),
+                                                      C.byref(s), C.byref(ps), C.byref(rows), C.byref(cols)))
+        shape = (int(rows.value), int(cols.value))
+        return ProviderSpectralResult(self._handle(s.value, shape), self._handle(ps.value, shape), *shape)
 
     def fft_extract_real(self, handle) -> GpuTensorHandle:
         """lib.rs:2639-2644: the real parts of a complex tensor as a real tensor."""

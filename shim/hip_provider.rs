@@ -17,7 +17,7 @@ use runmat_accelerate_api::{
     AccelProvider, AccelProviderFuture, ApiDeviceInfo, CorrcoefNormalization, CorrcoefOptions, CorrcoefRows, CovNormalization, CovRows, CovarianceOptions, FindDirection, GpuTensorHandle, GpuTensorStorage,
     HostLogicalOwned, HostTensorOwned, HostTensorView, IsMemberOptions, IsMemberResult, SetdiffOptions, SetdiffOrder, SetdiffResult, UnionOptions, UnionOrder, UnionResult, UniqueOccurrence, UniqueOptions, UniqueOrder, UniqueResult, ImageNormalizeDescriptor, ImfilterMode, ImfilterOptions, ImfilterPadding, ImfilterShape, KernelAttrTelemetry, MeshgridAxisView, ProviderMeshgridResult, ProviderPolyderQuotient, ProviderPolyvalOptions, KernelLaunchTelemetry, MatmulEpilogue,
     PowerStepEpilogue, ProviderBandwidth, ProviderCovarianceToCorrelationResult, ProviderHilbertRequest, ProviderCondNorm, ProviderPinvOptions, ProviderIirFilterOptions, ProviderIirFilterResult, ProviderInterp1Extrapolation, ProviderInterp1Method, ProviderInterp1Request, ProviderConv1dOptions, ProviderConvMode, ProviderConvOrientation, ProviderCholResult, ProviderCummaxResult, ProviderCumminResult, ProviderDispatchStats, ProviderInvOptions, ProviderFallbackStat, ProviderFindResult, ProviderHermitianKind, ProviderLinsolveOptions,
-    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
+    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest, ProviderSpectralResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
     ProviderAdamUpdateRequest, ProviderAdamUpdateResult, ProviderBlackScholesPriceRequest, ProviderBlackScholesPriceResult, ProviderCrossentropyMode, ProviderCrossentropyRequest, ProviderCrossentropyResult,
     ProviderStdNormalization, ProviderSymmetryKind, ProviderTelemetry, ProviderTrapezoidSpacing, ReduceDimResult, ReductionFlavor, ScaleOp, SortComparison, SortOrder, SortResult, SortRowsColumnSpec,
 };
@@ -1042,6 +1042,29 @@ impl AccelProvider for HipProvider {
             let len = request.length.map(|l| l as i64).unwrap_or(-1);
             check(unsafe { rmhip_hilbert(self.ctx, self.own(request.input)?, len, request.dim as c_int, &mut out) })?;
             self.complex_handle(out)
+        })
+    }
+    // uniform_spectral_estimate: spectrogram (Sliding) / pwelch (ColumnSliding) / periodogram (FoldedColumns); Err for what
+    // validate_uniform_spectral_request refuses and for lengths the transforms do not take -> the builtins' host path
+    fn uniform_spectral_estimate<'a>(&'a self, _request: &'a ProviderSpectralRequest<'a>) -> AccelProviderFuture<'a, ProviderSpectralResult> {
+        Box::pin(async move {
+            let (mode, hop, input_rows, fpc) = match _request.frame_mode {
+                ProviderSpectralFrameMode::Sliding { hop } => (0, hop, 0, 0),
+                ProviderSpectralFrameMode::ColumnSliding { hop, input_rows, frames_per_column } => (1, hop, input_rows, frames_per_column),
+                ProviderSpectralFrameMode::FoldedColumns { input_rows } => (2, 0, input_rows, 0),
+            };
+            let range = match _request.range {
+                ProviderSpectralRange::Onesided => 0,
+                ProviderSpectralRange::Twosided => 1,
+                ProviderSpectralRange::Centered => 2,
+            };
+            let (mut s, mut ps, mut rows, mut cols) = (0u64, 0u64, 0usize, 0usize);
+            check(unsafe {
+                rmhip_spectral_estimate(self.ctx, self.own(_request.input)?, _request.input_len, _request.input_complex as c_int, _request.window.as_ptr(),
+                                        _request.window.len(), _request.nfft, _request.frame_count, mode, hop, input_rows, fpc, range, _request.denominator,
+                                        &mut s, &mut ps, &mut rows, &mut cols)
+            })?;
+            Ok(ProviderSpectralResult { s: self.complex_handle(s)?, ps: self.handle(ps)?, rows, cols })
         })
     }
     fn fft_extract_real<'a>(&'a self, handle: &'a GpuTensorHandle) -> AccelProviderFuture<'a, GpuTensorHandle> {
