@@ -99,6 +99,29 @@ int main() {
             }
         }
         {
+            // signal_envelope (lib.rs:2566-2571): rms over a centred window of 3 on [0 3 4 0] (envelope.rs rms_envelope_uses_centered_window),
+            // the analytic envelope of the alternating [1 0 -1 0] (|z| = 1 everywhere, mean 0), and a NaN sample refused as INVALID
+            rmhip::ProviderEnvelopeRequest q;
+            q.input = p.upload({0, 3, 4, 0}, {4, 1});
+            q.channel_len = 4, q.channel_count = 1, q.output_shape = {4, 1};
+            q.method.kind = rmhip::ProviderEnvelopeMethod::Rms, q.method.param = 3;
+            auto env = p.signal_envelope(q);
+            const double r = std::sqrt(25.0 / 3.0);
+            ok = ok && env.upper.shape == std::vector<size_t>{4, 1} && near(p.download(env.upper).data, {std::sqrt(4.5), r, r, std::sqrt(8.0)}, 1e-15) &&
+                 near(p.download(env.lower).data, {-std::sqrt(4.5), -r, -r, -std::sqrt(8.0)}, 1e-15);
+            q.input = p.upload({1, 0, -1, 0}, {4, 1});
+            q.method.kind = rmhip::ProviderEnvelopeMethod::Analytic;
+            env = p.signal_envelope(q);
+            ok = ok && near(p.download(env.upper).data, {1, 1, 1, 1}, 1e-14) && near(p.download(env.lower).data, {-1, -1, -1, -1}, 1e-14);
+            q.input = p.upload({1, std::nan(""), -1, 0}, {4, 1});
+            try {
+                p.signal_envelope(q);
+                ok = false;
+            } catch (const rmhip::ProviderError& e) {
+                ok = ok && e.code == RMHIP_ERR_INVALID;
+            }
+        }
+        {
             // ProviderPrecision::F32 (lib.rs:815-818): host views stay f64, storage is f32, results round once
             rmhip::HipProvider q(0, 32);
             ok = ok && std::string(q.precision()) == "F32";

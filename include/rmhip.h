@@ -578,6 +578,41 @@ RMHIP_API int rmhip_hilbert(rmhip_ctx* ctx, rmhip_buf a, long long len_or_neg, i
 RMHIP_API int rmhip_spectral_estimate(rmhip_ctx* ctx, rmhip_buf input, size_t input_len, int input_complex, const double* window, size_t window_len, size_t nfft,
                                       size_t frame_count, int frame_mode, size_t hop, size_t input_rows, size_t frames_per_column, int range, double denominator,
                                       rmhip_buf* s, rmhip_buf* ps, size_t* rows, size_t* cols);
+/* `signal_envelope(request)` (lib.rs:2566-2571; `ProviderEnvelopeRequest { input, channel_len, channel_count, output_shape, method }` ->
+ * `ProviderEnvelopeResult { upper, lower }`, lib.rs:310-329): the hook behind `envelope` for the analytic (default), analytic with a filter
+ * length, and rms methods (CPU builtin: builtins/math/signal/envelope.rs; `peak` gathers by design).  `method` 0 is Analytic, 1 is
+ * AnalyticFir { filter_len = param }, 2 is Rms { window_len = param }; `param` is ignored for method 0.
+ * The input is a real tensor of n * m elements, n = channel_len, m = channel_count; channel c is elements c*n .. c*n + n - 1 of the
+ * storage.  `upper` and `lower` are real tensors of shape `out_shape`.  Per channel, with x its samples:
+ *   method 0 (Analytic)     mu = sum(x) / n, c_i = x_i - mu, z = ifft(fft(c) .* mask) with the one-sided mask of `rmhip_hilbert`
+ *                           (1, 2 ... 2, [1], 0 ... 0); upper_i = mu + |z_i|, lower_i = mu - |z_i|.  n == 1: upper = lower = x.
+ *                           The signal is centred BEFORE the transform (never transformed whole with bin 0 cleared): a signal riding
+ *                           on a large offset otherwise loses its envelope to the rounding of the offset's spectrum.
+ *   method 1 (AnalyticFir)  mu and c as above; q_i = sum over t = 0 .. L-1 with 0 <= i + t - floor(L/2) < n of c[i + t - floor(L/2)] * k[t],
+ *                           added in ascending t; upper / lower = mu +- hypot(c_i, q_i).  The sum is a correlation aligned at floor(L/2),
+ *                           not at the symmetric centre (asymmetric for even L), as the builtin has it.  Taps k[t] = ideal(t - (L-1)/2) *
+ *                           kaiser(t): ideal(k) = 0 for k = 0 and for even integer k, else 2 / (pi k); kaiser(t) = I0(8 sqrt(max(0, 1 - r^2)))
+ *                           / I0(8), r = 2t / (L-1) - 1, and 1 when L <= 1; I0(x) is the power series sum (x^2/4)^j / (j!)^2 stopped after
+ *                           32 terms or when a term is <= 1e-15 of the sum.  The taps are computed on the host in f64 in exactly that
+ *                           operation order (no contraction) and uploaded.
+ *   method 2 (Rms)          hb = (w-1)/2, ha = w/2 (integer division), s = max(0, i - hb), e = min(n, i + ha + 1); upper_i =
+ *                           sqrt((sum over j = s .. e-1 of x_j^2) / (e - s)), added in ascending j; lower_i = -upper_i.  No mean is removed.
+ *                           The CPU forms the window sum as a difference of two prefix sums; the direct sum here is the more accurate of
+ *                           the two, and parity is by tolerance.
+ * The mean is a tree sum, not the CPU's serial one: parity of methods 0 and 1 is by tolerance too (tests/test_gpu_envelope.py derives the bounds).
+ * RMHIP_ERR_INVALID: null outputs; an unknown method; n == 0 or m == 0; L == 0 or w == 0; n * m or prod(out_shape) overflowing;
+ * prod(out_shape) != n * m, or n * m differing from the tensor's element count; an input shape that is neither [n, m] nor, for m == 1, one
+ * of [n], [n, 1], [1, n]; any NaN or +-Inf in the input (the builtin raises InvalidSignal for those; on this `Err` it gathers and raises
+ * exactly that).  The last is found on the device in the pass that forms the means; the call reads one verdict word back.
+ * RMHIP_ERR_UNSUPPORTED: a complex input; for method 0 a channel length beyond what `rmhip_fft_dim` transforms along dimension 0 (a power of
+ * two above 2^27, any other length above 2^23); for methods 1 and 2 more than 2^36 products n * min(L or w, n) * m - a cap, not a
+ * measurement: a few milliseconds of fp64 VALU work by the issue rate in README.md (an unmeasured estimate), past which the CPU's O(n)
+ * prefix form wins; more workgroups than a launch takes.  Nothing is allocated or left behind on any error path.
+ * Precision-32 context: the f32 storage is read in place, arithmetic is f64 - the transform included, as `rmhip_fft_dim` does it - and
+ * each output is rounded once on store. */
+/* @serves signal_envelope */
+RMHIP_API int rmhip_signal_envelope(rmhip_ctx* ctx, rmhip_buf input, size_t channel_len, size_t channel_count, const size_t* out_shape, size_t out_rank, int method,
+                                    size_t param, rmhip_buf* upper, rmhip_buf* lower);
 /* `complex_from_real(real)` (imag_or_0 == 0) / `complex_from_real_imag(real, imag)` (lib.rs:1940-1959): equal shapes, or either
  * operand a one-element tensor that expands. */
 /* @serves complex_from_real complex_from_real_imag */

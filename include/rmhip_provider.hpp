@@ -107,6 +107,21 @@ struct ProviderSpectralResult {
     size_t rows = 0, cols = 0;
 };
 
+// lib.rs:310-329: the request of signal_envelope and its result
+struct ProviderEnvelopeMethod {
+    enum Kind { Analytic = 0, AnalyticFir = 1, Rms = 2 } kind = Analytic;
+    size_t param = 0;  // AnalyticFir: filter_len; Rms: window_len
+};
+struct ProviderEnvelopeRequest {
+    GpuTensorHandle input;
+    size_t channel_len = 0, channel_count = 0;
+    std::vector<size_t> output_shape;
+    ProviderEnvelopeMethod method;
+};
+struct ProviderEnvelopeResult {
+    GpuTensorHandle upper, lower;  // real, the request's output_shape
+};
+
 class HipProvider {
 public:
     // precision_bits: 64 or 32 (ProviderPrecision, lib.rs:815-818), fixed for the provider's lifetime
@@ -988,6 +1003,14 @@ public:
                                       (int)q.frame_mode.kind, q.frame_mode.hop, q.frame_mode.input_rows, q.frame_mode.frames_per_column, (int)q.range, q.denominator,
                                       &s, &ps, &rows, &cols));
         return ProviderSpectralResult{with_shape(s), with_shape(ps), rows, cols};
+    }
+    // lib.rs:2566-2571: upper and lower envelope of every channel (rmhip.h states the three methods); throws INVALID or UNSUPPORTED for
+    // what the header lists as refused, a NaN / Inf sample among the former
+    ProviderEnvelopeResult signal_envelope(const ProviderEnvelopeRequest& q) const {
+        uint64_t upper = 0, lower = 0;
+        check(rmhip_signal_envelope(ctx_, own(q.input), q.channel_len, q.channel_count, q.output_shape.data(), q.output_shape.size(), (int)q.method.kind,
+                                    q.method.param, &upper, &lower));
+        return ProviderEnvelopeResult{with_shape(upper), with_shape(lower)};
     }
     GpuTensorHandle fft_extract_real(const GpuTensorHandle& a) const {
         uint64_t out = 0;

@@ -7,6 +7,7 @@
 //   interp1           lib.rs:2458-2463    (runmat-accelerate/src/simple_provider.rs:1396-1472, 8135-8204)
 //   polyval           lib.rs:1652-1660    (builtins/math/poly/polyval.rs:886-905, 352-435)
 //   moving_window     lib.rs:2852-2857    (builtins/math/reduction/moving.rs:737-825, 929-1003, 1198-1237, 1282-1323)
+//   signal_envelope   lib.rs:310-329, 2566-2571   (builtins/math/signal/envelope.rs)
 // The convolutions are DIRECT sums in the CPU's order (output n receives a[i] * b[n - i] for i ascending, every product rounded before it
 // is added - this file keeps contraction off): bit-exact against the oracle.  One thread per output point, neighbouring threads read
 // neighbouring signal points, the kernel operand is staged in LDS when it fits.
@@ -632,7 +633,324 @@ __global__ void __launch_bounds__(kB) k_poly_first(const double* __restrict__ x,
     if (threadIdx.x == 0) *first = best;
 }
 
+// ---- signal_envelope (lib.rs:310-329, :2566-2571; builtins/math/signal/envelope.rs) ----------------------------------------------------
+// rmhip.h states the three methods.  The tensor is m channels of n consecutive samples.  k_env_stats sums every channel and looks for
+// non-finite samples in the same pass; the mean goes to every later kernel as a table of m doubles.  Analytic: k_env_center writes
+// x - mu, the library's own rmhip_hilbert transforms it, k_env_bounds forms mu +- |z|.  AnalyticFir / Rms: one thread per output walks
+// its taps or its window in ascending order, every product rounded before it is added, over samples a workgroup staged in LDS once.
+// T is the storage type read in place (f32 on a precision-32 context), TO the storage type of the results; arithmetic is f64.
+typedef double env_v2d __attribute__((ext_vector_type(2)));
+typedef float env_v4f __attribute__((ext_vector_type(4)));
+template <class T>
+struct EnvVec;
+template <>
+struct EnvVec<double> {
+    typedef env_v2d type;
+    static constexpr int N = 2;
+};
+template <>
+struct EnvVec<float> {
+    typedef env_v4f type;
+    static constexpr int N = 4;
+};
+
+constexpr u64 ENV_WAVE_MAX = 4096;        // channels shorter than this are summed by one wave each, longer ones by `parts` workgroups
+constexpr u64 ENV_PART_MIN = 8192;        // samples per workgroup at least, when a channel is split
+constexpr u64 ENV_PARTS_MAX = 64;
+constexpr size_t ENV_LDS_BYTES = 48u * 1024;  // staged samples + taps of k_env_fir / k_env_rms; beyond it they read global memory
+constexpr u64 ENV_WORK_MAX = 1ull << 36;  // products of the direct FIR / RMS sums (rmhip.h: a cap, not a measurement)
+
+// the channel of flat element e (a 64-bit division is ~40 instructions: 32-bit when the tensor has fewer than 2^32 elements)
+__device__ __forceinline__ u64 env_channel(u64 e, u64 n, u64 total) {
+    return total <= 0xffffffffull ? (u64)((unsigned)e / (unsigned)n) : e / n;
+}
+
+// sums[c * parts + p] = the sum of part p of channel c (divided by `divisor` when that is not 0), *verdict lowered to 0 when any
+// sample is NaN or +-Inf.  A team - one wave when per_wave, else the workgroup - owns one (channel, part): scalar loads up to the first
+// 16-byte boundary, 16-byte loads (four in flight per lane) from there, scalar loads for the rest; lanes are added in a fixed tree.
+// Every failing team stores the same word: a plain store, no atomic.
+template <class T>
+__global__ void __launch_bounds__(kB) k_env_stats(const T* __restrict__ x, u64 n, u64 m, u64 parts, u64 part_len, int per_wave, double divisor,
+                                                  double* __restrict__ sums, unsigned* __restrict__ verdict) {
+    typedef typename EnvVec<T>::type V;
+    constexpr int N = EnvVec<T>::N;
+    __shared__ double wave_sum[kB / 64];
+    __shared__ int wave_bad[kB / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 team = per_wave ? (u64)blockIdx.x * (kB / 64) + wave : (u64)blockIdx.x;
+    const unsigned tid = per_wave ? lane : threadIdx.x, tsize = per_wave ? 64 : kB;
+    const bool live = team < m * parts;
+    double acc = 0.0;
+    bool bad = false;
+    if (live) {
+        const u64 c = team / parts, p = team - c * parts;
+        const u64 lo = p * part_len, hi = lo + part_len < n ? lo + part_len : n;
+        const T* src = x + c * n + lo;
+        const u64 len = hi > lo ? hi - lo : 0;
+        u64 head = ((16 - ((uintptr_t)src & 15)) & 15) / sizeof(T);
+        if (head > len) head = len;
+        const u64 nvec = (len - head) / N;
+        for (u64 i = tid; i < head; i += tsize) {
+            const double v = (double)src[i];
+            bad |= !__builtin_isfinite(v);
+            acc = acc + v;
+        }
+        const V* body = reinterpret_cast<const V*>(src + head);
+        for (u64 i0 = tid; i0 < nvec; i0 += 4ull * tsize) {
+            V v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const u64 i = i0 + (u64)u * tsize;
+                v[u] = V{};
+                if (i < nvec) v[u] = __builtin_nontemporal_load(body + i);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int l = 0; l < N; ++l) {
+                    const double s = (double)v[u][l];
+                    bad |= !__builtin_isfinite(s);
+                    acc = acc + s;
+                }
+        }
+        for (u64 i = head + nvec * N + tid; i < len; i += tsize) {
+            const double v = (double)src[i];
+            bad |= !__builtin_isfinite(v);
+            acc = acc + v;
+        }
+    }
+    int flag = bad ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc = acc + __shfl_xor(acc, o);
+        flag |= __shfl_xor(flag, o);
+    }
+    if (!per_wave) {
+        if (lane == 0) wave_sum[wave] = acc, wave_bad[wave] = flag;
+        __syncthreads();
+        if (threadIdx.x != 0) return;
+        acc = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+        flag = wave_bad[0] | wave_bad[1] | wave_bad[2] | wave_bad[3];
+    } else if (lane != 0) {
+        return;
+    }
+    if (!live) return;
+    sums[team] = divisor != 0.0 ? acc / divisor : acc;
+    if (flag && verdict) *verdict = 0u;
+}
+
+template <class T>
+__global__ void __launch_bounds__(kB) k_env_center(const T* __restrict__ x, const double* __restrict__ mu, u64 n, u64 total, double* __restrict__ out) {
+    const u64 e = (u64)blockIdx.x * kB + threadIdx.x;
+    if (e >= total) return;
+    out[e] = (double)x[e] - mu[env_channel(e, n, total)];
+}
+
+// upper = mu + |z|, lower = mu - |z|; z == nullptr (one-sample channels): |z| = 0, both are the sample itself
+template <class TO>
+__global__ void __launch_bounds__(kB) k_env_bounds(const double2* __restrict__ z, const double* __restrict__ mu, u64 n, u64 total, TO* __restrict__ upper,
+                                                   TO* __restrict__ lower) {
+    const u64 e = (u64)blockIdx.x * kB + threadIdx.x;
+    if (e >= total) return;
+    const double mean = mu[env_channel(e, n, total)];
+    double mag = 0.0;
+    if (z) {
+        const double2 v = z[e];
+        mag = hypot(v.x, v.y);
+    }
+    upper[e] = (TO)(mean + mag);
+    lower[e] = (TO)(mean - mag);
+}
+
+// The samples a workgroup's kB outputs read: flat elements [base, base + count) of the tensor, base = e0 - before (not below 0), as f64
+// in LDS (squared for the RMS sum).  The range is clamped to the TENSOR here, for the loads' sake; every thread clamps its own taps to
+// its CHANNEL, so a sample of a neighbouring channel that happens to be staged is never read.
+template <class T, bool SQUARE>
+__device__ __forceinline__ u64 env_stage(const T* __restrict__ x, u64 e0, u64 before, u64 after, u64 total, double* __restrict__ tile) {
+    const u64 base = e0 >= before ? e0 - before : 0;
+    u64 end = e0 + kB + after;
+    if (end > total) end = total;
+    const unsigned count = (unsigned)(end - base);
+    for (unsigned j = threadIdx.x; j < count; j += kB) {
+        const double v = (double)x[base + j];
+        tile[j] = SQUARE ? v * v : v;
+    }
+    return base;
+}
+
+// AnalyticFir: q_i = sum over t ascending of (x[i + t - half] - mu) * k[t] for the taps whose sample lies in the channel, then
+// mu +- hypot(x_i - mu, q_i).  `taps` holds k[t0 .. t0 + ntaps): the only taps some output of an n-sample channel can reach.
+// before / after: the halo (already limited to n - 1) staged on either side when in_lds.
+template <class T, class TO>
+__global__ void __launch_bounds__(kB) k_env_fir(const T* __restrict__ x, const double* __restrict__ mu, const double* __restrict__ taps, u64 n, u64 total, u64 filter_len,
+                                                u64 half, u64 t0, unsigned ntaps, u64 before, u64 after, int in_lds, TO* __restrict__ upper, TO* __restrict__ lower) {
+    extern __shared__ double tile[];
+    const u64 e0 = (u64)blockIdx.x * kB;
+    u64 base = 0;
+    double* ktile = tile;
+    if (in_lds) {
+        base = env_stage<T, false>(x, e0, before, after, total, tile);
+        ktile = tile + (kB + before + after);
+        for (unsigned j = threadIdx.x; j < ntaps; j += kB) ktile[j] = taps[j];
+        __syncthreads();
+    }
+    const u64 e = e0 + threadIdx.x;
+    if (e >= total) return;
+    const u64 c = env_channel(e, n, total), i = e - c * n;
+    const double mean = mu[c];
+    // taps t_lo .. t_hi: 0 <= i + t - half < n and t < filter_len
+    const u64 t_lo = half > i ? half - i : 0;
+    u64 t_hi = (n - 1 - i) + half;
+    if (t_hi > filter_len - 1) t_hi = filter_len - 1;
+    double q = 0.0;
+    if (t_hi >= t_lo) {
+        const unsigned cnt = (unsigned)(t_hi - t_lo + 1);
+        const u64 first = e + t_lo - half;  // flat index of the first sample: inside the channel
+        if (in_lds) {
+            const double* sp = tile + (first - base);
+            const double* kp = ktile + (t_lo - t0);
+#pragma unroll 4
+            for (unsigned k = 0; k < cnt; ++k) {
+                const double p = (sp[k] - mean) * kp[k];
+                q = q + p;
+            }
+        } else {
+            const T* sp = x + first;
+            const double* kp = taps + (t_lo - t0);
+#pragma unroll 4
+            for (unsigned k = 0; k < cnt; ++k) {
+                const double p = ((double)sp[k] - mean) * kp[k];
+                q = q + p;
+            }
+        }
+    }
+    const double re = (in_lds ? tile[e - base] : (double)x[e]) - mean;
+    const double mag = n == 1 ? 0.0 : hypot(re, q);
+    upper[e] = (TO)(mean + mag);
+    lower[e] = (TO)(mean - mag);
+}
+
+// Rms: upper_i = sqrt(sum of x_j^2 over j = s .. e - 1 ascending / (e - s)), s = max(0, i - hb), e = min(n, i + ha + 1); lower = -upper.
+// No mean is removed.  before / after: min(hb, n - 1) and min(ha, n - 1).
+template <class T, class TO>
+__global__ void __launch_bounds__(kB) k_env_rms(const T* __restrict__ x, u64 n, u64 total, u64 before, u64 after, int in_lds, TO* __restrict__ upper,
+                                                TO* __restrict__ lower) {
+    extern __shared__ double tile[];
+    const u64 e0 = (u64)blockIdx.x * kB;
+    u64 base = 0;
+    if (in_lds) {
+        base = env_stage<T, true>(x, e0, before, after, total, tile);
+        __syncthreads();
+    }
+    const u64 e = e0 + threadIdx.x;
+    if (e >= total) return;
+    const u64 c = env_channel(e, n, total), i = e - c * n;
+    const u64 s = i > before ? i - before : 0;  // (before = min(hb, n - 1): the same start)
+    const u64 stop = i + after + 1 < n ? i + after + 1 : n;
+    const unsigned cnt = (unsigned)(stop - s);
+    const u64 first = c * n + s;
+    double acc = 0.0;
+    if (in_lds) {
+        const double* sp = tile + (first - base);
+#pragma unroll 4
+        for (unsigned k = 0; k < cnt; ++k) acc = acc + sp[k];
+    } else {
+        const T* sp = x + first;
+#pragma unroll 4
+        for (unsigned k = 0; k < cnt; ++k) {
+            const double v = (double)sp[k];
+            const double p = v * v;
+            acc = acc + p;
+        }
+    }
+    const double r = sqrt(acc / (double)cnt);
+    const TO up = (TO)r;
+    upper[e] = up;
+    lower[e] = -up;
+}
+
+// modified Bessel function I0 as envelope.rs sums it: at most 32 further terms, stopped when a term is <= 1e-15 of the sum
+double env_bessel_i0(double x) {
+    const double y = x * x / 4.0;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k <= 32; ++k) {
+        term *= y / (double)(k * k);
+        sum += term;
+        if (std::fabs(term) <= std::fabs(sum) * 1.0e-15) break;
+    }
+    return sum;
+}
+
+// tap t of the Kaiser-windowed (beta 8) Hilbert transformer of `len` taps (envelope.rs hilbert_fir_kernel), in its operation order
+double env_fir_tap(u64 t, u64 len) {
+    const double center = ((double)len - 1.0) / 2.0;
+    const double k = (double)t - center;
+    double ideal;
+    if (std::fabs(k) <= 1.0e-12) {
+        ideal = 0.0;
+    } else {
+        const double rounded = std::round(k);
+        if (std::fabs(rounded - k) <= 1.0e-12 && std::fmod(std::fabs(rounded), 2.0) == 0.0) ideal = 0.0;
+        else ideal = 2.0 / (3.14159265358979323846 * k);
+    }
+    double window = 1.0;
+    if (len > 1) {
+        const double ratio = 2.0 * (double)t / (double)(len - 1) - 1.0;
+        const double argument = 8.0 * std::sqrt(std::max(1.0 - ratio * ratio, 0.0));
+        window = env_bessel_i0(argument) / env_bessel_i0(8.0);
+    }
+    return ideal * window;
+}
+
+struct EnvPrecision64 {  // the analytic path's transform runs in f64 on a precision-32 context too (rmhip.h): held for the nested call
+    Context* c;
+    int saved;
+    explicit EnvPrecision64(Context* ctx) : c(ctx), saved(ctx->precision) { c->precision = 64; }
+    ~EnvPrecision64() { c->precision = saved; }
+};
+
 inline unsigned grid_for(u64 n) { return (unsigned)((n + kB - 1) / kB); }
+
+// per-channel means of the [n, m] tensor into mu[0 .. m), the verdict word lowered when a sample is not finite
+template <class T>
+int env_means(Context* c, const T* x, u64 n, u64 m, double* mu, double* partial, u64 parts, u64 part_len, unsigned* verdict) {
+    if (parts == 1) {
+        const int per_wave = n < ENV_WAVE_MAX;
+        const u64 blocks = per_wave ? (m + kB / 64 - 1) / (kB / 64) : m;
+        hipLaunchKernelGGL(k_env_stats<T>, dim3((unsigned)blocks), dim3(kB), 0, c->stream, x, n, m, (u64)1, n, per_wave, (double)n, mu, verdict);
+        c->tel.kernel_launches++;
+    } else {
+        hipLaunchKernelGGL(k_env_stats<T>, dim3((unsigned)(m * parts)), dim3(kB), 0, c->stream, x, n, m, parts, part_len, 0, 0.0, partial, verdict);
+        // the parts of a channel, added by one wave, and the division by n
+        hipLaunchKernelGGL(k_env_stats<double>, dim3((unsigned)((m + kB / 64 - 1) / (kB / 64))), dim3(kB), 0, c->stream, (const double*)partial, parts, m, (u64)1, parts, 1,
+                           (double)n, mu, (unsigned*)nullptr);
+        c->tel.kernel_launches += 2;
+    }
+    RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
+}
+
+template <class T, class TO>
+int env_launch(Context* c, int method, const T* x, const double* mu, const double2* z, const double* taps, u64 n, u64 total, u64 param, u64 t0, unsigned ntaps,
+               TO* upper, TO* lower) {
+    const dim3 grid(grid_for(total)), block(kB);
+    if (method == 0) {
+        hipLaunchKernelGGL(k_env_bounds<TO>, grid, block, 0, c->stream, z, mu, n, total, upper, lower);
+    } else if (method == 1) {
+        const u64 half = param / 2, before = std::min<u64>(half, n - 1), after = std::min<u64>(param - 1 - half, n - 1);
+        const size_t bytes = (size_t)(kB + before + after + ntaps) * sizeof(double);
+        const int in_lds = bytes <= ENV_LDS_BYTES;
+        hipLaunchKernelGGL((k_env_fir<T, TO>), grid, block, in_lds ? bytes : 0, c->stream, x, mu, taps, n, total, param, half, t0, ntaps, before, after, in_lds, upper, lower);
+    } else {
+        const u64 before = std::min<u64>((param - 1) / 2, n - 1), after = std::min<u64>(param / 2, n - 1);
+        const size_t bytes = (size_t)(kB + before + after) * sizeof(double);
+        const int in_lds = bytes <= ENV_LDS_BYTES;
+        hipLaunchKernelGGL((k_env_rms<T, TO>), grid, block, in_lds ? bytes : 0, c->stream, x, n, total, before, after, in_lds, upper, lower);
+    }
+    c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
+}
 
 }  // namespace
 }  // namespace rmhip
@@ -1073,6 +1391,128 @@ int rmhip_window(rmhip_ctx* ctx, int kind, size_t len, int periodic, rmhip_buf* 
     hipLaunchKernelGGL(k_window, dim3(grid_for(len)), dim3(kB), 0, c->stream, kind, (u64)len, denom, ob.data());
     c->tel.kernel_launches++;
     RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
+}
+
+int rmhip_signal_envelope(rmhip_ctx* ctx, rmhip_buf input, size_t channel_len, size_t channel_count, const size_t* out_shape, size_t out_rank, int method, size_t param,
+                          rmhip_buf* upper, rmhip_buf* lower) {
+    CTX_OR_FAIL(ctx);
+    if (!upper || !lower || (out_rank && !out_shape)) return fail(RMHIP_ERR_INVALID, "signal_envelope: null argument");
+    *upper = *lower = 0;
+    if (method < 0 || method > 2) return fail(RMHIP_ERR_INVALID, "signal_envelope: method %d", method);
+    const u64 n = channel_len, m = channel_count;
+    if (n == 0 || m == 0) return fail(RMHIP_ERR_INVALID, "signal_envelope: empty signal");
+    if (method != 0 && param == 0) return fail(RMHIP_ERR_INVALID, "signal_envelope: %s must be positive", method == 1 ? "filter length" : "window length");
+    size_t total = 0, out_total = 1;
+    if (__builtin_mul_overflow(channel_len, channel_count, &total)) return fail(RMHIP_ERR_INVALID, "signal_envelope: signal size exceeds provider limits");
+    for (size_t d = 0; d < out_rank; ++d)
+        if (__builtin_mul_overflow(out_total, out_shape[d], &out_total)) return fail(RMHIP_ERR_INVALID, "signal_envelope: output size exceeds provider limits");
+    if (out_total != total) return fail(RMHIP_ERR_INVALID, "signal_envelope: output shape does not hold channel_len * channel_count elements");
+    Buffer raw;
+    RMHIP_TRY(c->lookup(input, &raw));
+    if (raw.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "signal_envelope: complex input is not supported");
+    if (raw.numel != total) return fail(RMHIP_ERR_INVALID, "signal_envelope: the signal holds %zu elements, the request names %zu", raw.numel, total);
+    {
+        const std::vector<size_t>& s = raw.shape;
+        const bool matrix = s.size() == 2 && s[0] == n && s[1] == m;
+        const bool vector = m == 1 && ((s.size() == 1 && s[0] == n) || (s.size() == 2 && ((s[0] == n && s[1] == 1) || (s[0] == 1 && s[1] == n))));
+        if (!matrix && !vector) return fail(RMHIP_ERR_INVALID, "signal_envelope: the signal's shape is not channel_len x channel_count");
+    }
+    if (method == 0) {
+        // what rmhip_fft_dim transforms along dimension 0: a power of two up to 2^27, any other length up to 2^23
+        const bool pow2 = (n & (n - 1)) == 0;
+        if (pow2 ? n > (1ull << 27) : n > (1ull << 23)) return fail(RMHIP_ERR_UNSUPPORTED, "signal_envelope: channel length %llu", n);
+    } else {
+        u64 work = 0;
+        if (__builtin_mul_overflow(n, std::min<u64>(param, n), &work) || __builtin_mul_overflow(work, m, &work) || work > ENV_WORK_MAX)
+            return fail(RMHIP_ERR_UNSUPPORTED, "signal_envelope: %llu x %llu samples under %zu taps: more than 2^36 products", n, m, param);
+    }
+    // a channel is summed by one wave, one workgroup, or - few long channels - by up to 64 workgroups and a second, tiny launch
+    u64 parts = 1, part_len = n;
+    if (n >= ENV_WAVE_MAX) {
+        parts = std::min<u64>(std::min<u64>(ENV_PARTS_MAX, std::max<u64>(1, n / ENV_PART_MIN)), std::max<u64>(1, (u64)c->num_cus * 4 / m));
+        part_len = (n + parts - 1) / parts;
+        parts = (n + part_len - 1) / part_len;
+    }
+    if (total > 0x7fffffffull * kB || m * parts > 0x7fffffffull) return fail(RMHIP_ERR_UNSUPPORTED, "signal_envelope: %llu channels of %llu samples", m, n);
+
+    Buffer xb;
+    bool in32 = c->precision == 32;
+    if (in32) RMHIP_TRY(get_operand(c, input, &xb, &in32));  // f32 storage read in place; anything else as f64
+    else RMHIP_TRY(c->get(input, &xb));
+    const bool out32 = c->precision == 32;
+
+    std::shared_ptr<Allocation> mu, partial, taps;
+    RMHIP_TRY(c->alloc_device(m, &mu));
+    if (parts > 1) RMHIP_TRY(c->alloc_device(m * parts, &partial));
+    if (!c->verdict_word) RMHIP_HIP_CHECK(hipMalloc((void**)&c->verdict_word, sizeof(unsigned)));
+    RMHIP_HIP_CHECK(hipMemsetAsync(c->verdict_word, 0xff, sizeof(unsigned), c->stream));
+    double* part_ptr = partial ? partial->ptr : nullptr;
+    RMHIP_TRY(in32 ? env_means<float>(c, xb.data_f32(), n, m, mu->ptr, part_ptr, parts, part_len, c->verdict_word)
+                   : env_means<double>(c, xb.data(), n, m, mu->ptr, part_ptr, parts, part_len, c->verdict_word));
+    unsigned code = 0xffffffffu;  // the call's one read-back: envelope.rs raises InvalidSignal for NaN / Inf, and so does the caller's host path
+    RMHIP_HIP_CHECK(hipMemcpyAsync(&code, c->verdict_word, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (code != 0xffffffffu) return fail(RMHIP_ERR_INVALID, "signal_envelope: the signal must contain finite values");
+
+    // the taps some output can reach: t in [half - (n - 1), half + n - 1], at most 2 n - 1 of them however long the filter
+    std::vector<double> host_taps;
+    u64 t0 = 0;
+    if (method == 1) {
+        const u64 half = param / 2;
+        t0 = half > n - 1 ? half - (n - 1) : 0;
+        const u64 t1 = std::min<u64>(param - 1, half + (n - 1));
+        host_taps.resize(t1 - t0 + 1);
+        for (u64 t = t0; t <= t1; ++t) host_taps[t - t0] = env_fir_tap(t, param);
+        RMHIP_TRY(c->alloc_device(host_taps.size(), &taps));
+        RMHIP_HIP_CHECK(hipMemcpyAsync(taps->ptr, host_taps.data(), host_taps.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+
+    Buffer ub, lb;
+    int rc = out32 ? c->new_buffer_f32(out_shape, out_rank, upper, &ub) : c->new_buffer(out_shape, out_rank, upper, &ub);
+    if (rc == RMHIP_OK) rc = out32 ? c->new_buffer_f32(out_shape, out_rank, lower, &lb) : c->new_buffer(out_shape, out_rank, lower, &lb);
+    rmhip_buf centred = 0, analytic = 0;
+    Buffer zb;
+    if (rc == RMHIP_OK && method == 0 && n > 1) {
+        Buffer cb;  // the centred [n, m] temporary: f64 in either precision mode, never queued for narrowing
+        cb.shape = {(size_t)n, (size_t)m};
+        cb.numel = total;
+        rc = c->alloc_device(total, &cb.alloc);
+        if (rc == RMHIP_OK) {
+            if (in32) hipLaunchKernelGGL(k_env_center<float>, dim3(grid_for(total)), dim3(kB), 0, c->stream, xb.data_f32(), mu->ptr, n, (u64)total, cb.data());
+            else hipLaunchKernelGGL(k_env_center<double>, dim3(grid_for(total)), dim3(kB), 0, c->stream, xb.data(), mu->ptr, n, (u64)total, cb.data());
+            c->tel.kernel_launches++;
+            if (hipGetLastError() != hipSuccess) rc = fail(RMHIP_ERR_HIP, "signal_envelope: launch failed");
+        }
+        if (rc == RMHIP_OK) rc = c->register_buffer(std::move(cb), &centred);
+        if (rc == RMHIP_OK) {
+            EnvPrecision64 hold(c);
+            rc = rmhip_hilbert(ctx, centred, -1, 0, &analytic);
+        }
+        if (centred) rmhip_free(ctx, centred);
+        if (rc == RMHIP_OK) rc = c->get_any(analytic, &zb);
+    }
+    if (rc == RMHIP_OK) {
+        const double2* z = zb.alloc ? reinterpret_cast<const double2*>(zb.data()) : nullptr;
+        const double* tp = taps ? taps->ptr : nullptr;
+        const unsigned ntaps = (unsigned)host_taps.size();
+        if (in32) rc = env_launch<float, float>(c, method, xb.data_f32(), mu->ptr, z, tp, n, total, param, t0, ntaps, ub.data_f32(), lb.data_f32());
+        else if (out32) rc = env_launch<double, float>(c, method, xb.data(), mu->ptr, z, tp, n, total, param, t0, ntaps, ub.data_f32(), lb.data_f32());
+        else rc = env_launch<double, double>(c, method, xb.data(), mu->ptr, z, tp, n, total, param, t0, ntaps, ub.data(), lb.data());
+    }
+    if (analytic) {
+        zb = Buffer();
+        rmhip_free(ctx, analytic);
+    }
+    if (rc != RMHIP_OK) {
+        if (*upper) rmhip_free(ctx, *upper);
+        if (*lower) rmhip_free(ctx, *lower);
+        *upper = *lower = 0;
+        return rc;
+    }
+    if (method == 0) c->record_launch("envelope", {{"channel_len", n}, {"channels", m}}, {{"analytic", 1}});
+    else if (method == 1) c->record_launch("envelope", {{"channel_len", n}, {"channels", m}}, {{"analytic_fir", param}});
+    else c->record_launch("envelope", {{"channel_len", n}, {"channels", m}}, {{"rms", param}});
     return RMHIP_OK;
 }
 

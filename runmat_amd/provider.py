@@ -217,6 +217,42 @@ class ProviderSpectralResult:
     cols: int
 
 
+@dataclass(frozen=True)
+class ProviderEnvelopeMethod:
+    """`ProviderEnvelopeMethod` (lib.rs:310-314): `code` is rmhip_signal_envelope's `method`, `param` the filter or window length."""
+    code: int
+    param: int = 0
+
+    @staticmethod
+    def Analytic() -> "ProviderEnvelopeMethod":
+        return ProviderEnvelopeMethod(0)
+
+    @staticmethod
+    def AnalyticFir(filter_len: int) -> "ProviderEnvelopeMethod":
+        return ProviderEnvelopeMethod(1, int(filter_len))
+
+    @staticmethod
+    def Rms(window_len: int) -> "ProviderEnvelopeMethod":
+        return ProviderEnvelopeMethod(2, int(window_len))
+
+
+@dataclass
+class ProviderEnvelopeRequest:
+    """`ProviderEnvelopeRequest` (lib.rs:316-323): `channel_count` channels of `channel_len` consecutive samples."""
+    input: GpuTensorHandle
+    channel_len: int
+    channel_count: int
+    output_shape: Sequence[int]
+    method: ProviderEnvelopeMethod
+
+
+@dataclass
+class ProviderEnvelopeResult:
+    """`ProviderEnvelopeResult` (lib.rs:325-329): two real tensors of the request's `output_shape`."""
+    upper: GpuTensorHandle
+    lower: GpuTensorHandle
+
+
 @dataclass
 class ProviderLinsolveOptions:
     """lib.rs:679-690"""
@@ -1565,6 +1601,17 @@ class HipProvider:
                                                       C.byref(s), C.byref(ps), C.byref(rows), C.byref(cols)))
         shape = (int(rows.value), int(cols.value))
         return ProviderSpectralResult(self._handle(s.value, shape), self._handle(ps.value, shape), *shape)
+
+    def signal_envelope(self, request: ProviderEnvelopeRequest) -> ProviderEnvelopeResult:
+        """lib.rs:2566-2571: the upper and lower envelope of every channel by the analytic, FIR-quadrature or RMS method; rmhip.h
+        states the three.  A request the header lists as refused raises with code INVALID (a NaN or Inf sample among them) or
+        UNSUPPORTED and leaves nothing behind."""
+        shape = tuple(int(d) for d in request.output_shape)
+        dims = (C.c_size_t * max(1, len(shape)))(*shape)
+        upper, lower = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.rmhip_signal_envelope(self._ctx, self._id(request.input), int(request.channel_len), int(request.channel_count), dims, len(shape),
+                                                    int(request.method.code), int(request.method.param), C.byref(upper), C.byref(lower)))
+        return ProviderEnvelopeResult(self._handle(upper.value, shape), self._handle(lower.value, shape))
 
     def fft_extract_real(self, handle) -> GpuTensorHandle:
         """lib.rs:2639-2644: the real parts of a complex tensor as a real tensor."""

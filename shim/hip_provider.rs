@@ -17,7 +17,7 @@ use runmat_accelerate_api::{
     AccelProvider, AccelProviderFuture, ApiDeviceInfo, CorrcoefNormalization, CorrcoefOptions, CorrcoefRows, CovNormalization, CovRows, CovarianceOptions, FindDirection, GpuTensorHandle, GpuTensorStorage,
     HostLogicalOwned, HostTensorOwned, HostTensorView, IsMemberOptions, IsMemberResult, SetdiffOptions, SetdiffOrder, SetdiffResult, UnionOptions, UnionOrder, UnionResult, UniqueOccurrence, UniqueOptions, UniqueOrder, UniqueResult, ImageNormalizeDescriptor, ImfilterMode, ImfilterOptions, ImfilterPadding, ImfilterShape, KernelAttrTelemetry, MeshgridAxisView, ProviderMeshgridResult, ProviderPolyderQuotient, ProviderPolyvalOptions, KernelLaunchTelemetry, MatmulEpilogue,
     PowerStepEpilogue, ProviderBandwidth, ProviderCovarianceToCorrelationResult, ProviderHilbertRequest, ProviderCondNorm, ProviderPinvOptions, ProviderIirFilterOptions, ProviderIirFilterResult, ProviderInterp1Extrapolation, ProviderInterp1Method, ProviderInterp1Request, ProviderConv1dOptions, ProviderConvMode, ProviderConvOrientation, ProviderCholResult, ProviderCummaxResult, ProviderCumminResult, ProviderDispatchStats, ProviderInvOptions, ProviderFallbackStat, ProviderFindResult, ProviderHermitianKind, ProviderLinsolveOptions,
-    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest, ProviderSpectralResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
+    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest, ProviderSpectralResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
     ProviderAdamUpdateRequest, ProviderAdamUpdateResult, ProviderBlackScholesPriceRequest, ProviderBlackScholesPriceResult, ProviderCrossentropyMode, ProviderCrossentropyRequest, ProviderCrossentropyResult,
     ProviderStdNormalization, ProviderSymmetryKind, ProviderTelemetry, ProviderTrapezoidSpacing, ReduceDimResult, ReductionFlavor, ScaleOp, SortComparison, SortOrder, SortResult, SortRowsColumnSpec,
 };
@@ -1065,6 +1065,23 @@ impl AccelProvider for HipProvider {
                                         &mut s, &mut ps, &mut rows, &mut cols)
             })?;
             Ok(ProviderSpectralResult { s: self.complex_handle(s)?, ps: self.handle(ps)?, rows, cols })
+        })
+    }
+    // signal_envelope: analytic / FIR-quadrature / RMS envelopes per channel; Err for what rmhip.h lists as refused (a NaN or Inf sample
+    // among them) -> the builtin gathers and takes its host path, which raises InvalidSignal for such data
+    fn signal_envelope<'a>(&'a self, _request: &'a ProviderEnvelopeRequest<'a>) -> AccelProviderFuture<'a, ProviderEnvelopeResult> {
+        Box::pin(async move {
+            let (method, param) = match _request.method {
+                ProviderEnvelopeMethod::Analytic => (0, 0),
+                ProviderEnvelopeMethod::AnalyticFir { filter_len } => (1, filter_len),
+                ProviderEnvelopeMethod::Rms { window_len } => (2, window_len),
+            };
+            let (mut upper, mut lower) = (0u64, 0u64);
+            check(unsafe {
+                rmhip_signal_envelope(self.ctx, self.own(_request.input)?, _request.channel_len, _request.channel_count, _request.output_shape.as_ptr(),
+                                      _request.output_shape.len(), method, param, &mut upper, &mut lower)
+            })?;
+            Ok(ProviderEnvelopeResult { upper: self.handle(upper)?, lower: self.handle(lower)? })
         })
     }
     fn fft_extract_real<'a>(&'a self, handle: &'a GpuTensorHandle) -> AccelProviderFuture<'a, GpuTensorHandle> {
