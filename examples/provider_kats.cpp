@@ -122,6 +122,16 @@ int main() {
             }
         }
         {
+            // mode_values (lib.rs:2846-2851): the tie of [1 1 2 2] (mode.rs:901-923 mode_ties_return_smallest_with_sorted_set): M = 1, F = 2, C = {[1; 2]}
+            rmhip::ProviderModeRequest q;
+            q.input = p.upload({1, 1, 2, 2}, {1, 4});
+            q.want_frequency = q.want_ties = true;
+            auto mo = p.mode_values(q);
+            ok = ok && mo.values.shape == std::vector<size_t>{1, 1} && eq(p.download(mo.values).data, {1}) && eq(p.download(mo.frequencies).data, {2}) &&
+                 mo.ties.values.shape == std::vector<size_t>{2, 1} && eq(mo.ties.values.data, {1, 2}) && mo.ties.offsets == std::vector<size_t>{0} &&
+                 mo.ties.counts == std::vector<size_t>{2};
+        }
+        {
             // ProviderPrecision::F32 (lib.rs:815-818): host views stay f64, storage is f32, results round once
             rmhip::HipProvider q(0, 32);
             ok = ok && std::string(q.precision()) == "F32";

@@ -328,6 +328,27 @@ RMHIP_API int rmhip_sort_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, int descend, 
  * (median.rs:531-541), which is a different number on general inputs: callers wanting that chain the per-dimension form. */
 /* @serves reduce_median reduce_median_dim */
 RMHIP_API int rmhip_reduce_median(rmhip_ctx* ctx, rmhip_buf a, int dim, rmhip_buf* out);
+/* `mode_values(request)` (lib.rs:2846-2851; `ProviderModeRequest { input, axes, want_frequency, want_ties }` -> `ProviderModeResult { values,
+ * frequencies, ties }`, lib.rs:1005-1049; mode.rs:436-576, 806-853): the hook behind `mode(A)`, `mode(A, dim)`, `mode(A, "all")` and
+ * `[M, F, C] = mode(...)`.  `dim` >= 0 is `ProviderModeAxes::Dim` (zero-based), -1 is `All`, -2 is `Default`: the first dimension whose
+ * extent is not 1, else dimension 0 (mode.rs:436-445).  Per slice (mode.rs:806-846): NaNs are ignored; values are counted by bit pattern
+ * with -0 and +0 one value that keeps the bits of its first occurrence in slice order; M is the smallest value with the highest count, F
+ * that count, the tied set every value with that count, ascending; +-Inf count like any other value.  An empty or all-NaN slice gives the
+ * canonical quiet NaN (0x7ff8000000000000, whatever payload the input's NaNs had), F = 0 and an empty tied set.  Shapes (mode.rs:448-576):
+ * `All` -> [1, 1]; otherwise the operand's (a scalar is [1, 1], a vector [n, 1]) with extent 1 at the reduced dimension; a dimension at or
+ * beyond the rank leaves the shape, every slice being one element (M = the element, or the canonical NaN for a NaN; F = 1 or 0).  A
+ * reduced extent of 0 or an empty operand gives that shape filled with NaN / 0 ([0, 3] along 0 -> [1, 3] of NaN, [3, 0] -> [1, 0]).
+ * `values` is always produced; `frequencies` only when want_frequency != 0 (else *frequencies = 0); *n_slices = numel(values).
+ * want_ties != 0: the tied sets as HOST data in the ragged form of `ProviderModeTiedSets` (the convention of rmhip_unique): the caller
+ * gives room for numel(a) doubles in tie_values_host and for n_slices entries each in tie_offsets_host and tie_counts_host; *tie_total
+ * values are written, slice after slice in column-major order of the output, ascending inside a slice.  With want_ties == 0 the four tie
+ * pointers may be null.  Null values / frequencies / n_slices (or tie pointers when ties are wanted) and dim < -2 are INVALID; a refused
+ * call leaves no buffer behind.  Without ties the stream is not synchronised; with ties the host waits for the total, then for the one
+ * copy that brings values, offsets and counts.  Every result is a copy of an input element or an integer count: bit-exact.  In a
+ * precision-32 context F is stored as f32 like every other buffer: exact up to 2^24, like find's indices. */
+/* @serves mode_values */
+RMHIP_API int rmhip_mode_values(rmhip_ctx* ctx, rmhip_buf a, int dim, int want_frequency, int want_ties, rmhip_buf* values, rmhip_buf* frequencies, size_t* n_slices,
+                                size_t* tie_total, double* tie_values_host, size_t* tie_offsets_host, size_t* tie_counts_host);
 
 /* `find(a, limit, direction)` (lib.rs:2937-2944 -> ProviderFindResult { linear, rows, cols, values } :623-628; find.rs:593-633,
  * simple_provider.rs:7500-7575): the elements != 0 (a NaN counts) in ascending linear order (last == 0) or in DESCENDING order from the

@@ -122,6 +122,26 @@ struct ProviderEnvelopeResult {
     GpuTensorHandle upper, lower;  // real, the request's output_shape
 };
 
+// lib.rs:1005-1049: the request of mode_values and its result
+struct ProviderModeAxes {
+    enum Kind { Default = 0, Dim = 1, All = 2 } kind = Default;
+    size_t dim = 0;  // Dim: zero-based
+};
+struct ProviderModeRequest {
+    GpuTensorHandle input;
+    ProviderModeAxes axes;
+    bool want_frequency = false, want_ties = false;
+};
+struct ProviderModeTiedSets {  // slice k (column-major order of the output) owns values.data[offsets[k] .. offsets[k] + counts[k])
+    HostTensorOwned values;    // [total, 1], ascending per slice
+    std::vector<size_t> offsets, counts;
+};
+struct ProviderModeResult {
+    GpuTensorHandle values, frequencies;  // frequencies: buffer_id 0 unless asked for
+    bool has_frequencies = false, has_ties = false;
+    ProviderModeTiedSets ties;
+};
+
 class HipProvider {
 public:
     // precision_bits: 64 or 32 (ProviderPrecision, lib.rs:815-818), fixed for the provider's lifetime
@@ -845,6 +865,37 @@ public:
         check(rmhip_unique(ctx_, own(a), stable ? 1 : 0, last_occurrence ? 1 : 0, &count, r.values.data.data(), r.ia.data.data(), r.ic.data.data()));
         r.values.data.resize(count), r.ia.data.resize(count);
         r.values.shape = {count, 1}, r.ia.shape = {count, 1}, r.ic.shape = {n, 1};
+        return r;
+    }
+    // lib.rs:2846-2851; mode.rs:436-576, 806-853: per slice the smallest of the most frequent values, NaNs ignored
+    ProviderModeResult mode_values(const ProviderModeRequest& q) const {
+        const int dim = q.axes.kind == ProviderModeAxes::All ? -1 : (q.axes.kind == ProviderModeAxes::Default ? -2 : (int)q.axes.dim);
+        std::vector<size_t> shape = q.input.shape;  // the library's matrix_shape, to size the tie arrays
+        if (shape.empty()) shape = {1, 1};
+        if (shape.size() == 1) shape.push_back(1);
+        size_t d = q.axes.dim, n = 1, slices = 1;
+        if (dim == -2) {
+            d = 0;
+            for (size_t k = 0; k < shape.size(); ++k)
+                if (shape[k] != 1) {
+                    d = k;
+                    break;
+                }
+        }
+        for (size_t k = 0; k < shape.size(); ++k) n *= shape[k], slices *= (dim != -1 && k == d) ? 1 : shape[k];
+        if (dim == -1) slices = 1;
+        ProviderModeResult r;
+        r.has_frequencies = q.want_frequency, r.has_ties = q.want_ties;
+        r.ties.values.data.resize(n ? n : 1), r.ties.offsets.resize(slices ? slices : 1), r.ties.counts.resize(slices ? slices : 1);
+        uint64_t hv = 0, hf = 0;
+        size_t count = 0, total = 0;
+        check(rmhip_mode_values(ctx_, own(q.input), dim, q.want_frequency ? 1 : 0, q.want_ties ? 1 : 0, &hv, &hf, &count, q.want_ties ? &total : nullptr,
+                                q.want_ties ? r.ties.values.data.data() : nullptr, q.want_ties ? r.ties.offsets.data() : nullptr,
+                                q.want_ties ? r.ties.counts.data() : nullptr));
+        r.values = with_shape(hv);
+        if (q.want_frequency) r.frequencies = with_shape(hf);
+        r.ties.values.data.resize(total), r.ties.offsets.resize(q.want_ties ? count : 0), r.ties.counts.resize(q.want_ties ? count : 0);
+        r.ties.values.shape = {total, 1};
         return r;
     }
     struct UnionResult {  // lib.rs:1140-1146

@@ -8,10 +8,10 @@ Nothing here generates requests: the WGSL text RunMat's planner puts on the wire
 reproduced for tests and bench.py by the request emitter under tests/, outside the product package; the
 sharded Monte-Carlo drivers take their two shaders as arguments.
 """
-from .provider import (GpuTensorHandle, HipProvider, PagefunOp, PagefunRequest, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderError, ProviderLinsolveOptions, ProviderLinsolveResult,
+from .provider import (GpuTensorHandle, HipProvider, ModeResult, ModeTiedSets, PagefunOp, PagefunRequest, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderError, ProviderLinsolveOptions, ProviderLinsolveResult,
                        ProviderLuResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest,
                        ProviderSpectralResult, ReduceDimResult, ReductionFlavor, wgsl_compile_check, wgsl_translate)
 
-__all__ = ["GpuTensorHandle", "HipProvider", "PagefunOp", "PagefunRequest", "ProviderEigResult", "ProviderEnvelopeMethod", "ProviderEnvelopeRequest", "ProviderEnvelopeResult", "ProviderError", "ProviderLinsolveOptions", "ProviderLinsolveResult",
+__all__ = ["GpuTensorHandle", "HipProvider", "ModeResult", "ModeTiedSets", "PagefunOp", "PagefunRequest", "ProviderEigResult", "ProviderEnvelopeMethod", "ProviderEnvelopeRequest", "ProviderEnvelopeResult", "ProviderError", "ProviderLinsolveOptions", "ProviderLinsolveResult",
            "ProviderLuResult", "ProviderQrOptions", "ProviderQrPivot", "ProviderQrResult", "ProviderSpectralFrameMode", "ProviderSpectralRange", "ProviderSpectralRequest",
            "ProviderSpectralResult", "ReduceDimResult", "ReductionFlavor", "wgsl_compile_check", "wgsl_translate"]

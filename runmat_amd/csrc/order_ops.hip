@@ -3,6 +3,7 @@
 //   diff_dim                      lib.rs:2596-2603    (diff.rs:439-507; the provider form simple_provider.rs:6474-6496)
 //   reduce_median(_dim)           lib.rs:2833-2845    (median.rs:644-741; simple_provider.rs:7167-7270)
 //   sort_dim                      lib.rs:2358-2366    (sorting_sets/sort.rs:413-468, 538-574)
+//   mode_values                   lib.rs:1005-1049, 2846-2851   (stats/summary/mode.rs:436-576, 806-853)
 // Integer / comparison work on f64 data: every result is a copy of an input element, a position, or one rounded operation
 // (a difference, the mean of two middle elements) - bit-exact against the oracle.
 //   * running extremes: the (value, first position, NaN state) triple is associative, so lines are scanned in any grouping - a wave per
@@ -11,11 +12,14 @@
 //   * sort / median: every line becomes (u64 key, u32 position) pairs in a workspace padded to a power of two - the key orders the
 //     values exactly as compare_real_values does (NaNs last / first, |x| then x, -0 == +0) and the position breaks ties, which IS the
 //     stable order - and is sorted by a bitonic network: all steps below 2048 elements in LDS, the wider ones in global passes.
+//   * mode: equal values are neighbours in the sorted pairs, so a value's count is the length of its run and the run's head its first
+//     occurrence; one pass finds the longest run per line (section "mode" at the end).
 #include <algorithm>
 #include <cstring>
 #include <limits>
 
 #include "common.h"
+#include "mode_runs.h"
 
 using namespace rmhip;
 
@@ -1348,4 +1352,327 @@ int rmhip_sort_rows(rmhip_ctx* ctx, rmhip_buf a, const size_t* column_index, con
         *sorted = *indices = 0;
     }
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// mode (mode.rs:806-853): after sort_lines a line's equal values are neighbours, NaNs and padding (key ~0) last.  A RUN is a maximal
+// stretch of equal keys other than ~0: its length is the value's count, its head - the sort is stable - the value's first occurrence
+// (the zero whose sign bit the result keeps), and runs ascend by value, so the first of the longest runs is M.  Every unit of work
+// (mode_runs.h: a wave per line, or a workgroup per chunk of a longer line) owns the runs that START in its stretch: a wave walks its
+// stretch in rows of 64 from the end, a ballot of the row's boundaries (key != the key before it, the one before the stretch included)
+// gives every head the distance to the next boundary, and the one run still open at the stretch's end is closed by the first boundary
+// of a later wave of the workgroup or, for the chunk's last, by ONE upper-bound search over the rest of the line.  Candidates are single
+// ordered words (longer, then earlier head); no atomics, no float arithmetic but the count's conversion: the same bits on every run.
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace rmhip {
+namespace {
+
+constexpr u64 MODE_PAD = ~0ull;  // sort_key of a NaN and of padding; never of a number
+
+struct ModeStretch {
+    u64 best;   // the best run that starts AND ends in the stretch
+    u32 first;  // the stretch's first boundary (index in the line), MODE_NONE: none
+    u32 open;   // head of the run that reaches the stretch's end, MODE_NONE: none (or it is padding)
+};
+
+// one wave over [s0, s1) of a sorted line `lk`; `lr` (or null): the run length at every head, 0 elsewhere - the open head is left to the caller
+__device__ __forceinline__ ModeStretch mode_stretch(const u64* __restrict__ lk, u32* __restrict__ lr, u32 s0, u32 s1, int lane) {
+    ModeStretch st;
+    st.best = 0;
+    st.first = MODE_NONE;  // while walking: the first boundary after the rows done so far
+    st.open = MODE_NONE;
+    for (u32 r = (s1 - s0 + 63) >> 6; r-- > 0;) {
+        const u32 i = s0 + (r << 6) + (u32)lane;
+        const bool in = i < s1;
+        const u64 key = in ? lk[i] : MODE_PAD;
+        u64 prev = __shfl_up(key, 1);
+        if (lane == 0 && in && i > 0) prev = lk[i - 1];
+        const bool bnd = in && (i == 0 || key != prev);
+        const u64 mask = __ballot(bnd);
+        const u64 above = lane == 63 ? 0ull : mask >> (lane + 1);
+        const u32 nb = above ? i + (u32)__ffsll((long long)above) : st.first;  // the next boundary after i
+        if (bnd && key != MODE_PAD) {
+            if (nb == MODE_NONE) {
+                st.open = i;
+            } else {
+                st.best = mode_cand_best(st.best, mode_cand(nb - i, i));
+                if (lr) lr[i] = nb - i;
+            }
+        } else if (in && lr) {
+            lr[i] = 0;
+        }
+        if (mask) st.first = s0 + (r << 6) + (u32)__ffsll((long long)mask) - 1;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        st.best = mode_cand_best(st.best, __shfl_xor(st.best, o));
+        const u32 other = __shfl_xor(st.open, o);  // at most one lane holds an open head
+        st.open = other < st.open ? other : st.open;
+    }
+    return st;
+}
+
+// M / F / the best length of one line from its winning candidate
+__device__ __forceinline__ void mode_write(const double* __restrict__ x, const u32* __restrict__ lpos, Lines g, u64 line, u64 cand, double* __restrict__ M,
+                                           double* __restrict__ F, u32* __restrict__ best_len) {
+    const u32 len = mode_cand_len(cand);
+    double m = quiet_nan();
+    if (len) m = x[(line / g.pre) * g.pre * g.len + line % g.pre + (u64)lpos[mode_cand_head(cand)] * g.pre];
+    M[line] = m;
+    if (F) F[line] = (double)len;
+    if (best_len) best_len[line] = len;
+}
+
+// WPU waves per unit: 1 - a wave per line, MODE_WAVES lines per workgroup; MODE_WAVES - a workgroup per chunk, a quarter per wave
+template <int WPU>
+__global__ void __launch_bounds__(64 * MODE_WAVES) k_mode_runs(const double* __restrict__ x, const u64* __restrict__ keys, const u32* __restrict__ pos, Lines g, u64 lp,
+                                                               u64 chunk, u64 per_line, u64 nunits, u64* __restrict__ cand, u32* __restrict__ runlen,
+                                                               u32* __restrict__ best_len, double* __restrict__ M, double* __restrict__ F) {
+    __shared__ u32 sh_first[MODE_WAVES];
+    __shared__ u64 sh_best[MODE_WAVES];
+    __shared__ u32 sh_end;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const u64 unit = WPU == 1 ? (u64)blockIdx.x * MODE_WAVES + w : (u64)blockIdx.x;
+    if (unit >= nunits) return;  // whole waves (WPU 1) or whole workgroups
+    const u64 line = unit / per_line;
+    const u32 c0 = (u32)((unit % per_line) * chunk), c1 = c0 + (u32)chunk;
+    const u64* lk = keys + line * lp;
+    u32* lr = runlen ? runlen + line * lp : nullptr;
+    const u32 q = (u32)chunk / WPU, s0 = c0 + (WPU == 1 ? 0u : (u32)w * q);
+    ModeStretch st = mode_stretch(lk, lr, s0, s0 + q, lane);
+    u32 end = (u32)lp;  // WPU 1: the unit is the line
+    if (WPU > 1) {
+        if (lane == 0) sh_first[w] = st.first;
+        if (threadIdx.x == 64 * (WPU - 1)) {  // where the chunk's last run ends: the one search of the chunk
+            u32 e = c1;
+            if ((u64)c1 < lp && lk[c1 - 1] != MODE_PAD) e = (u32)mode_upper_bound(lk, c1, lp, lk[c1 - 1]);
+            sh_end = e;
+        }
+        __syncthreads();
+        end = sh_end;
+        for (int v = WPU - 1; v > w; --v)
+            if (sh_first[v] != MODE_NONE) end = sh_first[v];
+    }
+    if (st.open != MODE_NONE) {
+        st.best = mode_cand_best(st.best, mode_cand(end - st.open, st.open));
+        if (lr && lane == 0) lr[st.open] = end - st.open;
+    }
+    u64 best = st.best;
+    if (WPU > 1) {
+        if (lane == 0) sh_best[w] = best;
+        __syncthreads();
+        if (threadIdx.x != 0) return;
+        for (int v = 1; v < WPU; ++v) best = mode_cand_best(best, sh_best[v]);
+    } else if (lane != 0) {
+        return;
+    }
+    if (per_line > 1) cand[unit] = best;
+    else mode_write(x, pos + line * lp, g, line, best, M, F, best_len);
+}
+
+// lines of several chunks: a wave per line combines the chunks' candidates, every lane a stretch of consecutive chunks
+__global__ void __launch_bounds__(256) k_mode_pick(const double* __restrict__ x, const u32* __restrict__ pos, Lines g, u64 lp, u64 per_line, u64 nlines,
+                                                   const u64* __restrict__ cand, double* __restrict__ M, double* __restrict__ F, u32* __restrict__ best_len) {
+    const u64 line = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (line >= nlines) return;
+    const u64 per = (per_line + 63) / 64, k0 = (u64)lane * per, k1 = (k0 + per < per_line) ? k0 + per : per_line;
+    u64 best = 0;
+    for (u64 k = k0; k < k1; ++k) best = mode_cand_best(best, cand[line * per_line + k]);
+    for (int o = 32; o > 0; o >>= 1) best = mode_cand_best(best, __shfl_xor(best, o));
+    if (lane == 0) mode_write(x, pos + line * lp, g, line, best, M, F, best_len);
+}
+
+// tied sets: the heads whose run is as long as their line's best, compacted in order.  A wave per chunk (line-major, so a line's first
+// chunk carries the line's offset): pass 1 counts, k_find_scan turns the counts into 64-bit offsets, pass 2 places the values.
+__global__ void __launch_bounds__(256) k_mode_tie_count(const u32* __restrict__ runlen, const u32* __restrict__ best_len, u64 lp, u64 chunk, u64 per_line, u64 nunits,
+                                                        u32* __restrict__ counts) {
+    const u64 unit = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (unit >= nunits) return;
+    const u64 line = unit / per_line, c0 = (unit % per_line) * chunk;
+    const u32 bl = best_len[line];
+    u32 cnt = 0;
+    for (u64 r = 0; r < chunk; r += 64) {
+        const u64 i = c0 + r + lane;
+        const bool hit = r + lane < chunk && bl != 0 && runlen[line * lp + i] == bl;
+        cnt += (u32)__popcll(__ballot(hit));
+    }
+    if (lane == 0) counts[unit] = cnt;
+}
+
+__global__ void __launch_bounds__(256) k_mode_tie_emit(const double* __restrict__ x, const u32* __restrict__ pos, const u32* __restrict__ runlen,
+                                                       const u32* __restrict__ best_len, Lines g, u64 lp, u64 chunk, u64 per_line, u64 nunits,
+                                                       const u64* __restrict__ offsets, const u64* __restrict__ total, double* __restrict__ values,
+                                                       u64* __restrict__ line_off, u64* __restrict__ line_cnt) {
+    const u64 unit = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (unit >= nunits) return;
+    const u64 line = unit / per_line, c0 = (unit % per_line) * chunk;
+    const u64 count = *total;
+    u64 off = offsets[unit];
+    if (unit % per_line == 0 && lane == 0) {
+        line_off[line] = off;
+        line_cnt[line] = (unit + per_line < nunits ? offsets[unit + per_line] : count) - off;
+    }
+    const u32 bl = best_len[line];
+    if (bl == 0) return;
+    const u64 base = (line / g.pre) * g.pre * g.len + line % g.pre;
+    for (u64 r = 0; r < chunk && off < count; r += 64) {
+        const u64 i = c0 + r + lane;
+        const bool hit = r + lane < chunk && runlen[line * lp + i] == bl;
+        const u64 mask = __ballot(hit);
+        const u64 at = off + (u64)__popcll(mask & ((1ull << lane) - 1ull));
+        if (hit && at < count) values[at] = x[base + (u64)pos[line * lp + i] * g.pre];
+        off += (u64)__popcll(mask);
+    }
+}
+
+// slices of one element (an extent of 1, a dimension beyond the rank): the element, or the canonical NaN and a count of 0 for a NaN
+__global__ void __launch_bounds__(256) k_mode_single(const double* __restrict__ x, u64 n, double* __restrict__ M, double* __restrict__ F) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double v = x[i];
+    const bool nan = v != v;
+    M[i] = nan ? quiet_nan() : v;
+    if (F) F[i] = nan ? 0.0 : 1.0;
+}
+
+struct ModeTies {  // host side of the ragged tied sets (null when not wanted)
+    size_t* total;
+    double* values;
+    size_t *offsets, *counts;
+};
+
+// lines of >= 2 elements: sort, scan the runs, pick; tied sets through the compaction
+int mode_sorted(Context* c, const double* x, Lines g, double* M, double* F, const ModeTies* ties) {
+    static_assert(sizeof(size_t) == sizeof(u64), "tie offsets and counts travel as 64-bit words");
+    const u64 nlines = g.pre * g.post;
+    SortSpace ws;
+    RMHIP_TRY(sort_lines(c, x, g, 0, 0, &ws));
+    const u64 lp = ws.lp;
+    const ModeGeom mg = mode_geometry(lp);
+    const u64 nunits = nlines * mg.per_line;
+    // work arrays: candidates (u64) | chunk offsets (u64) | total (u64) | run lengths (u32) | best length per line (u32) | chunk counts (u32)
+    const u64 n_cand = mg.per_line > 1 ? nunits : 0, n_off = ties ? nunits + 1 : 0, n_run = ties ? nlines * lp : 0, n_best = ties ? nlines : 0, n_cnt = ties ? nunits : 0;
+    std::shared_ptr<Allocation> wk;
+    RMHIP_TRY(c->alloc_device(n_cand + n_off + (n_run + 1) / 2 + (n_best + 1) / 2 + (n_cnt + 1) / 2 + 1, &wk));
+    u64* cand = (u64*)wk->ptr;
+    u64 *offsets = cand + n_cand, *total = offsets + (ties ? nunits : 0);
+    u32* runlen = (u32*)(cand + n_cand + n_off);
+    u32 *best_len = runlen + 2 * ((n_run + 1) / 2), *counts = best_len + 2 * ((n_best + 1) / 2);
+    if (!ties) runlen = best_len = counts = nullptr;
+    const unsigned grid = (unsigned)mode_grid(mg, nlines);
+    if (mg.wave) hipLaunchKernelGGL(k_mode_runs<1>, dim3(grid), dim3(64 * MODE_WAVES), 0, c->stream, x, ws.keys, ws.pos, g, lp, mg.chunk, mg.per_line, nunits, cand, runlen, best_len, M, F);
+    else hipLaunchKernelGGL(k_mode_runs<MODE_WAVES>, dim3(grid), dim3(64 * MODE_WAVES), 0, c->stream, x, ws.keys, ws.pos, g, lp, mg.chunk, mg.per_line, nunits, cand, runlen, best_len, M, F);
+    c->tel.kernel_launches++;
+    if (mg.per_line > 1) {
+        hipLaunchKernelGGL(k_mode_pick, dim3((unsigned)((nlines + 3) / 4)), dim3(256), 0, c->stream, x, ws.pos, g, lp, mg.per_line, nlines, cand, M, F, best_len);
+        c->tel.kernel_launches++;
+    }
+    RMHIP_HIP_CHECK(hipGetLastError());
+    if (!ties) return RMHIP_OK;
+    const unsigned wgrid = (unsigned)((nunits + 3) / 4);
+    hipLaunchKernelGGL(k_mode_tie_count, dim3(wgrid), dim3(256), 0, c->stream, runlen, best_len, lp, mg.chunk, mg.per_line, nunits, counts);
+    hipLaunchKernelGGL(k_find_scan, dim3(1), dim3(1024), 0, c->stream, counts, nunits, offsets, total);
+    c->tel.kernel_launches += 2;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    unsigned long long found = 0;
+    RMHIP_HIP_CHECK(hipMemcpyAsync(&found, total, sizeof(found), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // the tie data's size is part of the answer
+    std::shared_ptr<Allocation> out;  // values (found doubles) | line offsets (u64) | line counts (u64)
+    RMHIP_TRY(c->alloc_device(found + 2 * nlines, &out));
+    u64* line_off = (u64*)(out->ptr + found);
+    hipLaunchKernelGGL(k_mode_tie_emit, dim3(wgrid), dim3(256), 0, c->stream, x, ws.pos, runlen, best_len, g, lp, mg.chunk, mg.per_line, nunits, offsets, total, out->ptr, line_off,
+                       line_off + nlines);
+    c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    std::vector<u64> host(found + 2 * nlines);
+    RMHIP_HIP_CHECK(hipMemcpyAsync(host.data(), out->ptr, host.size() * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // `host` is read next
+    if (found) std::memcpy(ties->values, host.data(), found * sizeof(double));
+    std::memcpy(ties->offsets, host.data() + found, nlines * sizeof(u64));
+    std::memcpy(ties->counts, host.data() + found + nlines, nlines * sizeof(u64));
+    *ties->total = (size_t)found;
+    c->tel.download_bytes += (host.size() + 1) * sizeof(u64);
+    return RMHIP_OK;
+}
+
+// slices of one element: M / F elementwise; the tied sets are the non-NaN elements in order, one download of M
+int mode_single(Context* c, const double* x, u64 n, double* M, double* F, const ModeTies* ties) {
+    hipLaunchKernelGGL(k_mode_single, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, x, n, M, F);
+    c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    if (!ties) return RMHIP_OK;
+    std::vector<double> m(n);
+    RMHIP_HIP_CHECK(hipMemcpyAsync(m.data(), M, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    size_t total = 0;
+    for (u64 i = 0; i < n; ++i) {
+        ties->offsets[i] = total;
+        ties->counts[i] = m[i] != m[i] ? 0 : 1;
+        if (ties->counts[i]) ties->values[total++] = m[i];
+    }
+    *ties->total = total;
+    c->tel.download_bytes += n * sizeof(double);
+    return RMHIP_OK;
+}
+
+}  // namespace
+}  // namespace rmhip
+
+int rmhip_mode_values(rmhip_ctx* ctx, rmhip_buf a, int dim, int want_frequency, int want_ties, rmhip_buf* values, rmhip_buf* frequencies, size_t* n_slices,
+                      size_t* tie_total, double* tie_values_host, size_t* tie_offsets_host, size_t* tie_counts_host) {
+    CTX_OR_FAIL(ctx);
+    if (!values || !frequencies || !n_slices) return fail(RMHIP_ERR_INVALID, "mode_values: null output");
+    if (want_ties && (!tie_total || !tie_values_host || !tie_offsets_host || !tie_counts_host)) return fail(RMHIP_ERR_INVALID, "mode_values: null tie output");
+    if (dim < -2) return fail(RMHIP_ERR_INVALID, "mode_values: dim %d (>= 0: a dimension, -1: all, -2: default)", dim);
+    *values = *frequencies = 0;
+    *n_slices = 0;
+    if (want_ties) *tie_total = 0;
+    Buffer ab, mb, fb;
+    RMHIP_TRY(c->get(a, &ab));
+    const std::vector<size_t> shape = matrix_shape(ab.shape);
+    if (dim == -2) {  // the first dimension whose extent is not 1, else the first (mode.rs:436-445)
+        dim = 0;
+        for (size_t d = 0; d < shape.size(); ++d)
+            if (shape[d] != 1) {
+                dim = (int)d;
+                break;
+            }
+    }
+    Lines g{1, ab.numel, 1};  // all: every element one slice -> [1, 1] (mode.rs:447-455)
+    std::vector<size_t> oshape{1, 1};
+    if (dim >= 0 && (size_t)dim >= shape.size()) {  // beyond the rank: slices of one element, the operand's shape (mode.rs:486-515)
+        g = Lines{ab.numel, 1, 1};
+        oshape = shape;
+    } else if (dim >= 0) {
+        RMHIP_TRY(lines_of(shape, dim, "mode_values", &g));
+        oshape = shape;
+        oshape[dim] = 1;
+    }
+    const u64 nlines = g.pre * g.post;
+    RMHIP_TRY(c->new_buffer(oshape.data(), oshape.size(), values, &mb));
+    int rc = want_frequency ? c->new_buffer(oshape.data(), oshape.size(), frequencies, &fb) : RMHIP_OK;
+    double* F = want_frequency ? fb.data() : nullptr;
+    const ModeTies ties{tie_total, tie_values_host, tie_offsets_host, tie_counts_host};
+    if (rc == RMHIP_OK && nlines > 0) {
+        if (g.len == 0) {  // empty slices: NaN, 0 and empty tied sets (mode.rs:520-522)
+            rc = launch_fill(c, mb.data(), nlines, std::numeric_limits<double>::quiet_NaN());
+            if (rc == RMHIP_OK && F) rc = launch_fill(c, F, nlines, 0.0);
+            if (want_ties)
+                for (u64 l = 0; l < nlines; ++l) tie_offsets_host[l] = tie_counts_host[l] = 0;
+        } else if (g.len == 1) {
+            rc = mode_single(c, ab.data(), nlines, mb.data(), F, want_ties ? &ties : nullptr);
+        } else {
+            rc = mode_sorted(c, ab.data(), g, mb.data(), F, want_ties ? &ties : nullptr);
+        }
+    }
+    if (rc != RMHIP_OK) {
+        rmhip_free(ctx, *values);
+        if (*frequencies) rmhip_free(ctx, *frequencies);
+        *values = *frequencies = 0;
+        return rc;
+    }
+    *n_slices = (size_t)nlines;
+    return RMHIP_OK;
 }

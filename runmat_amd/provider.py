@@ -254,6 +254,23 @@ class ProviderEnvelopeResult:
 
 
 @dataclass
+class ModeTiedSets:
+    """`ProviderModeTiedSets` (lib.rs:1027-1036): the tied values of all slices, ascending per slice ([total, 1]); slice k, in column-major
+    order of the output, owns `values[offsets[k] : offsets[k] + counts[k]]`."""
+    values: np.ndarray
+    offsets: List[int]
+    counts: List[int]
+
+
+@dataclass
+class ModeResult:
+    """`ProviderModeResult` (lib.rs:1038-1049): `values` (M) stays resident, `frequencies` (F) when asked for, `ties` (C) as host data."""
+    values: GpuTensorHandle
+    frequencies: Optional[GpuTensorHandle]
+    ties: Optional[ModeTiedSets]
+
+
+@dataclass
 class ProviderLinsolveOptions:
     """lib.rs:679-690"""
     lower: bool = False
@@ -774,6 +791,30 @@ class HipProvider:
         out = C.c_uint64()
         self._check(self._lib.rmhip_reduce_median(self._ctx, self._id(a), int(dim), C.byref(out)))
         return self._handle(out.value)
+
+    def mode_values(self, input, axes="default", want_frequency: bool = False, want_ties: bool = False) -> ModeResult:
+        """lib.rs:2846-2851 (`ProviderModeRequest`, `ProviderModeAxes::{Default, Dim(zero-based), All}`): per slice the smallest of the most
+        frequent values, NaNs ignored (mode.rs:806-853); `axes` is "default", "all" or a zero-based dimension."""
+        if axes == "default":
+            dim = -2
+        elif axes == "all":
+            dim = -1
+        elif isinstance(axes, (int, np.integer)) and not isinstance(axes, bool) and axes >= 0:
+            dim = int(axes)
+        else:
+            raise ProviderError(_lib.ERR_INVALID, f"mode_values: axes {axes!r}")
+        shape = tuple(input.shape) if len(input.shape) >= 2 else ((input.shape[0], 1) if len(input.shape) == 1 else (1, 1))
+        n = int(np.prod(shape, dtype=np.int64))
+        d = next((k for k, e in enumerate(shape) if e != 1), 0) if dim == -2 else dim
+        slices = 1 if d == -1 else n if d >= len(shape) else int(np.prod(shape[:d] + shape[d + 1:], dtype=np.int64))
+        hv, hf, count, total = C.c_uint64(), C.c_uint64(), C.c_size_t(), C.c_size_t()
+        tv = np.empty(max(n, 1))
+        off, cnt = (C.c_size_t * max(slices, 1))(), (C.c_size_t * max(slices, 1))()
+        ties = (C.byref(total), tv.ctypes.data_as(C.POINTER(C.c_double)), off, cnt) if want_ties else (None, None, None, None)
+        self._check(self._lib.rmhip_mode_values(self._ctx, self._id(input), dim, 1 if want_frequency else 0, 1 if want_ties else 0, C.byref(hv), C.byref(hf),
+                                                C.byref(count), *ties))
+        sets = ModeTiedSets(tv[:total.value].reshape(-1, 1).copy(), list(off[:count.value]), list(cnt[:count.value])) if want_ties else None
+        return ModeResult(self._handle(hv.value), self._handle(hf.value) if want_frequency else None, sets)
 
     def reduce_prod(self, a): return self._reduce("prod", a, -1)
     def reduce_prod_dim(self, a, dim): return self._reduce("prod", a, dim)

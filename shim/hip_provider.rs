@@ -17,7 +17,7 @@ use runmat_accelerate_api::{
     AccelProvider, AccelProviderFuture, ApiDeviceInfo, CorrcoefNormalization, CorrcoefOptions, CorrcoefRows, CovNormalization, CovRows, CovarianceOptions, FindDirection, GpuTensorHandle, GpuTensorStorage,
     HostLogicalOwned, HostTensorOwned, HostTensorView, IsMemberOptions, IsMemberResult, SetdiffOptions, SetdiffOrder, SetdiffResult, UnionOptions, UnionOrder, UnionResult, UniqueOccurrence, UniqueOptions, UniqueOrder, UniqueResult, ImageNormalizeDescriptor, ImfilterMode, ImfilterOptions, ImfilterPadding, ImfilterShape, KernelAttrTelemetry, MeshgridAxisView, ProviderMeshgridResult, ProviderPolyderQuotient, ProviderPolyvalOptions, KernelLaunchTelemetry, MatmulEpilogue,
     PowerStepEpilogue, ProviderBandwidth, ProviderCovarianceToCorrelationResult, ProviderHilbertRequest, ProviderCondNorm, ProviderPinvOptions, ProviderIirFilterOptions, ProviderIirFilterResult, ProviderInterp1Extrapolation, ProviderInterp1Method, ProviderInterp1Request, ProviderConv1dOptions, ProviderConvMode, ProviderConvOrientation, ProviderCholResult, ProviderCummaxResult, ProviderCumminResult, ProviderDispatchStats, ProviderInvOptions, ProviderFallbackStat, ProviderFindResult, ProviderHermitianKind, ProviderLinsolveOptions,
-    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest, ProviderSpectralResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
+    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderModeAxes, ProviderModeRequest, ProviderModeResult, ProviderModeTiedSets, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest, ProviderSpectralResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
     ProviderAdamUpdateRequest, ProviderAdamUpdateResult, ProviderBlackScholesPriceRequest, ProviderBlackScholesPriceResult, ProviderCrossentropyMode, ProviderCrossentropyRequest, ProviderCrossentropyResult,
     ProviderStdNormalization, ProviderSymmetryKind, ProviderTelemetry, ProviderTrapezoidSpacing, ReduceDimResult, ReductionFlavor, ScaleOp, SortComparison, SortOrder, SortResult, SortRowsColumnSpec,
 };
@@ -1082,6 +1082,53 @@ impl AccelProvider for HipProvider {
                                       _request.output_shape.len(), method, param, &mut upper, &mut lower)
             })?;
             Ok(ProviderEnvelopeResult { upper: self.handle(upper)?, lower: self.handle(lower)? })
+        })
+    }
+    // mode_values: per slice the smallest of the most frequent values (NaNs ignored), its count, and the tied sets as host data in the ragged
+    // form of ProviderModeTiedSets; rmhip.h states the axes codes (-1 All, -2 Default) and the degenerate shapes
+    fn mode_values<'a>(&'a self, request: &'a ProviderModeRequest<'a>) -> AccelProviderFuture<'a, ProviderModeResult> {
+        Box::pin(async move {
+            let dim: c_int = match request.axes {
+                ProviderModeAxes::Default => -2,
+                ProviderModeAxes::Dim(d) => c_int::try_from(d).map_err(|_| anyhow!("mode_values: dimension {d} exceeds provider limits"))?,
+                _ => -1, // the variant that collapses every element
+            };
+            // the library's matrix_shape, to size the tie arrays: numel(input) values, one offset and one count per output slice
+            let mut shape = request.input.shape.clone();
+            while shape.len() < 2 {
+                shape.push(1);
+            }
+            let n: usize = shape.iter().product();
+            let reduced = match request.axes {
+                ProviderModeAxes::Default => Some(shape.iter().position(|&e| e != 1).unwrap_or(0)),
+                ProviderModeAxes::Dim(d) => Some(d),
+                _ => None,
+            };
+            let slices: usize = match reduced {
+                None => 1,
+                Some(d) => shape.iter().enumerate().map(|(k, &e)| if k == d { 1 } else { e }).product(),
+            };
+            let mut tie_values = vec![0.0f64; n.max(1)];
+            let (mut offsets, mut counts) = (vec![0usize; slices.max(1)], vec![0usize; slices.max(1)]);
+            let (mut values, mut frequencies, mut count, mut total) = (0u64, 0u64, 0usize, 0usize);
+            let ties = request.want_ties;
+            check(unsafe {
+                rmhip_mode_values(self.ctx, self.own(request.input)?, dim, request.want_frequency as c_int, ties as c_int, &mut values, &mut frequencies, &mut count,
+                                  if ties { &mut total } else { std::ptr::null_mut() }, if ties { tie_values.as_mut_ptr() } else { std::ptr::null_mut() },
+                                  if ties { offsets.as_mut_ptr() } else { std::ptr::null_mut() }, if ties { counts.as_mut_ptr() } else { std::ptr::null_mut() })
+            })?;
+            tie_values.truncate(total);
+            offsets.truncate(count);
+            counts.truncate(count);
+            Ok(ProviderModeResult {
+                values: self.handle(values)?,
+                frequencies: if request.want_frequency { Some(self.handle(frequencies)?) } else { None },
+                ties: if ties {
+                    Some(ProviderModeTiedSets { values: HostTensorOwned { data: tie_values, shape: vec![total, 1], storage: GpuTensorStorage::Real }, offsets, counts })
+                } else {
+                    None
+                },
+            })
         })
     }
     fn fft_extract_real<'a>(&'a self, handle: &'a GpuTensorHandle) -> AccelProviderFuture<'a, GpuTensorHandle> {
