@@ -160,11 +160,11 @@ __device__ __forceinline__ double unary_op(double v) {
         case RMHIP_ACOSH: return acosh(v);
         case RMHIP_ATANH: return atanh(v);
         case RMHIP_EXP: return exp(v);
-        case RMHIP_EXPM1: return expm1(v);
+        case RMHIP_EXPM1: return rm_expm1(v);  // skel_common.h: expm1(-0) = -0
         case RMHIP_LOG: return log(v);
         case RMHIP_LOG2: return log2(v);
         case RMHIP_LOG10: return log10(v);
-        case RMHIP_LOG1P: return log1p(v);
+        case RMHIP_LOG1P: return rm_log1p(v);
         case RMHIP_SQRT: return sqrt(v);
         case RMHIP_ABS: return fabs(v);
         case RMHIP_SIGN: return rm_sign(v);

@@ -51,6 +51,11 @@ __device__ __forceinline__ double rm_rem(double l, double r) {
     return l - r * trunc(l / r);
 }
 
+// expm1 / log1p: the device library returns +0 for -0; C Annex F (F.10.3.3, F.10.3.9), and with it the libm behind f64::exp_m1 /
+// ln_1p of the CPU builtins, keep the sign of a zero argument.  One compare and select around the library call.
+__device__ __forceinline__ double rm_expm1(double x) { return x == 0.0 ? x : expm1(x); }
+__device__ __forceinline__ double rm_log1p(double x) { return x == 0.0 ? x : log1p(x); }
+
 // sinc: crates/runmat-runtime/src/builtins/math/.../sinc.rs:302-311
 __device__ __forceinline__ double rm_sinc(double v) {
     if (v == 0.0) return 1.0;

@@ -371,8 +371,8 @@ const std::unordered_map<std::string, FnInfo>& fn_table() {
         {"sinh", {"sinh", 1}},     {"cosh", {"cosh", 1}},     {"tanh", {"tanh", 1}},
         {"asinh", {"asinh", 1}},   {"acosh", {"acosh", 1}},   {"atanh", {"atanh", 1}},
         {"exp", {"exp", 1}},       {"exp2", {"exp2", 1}},     {"log", {"log", 1}},
-        {"log2", {"log2", 1}},     {"log10", {"log10", 1}},   {"log1p", {"log1p", 1}},
-        {"expm1", {"expm1", 1}},   {"sqrt", {"sqrt", 1}},     {"abs", {"fabs", 1}},
+        {"log2", {"log2", 1}},     {"log10", {"log10", 1}},   {"log1p", {"rm_log1p", 1}},
+        {"expm1", {"rm_expm1", 1}},   {"sqrt", {"sqrt", 1}},     {"abs", {"fabs", 1}},
         {"floor", {"floor", 1}},   {"ceil", {"ceil", 1}},     {"round", {"round", 1}},
         {"trunc", {"trunc", 1}},   {"sign", {"rm_sign", 1}},  {"atan2", {"atan2", 2}},
         {"hypot", {"hypot", 2}},   {"pow", {"rm_pow", 2}},       {"max", {"rm_max", 2}},
