@@ -132,6 +132,28 @@ int main() {
                  mo.ties.counts == std::vector<size_t>{2};
         }
         {
+            // modulate_constellation / modulate_bits_constellation (lib.rs:1961-1977): the Gray 4-QAM table of qammod.rs:675-682 over the symbols
+            // [0 1 2 3] and over the bit columns [0 0; 1 1] of qammod.rs:782-791 (one symbol per column), and a symbol of 4 refused as INVALID
+            rmhip::ProviderModulationRequest q;
+            q.constellation = {-1, 1, -1, -1, 1, 1, 1, -1};
+            q.input = p.upload({0, 1, 2, 3}, {1, 4});
+            auto pts = p.modulate_constellation(q);
+            ok = ok && pts.shape == std::vector<size_t>{1, 4} && p.is_complex(pts) && eq(p.download(pts).data, {-1, 1, -1, -1, 1, 1, 1, -1});
+            rmhip::ProviderBitModulationRequest b;
+            b.constellation = q.constellation;
+            b.input = p.upload({0, 0, 1, 1}, {2, 2});
+            b.input_rows = 2, b.bits_per_symbol = 2;
+            auto sym = p.modulate_bits_constellation(b);
+            ok = ok && sym.shape == std::vector<size_t>{1, 2} && p.is_complex(sym) && eq(p.download(sym).data, {-1, 1, 1, -1});
+            q.input = p.upload({0, 4}, {1, 2});
+            try {
+                p.modulate_constellation(q);
+                ok = false;
+            } catch (const rmhip::ProviderError& e) {
+                ok = ok && e.code == RMHIP_ERR_INVALID && std::string(e.what()).find("symbols must be in range") != std::string::npos;
+            }
+        }
+        {
             // ProviderPrecision::F32 (lib.rs:815-818): host views stay f64, storage is f32, results round once
             rmhip::HipProvider q(0, 32);
             ok = ok && std::string(q.precision()) == "F32";

@@ -646,6 +646,44 @@ RMHIP_API int rmhip_zeros_complex(rmhip_ctx* ctx, const size_t* shape, size_t ra
 /* @serves fft_extract_real */
 RMHIP_API int rmhip_complex_real(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf* out);
 
+/* ---- modulation: symbols and bits to constellation points (comms_ops.hip) -------------------------------------------------------------
+ * The two hooks `qammod` and `pskmod` call on a resident tensor (builtins/comms/qammod.rs:71-119, pskmod.rs:73-121).  Request structs:
+ * lib.rs:340-356; trait methods: lib.rs:1961-1977; the contract is the in-process provider, simple_provider.rs:4143-4310 (the wgpu
+ * shader ranks errors by code before index; this library restates the CPU loop).  `constellation` is `n_values` = 2 * order HOST doubles,
+ * (re, im) pairs by symbol index; the result is a COMPLEX-INTERLEAVED tensor whose element i is the pair of symbol i - a copy, bit for
+ * bit.  In a precision-32 context the input is read from its f32 storage and widened (exact; every check stays in f64 with 1e-9) and the
+ * result's values are rounded through f32, storage staying 2 x f64 as for every complex result.  Lazy inputs (repmat / transpose views,
+ * lazy random_normal) are materialised on use.  Host transfers: the table upload and one 64-bit verdict read, the call's only
+ * synchronisation.
+ * `modulate_constellation { input, constellation }`: per element v of the real `input`, in linear order, three checks in turn -
+ *   1. v is finite                                   else "modulate_constellation: symbols must be finite integers";
+ *   2. r = round(v), |v - r| <= 1e-9 and r >= 0.0    else "modulate_constellation: symbols must be nonnegative integers";
+ *   3. r < order, compared in floating point         else "modulate_constellation: symbols must be in range"
+ * - and the result has the input's shape (an empty input gives an empty complex tensor of that shape).  So -0.0 and -1e-10 are symbol
+ * 0, 2.0000000004 is symbol 2, 0.5 and -1 fail check 2, 1e300 fails check 3.
+ * `modulate_bits_constellation { input, input_rows, bits_per_symbol, constellation }`: input_rows is a multiple of bits_per_symbol (bps),
+ * so the CPU's channel / group / bit loops walk the input in linear order: group k is elements [k * bps, (k + 1) * bps), most
+ * significant bit first, and output element k is the pair of its symbol.  The output shape is the input's with shape[0] = input_rows /
+ * bps ([4, 0] with bps 2 gives an empty [2, 0]).  Per bit: finite, else "modulate_bits_constellation: bits must be finite"; then
+ * |v - round(v)| <= 1e-9 and round(v) is 0 or 1, else "...: bits must be 0 or 1" (-1e-10 is bit 0); after a group's last bit: symbol <
+ * order, else "...: symbols must be in range" - a table shorter than 2^bps is legal until a symbol reaches beyond it.
+ * Which error: the CPU stops at the first failing element in traversal order, at its first failing check.  Every failing element forms
+ * the key (linear index << 2) | check number on the device (a group's range error with the index of its last bit) and the launch keeps
+ * the minimum, which does not depend on scheduling.  The call then frees its output and returns RMHIP_ERR_INVALID; `rmhip_last_error()`
+ * carries the message above.  A value that fails never indexes the table.
+ * Refused on the host, in this order: an unknown id RMHIP_ERR_NOT_FOUND; a complex input RMHIP_ERR_UNSUPPORTED ("modulate_constellation
+ * requires a real-valued symbol input" / "modulate_bits_constellation requires a real-valued bit input"); an empty, odd-length or null
+ * table RMHIP_ERR_INVALID ("... requires interleaved real/imag constellation pairs"); input_rows == 0 or bps == 0 ("...: invalid bit
+ * grouping"), input_rows % bps != 0 ("...: bit rows must be a multiple of bits_per_symbol"), shape[0] != input_rows ("...: input_rows
+ * must match the input leading dimension"), all RMHIP_ERR_INVALID; bps > 32 RMHIP_ERR_UNSUPPORTED (the CPU's usize shift is no contract
+ * there; the wgpu provider caps the order at u32 too); a table of more than 2^32 - 1 points RMHIP_ERR_UNSUPPORTED.  A refused call
+ * leaves no buffer behind.  With these two this header serves 228 of the trait's 243 methods. */
+/* @serves modulate_constellation */
+RMHIP_API int rmhip_modulate_constellation(rmhip_ctx* ctx, rmhip_buf input, const double* constellation, size_t n_values, rmhip_buf* out);
+/* @serves modulate_bits_constellation */
+RMHIP_API int rmhip_modulate_bits_constellation(rmhip_ctx* ctx, rmhip_buf input, size_t input_rows, size_t bits_per_symbol, const double* constellation,
+                                                size_t n_values, rmhip_buf* out);
+
 /* `ishermitian(matrix, kind, tolerance)` for this backend's real data (lib.rs:3126-3138; ishermitian.rs:455-482, 522-530): the test of
  * `rmhip_issymmetric` with one more rule - the Hermitian kind fails on a NaN diagonal entry.  Same shape rules and errors. */
 /* @serves ishermitian */

@@ -122,6 +122,18 @@ struct ProviderEnvelopeResult {
     GpuTensorHandle upper, lower;  // real, the request's output_shape
 };
 
+// lib.rs:340-356: the requests of modulate_constellation and modulate_bits_constellation
+struct ProviderModulationRequest {
+    GpuTensorHandle input;
+    std::vector<double> constellation;  // (real, imag) pairs interleaved by symbol index
+};
+struct ProviderBitModulationRequest {
+    GpuTensorHandle input;
+    size_t input_rows = 0;       // bit rows of the input before grouping
+    size_t bits_per_symbol = 0;  // input bits that form one output symbol
+    std::vector<double> constellation;
+};
+
 // lib.rs:1005-1049: the request of mode_values and its result
 struct ProviderModeAxes {
     enum Kind { Default = 0, Dim = 1, All = 2 } kind = Default;
@@ -1076,6 +1088,19 @@ public:
     GpuTensorHandle complex_from_real_imag(const GpuTensorHandle& re, const GpuTensorHandle& im) const {  // lib.rs:1949-1959
         uint64_t out = 0;
         check(rmhip_complex(ctx_, own(re), own(im), &out));
+        return with_shape(out);
+    }
+    // lib.rs:1961-1968: symbols (nonnegative integers below the order, to within 1e-9) to their constellation pairs, a complex tensor of the
+    // input's shape; the first failing element in linear order throws INVALID with the CPU provider's message
+    GpuTensorHandle modulate_constellation(const ProviderModulationRequest& q) const {
+        uint64_t out = 0;
+        check(rmhip_modulate_constellation(ctx_, own(q.input), q.constellation.data(), q.constellation.size(), &out));
+        return with_shape(out);
+    }
+    // lib.rs:1970-1977: groups of bits_per_symbol bits, most significant first, down every column of input_rows rows
+    GpuTensorHandle modulate_bits_constellation(const ProviderBitModulationRequest& q) const {
+        uint64_t out = 0;
+        check(rmhip_modulate_bits_constellation(ctx_, own(q.input), q.input_rows, q.bits_per_symbol, q.constellation.data(), q.constellation.size(), &out));
         return with_shape(out);
     }
     bool ishermitian(const GpuTensorHandle& m, bool skew, double tolerance) const {  // lib.rs:3126-3138

@@ -529,6 +529,12 @@ SolveKnobs solve_knobs();
 bool small_solve_applies(size_t n, size_t nrhs);
 int small_solve_device(Context* c, const double* A, const double* B, size_t n, size_t nrhs, double* X, double* min_abs, double* max_abs, size_t* bad);
 
+// comms_ops.hip: constellation look-ups validated on the device.  `in` is f64 or (f32) f32 storage of n elements, `table` order (re, im) pairs on
+// the device, `out` the complex result (n points; n / bps for bits), `verdict` a device word holding MOD_KEY_NONE that failing elements lower
+// (modulate_check.h)
+int launch_modulate_symbols(Context* c, const void* in, bool f32, const double* table, size_t order, size_t n, double* out, unsigned long long* verdict);
+int launch_modulate_bits(Context* c, const void* in, bool f32, const double* table, size_t order, size_t n, unsigned bps, double* out, unsigned long long* verdict);
+
 // opaque handle -> Context (rmhip_core.cpp)
 Context* context_of(rmhip_ctx* h);
 // Precision-32 contexts: fetch an operand for a kernel that has an f32-storage variant (rmhip_ops.cpp).  `*native` stays true while

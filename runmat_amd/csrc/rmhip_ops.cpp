@@ -1,5 +1,5 @@
 // rmhip_ops.cpp -- the operator half of the C ABI (include/rmhip.h): fused elementwise / fused
-// reduction dispatch, per-op kernels, reductions, the matmul family, rank / cond / pinv, covariance, transpose, rng, pagefun.
+// reduction dispatch, per-op kernels, reductions, the matmul family, rank / cond / pinv, covariance, transpose, rng, pagefun, modulation.
 // The dense solves (lu, mldivide, mrdivide, inv, linsolve, rmhip_blk_*) are solve.cpp.
 // Host-side logic mirrors the provider duties of the reference's backends:
 //   broadcast shape/stride preparation  backend/wgpu/provider/ops/elementwise.rs:1655-1697
@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "host_shape.h"
+#include "modulate_check.h"
 #include "reduce_plan.h"
 #include "wgsl_front.h"
 
@@ -1479,6 +1480,104 @@ int rmhip_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inpu
     c->record_launch("pagefun", {{"m", m}, {"n", n}, {"k", k}, {"pages", pages}},
                      {{"tier", (uint64_t)tier}, {"page_rank", (uint64_t)pm.rank}, {"pages_per_block", tuning}});
     return RMHIP_OK;
+}
+
+}  // extern "C"
+
+// ---- modulation (comms_ops.hip) ---------------------------------------------------------------------------------------------------------
+namespace {
+
+// What the two modulation hooks share once their arguments passed: the operand (f32 storage read in place by a precision-32 context, views
+// and lazy normals materialised), the table on the device, the complex result, the launch and the one read of the verdict key.
+// bps == 0: symbols.  `message`: the CPU's text for codes 1, 2, 3 (modulate_check.h).
+int modulate_run(Context* c, rmhip_ctx* ctx, rmhip_buf input, const double* constellation, size_t n_values, unsigned bps, const std::vector<size_t>& out_shape,
+                 const char* const message[3], rmhip_buf* out) {
+    bool f32 = c->precision == 32;
+    Buffer ib, ob;
+    if (f32) RMHIP_TRY(get_operand(c, input, &ib, &f32));
+    else RMHIP_TRY(c->get(input, &ib));
+    const size_t order = n_values / 2, n = ib.numel;
+    if (order > 0xffffffffull) return fail(RMHIP_ERR_UNSUPPORTED, "modulation: a constellation of %zu points (symbol numbers are 32-bit on the device)", order);
+    RMHIP_TRY(c->new_buffer_complex(out_shape.data(), out_shape.size(), out, &ob));
+    if (n == 0) return RMHIP_OK;
+    // the host's table, as rmhip_spectral_estimate takes its window; a precision-32 context rounds a complex result's VALUES through f32
+    std::vector<double> rounded;
+    if (c->precision == 32) {
+        rounded.assign(constellation, constellation + n_values);
+        for (double& v : rounded) v = (double)(float)v;
+        constellation = rounded.data();
+    }
+    std::shared_ptr<Allocation> table, key;
+    int rc = c->alloc_device(n_values, &table);
+    if (rc == RMHIP_OK) rc = c->alloc_device(1, &key);
+    unsigned long long* const key_dev = rc == RMHIP_OK ? reinterpret_cast<unsigned long long*>(key->ptr) : nullptr;
+    unsigned long long verdict = MOD_KEY_NONE;
+    auto hip_ok = [&](hipError_t e, const char* what) {
+        if (rc == RMHIP_OK && e != hipSuccess) rc = fail(RMHIP_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    };
+    if (rc == RMHIP_OK) hip_ok(hipMemcpyAsync(table->ptr, constellation, n_values * sizeof(double), hipMemcpyHostToDevice, c->stream), "table upload");
+    if (rc == RMHIP_OK) hip_ok(hipMemsetAsync(key_dev, 0xff, sizeof(unsigned long long), c->stream), "verdict reset");
+    if (rc == RMHIP_OK)
+        rc = bps ? launch_modulate_bits(c, ib.data(), f32, table->ptr, order, n, bps, ob.data(), key_dev)
+                 : launch_modulate_symbols(c, ib.data(), f32, table->ptr, order, n, ob.data(), key_dev);
+    // the call's only synchronisation (it also outlives `rounded`)
+    if (rc == RMHIP_OK) hip_ok(hipMemcpyAsync(&verdict, key_dev, sizeof(verdict), hipMemcpyDeviceToHost, c->stream), "verdict read");
+    if (rc == RMHIP_OK) hip_ok(hipStreamSynchronize(c->stream), "verdict read");
+    else (void)hipStreamSynchronize(c->stream);
+    if (rc == RMHIP_OK && verdict != MOD_KEY_NONE) {
+        const unsigned code = mod_key_code(verdict);
+        rc = fail(RMHIP_ERR_INVALID, "%s", message[code >= 1 && code <= 3 ? code - 1 : 2]);
+    }
+    if (rc != RMHIP_OK) {
+        rmhip_free(ctx, *out);
+        *out = 0;
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhip_modulate_constellation(rmhip_ctx* ctx, rmhip_buf input, const double* constellation, size_t n_values, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "modulate_constellation: null out");
+    *out = 0;
+    Buffer raw;
+    RMHIP_TRY(c->lookup(input, &raw));
+    // simple_provider.rs:4148-4156
+    if (raw.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "modulate_constellation requires a real-valued symbol input");
+    if (n_values == 0 || n_values % 2 != 0 || !constellation)
+        return fail(RMHIP_ERR_INVALID, "modulate_constellation requires interleaved real/imag constellation pairs");
+    static const char* const kMessage[3] = {"modulate_constellation: symbols must be finite integers",
+                                            "modulate_constellation: symbols must be nonnegative integers",
+                                            "modulate_constellation: symbols must be in range"};
+    return modulate_run(c, ctx, input, constellation, n_values, 0, raw.shape, kMessage, out);
+}
+
+int rmhip_modulate_bits_constellation(rmhip_ctx* ctx, rmhip_buf input, size_t input_rows, size_t bits_per_symbol, const double* constellation, size_t n_values,
+                                      rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "modulate_bits_constellation: null out");
+    *out = 0;
+    Buffer raw;
+    RMHIP_TRY(c->lookup(input, &raw));
+    // simple_provider.rs:4215-4259, in its order
+    if (raw.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "modulate_bits_constellation requires a real-valued bit input");
+    if (n_values == 0 || n_values % 2 != 0 || !constellation)
+        return fail(RMHIP_ERR_INVALID, "modulate_bits_constellation requires interleaved real/imag constellation pairs");
+    if (input_rows == 0 || bits_per_symbol == 0) return fail(RMHIP_ERR_INVALID, "modulate_bits_constellation: invalid bit grouping");
+    if (input_rows % bits_per_symbol != 0) return fail(RMHIP_ERR_INVALID, "modulate_bits_constellation: bit rows must be a multiple of bits_per_symbol");
+    if (raw.shape.empty() || raw.shape[0] != input_rows)
+        return fail(RMHIP_ERR_INVALID, "modulate_bits_constellation: input_rows must match the input leading dimension");
+    // the CPU shifts a usize; symbols here are cut out of 32 bits (the wgpu provider caps the order at u32 as well)
+    if (bits_per_symbol > (size_t)MOD_BPS_MAX)
+        return fail(RMHIP_ERR_UNSUPPORTED, "modulate_bits_constellation: %zu bits per symbol (at most %d are served)", bits_per_symbol, MOD_BPS_MAX);
+    std::vector<size_t> out_shape = raw.shape;
+    out_shape[0] = input_rows / bits_per_symbol;
+    static const char* const kMessage[3] = {"modulate_bits_constellation: bits must be finite", "modulate_bits_constellation: bits must be 0 or 1",
+                                            "modulate_bits_constellation: symbols must be in range"};
+    return modulate_run(c, ctx, input, constellation, n_values, (unsigned)bits_per_symbol, out_shape, kMessage, out);
 }
 
 }  // extern "C"

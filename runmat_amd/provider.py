@@ -1672,6 +1672,26 @@ class HipProvider:
         self._check(self._lib.rmhip_complex(self._ctx, self._id(real), self._id(imag), C.byref(out)))
         return self._handle(out.value)
 
+    # -- modulation (comms_ops.hip) --------------------------------------------------------------------
+    def modulate_constellation(self, input, constellation) -> GpuTensorHandle:
+        """lib.rs:1961-1968 (`ProviderModulationRequest { input, constellation }`): every element of the real `input`, a nonnegative integer
+        below the order to within 1e-9, replaced by its (re, im) pair of `constellation` (2 * order host doubles) -> complex tensor of the
+        input's shape.  The first failing element in linear order raises with code INVALID and the CPU provider's message."""
+        table = np.ascontiguousarray(np.asarray(constellation, dtype=np.float64).reshape(-1))
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_modulate_constellation(self._ctx, self._id(input), table.ctypes.data_as(C.POINTER(C.c_double)), table.size, C.byref(out)))
+        return self._handle(out.value)
+
+    def modulate_bits_constellation(self, input, input_rows: int, bits_per_symbol: int, constellation) -> GpuTensorHandle:
+        """lib.rs:1970-1977 (`ProviderBitModulationRequest { input, input_rows, bits_per_symbol, constellation }`): groups of `bits_per_symbol`
+        consecutive bits (most significant first) down every column of `input_rows` rows form symbols, each replaced by its pair of
+        `constellation` -> complex tensor of the input's shape with shape[0] = input_rows / bits_per_symbol."""
+        table = np.ascontiguousarray(np.asarray(constellation, dtype=np.float64).reshape(-1))
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_modulate_bits_constellation(self._ctx, self._id(input), int(input_rows), int(bits_per_symbol),
+                                                                table.ctypes.data_as(C.POINTER(C.c_double)), table.size, C.byref(out)))
+        return self._handle(out.value)
+
     def ishermitian(self, matrix, kind: str = "hermitian", tolerance: float = 0.0) -> bool:
         """lib.rs:3126-3138 (`ProviderHermitianKind::{Hermitian, Skew}`), real data: issymmetric's test plus "a NaN diagonal fails"."""
         if kind not in ("hermitian", "skew"):

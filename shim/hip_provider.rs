@@ -17,7 +17,7 @@ use runmat_accelerate_api::{
     AccelProvider, AccelProviderFuture, ApiDeviceInfo, CorrcoefNormalization, CorrcoefOptions, CorrcoefRows, CovNormalization, CovRows, CovarianceOptions, FindDirection, GpuTensorHandle, GpuTensorStorage,
     HostLogicalOwned, HostTensorOwned, HostTensorView, IsMemberOptions, IsMemberResult, SetdiffOptions, SetdiffOrder, SetdiffResult, UnionOptions, UnionOrder, UnionResult, UniqueOccurrence, UniqueOptions, UniqueOrder, UniqueResult, ImageNormalizeDescriptor, ImfilterMode, ImfilterOptions, ImfilterPadding, ImfilterShape, KernelAttrTelemetry, MeshgridAxisView, ProviderMeshgridResult, ProviderPolyderQuotient, ProviderPolyvalOptions, KernelLaunchTelemetry, MatmulEpilogue,
     PowerStepEpilogue, ProviderBandwidth, ProviderCovarianceToCorrelationResult, ProviderHilbertRequest, ProviderCondNorm, ProviderPinvOptions, ProviderIirFilterOptions, ProviderIirFilterResult, ProviderInterp1Extrapolation, ProviderInterp1Method, ProviderInterp1Request, ProviderConv1dOptions, ProviderConvMode, ProviderConvOrientation, ProviderCholResult, ProviderCummaxResult, ProviderCumminResult, ProviderDispatchStats, ProviderInvOptions, ProviderFallbackStat, ProviderFindResult, ProviderHermitianKind, ProviderLinsolveOptions,
-    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderModeAxes, ProviderModeRequest, ProviderModeResult, ProviderModeTiedSets, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest, ProviderSpectralResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
+    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderModeAxes, ProviderModeRequest, ProviderModeResult, ProviderModeTiedSets, ProviderModulationRequest, ProviderBitModulationRequest, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest, ProviderSpectralResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
     ProviderAdamUpdateRequest, ProviderAdamUpdateResult, ProviderBlackScholesPriceRequest, ProviderBlackScholesPriceResult, ProviderCrossentropyMode, ProviderCrossentropyRequest, ProviderCrossentropyResult,
     ProviderStdNormalization, ProviderSymmetryKind, ProviderTelemetry, ProviderTrapezoidSpacing, ReduceDimResult, ReductionFlavor, ScaleOp, SortComparison, SortOrder, SortResult, SortRowsColumnSpec,
 };
@@ -1143,6 +1143,26 @@ impl AccelProvider for HipProvider {
     }
     fn complex_from_real_imag<'a>(&'a self, real: &'a GpuTensorHandle, imag: &'a GpuTensorHandle) -> AccelProviderFuture<'a, GpuTensorHandle> {
         Box::pin(async move { self.complex(real, Some(imag)) })
+    }
+    // modulate_constellation / modulate_bits_constellation: the hooks qammod and pskmod call on a resident tensor - symbols, or groups of bits
+    // (most significant first), replaced by their (re, im) pairs of the host table; validated on the device, and the first failing element
+    // in the CPU's traversal order decides the Err (rmhip.h lists the messages) -> the builtins gather and raise their own error
+    fn modulate_constellation<'a>(&'a self, request: ProviderModulationRequest<'a>) -> AccelProviderFuture<'a, GpuTensorHandle> {
+        Box::pin(async move {
+            let mut out = 0u64;
+            check(unsafe { rmhip_modulate_constellation(self.ctx, self.own(request.input)?, request.constellation.as_ptr(), request.constellation.len(), &mut out) })?;
+            self.complex_handle(out)
+        })
+    }
+    fn modulate_bits_constellation<'a>(&'a self, request: ProviderBitModulationRequest<'a>) -> AccelProviderFuture<'a, GpuTensorHandle> {
+        Box::pin(async move {
+            let mut out = 0u64;
+            check(unsafe {
+                rmhip_modulate_bits_constellation(self.ctx, self.own(request.input)?, request.input_rows, request.bits_per_symbol, request.constellation.as_ptr(),
+                                                  request.constellation.len(), &mut out)
+            })?;
+            self.complex_handle(out)
+        })
     }
     fn ishermitian<'a>(&'a self, matrix: &'a GpuTensorHandle, kind: ProviderHermitianKind, tolerance: f64) -> AccelProviderFuture<'a, bool> {
         Box::pin(async move {
