@@ -390,6 +390,30 @@ RMHIP_API int rmhip_setdiff(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, int stable
  * both in a's shape, numel(a) entries (`HostLogicalOwned` / `HostTensorOwned`). */
 /* @serves ismember */
 RMHIP_API int rmhip_ismember(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, unsigned char* mask_host, double* loc_host);
+/* ---- the 'rows' forms of the four set hooks (`options.rows == true`; lib.rs:1110-1146, 1237-1274).  A row is the tuple of its columns'
+ * canonical keys (`canonicalize_f64`, unique.rs:1347-1355: every NaN one key, both zeros one key); an output row keeps the bits of its
+ * FIRST occurrence; sorted order is lexicographic by `compare_f64`, column 0 first, NaN after every number (`compare_numeric_rows`,
+ * :1357-1379).  One stable sort pass per column, last column first, then integer work on the row permutation: bit-exact.  Host results,
+ * column-major.  Operands must have rank 2 (ismember: at most 2) and equal column counts, else RMHIP_ERR_SHAPE with the CPU's message.
+ * `unique(handle, options)` with rows (unique.rs:558-662): values_host [count, cols] with leading dimension count (room: rows * cols
+ * doubles), ia_host [count, 1] the 1-based first (last_occurrence != 0: last) row of each distinct row (room: rows), ic_host [rows, 1] the
+ * 1-based rank of every row.  rows == 0: count 0, nothing written; cols == 0 with rows > 0 is refused as on the CPU (`ic` cannot be built). */
+/* @serves unique */
+RMHIP_API int rmhip_unique_rows(rmhip_ctx* ctx, rmhip_buf a, int stable, int last_occurrence, size_t* count, double* values_host, double* ia_host, double* ic_host);
+/* `union(a, b, options)` / `setdiff(a, b, options)` with rows (union.rs:546-622, 1281-1330; setdiff.rs:498-552, 891-930): union - the
+ * distinct rows of a's rows followed by b's (first occurrences; sorted, or stable != 0: in order of appearance), ia the 1-based rows of a of
+ * the entries first seen in a, ib those of b of the rest, both in output order; values_host [count, cols] needs (rows_a + rows_b) * cols
+ * doubles, ia_host rows_a, ib_host rows_b.  setdiff - a's distinct rows that do not occur in b, with their first rows in a; rows_a * cols
+ * and rows_a doubles.  Without columns every row is the same row: count is 0 or 1 and no value is written. */
+/* @serves union */
+RMHIP_API int rmhip_union_rows(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, int stable, size_t* count, double* values_host, size_t* ia_count, double* ia_host,
+                               size_t* ib_count, double* ib_host);
+/* @serves setdiff */
+RMHIP_API int rmhip_setdiff_rows(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, int stable, size_t* count, double* values_host, double* ia_host);
+/* `ismember(a, b, options)` with rows (ismember.rs:440-480; `tensor_rows_cols` :755-765: rank 0 / 1 / 2 is (1, 1) / (n, 1) / (r, c)):
+ * mask_host[r] = 1 when row r of a occurs among b's rows, loc_host[r] = the 1-based LOWEST such row of b or 0; both [rows_a, 1]. */
+/* @serves ismember */
+RMHIP_API int rmhip_ismember_rows(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, unsigned char* mask_host, double* loc_host);
 /* ---- subscript / grid / slice-write hooks and the per-element forms of a real tensor (runmat_amd/csrc/index_ops.hip): bit-exact ----
  * `ndgrid(request)` (lib.rs:1567-1569, ProviderNdgridRequest :3395-3399; simple_provider.rs:2784-2855): for the first `output_count` axes
  * (resident vectors whose lengths equal the leading output extents) the grid out_d[i] = axis_d[(i / stride_d) % extent_d] of shape

@@ -865,7 +865,7 @@ public:
         check(rmhip_issymmetric(ctx_, own(m), skew ? 1 : 0, tolerance, &r));
         return r != 0;
     }
-    // lib.rs:2645-2651 (elements; rows: not served) -> host tensors [count, 1], [count, 1], [numel, 1]
+    // lib.rs:2645-2651, elements -> host tensors [count, 1], [count, 1], [numel, 1]; `UniqueOptions.rows`: unique_rows below
     struct UniqueResult {
         HostTensorOwned values, ia, ic;
     };
@@ -877,6 +877,17 @@ public:
         check(rmhip_unique(ctx_, own(a), stable ? 1 : 0, last_occurrence ? 1 : 0, &count, r.values.data.data(), r.ia.data.data(), r.ic.data.data()));
         r.values.data.resize(count), r.ia.data.resize(count);
         r.values.shape = {count, 1}, r.ia.shape = {count, 1}, r.ic.shape = {n, 1};
+        return r;
+    }
+    // `UniqueOptions.rows` (unique.rs:558-662) -> host tensors [count, cols], [count, 1], [rows, 1]; a has rank 2
+    UniqueResult unique_rows(const GpuTensorHandle& a, bool stable, bool last_occurrence) const {
+        const size_t rows = a.shape.size() == 2 ? a.shape[0] : 0, cols = a.shape.size() == 2 ? a.shape[1] : 0;
+        UniqueResult r;
+        r.values.data.resize(rows * cols), r.ia.data.resize(rows), r.ic.data.resize(rows);
+        size_t count = 0;
+        check(rmhip_unique_rows(ctx_, own(a), stable ? 1 : 0, last_occurrence ? 1 : 0, &count, r.values.data.data(), r.ia.data.data(), r.ic.data.data()));
+        r.values.data.resize(count * cols), r.ia.data.resize(count);
+        r.values.shape = {count, cols}, r.ia.shape = {count, 1}, r.ic.shape = {rows, 1};
         return r;
     }
     // lib.rs:2846-2851; mode.rs:436-576, 806-853: per slice the smallest of the most frequent values, NaNs ignored
@@ -944,6 +955,35 @@ public:
         r.mask.resize(a.numel()), r.loc.data.resize(a.numel());
         r.shape = a.shape, r.loc.shape = a.shape;
         check(rmhip_ismember(ctx_, own(a), own(b), r.mask.data(), r.loc.data.data()));
+        return r;
+    }
+    // the 'rows' forms (`options.rows`; union.rs:546-622, setdiff.rs:498-552, ismember.rs:440-480): values [count, cols], the index lists [k, 1]
+    UnionResult set_union_rows(const GpuTensorHandle& a, const GpuTensorHandle& b, bool stable) const {
+        const size_t ra = a.shape.size() == 2 ? a.shape[0] : 0, rb = b.shape.size() == 2 ? b.shape[0] : 0, cols = a.shape.size() == 2 ? a.shape[1] : 0;
+        UnionResult r;
+        r.values.data.resize((ra + rb) * cols), r.ia.data.resize(ra), r.ib.data.resize(rb);
+        size_t n = 0, na = 0, nb = 0;
+        check(rmhip_union_rows(ctx_, own(a), own(b), stable ? 1 : 0, &n, r.values.data.data(), &na, r.ia.data.data(), &nb, r.ib.data.data()));
+        r.values.data.resize(n * cols), r.ia.data.resize(na), r.ib.data.resize(nb);
+        r.values.shape = {n, cols}, r.ia.shape = {na, 1}, r.ib.shape = {nb, 1};
+        return r;
+    }
+    SetdiffResult setdiff_rows(const GpuTensorHandle& a, const GpuTensorHandle& b, bool stable) const {
+        const size_t ra = a.shape.size() == 2 ? a.shape[0] : 0, cols = a.shape.size() == 2 ? a.shape[1] : 0;
+        SetdiffResult r;
+        r.values.data.resize(ra * cols), r.ia.data.resize(ra);
+        size_t n = 0;
+        check(rmhip_setdiff_rows(ctx_, own(a), own(b), stable ? 1 : 0, &n, r.values.data.data(), r.ia.data.data()));
+        r.values.data.resize(n * cols), r.ia.data.resize(n);
+        r.values.shape = {n, cols}, r.ia.shape = {n, 1};
+        return r;
+    }
+    IsMemberResult ismember_rows(const GpuTensorHandle& a, const GpuTensorHandle& b) const {  // rank 0 / 1 / 2: (1, 1) / (n, 1) / (r, c)
+        const size_t ra = a.shape.empty() ? 1 : (a.shape.size() <= 2 ? a.shape[0] : 0);
+        IsMemberResult r;
+        r.mask.resize(ra), r.loc.data.resize(ra);
+        r.shape = {ra, 1}, r.loc.shape = {ra, 1};
+        check(rmhip_ismember_rows(ctx_, own(a), own(b), r.mask.data(), r.loc.data.data()));
         return r;
     }
     // lib.rs:1809-1817; padding 0 constant / 1 replicate / 2 symmetric / 3 circular; shape 0 same / 1 full / 2 valid

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "mode_runs.h"
+#include "row_keys.h"
 
 using namespace rmhip;
 
@@ -559,6 +560,31 @@ __global__ void __launch_bounds__(256) k_rows_emit(const double* __restrict__ x,
     if (col == 0) indices[r] = (double)src + 1.0;
 }
 
+// the stable passes of sortrows over `n_columns` keys, last key first; column_index == null: every column of `cols`, ascending (the order
+// of the 'rows' set forms).  *perm: the row at every rank, inside *pm - or null when no listed column exists (the rows as they are).
+int rows_order(Context* c, const double* x, u64 rows, u64 cols, const size_t* column_index, const int* column_descend, size_t n_columns, int by_abs, SortSpace* ws,
+               std::shared_ptr<Allocation>* pm, u32** perm) {
+    *perm = nullptr;
+    RMHIP_TRY(sort_alloc(c, 1, rows, ws));
+    RMHIP_TRY(c->alloc_device(rows, pm));  // two u32 arrays of `rows`
+    u32 *cur = nullptr, *nxt = (u32*)(*pm)->ptr;
+    for (size_t s = n_columns; s-- > 0;) {  // the last key first: every pass is stable (ties keep the ranks of the pass before)
+        const u64 col = column_index ? (u64)column_index[s] : (u64)s;
+        if (col >= cols) continue;  // sortrows_host.rs:86-88
+        hipLaunchKernelGGL(k_rows_keys, dim3((unsigned)((ws->total + 255) / 256)), dim3(256), 0, c->stream, x, rows, col, cur, column_descend && column_descend[s] ? 1 : 0,
+                           by_abs ? 1 : 0, ws->keys, ws->pos, ws->total);
+        c->tel.kernel_launches++;
+        RMHIP_TRY(sort_pairs(c, ws));
+        hipLaunchKernelGGL(k_rows_compose, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, cur, ws->pos, rows, nxt);
+        c->tel.kernel_launches++;
+        u32* was = cur;
+        cur = nxt;
+        nxt = was ? was : (u32*)(*pm)->ptr + rows;
+    }
+    *perm = cur;
+    return RMHIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // find: ordered stream compaction.  A wave owns FIND_ROWS rows of 64 consecutive scan positions; pass 1 counts its nonzeros, one
 // workgroup turns the counts into offsets, pass 2 places every nonzero at offset + (number of nonzeros before it in the wave).
@@ -948,6 +974,66 @@ __global__ void __launch_bounds__(256) k_ismember(const double* __restrict__ a, 
     loc[i] = hit ? (double)pos[lo] + 1.0 : 0.0;
 }
 
+// ---- the 'rows' forms (unique.rs:558-662, union.rs:546-622, setdiff.rs:498-552, ismember.rs:440-480): a row is the tuple of its columns'
+// canonical keys (row_keys.h).  After one stable pass per column, last column first, `perm[r]` is the row at rank r in lexicographic
+// order and equal rows are neighbours in ascending row order - the element forms' picture with `perm` in the place of `pos`. ----
+
+// k_group_heads over rows: rank r opens a group when any column's key differs between rows perm[r] and perm[r - 1]
+__global__ void __launch_bounds__(256) k_row_heads(const double* __restrict__ x, u64 rows, u64 cols, const u32* __restrict__ perm, u32* __restrict__ flags,
+                                                   u32* __restrict__ counts) {
+    __shared__ u32 part[4];
+    const u64 base = (u64)blockIdx.x * SCAN_CHUNK + threadIdx.x * 4;
+    u32 cnt = 0;
+    for (int e = 0; e < 4; ++e) {
+        const u64 i = base + e;
+        if (i >= rows) break;
+        const u32 f = (i == 0 || rowkeys::rows_differ(x, rows, perm[i], perm[i - 1], cols)) ? 1u : 0u;
+        flags[i] = f;
+        cnt += f;
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// values[r + col * groups] = x[first row of the r-th group + col * rows] (consecutive threads: consecutive ranks of one column); the
+// threads of column 0 also write ia and rank_of, as k_unique_outputs does
+__global__ void __launch_bounds__(256) k_rows_gather(const double* __restrict__ x, u64 rows, const u32* __restrict__ order, const u32* __restrict__ first_pos,
+                                                     const u32* __restrict__ last_pos, u64 groups, u64 total, int take_last, double* __restrict__ values,
+                                                     double* __restrict__ ia, u32* __restrict__ rank_of) {
+    const u64 o = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    const u64 r = o % groups, col = o / groups;
+    const u32 g = order ? order[r] : (u32)r;
+    values[o] = x[first_pos[g] + col * rows];  // the row keeps the bits of its first occurrence (unique.rs:601-607)
+    if (col == 0) {
+        ia[r] = (double)(take_last ? last_pos[g] : first_pos[g]) + 1.0;
+        rank_of[g] = (u32)r;
+    }
+}
+
+// [rows_a + rows_b, cols]: a's rows, then b's
+__global__ void __launch_bounds__(256) k_rows_stack(const double* __restrict__ a, u64 rows_a, const double* __restrict__ b, u64 rows_b, u64 total,
+                                                    double* __restrict__ out) {
+    const u64 o = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    const u64 n = rows_a + rows_b, r = o % n, col = o / n;
+    out[o] = r < rows_a ? a[r + col * rows_a] : b[(r - rows_a) + col * rows_b];
+}
+
+// mask / loc of every row of a (leading dimension rows_a) against b's rows in sorted order: the first rank that is not before the probe
+// holds - the passes are stable - b's lowest equal row
+__global__ void __launch_bounds__(256) k_rows_member(const double* __restrict__ a, u64 rows_a, const double* __restrict__ b, u64 rows_b, u64 cols,
+                                                     const u32* __restrict__ perm_b, unsigned char* __restrict__ mask, double* __restrict__ loc) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows_a) return;
+    const u64 lo = rowkeys::lower_bound(b, rows_b, cols, perm_b, a, i, rows_a);
+    const bool hit = lo < rows_b && rowkeys::compare_rows(b, perm_b[lo], rows_b, a, i, rows_a, cols) == 0;
+    mask[i] = hit ? 1 : 0;
+    loc[i] = hit ? (double)perm_b[lo] + 1.0 : 0.0;
+}
+
 }  // namespace
 }  // namespace rmhip
 
@@ -1172,6 +1258,83 @@ int unique_device(Context* c, const double* x, u64 n, int stable, int last_occur
     RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // (the work arrays above are released on return)
     return RMHIP_OK;
 }
+
+struct UniqueRowsDev {
+    std::shared_ptr<Allocation> outs;  // values [groups, cols] | ia | ic
+    double *dv = nullptr, *dia = nullptr, *dic = nullptr;
+    u64 groups = 0;
+};
+
+bool grid_fits(u64 threads) { return (threads + 255) / 256 <= 0x7fffffffull; }
+
+// the distinct rows of the column-major x [rows, cols] (rows > 0, cols > 0) with their first / last rows and the inverse map, left on
+// the device: unique_device with the row order in the place of the element sort
+int unique_rows_device(Context* c, const double* x, u64 rows, u64 cols, int stable, int last_occurrence, UniqueRowsDev* r) {
+    if (!grid_fits(rows * cols)) return fail(RMHIP_ERR_UNSUPPORTED, "rows: a matrix of %llu elements", rows * cols);
+    SortSpace ws;
+    std::shared_ptr<Allocation> pm;
+    u32* perm = nullptr;
+    RMHIP_TRY(rows_order(c, x, rows, cols, nullptr, nullptr, (size_t)cols, 0, &ws, &pm, &perm));
+    const u64 n = rows, nchunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    // u32 work arrays: flags n | gid n | first n | last n | rank n | counts nchunks | offsets nchunks | total 2
+    std::shared_ptr<Allocation> wk;
+    RMHIP_TRY(c->alloc_device((5 * n + 2 * nchunks + 2 + 1) / 2 + 1, &wk));
+    u32* flags = (u32*)wk->ptr;
+    u32 *gid = flags + n, *first_pos = gid + n, *last_pos = first_pos + n, *rank_of = last_pos + n, *counts = rank_of + n, *offsets = counts + nchunks, *total = offsets + nchunks;
+    hipLaunchKernelGGL(k_row_heads, dim3((unsigned)nchunks), dim3(256), 0, c->stream, x, rows, cols, perm, flags, counts);
+    hipLaunchKernelGGL(k_chunk_offsets, dim3(1), dim3(1024), 0, c->stream, counts, nchunks, offsets, total);
+    hipLaunchKernelGGL(k_group_ids, dim3((unsigned)nchunks), dim3(256), 0, c->stream, flags, offsets, perm, n, gid, first_pos, last_pos);
+    c->tel.kernel_launches += 3;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    u32 groups32 = 0;
+    RMHIP_HIP_CHECK(hipMemcpyAsync(&groups32, total, sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // the outputs' size is part of the answer
+    const u64 groups = groups32;
+    RMHIP_TRY(c->alloc_device(groups * cols + groups + n, &r->outs));
+    r->dv = r->outs->ptr, r->dia = r->dv + groups * cols, r->dic = r->dia + groups, r->groups = groups;
+    const u32* order = nullptr;
+    SortSpace ws2;
+    std::shared_ptr<Allocation> fp;
+    if (stable && groups > 1) {  // groups in order of their first row (unique.rs:614-617: `order` stays the insertion order)
+        RMHIP_TRY(c->alloc_device(groups, &fp));
+        hipLaunchKernelGGL(k_u32_to_double, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, c->stream, first_pos, groups, fp->ptr);
+        c->tel.kernel_launches++;
+        RMHIP_TRY(sort_lines(c, fp->ptr, Lines{1, groups, 1}, 0, 0, &ws2));
+        order = ws2.pos;
+    }
+    hipLaunchKernelGGL(k_rows_gather, dim3((unsigned)((groups * cols + 255) / 256)), dim3(256), 0, c->stream, x, rows, order, first_pos, last_pos, groups, groups * cols,
+                       last_occurrence ? 1 : 0, r->dv, r->dia, rank_of);
+    hipLaunchKernelGGL(k_unique_inverse, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, perm, gid, rank_of, n, r->dic);
+    c->tel.kernel_launches += 2;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // (the work arrays above are released on return)
+    return RMHIP_OK;
+}
+
+// mask (bytes) and loc (f64) of the rows of a [rows_a, cols] in b [rows_b, cols] (all extents > 0), left on the device in *outs: loc | mask
+int rows_member_device(Context* c, const double* a, u64 rows_a, const double* b, u64 rows_b, u64 cols, std::shared_ptr<Allocation>* outs) {
+    if (!grid_fits(rows_b * cols) || !grid_fits(rows_a)) return fail(RMHIP_ERR_UNSUPPORTED, "rows: a matrix of %llu elements", rows_b * cols);
+    SortSpace ws;
+    std::shared_ptr<Allocation> pm;
+    u32* perm = nullptr;
+    RMHIP_TRY(rows_order(c, b, rows_b, cols, nullptr, nullptr, (size_t)cols, 0, &ws, &pm, &perm));
+    RMHIP_TRY(c->alloc_device(rows_a + (rows_a + 7) / 8, outs));
+    double* dloc = (*outs)->ptr;
+    hipLaunchKernelGGL(k_rows_member, dim3((unsigned)((rows_a + 255) / 256)), dim3(256), 0, c->stream, a, rows_a, b, rows_b, cols, perm, (unsigned char*)(dloc + rows_a), dloc);
+    c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // b's order is released on return
+    return RMHIP_OK;
+}
+
+// the operands of the two-matrix 'rows' forms: rank exactly 2, equal column counts (union.rs:551-561, setdiff.rs:503-510)
+int rows_operands(Context* c, const char* what, rmhip_buf a, rmhip_buf b, Buffer* ab, Buffer* bb) {
+    RMHIP_TRY(c->get(a, ab));
+    RMHIP_TRY(c->get(b, bb));
+    if (ab->shape.size() != 2 || bb->shape.size() != 2) return fail(RMHIP_ERR_SHAPE, "%s: 'rows' option requires 2-D numeric matrices", what);
+    if (ab->shape[1] != bb->shape[1]) return fail(RMHIP_ERR_SHAPE, "%s: inputs must have the same number of columns when using 'rows'", what);
+    return RMHIP_OK;
+}
 }  // namespace
 }  // namespace rmhip
 
@@ -1295,6 +1458,135 @@ int rmhip_ismember(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, unsigned char* mask
     return RMHIP_OK;
 }
 
+int rmhip_unique_rows(rmhip_ctx* ctx, rmhip_buf a, int stable, int last_occurrence, size_t* count, double* values_host, double* ia_host, double* ic_host) {
+    CTX_OR_FAIL(ctx);
+    if (!count) return fail(RMHIP_ERR_INVALID, "unique: null count");
+    Buffer ab;
+    RMHIP_TRY(c->get(a, &ab));
+    *count = 0;
+    if (ab.shape.size() != 2) return fail(RMHIP_ERR_SHAPE, "unique: 'rows' option requires a 2-D matrix input");
+    const u64 rows = ab.shape[0], cols = ab.shape[1];
+    if (rows == 0) return RMHIP_OK;  // unique.rs:571-583: three empty tensors
+    if (cols == 0)                   // ... where `ic` of [rows, 1] without data fails Tensor::new
+        return fail(RMHIP_ERR_SHAPE, "unique: Tensor data length 0 doesn't match shape [%llu, 1] (%llu elements)", rows, rows);
+    if (!values_host || !ia_host || !ic_host) return fail(RMHIP_ERR_INVALID, "unique: null output");
+    UniqueRowsDev r;
+    RMHIP_TRY(unique_rows_device(c, ab.data(), rows, cols, stable, last_occurrence, &r));
+    RMHIP_HIP_CHECK(hipMemcpyAsync(values_host, r.dv, r.groups * cols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipMemcpyAsync(ia_host, r.dia, r.groups * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipMemcpyAsync(ic_host, r.dic, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->tel.download_bytes += (r.groups * cols + r.groups + rows) * sizeof(double);
+    *count = r.groups;
+    return RMHIP_OK;
+}
+
+int rmhip_union_rows(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, int stable, size_t* count, double* values_host, size_t* ia_count, double* ia_host, size_t* ib_count,
+                     double* ib_host) {
+    CTX_OR_FAIL(ctx);
+    if (!count || !ia_count || !ib_count) return fail(RMHIP_ERR_INVALID, "union: null count");
+    Buffer ab, bb;
+    RMHIP_TRY(rows_operands(c, "union", a, b, &ab, &bb));
+    const u64 ra = ab.shape[0], rb = bb.shape[0], cols = ab.shape[1], n = ra + rb;
+    *count = *ia_count = *ib_count = 0;
+    if (n == 0) return RMHIP_OK;
+    if ((ra && !ia_host) || (rb && !ib_host) || (cols && !values_host)) return fail(RMHIP_ERR_INVALID, "union: null output");
+    if (cols == 0) {  // every row without columns is the same row (union.rs:570-619): one entry, first seen in a when a has a row
+        *count = 1;
+        if (ra) ia_host[0] = 1.0, *ia_count = 1;
+        else ib_host[0] = 1.0, *ib_count = 1;
+        return RMHIP_OK;
+    }
+    // union.rs:570-619 + 1281-1330: the map over a's rows, then b's, is unique-rows of the two stacked, first occurrences; an entry first
+    // seen in a reports that row in ia, the others their row of b in ib - both in output order
+    if (!grid_fits(n * cols)) return fail(RMHIP_ERR_UNSUPPORTED, "rows: a matrix of %llu elements", n * cols);
+    std::shared_ptr<Allocation> cat;
+    RMHIP_TRY(c->alloc_device(n * cols, &cat));
+    hipLaunchKernelGGL(k_rows_stack, dim3((unsigned)((n * cols + 255) / 256)), dim3(256), 0, c->stream, ab.data(), ra, bb.data(), rb, n * cols, cat->ptr);
+    c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    UniqueRowsDev r;
+    RMHIP_TRY(unique_rows_device(c, cat->ptr, n, cols, stable, 0, &r));
+    std::vector<double> first(r.groups);
+    RMHIP_HIP_CHECK(hipMemcpyAsync(values_host, r.dv, r.groups * cols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipMemcpyAsync(first.data(), r.dia, r.groups * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    size_t ia = 0, ib = 0;
+    for (u64 g = 0; g < r.groups; ++g) {
+        if (first[g] <= (double)ra) ia_host[ia++] = first[g];
+        else ib_host[ib++] = first[g] - (double)ra;
+    }
+    c->tel.download_bytes += (r.groups * cols + r.groups) * sizeof(double);
+    *count = r.groups, *ia_count = ia, *ib_count = ib;
+    return RMHIP_OK;
+}
+
+int rmhip_setdiff_rows(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, int stable, size_t* count, double* values_host, double* ia_host) {
+    CTX_OR_FAIL(ctx);
+    if (!count) return fail(RMHIP_ERR_INVALID, "setdiff: null count");
+    Buffer ab, bb;
+    RMHIP_TRY(rows_operands(c, "setdiff", a, b, &ab, &bb));
+    const u64 ra = ab.shape[0], rb = bb.shape[0], cols = ab.shape[1];
+    *count = 0;
+    if (ra == 0) return RMHIP_OK;
+    if (!ia_host || (cols && !values_host)) return fail(RMHIP_ERR_INVALID, "setdiff: null output");
+    if (cols == 0) {  // a's one distinct (empty) row stays unless b has a row at all (setdiff.rs:516-549)
+        if (rb == 0) ia_host[0] = 1.0, *count = 1;
+        return RMHIP_OK;
+    }
+    // setdiff.rs:516-549: a's distinct rows (first occurrences, in the requested order) whose key does not occur among b's rows
+    UniqueRowsDev r;
+    RMHIP_TRY(unique_rows_device(c, ab.data(), ra, cols, stable, 0, &r));
+    const u64 g = r.groups;
+    std::vector<double> v(g * cols), first(g);
+    std::vector<unsigned char> hit(g, 0);
+    if (rb) {
+        std::shared_ptr<Allocation> m;
+        RMHIP_TRY(rows_member_device(c, r.dv, g, bb.data(), rb, cols, &m));
+        RMHIP_HIP_CHECK(hipMemcpyAsync(hit.data(), (unsigned char*)(m->ptr + g), g, hipMemcpyDeviceToHost, c->stream));
+        RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    RMHIP_HIP_CHECK(hipMemcpyAsync(v.data(), r.dv, g * cols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipMemcpyAsync(first.data(), r.dia, g * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    size_t kept = 0;
+    for (u64 k = 0; k < g; ++k)
+        if (!hit[k]) ia_host[kept++] = first[k];
+    for (u64 col = 0; col < cols; ++col) {  // [kept, cols], leading dimension kept
+        size_t w = 0;
+        for (u64 k = 0; k < g; ++k)
+            if (!hit[k]) values_host[w++ + col * kept] = v[k + col * g];
+    }
+    c->tel.download_bytes += (g * cols + g) * sizeof(double);
+    *count = kept;
+    return RMHIP_OK;
+}
+
+int rmhip_ismember_rows(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, unsigned char* mask_host, double* loc_host) {
+    CTX_OR_FAIL(ctx);
+    Buffer ab, bb;
+    RMHIP_TRY(c->get(a, &ab));
+    RMHIP_TRY(c->get(b, &bb));
+    if (ab.shape.size() > 2 || bb.shape.size() > 2) return fail(RMHIP_ERR_SHAPE, "ismember: 'rows' option requires 2-D numeric matrices");
+    const std::vector<size_t> sa = matrix_shape(ab.shape), sb = matrix_shape(bb.shape);  // tensor_rows_cols, ismember.rs:755-765
+    if (sa[1] != sb[1]) return fail(RMHIP_ERR_SHAPE, "ismember: inputs must have the same number of columns when using 'rows'");
+    const u64 ra = sa[0], rb = sb[0], cols = sa[1];
+    if (ra == 0) return RMHIP_OK;
+    if (!mask_host || !loc_host) return fail(RMHIP_ERR_INVALID, "ismember: null output");
+    if (rb == 0 || cols == 0) {  // nothing to match - or rows without columns, which all match b's first row (ismember.rs:447-472)
+        std::memset(mask_host, rb ? 1 : 0, ra);
+        for (u64 i = 0; i < ra; ++i) loc_host[i] = rb ? 1.0 : 0.0;
+        return RMHIP_OK;
+    }
+    std::shared_ptr<Allocation> outs;
+    RMHIP_TRY(rows_member_device(c, ab.data(), ra, bb.data(), rb, cols, &outs));
+    RMHIP_HIP_CHECK(hipMemcpyAsync(loc_host, outs->ptr, ra * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipMemcpyAsync(mask_host, (unsigned char*)(outs->ptr + ra), ra, hipMemcpyDeviceToHost, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->tel.download_bytes += ra * 9;
+    return RMHIP_OK;
+}
+
 int rmhip_sort_rows(rmhip_ctx* ctx, rmhip_buf a, const size_t* column_index, const int* column_descend, size_t n_columns, int by_abs, rmhip_buf* sorted,
                     rmhip_buf* indices) {
     CTX_OR_FAIL(ctx);
@@ -1315,23 +1607,7 @@ int rmhip_sort_rows(rmhip_ctx* ctx, rmhip_buf a, const size_t* column_index, con
     u32* perm = nullptr;
     if (rc == RMHIP_OK && rows > 1 && cols > 0 && ab.numel > 0) {
         SortSpace ws;
-        rc = sort_alloc(c, 1, rows, &ws);
-        if (rc == RMHIP_OK) rc = c->alloc_device(rows, &pm);  // two u32 arrays of `rows`
-        u32 *cur = nullptr, *nxt = pm ? (u32*)pm->ptr : nullptr;
-        for (size_t s = n_columns; s-- > 0 && rc == RMHIP_OK;) {  // the last key first: every pass is stable (ties keep the ranks of the pass before)
-            if (column_index[s] >= cols) continue;               // sortrows_host.rs:86-88
-            hipLaunchKernelGGL(k_rows_keys, dim3((unsigned)((ws.total + 255) / 256)), dim3(256), 0, c->stream, ab.data(), rows, (u64)column_index[s], cur, column_descend[s] ? 1 : 0,
-                               by_abs ? 1 : 0, ws.keys, ws.pos, ws.total);
-            c->tel.kernel_launches++;
-            rc = sort_pairs(c, &ws);
-            if (rc != RMHIP_OK) break;
-            hipLaunchKernelGGL(k_rows_compose, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, cur, ws.pos, rows, nxt);
-            c->tel.kernel_launches++;
-            u32* was = cur;
-            cur = nxt;
-            nxt = was ? was : (u32*)pm->ptr + rows;
-        }
-        perm = cur;
+        rc = rows_order(c, ab.data(), rows, cols, column_index, column_descend, n_columns, by_abs, &ws, &pm, &perm);
         if (rc == RMHIP_OK && perm) {
             hipLaunchKernelGGL(k_rows_emit, dim3((unsigned)((ab.numel + 255) / 256)), dim3(256), 0, c->stream, ab.data(), perm, rows, (u64)ab.numel, sb.data(), ib.data());
             c->tel.kernel_launches++;

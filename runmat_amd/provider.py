@@ -1437,7 +1437,8 @@ class HipProvider:
         return bool(res.value)
 
     def unique(self, handle, rows: bool = False, order: str = "sorted", occurrence: str = "first"):
-        """lib.rs:2645-2651 -> `UniqueResult { values, ia, ic }` as host arrays ([count, 1], [count, 1], [numel, 1])."""
+        """lib.rs:2645-2651 -> `UniqueResult { values, ia, ic }` as host arrays ([count, 1], [count, 1], [numel, 1]).  `rows=True` raises
+        here; the 'rows' form is `unique_rows`."""
         if rows:
             raise ProviderError(_lib.ERR_UNSUPPORTED, "unique: the 'rows' form is not served")
         if order not in ("sorted", "stable") or occurrence not in ("first", "last"):
@@ -1452,7 +1453,8 @@ class HipProvider:
         return values[:g].reshape(g, 1).copy(), ia[:g].reshape(g, 1).copy(), ic[:n].reshape(n, 1).copy()
 
     def union(self, a, b, rows: bool = False, order: str = "sorted"):
-        """lib.rs:2652-2659 -> `UnionResult { values, ia, ib }` as host arrays ([g, 1] each)."""
+        """lib.rs:2652-2659 -> `UnionResult { values, ia, ib }` as host arrays ([g, 1] each).  `rows=True` raises here; the 'rows' form is
+        `union_rows`."""
         if rows:
             raise ProviderError(_lib.ERR_UNSUPPORTED, "union: the 'rows' form is not served")
         if order not in ("sorted", "stable"):
@@ -1466,7 +1468,7 @@ class HipProvider:
         return values[:cnt.value].reshape(-1, 1).copy(), ia[:ca.value].reshape(-1, 1).copy(), ib[:cb.value].reshape(-1, 1).copy()
 
     def setdiff(self, a, b, rows: bool = False, order: str = "sorted"):
-        """lib.rs:2660-2667 -> `SetdiffResult { values, ia }` as host arrays."""
+        """lib.rs:2660-2667 -> `SetdiffResult { values, ia }` as host arrays.  `rows=True` raises here; the 'rows' form is `setdiff_rows`."""
         if rows:
             raise ProviderError(_lib.ERR_UNSUPPORTED, "setdiff: the 'rows' form is not served")
         if order not in ("sorted", "stable"):
@@ -1479,13 +1481,66 @@ class HipProvider:
         return values[:cnt.value].reshape(-1, 1).copy(), ia[:cnt.value].reshape(-1, 1).copy()
 
     def ismember(self, a, b, rows: bool = False):
-        """lib.rs `ismember` -> `IsMemberResult { mask, loc }` as host arrays in a's shape (mask: uint8)."""
+        """lib.rs `ismember` -> `IsMemberResult { mask, loc }` as host arrays in a's shape (mask: uint8).  `rows=True` raises here; the
+        'rows' form is `ismember_rows`."""
         if rows:
             raise ProviderError(_lib.ERR_UNSUPPORTED, "ismember: the 'rows' form is not served")
         n = int(np.prod(a.shape, dtype=np.int64)) if len(a.shape) else 1
         mask, loc = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1))
         self._check(self._lib.rmhip_ismember(self._ctx, self._id(a), self._id(b), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), loc.ctypes.data_as(C.POINTER(C.c_double))))
         return mask[:n].reshape(a.shape, order="F").copy(), loc[:n].reshape(a.shape, order="F").copy()
+
+    @staticmethod
+    def _rows_cols(h):
+        """(rows, cols) as the library's matrix_shape reads a handle of rank <= 2; a higher rank sizes nothing (the call is refused)"""
+        sh = tuple(int(e) for e in h.shape)
+        return (1, 1) if len(sh) == 0 else (sh[0], 1) if len(sh) == 1 else (sh[0], sh[1]) if len(sh) == 2 else (0, 0)
+
+    def unique_rows(self, handle, order: str = "sorted", occurrence: str = "first"):
+        """`unique` with `UniqueOptions.rows` (lib.rs:1110-1116; unique.rs:558-662) -> host arrays: the distinct rows [count, cols], ia
+        [count, 1] (the first or last row of each), ic [rows, 1] (the rank of every row)."""
+        if order not in ("sorted", "stable") or occurrence not in ("first", "last"):
+            raise RmhipError(1, f"unique: order {order!r} / occurrence {occurrence!r}")
+        rows, cols = self._rows_cols(handle)
+        values, ia, ic = np.empty(max(rows * cols, 1)), np.empty(max(rows, 1)), np.empty(max(rows, 1))
+        count = C.c_size_t()
+        ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(self._lib.rmhip_unique_rows(self._ctx, self._id(handle), 1 if order == "stable" else 0, 1 if occurrence == "last" else 0, C.byref(count),
+                                                ptr(values), ptr(ia), ptr(ic)))
+        g = count.value
+        return values[:g * cols].reshape((g, cols), order="F").copy(), ia[:g].reshape(g, 1).copy(), ic[:rows].reshape(rows, 1).copy()
+
+    def union_rows(self, a, b, order: str = "sorted"):
+        """`union` with `UnionOptions.rows` (union.rs:546-622) -> host arrays: values [count, cols], ia [na, 1], ib [nb, 1]."""
+        if order not in ("sorted", "stable"):
+            raise RmhipError(1, f"union: order {order!r}")
+        (ra, cols), (rb, _) = self._rows_cols(a), self._rows_cols(b)
+        values, ia, ib = np.empty(max((ra + rb) * cols, 1)), np.empty(max(ra, 1)), np.empty(max(rb, 1))
+        cnt, ca, cb = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(self._lib.rmhip_union_rows(self._ctx, self._id(a), self._id(b), 1 if order == "stable" else 0, C.byref(cnt), ptr(values), C.byref(ca), ptr(ia),
+                                               C.byref(cb), ptr(ib)))
+        g = cnt.value
+        return values[:g * cols].reshape((g, cols), order="F").copy(), ia[:ca.value].reshape(-1, 1).copy(), ib[:cb.value].reshape(-1, 1).copy()
+
+    def setdiff_rows(self, a, b, order: str = "sorted"):
+        """`setdiff` with `SetdiffOptions.rows` (setdiff.rs:498-552) -> host arrays: values [count, cols], ia [count, 1]."""
+        if order not in ("sorted", "stable"):
+            raise RmhipError(1, f"setdiff: order {order!r}")
+        ra, cols = self._rows_cols(a)
+        values, ia = np.empty(max(ra * cols, 1)), np.empty(max(ra, 1))
+        cnt = C.c_size_t()
+        ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(self._lib.rmhip_setdiff_rows(self._ctx, self._id(a), self._id(b), 1 if order == "stable" else 0, C.byref(cnt), ptr(values), ptr(ia)))
+        g = cnt.value
+        return values[:g * cols].reshape((g, cols), order="F").copy(), ia[:g].reshape(g, 1).copy()
+
+    def ismember_rows(self, a, b):
+        """`ismember` with `IsMemberOptions { rows: true }` (ismember.rs:440-480) -> mask (uint8) and loc, both [rows_a, 1]."""
+        ra, _ = self._rows_cols(a)
+        mask, loc = np.zeros(max(ra, 1), dtype=np.uint8), np.zeros(max(ra, 1))
+        self._check(self._lib.rmhip_ismember_rows(self._ctx, self._id(a), self._id(b), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), loc.ctypes.data_as(C.POINTER(C.c_double))))
+        return mask[:ra].reshape(ra, 1).copy(), loc[:ra].reshape(ra, 1).copy()
 
     def iir_filter(self, b, a, x, dim: int, zi=None, unit_denominator: bool = False):
         """lib.rs:2551-2559 -> `ProviderIirFilterResult { output, final_state }` as a pair of handles."""

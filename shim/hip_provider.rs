@@ -832,18 +832,29 @@ impl AccelProvider for HipProvider {
     }
     fn unique<'a>(&'a self, handle: &'a GpuTensorHandle, options: &'a UniqueOptions) -> AccelProviderFuture<'a, UniqueResult> {
         Box::pin(async move {
+            let stable = matches!(options.order, UniqueOrder::Stable) as c_int;
+            let last = matches!(options.occurrence, UniqueOccurrence::Last) as c_int;
+            let real = GpuTensorStorage::Real;
             if options.rows {
-                return Err(anyhow!("unique: the 'rows' form is not served by this provider"));
+                // [count, cols], [count, 1], [rows, 1]; a rank other than 2 sizes nothing and is refused by the library with the CPU's message
+                let (rows, cols) = if handle.shape.len() == 2 { (handle.shape[0], handle.shape[1]) } else { (0, 0) };
+                let (mut values, mut ia, mut ic) = (vec![0.0f64; rows * cols], vec![0.0f64; rows], vec![0.0f64; rows]);
+                let mut count = 0usize;
+                check(unsafe { rmhip_unique_rows(self.ctx, self.own(handle)?, stable, last, &mut count, values.as_mut_ptr(), ia.as_mut_ptr(), ic.as_mut_ptr()) })?;
+                values.truncate(count * cols);
+                ia.truncate(count);
+                return Ok(UniqueResult {
+                    values: HostTensorOwned { data: values, shape: vec![count, cols], storage: real },
+                    ia: HostTensorOwned { data: ia, shape: vec![count, 1], storage: real },
+                    ic: HostTensorOwned { data: ic, shape: vec![rows, 1], storage: real },
+                });
             }
             let n: usize = handle.shape.iter().product();
             let (mut values, mut ia, mut ic) = (vec![0.0f64; n], vec![0.0f64; n], vec![0.0f64; n]);
             let mut count = 0usize;
-            let stable = matches!(options.order, UniqueOrder::Stable) as c_int;
-            let last = matches!(options.occurrence, UniqueOccurrence::Last) as c_int;
             check(unsafe { rmhip_unique(self.ctx, self.own(handle)?, stable, last, &mut count, values.as_mut_ptr(), ia.as_mut_ptr(), ic.as_mut_ptr()) })?;
             values.truncate(count);
             ia.truncate(count);
-            let real = GpuTensorStorage::Real;
             Ok(UniqueResult {
                 values: HostTensorOwned { data: values, shape: vec![count, 1], storage: real },
                 ia: HostTensorOwned { data: ia, shape: vec![count, 1], storage: real },
@@ -853,20 +864,34 @@ impl AccelProvider for HipProvider {
     }
     fn union<'a>(&'a self, a: &'a GpuTensorHandle, b: &'a GpuTensorHandle, options: &'a UnionOptions) -> AccelProviderFuture<'a, UnionResult> {
         Box::pin(async move {
+            let stable = matches!(options.order, UnionOrder::Stable) as c_int;
+            let real = GpuTensorStorage::Real;
             if options.rows {
-                return Err(anyhow!("union: the 'rows' form is not served by this provider"));
+                let rc = |h: &GpuTensorHandle| if h.shape.len() == 2 { (h.shape[0], h.shape[1]) } else { (0, 0) };
+                let ((ra, cols), (rb, _)) = (rc(a), rc(b));
+                let (mut values, mut ia, mut ib) = (vec![0.0f64; (ra + rb) * cols], vec![0.0f64; ra], vec![0.0f64; rb]);
+                let (mut n, mut ca, mut cb) = (0usize, 0usize, 0usize);
+                check(unsafe {
+                    rmhip_union_rows(self.ctx, self.own(a)?, self.own(b)?, stable, &mut n, values.as_mut_ptr(), &mut ca, ia.as_mut_ptr(), &mut cb, ib.as_mut_ptr())
+                })?;
+                values.truncate(n * cols);
+                ia.truncate(ca);
+                ib.truncate(cb);
+                return Ok(UnionResult {
+                    values: HostTensorOwned { data: values, shape: vec![n, cols], storage: real },
+                    ia: HostTensorOwned { data: ia, shape: vec![ca, 1], storage: real },
+                    ib: HostTensorOwned { data: ib, shape: vec![cb, 1], storage: real },
+                });
             }
             let (na, nb): (usize, usize) = (a.shape.iter().product(), b.shape.iter().product());
             let (mut values, mut ia, mut ib) = (vec![0.0f64; na + nb], vec![0.0f64; na], vec![0.0f64; nb]);
             let (mut n, mut ca, mut cb) = (0usize, 0usize, 0usize);
-            let stable = matches!(options.order, UnionOrder::Stable) as c_int;
             check(unsafe {
                 rmhip_union(self.ctx, self.own(a)?, self.own(b)?, stable, &mut n, values.as_mut_ptr(), &mut ca, ia.as_mut_ptr(), &mut cb, ib.as_mut_ptr())
             })?;
             values.truncate(n);
             ia.truncate(ca);
             ib.truncate(cb);
-            let real = GpuTensorStorage::Real;
             Ok(UnionResult {
                 values: HostTensorOwned { data: values, shape: vec![n, 1], storage: real },
                 ia: HostTensorOwned { data: ia, shape: vec![ca, 1], storage: real },
@@ -876,17 +901,26 @@ impl AccelProvider for HipProvider {
     }
     fn setdiff<'a>(&'a self, a: &'a GpuTensorHandle, b: &'a GpuTensorHandle, options: &'a SetdiffOptions) -> AccelProviderFuture<'a, SetdiffResult> {
         Box::pin(async move {
+            let stable = matches!(options.order, SetdiffOrder::Stable) as c_int;
+            let real = GpuTensorStorage::Real;
             if options.rows {
-                return Err(anyhow!("setdiff: the 'rows' form is not served by this provider"));
+                let (ra, cols) = if a.shape.len() == 2 { (a.shape[0], a.shape[1]) } else { (0, 0) };
+                let (mut values, mut ia) = (vec![0.0f64; ra * cols], vec![0.0f64; ra]);
+                let mut n = 0usize;
+                check(unsafe { rmhip_setdiff_rows(self.ctx, self.own(a)?, self.own(b)?, stable, &mut n, values.as_mut_ptr(), ia.as_mut_ptr()) })?;
+                values.truncate(n * cols);
+                ia.truncate(n);
+                return Ok(SetdiffResult {
+                    values: HostTensorOwned { data: values, shape: vec![n, cols], storage: real },
+                    ia: HostTensorOwned { data: ia, shape: vec![n, 1], storage: real },
+                });
             }
             let na: usize = a.shape.iter().product();
             let (mut values, mut ia) = (vec![0.0f64; na], vec![0.0f64; na]);
             let mut n = 0usize;
-            let stable = matches!(options.order, SetdiffOrder::Stable) as c_int;
             check(unsafe { rmhip_setdiff(self.ctx, self.own(a)?, self.own(b)?, stable, &mut n, values.as_mut_ptr(), ia.as_mut_ptr()) })?;
             values.truncate(n);
             ia.truncate(n);
-            let real = GpuTensorStorage::Real;
             Ok(SetdiffResult {
                 values: HostTensorOwned { data: values, shape: vec![n, 1], storage: real },
                 ia: HostTensorOwned { data: ia, shape: vec![n, 1], storage: real },
@@ -896,7 +930,14 @@ impl AccelProvider for HipProvider {
     fn ismember<'a>(&'a self, a: &'a GpuTensorHandle, b: &'a GpuTensorHandle, options: &'a IsMemberOptions) -> AccelProviderFuture<'a, IsMemberResult> {
         Box::pin(async move {
             if options.rows {
-                return Err(anyhow!("ismember: the 'rows' form is not served by this provider"));
+                // `tensor_rows_cols` (ismember.rs:755-765): rank 0 / 1 / 2 is (1, 1) / (n, 1) / (r, c); both results are [rows_a, 1]
+                let ra = match a.shape.len() { 0 => 1, 1 | 2 => a.shape[0], _ => 0 };
+                let (mut mask, mut loc) = (vec![0u8; ra], vec![0.0f64; ra]);
+                check(unsafe { rmhip_ismember_rows(self.ctx, self.own(a)?, self.own(b)?, mask.as_mut_ptr(), loc.as_mut_ptr()) })?;
+                return Ok(IsMemberResult {
+                    mask: HostLogicalOwned { data: mask, shape: vec![ra, 1] },
+                    loc: HostTensorOwned { data: loc, shape: vec![ra, 1], storage: GpuTensorStorage::Real },
+                });
             }
             let n: usize = a.shape.iter().product();
             let (mut mask, mut loc) = (vec![0u8; n], vec![0.0f64; n]);
