@@ -241,7 +241,12 @@ enum rmhip_reduce_op { RMHIP_RSUM = 0, RMHIP_RMEAN, RMHIP_RMIN, RMHIP_RMAX, RMHI
                        RMHIP_REDUCE_OP_COUNT };
 /* dim < 0: reduce all elements -> shape [1,1] (simple_provider.rs:6728-6748).
  * dim 0 / 1 (zero-based, 2-D): -> [1,cols] / [rows,1] (simple_provider.rs:6750-6806).
- * nan_mode 0 = include (any NaN => NaN, sum.rs:1038-1045), 1 = omit. */
+ * nan_mode 0 = include (any NaN => NaN, sum.rs:1038-1045), 1 = omit.
+ * A slice with nothing to reduce - extent 0 along `dim`, or nan_mode 1 and only NaNs - gives 0 for sum (sum.rs:1055-1076), 1 for
+ * prod (prod.rs:963-984) and NaN for mean (mean.rs:1203-1206, 1252-1258); min and max of a slice of NaNs in nan_mode 1 are NaN
+ * (min.rs:1065-1068), and for extent 0, where the CPU returns an empty result this shape cannot express, NaN as well.
+ * min / max follow the CPU builtin's total order, the one rmhip_reduce_minmax_dim uses: -0 is below +0 (min.rs:1519-1531,
+ * max.rs:1715-1727), so for any slice both entry points return the same bits, whatever kernel serves the shape. */
 /* @serves reduce_sum reduce_sum_dim reduce_mean reduce_mean_dim reduce_min reduce_max reduce_prod reduce_prod_dim */
 RMHIP_API int rmhip_reduce(rmhip_ctx* ctx, int op, rmhip_buf a, int dim, int nan_mode,
                            rmhip_buf* out);

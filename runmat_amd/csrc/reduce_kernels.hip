@@ -163,8 +163,10 @@ template <int OP, class T>
 static int run_reduce(Context* c, int mean, int nan_mode, const T* x, size_t pre, size_t red, size_t post,
                       double* out) {
     if (pre == 0 || post == 0) return RMHIP_OK;  // no output slices
-    const ReducePlan p = plan_reduction(pre, red, post, c->num_cus, (unsigned)sizeof(T));
-    if (!p.valid) return fail(RMHIP_ERR_UNSUPPORTED, "reduce: geometry [%zu,%zu,%zu] exceeds launch limits", pre, red, post);
+    // which kernel, how many partials per slice, which finalize: reduce_plan.h route_reduction
+    const ReduceRoute rt = route_reduction(pre, red, post, c->num_cus, c->num_xcc, (unsigned)sizeof(T), (((uintptr_t)x) & 15) == 0);
+    if (!rt.valid) return fail(RMHIP_ERR_UNSUPPORTED, "reduce: geometry [%zu,%zu,%zu] exceeds launch limits", pre, red, post);
+    const ReducePlan& p = rt.plan;
     // Kernel B in its 16-byte form (two adjacent slices per thread, 256-thread blocks, non-temporal loads, the partial last
     // group of a chunk loaded together like the full ones) with THREE blocks per CU.  The block count matters more than
     // anything inside the kernel, and not monotonically (scripts/red_bpc_ab.sh, sum(x,2) in us for 8192^2 / 16384x4096 /
@@ -173,67 +175,83 @@ static int run_reduce(Context* c, int mean, int nan_mode, const T* x, size_t pre
     // and the streams run in lockstep; 1024 blocks (exactly four per CU) with 128-column chunks is the worst point
     // (112 us), 512 or 768 the best.  The generic kernel B at its 8 blocks per CU: 113.8 us.  A 1024-thread version with
     // 16 KiB of every column per block: 137 us.
-    uint64_t nsplit = p.nsplit;
-    // dev knobs (A/B only): RMHIP_RED_B_MODE 0 = generic kernel B, 1/2 = the 16-byte form with 8 / 4 loads in flight;
-    // RMHIP_RED_B_BPC = its target blocks per CU
+    // The number of windows along `pre` is a multiple of the XCD count.  Workgroups go to XCDs round robin in launch order
+    // (x fastest), so with gridDim.x % 8 == 0 a window - the same 4 KiB of every column - is always walked by the same XCD,
+    // whatever the chunk; otherwise the windows rotate over the XCDs from chunk to chunk.  Measured (sum(x,2), us, windows
+    // before -> after): 8200 x 8192 17 -> 24: 109 -> 90; 8256 x 8192 17 -> 24: 108 -> 95; 16400 x 4096 33 -> 40: 110 -> 97;
+    // 5000 x 13000 10 -> 16: 104 -> 84; 12000 x 6000: 93; shapes whose count already was a multiple of eight (8192, 7936,
+    // 8190, 16384 rows: 16 / 32 windows) are where round 2's 84-89 us came from - "rows a multiple of 512" was a proxy.
+    // The windows are balanced (128-byte granules) and a block has as many waves as its window needs.  (Also measured: two or
+    // four pairs per thread, 8-16 KiB of every column per block: 103-152 us.)
+    ReduceKernel kernel = rt.kernel;
+    uint64_t nsplit = rt.nsplit;
+    bool flat_final = rt.flat_final;
+    StridedWidePlan w = rt.wide;
+    // dev knobs (A/B only), overrides of the route: RMHIP_RED_B_MODE 0 = generic kernel B, 1/2 = the 16-byte form with 8 / 4 loads
+    // in flight; RMHIP_RED_B_BPC = its target blocks per CU; RMHIP_RED_B_X8=0 = the old window geometry; RMHIP_RED_B_CHUNK =
+    // columns per chunk
     static const int b_mode = getenv("RMHIP_RED_B_MODE") ? atoi(getenv("RMHIP_RED_B_MODE")) : 1;
     static const int b_bpc = getenv("RMHIP_RED_B_BPC") ? atoi(getenv("RMHIP_RED_B_BPC")) : 3;
-    const bool wide_b = !p.contiguous && b_mode > 0 && pre >= 512 && post <= 65535;
-    const bool wide_odd = wide_b && ((pre & 1) != 0 || (((uintptr_t)x) & 15) != 0);  // unaligned pairs + a scalar last row
-    unsigned wide_bx = 0, wide_win = RM_RBLOCK, wide_threads = RM_RBLOCK;
-    if (wide_b) {
-        // The number of windows along `pre` is a multiple of the XCD count.  Workgroups go to XCDs round robin in launch order
-        // (x fastest), so with gridDim.x % 8 == 0 a window - the same 4 KiB of every column - is always walked by the same XCD,
-        // whatever the chunk; otherwise the windows rotate over the XCDs from chunk to chunk.  Measured (sum(x,2), us, windows
-        // before -> after): 8200 x 8192 17 -> 24: 109 -> 90; 8256 x 8192 17 -> 24: 108 -> 95; 16400 x 4096 33 -> 40: 110 -> 97;
-        // 5000 x 13000 10 -> 16: 104 -> 84; 12000 x 6000: 93; shapes whose count already was a multiple of eight (8192, 7936,
-        // 8190, 16384 rows: 16 / 32 windows) are where round 2's 84-89 us came from - "rows a multiple of 512" was a proxy.
-        // The windows are balanced (128-byte granules) and a block has as many waves as its window needs.  RMHIP_RED_B_X8=0
-        // restores the old geometry.  (Also measured: two or four pairs per thread, 8-16 KiB of every column per block: 103-152 us.)
-        static const int b_x8 = getenv("RMHIP_RED_B_X8") ? atoi(getenv("RMHIP_RED_B_X8")) : 1;
-        const StridedWidePlan w = plan_strided_wide(pre, red, post, c->num_cus, c->num_xcc, (unsigned)sizeof(T), b_bpc, b_x8 != 0);  // reduce_plan.h
-        wide_bx = w.bx;
-        wide_win = w.win;
-        wide_threads = w.threads;
-        nsplit = w.nsplit;
-        static const long dev_chunk = getenv("RMHIP_RED_B_CHUNK") ? atol(getenv("RMHIP_RED_B_CHUNK")) : 0;  // dev knob: columns per chunk
-        if (dev_chunk > 0) nsplit = ceil_div_u64(red, (uint64_t)dev_chunk);
-        if (nsplit > 65535) nsplit = 65535;
+    static const int b_x8 = getenv("RMHIP_RED_B_X8") ? atoi(getenv("RMHIP_RED_B_X8")) : 1;
+    static const long dev_chunk = getenv("RMHIP_RED_B_CHUNK") ? atol(getenv("RMHIP_RED_B_CHUNK")) : 0;
+    const bool wide = kernel == ReduceKernel::STRIDED_V2 || kernel == ReduceKernel::STRIDED_V2_ODD;
+    if (wide && (b_mode <= 0 || b_bpc != 3 || b_x8 == 0 || dev_chunk > 0)) {
+        if (b_mode <= 0) {
+            kernel = ReduceKernel::STRIDED;
+            nsplit = p.nsplit;
+        } else {
+            w = plan_strided_wide(pre, red, post, c->num_cus, c->num_xcc, (unsigned)sizeof(T), b_bpc, b_x8 != 0);
+            nsplit = w.nsplit;
+            if (dev_chunk > 0) nsplit = ceil_div_u64(red, (uint64_t)dev_chunk);
+            if (nsplit > 65535) nsplit = 65535;
+            if (nsplit < 1) nsplit = 1;
+        }
+        flat_final = reduce_flat_final(nsplit, p.nslices);
     }
-    const bool short_a = p.contiguous && red >= 1 && red < 256 && p.nslices >= 1024;  // many short contiguous slices: a tile of slices per block
-    if (short_a) nsplit = 1;
     const size_t nparts = (size_t)(p.nslices * nsplit);
     RMHIP_TRY(c->ensure_scratch(2 * nparts * sizeof(double)));
     double* pv = c->scratch;
     double* pn = c->scratch + nparts;
-    if (short_a) {
-        unsigned per_block = (unsigned)(SHORT_TILE / red);
-        if (per_block > RM_RBLOCK) per_block = RM_RBLOCK;
-        hipLaunchKernelGGL((k_reduce_short<OP, T>), dim3((unsigned)ceil_div_u64(p.nslices, per_block)), dim3(RM_RBLOCK), 0, c->stream, x, (rm_u64)red,
-                           (rm_u64)p.nslices, per_block, pv, pn);
-    } else if (p.contiguous && (red & 1) == 0 && red >= 2048 && (((uintptr_t)x) & 15) == 0)
-        hipLaunchKernelGGL((k_reduce_contig_v2<OP, T>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, x, (rm_u64)red,
-                           (rm_u64)p.nslices, (rm_u64)p.nsplit, pv, pn);
-    else if (p.contiguous && red >= 2048)  // odd slice length or an element-aligned base: the same kernel on unaligned pairs
-        hipLaunchKernelGGL((k_reduce_contig_v2<OP, T, true>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, x, (rm_u64)red,
-                           (rm_u64)p.nslices, (rm_u64)p.nsplit, pv, pn);
-    else if (p.contiguous)
-        hipLaunchKernelGGL((k_reduce_contig<OP, T>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, x,
-                           (rm_u64)red, (rm_u64)p.nslices, (rm_u64)p.nsplit, pv, pn);
-    else if (wide_b && b_mode == 2 && !wide_odd)
-        hipLaunchKernelGGL((k_reduce_strided_v2<OP, T, 4>), dim3(wide_bx, (unsigned)nsplit, (unsigned)post), dim3(wide_threads), 0, c->stream,
-                           x, (rm_u64)pre, (rm_u64)red, (rm_u64)nsplit, wide_win, pv, pn);
-    else if (wide_odd)
-        hipLaunchKernelGGL((k_reduce_strided_v2<OP, T, 8, true>), dim3(wide_bx, (unsigned)nsplit, (unsigned)post), dim3(wide_threads), 0, c->stream,
-                           x, (rm_u64)pre, (rm_u64)red, (rm_u64)nsplit, wide_win, pv, pn);
-    else if (wide_b)
-        hipLaunchKernelGGL((k_reduce_strided_v2<OP, T, 8>), dim3(wide_bx, (unsigned)nsplit, (unsigned)post), dim3(wide_threads), 0, c->stream,
-                           x, (rm_u64)pre, (rm_u64)red, (rm_u64)nsplit, wide_win, pv, pn);
-    else
-        hipLaunchKernelGGL((k_reduce_strided<OP, T>), dim3(p.gx, p.gy, p.gz), dim3(RM_RBLOCK), 0, c->stream, x,
-                           (rm_u64)pre, (rm_u64)red, (rm_u64)p.nsplit, p.tx, pv, pn);
+    const dim3 wide_grid(w.bx, (unsigned)nsplit, (unsigned)post);
+    switch (kernel) {
+        case ReduceKernel::SHORT: {
+            unsigned per_block = (unsigned)(SHORT_TILE / red);
+            if (per_block > RM_RBLOCK) per_block = RM_RBLOCK;
+            hipLaunchKernelGGL((k_reduce_short<OP, T>), dim3((unsigned)ceil_div_u64(p.nslices, per_block)), dim3(RM_RBLOCK), 0, c->stream, x,
+                               (rm_u64)red, (rm_u64)p.nslices, per_block, pv, pn);
+            break;
+        }
+        case ReduceKernel::CONTIG_V2:
+            hipLaunchKernelGGL((k_reduce_contig_v2<OP, T>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, x, (rm_u64)red,
+                               (rm_u64)p.nslices, (rm_u64)nsplit, pv, pn);
+            break;
+        case ReduceKernel::CONTIG_V2_ODD:
+            hipLaunchKernelGGL((k_reduce_contig_v2<OP, T, true>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, x, (rm_u64)red,
+                               (rm_u64)p.nslices, (rm_u64)nsplit, pv, pn);
+            break;
+        case ReduceKernel::CONTIG:
+            hipLaunchKernelGGL((k_reduce_contig<OP, T>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, x, (rm_u64)red,
+                               (rm_u64)p.nslices, (rm_u64)nsplit, pv, pn);
+            break;
+        case ReduceKernel::STRIDED_V2:
+            if (b_mode == 2)
+                hipLaunchKernelGGL((k_reduce_strided_v2<OP, T, 4>), wide_grid, dim3(w.threads), 0, c->stream, x, (rm_u64)pre, (rm_u64)red,
+                                   (rm_u64)nsplit, w.win, pv, pn);
+            else
+                hipLaunchKernelGGL((k_reduce_strided_v2<OP, T, 8>), wide_grid, dim3(w.threads), 0, c->stream, x, (rm_u64)pre, (rm_u64)red,
+                                   (rm_u64)nsplit, w.win, pv, pn);
+            break;
+        case ReduceKernel::STRIDED_V2_ODD:
+            hipLaunchKernelGGL((k_reduce_strided_v2<OP, T, 8, true>), wide_grid, dim3(w.threads), 0, c->stream, x, (rm_u64)pre, (rm_u64)red,
+                               (rm_u64)nsplit, w.win, pv, pn);
+            break;
+        case ReduceKernel::STRIDED:
+            hipLaunchKernelGGL((k_reduce_strided<OP, T>), dim3(p.gx, p.gy, p.gz), dim3(RM_RBLOCK), 0, c->stream, x, (rm_u64)pre,
+                               (rm_u64)red, (rm_u64)nsplit, p.tx, pv, pn);
+            break;
+    }
     RMHIP_HIP_CHECK(hipGetLastError());
-    if ((nsplit <= 8 && p.nslices >= 1024) || (nsplit <= 32 && p.nslices >= 16384)) {  // many slices, a handful of partials each: one thread per slice
+    if (flat_final) {  // many slices, a handful of partials each: one thread per slice
         hipLaunchKernelGGL((k_reduce_final_flat<OP>), dim3((unsigned)ceil_div_u64(p.nslices, RM_RBLOCK)), dim3(RM_RBLOCK), 0, c->stream, pv, pn,
                            (rm_u64)p.nslices, (rm_u64)nsplit, (rm_u64)red, mean, nan_mode, 1.0, out);
     } else {
@@ -327,36 +345,45 @@ __global__ void __launch_bounds__(RM_RBLOCK) k_dot_short(const T* __restrict__ a
 template <class T>
 static int reduce_dot_any(Context* c, const T* a, const T* b, size_t pre, size_t red, size_t post, double* out) {
     if (pre == 0 || post == 0) return RMHIP_OK;  // no output slices
-    ReducePlan p = plan_reduction(pre, red, post, c->num_cus, (unsigned)sizeof(T));
-    if (!p.valid) return fail(RMHIP_ERR_UNSUPPORTED, "dot: geometry [%zu,%zu,%zu] exceeds launch limits", pre, red, post);
-    const bool short_a = p.contiguous && red >= 1 && red < 256 && p.nslices >= 1024;
-    if (short_a) p.nsplit = 1;
-    const size_t nparts = (size_t)(p.nslices * p.nsplit);
+    const ReduceRoute rt = route_reduction(pre, red, post, c->num_cus, c->num_xcc, (unsigned)sizeof(T),
+                                           ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0, /*dot=*/true);  // reduce_plan.h
+    if (!rt.valid) return fail(RMHIP_ERR_UNSUPPORTED, "dot: geometry [%zu,%zu,%zu] exceeds launch limits", pre, red, post);
+    const ReducePlan& p = rt.plan;
+    const uint64_t nsplit = rt.nsplit;
+    const size_t nparts = (size_t)(p.nslices * nsplit);
     RMHIP_TRY(c->ensure_scratch(2 * nparts * sizeof(double)));
     double* pv = c->scratch;
     double* pn = c->scratch + nparts;
-    if (short_a) {
-        unsigned per_block = (unsigned)(SHORT_TILE / red);
-        if (per_block > RM_RBLOCK) per_block = RM_RBLOCK;
-        hipLaunchKernelGGL((k_dot_short<T>), dim3((unsigned)ceil_div_u64(p.nslices, per_block)), dim3(RM_RBLOCK), 0, c->stream, a, b, (rm_u64)red,
-                           (rm_u64)p.nslices, per_block, pv, pn);
-    } else if (p.contiguous && (red & 1) == 0 && red >= 2048 && ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0)
-        hipLaunchKernelGGL((k_dot_contig_v2<T>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, a, b, (rm_u64)red,
-                           (rm_u64)p.nslices, (rm_u64)p.nsplit, pv, pn);
-    else if (p.contiguous)
-        hipLaunchKernelGGL((k_dot_contig<T>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, a, b, (rm_u64)red,
-                           (rm_u64)p.nslices, (rm_u64)p.nsplit, pv, pn);
-    else
-        hipLaunchKernelGGL((k_dot_strided<T>), dim3(p.gx, p.gy, p.gz), dim3(RM_RBLOCK), 0, c->stream, a, b, (rm_u64)pre,
-                           (rm_u64)red, (rm_u64)p.nsplit, p.tx, pv, pn);
+    switch (rt.kernel) {
+        case ReduceKernel::SHORT: {
+            unsigned per_block = (unsigned)(SHORT_TILE / red);
+            if (per_block > RM_RBLOCK) per_block = RM_RBLOCK;
+            hipLaunchKernelGGL((k_dot_short<T>), dim3((unsigned)ceil_div_u64(p.nslices, per_block)), dim3(RM_RBLOCK), 0, c->stream, a, b,
+                               (rm_u64)red, (rm_u64)p.nslices, per_block, pv, pn);
+            break;
+        }
+        case ReduceKernel::CONTIG_V2:
+            hipLaunchKernelGGL((k_dot_contig_v2<T>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, a, b, (rm_u64)red,
+                               (rm_u64)p.nslices, (rm_u64)nsplit, pv, pn);
+            break;
+        case ReduceKernel::CONTIG:
+            hipLaunchKernelGGL((k_dot_contig<T>), dim3(p.gx, p.gy, p.gz), dim3(p.tx), 0, c->stream, a, b, (rm_u64)red,
+                               (rm_u64)p.nslices, (rm_u64)nsplit, pv, pn);
+            break;
+        case ReduceKernel::STRIDED:
+            hipLaunchKernelGGL((k_dot_strided<T>), dim3(p.gx, p.gy, p.gz), dim3(RM_RBLOCK), 0, c->stream, a, b, (rm_u64)pre,
+                               (rm_u64)red, (rm_u64)nsplit, p.tx, pv, pn);
+            break;
+        default: return fail(RMHIP_ERR_UNSUPPORTED, "dot: no kernel for route %s", reduce_kernel_name(rt.kernel));
+    }
     RMHIP_HIP_CHECK(hipGetLastError());
-    if (p.nsplit <= 8 && p.nslices >= 1024) {
+    if (rt.flat_final) {
         hipLaunchKernelGGL((k_reduce_final_flat<RM_RSUM>), dim3((unsigned)ceil_div_u64(p.nslices, RM_RBLOCK)), dim3(RM_RBLOCK), 0, c->stream, pv, pn,
-                           (rm_u64)p.nslices, (rm_u64)p.nsplit, (rm_u64)red, 0, 0, 1.0, out);
+                           (rm_u64)p.nslices, (rm_u64)nsplit, (rm_u64)red, 0, 0, 1.0, out);
     } else {
         const unsigned fb = (unsigned)ceil_div_u64(p.nslices, RM_RBLOCK / 64);
         hipLaunchKernelGGL((k_reduce_final<RM_RSUM>), dim3(fb), dim3(RM_RBLOCK), 0, c->stream, pv, pn, (rm_u64)p.nslices,
-                           (rm_u64)p.nsplit, (rm_u64)red, 0, 0, 1.0, out);
+                           (rm_u64)nsplit, (rm_u64)red, 0, 0, 1.0, out);
     }
     RMHIP_HIP_CHECK(hipGetLastError());
     c->tel.kernel_launches += 2;

@@ -114,9 +114,70 @@ inline StridedWidePlan plan_strided_wide(uint64_t pre, uint64_t red, uint64_t po
     const uint64_t max_split = ceil_div_u64(red, 16);
     w.nsplit = want < 1 ? 1 : want;
     if (w.nsplit > max_split) w.nsplit = max_split;
+    if (w.nsplit < 1) w.nsplit = 1;  // red == 0: one (empty) chunk per slice, the finalize writes the empty reduction's value
     w.nsplit = dealias_nsplit(red, w.nsplit, pre * elem_bytes, max_split);
     if (w.nsplit > 65535) w.nsplit = 65535;
     return w;
+}
+
+// ---- which kernel serves a [pre, red, post] reduction, with how many partials per slice, and which finalize folds them ----
+// The one place where the ahead-of-time reductions (reduce_kernels.hip: run_reduce, reduce_dot_any) choose; a pure function of the
+// shape, the device's CU / XCD counts, the storage width and the base address' alignment, so tests/cpp/reduce_route_check.cpp can
+// pin the choice without a GPU.  The developer knobs (RMHIP_RED_B_*) are overrides the launcher applies on top.
+enum class ReduceKernel { SHORT, CONTIG, CONTIG_V2, CONTIG_V2_ODD, STRIDED, STRIDED_V2, STRIDED_V2_ODD };
+inline const char* reduce_kernel_name(ReduceKernel k) {
+    switch (k) {
+        case ReduceKernel::SHORT: return "short";
+        case ReduceKernel::CONTIG: return "contig";
+        case ReduceKernel::CONTIG_V2: return "contig_v2";
+        case ReduceKernel::CONTIG_V2_ODD: return "contig_v2_odd";
+        case ReduceKernel::STRIDED: return "strided";
+        case ReduceKernel::STRIDED_V2: return "strided_v2";
+        case ReduceKernel::STRIDED_V2_ODD: return "strided_v2_odd";
+    }
+    return "?";
+}
+// Many slices with a handful of partials each: one thread per slice (rm_reduce_finalize_flat) instead of one wave.  The dot
+// launcher has only the first clause.
+inline bool reduce_flat_final(uint64_t nsplit, uint64_t nslices, bool dot = false) {
+    return (nsplit <= 8 && nslices >= 1024) || (!dot && nsplit <= 32 && nslices >= 16384);
+}
+struct ReduceRoute {
+    bool valid;            // false: plan_reduction refused the geometry
+    ReduceKernel kernel;
+    uint64_t nsplit;       // partials per slice as the kernel and the finalize see them
+    bool flat_final;
+    ReducePlan plan;       // grid / block of the SHORT-less kernels A and the generic kernel B
+    StridedWidePlan wide;  // geometry of STRIDED_V2 / STRIDED_V2_ODD (zero otherwise)
+};
+// `base_16B_aligned`: every operand's base address is a multiple of 16.  `dot`: the two-operand skeletons, which have no
+// unaligned-pair form of kernel A and no 16-byte form of kernel B.
+inline ReduceRoute route_reduction(uint64_t pre, uint64_t red, uint64_t post, int num_cus, int xcds, unsigned elem_bytes,
+                                   bool base_16B_aligned, bool dot = false) {
+    ReduceRoute r{};
+    r.plan = plan_reduction(pre, red, post, num_cus, elem_bytes);
+    r.valid = r.plan.valid;
+    if (!r.valid) return r;
+    const ReducePlan& p = r.plan;
+    r.nsplit = p.nsplit;
+    if (p.contiguous) {
+        if (red >= 1 && red < 256 && p.nslices >= 1024) {  // many short contiguous slices: a tile of slices per block
+            r.kernel = ReduceKernel::SHORT;
+            r.nsplit = 1;
+        } else if (red >= 2048 && (red & 1) == 0 && base_16B_aligned)
+            r.kernel = ReduceKernel::CONTIG_V2;
+        else if (red >= 2048 && !dot)  // odd slice length or an element-aligned base: the same kernel on unaligned pairs
+            r.kernel = ReduceKernel::CONTIG_V2_ODD;
+        else
+            r.kernel = ReduceKernel::CONTIG;
+    } else if (!dot && pre >= 512 && post <= 65535) {
+        r.wide = plan_strided_wide(pre, red, post, num_cus, xcds, elem_bytes);
+        r.nsplit = r.wide.nsplit;
+        r.kernel = (pre & 1) != 0 || !base_16B_aligned ? ReduceKernel::STRIDED_V2_ODD : ReduceKernel::STRIDED_V2;
+    } else
+        r.kernel = ReduceKernel::STRIDED;
+    r.flat_final = reduce_flat_final(r.nsplit, p.nslices, dot);
+    return r;
 }
 
 }  // namespace rmhip

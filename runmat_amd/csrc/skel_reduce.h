@@ -39,8 +39,12 @@ __device__ __forceinline__ RmAcc rm_acc_init() {
 }
 template <int OP>
 __device__ __forceinline__ double rm_combine(double a, double b) {
-    if (OP == RM_RMIN) return b < a ? b : a;
-    if (OP == RM_RMAX) return b > a ? b : a;
+    // The CPU builtin's total order (min.rs:1519-1531, max.rs:1715-1727): -0 is below +0, so the result's sign does not depend on
+    // which lane, chunk or kernel met which zero.  v_min_f64 / v_max_f64 order the zeros that way themselves, one instruction
+    // where compare-and-select takes three; neither operand is a NaN here (rm_acc_add counts NaNs instead of combining them).
+    // tests/test_gpu_reduce_paths.py test_minmax_consistency pins the zero order on the device.
+    if (OP == RM_RMIN) return __builtin_fmin(a, b);
+    if (OP == RM_RMAX) return __builtin_fmax(a, b);
     if (OP == RM_RPROD) return a * b;
     return a + b;
 }
