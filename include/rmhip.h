@@ -706,7 +706,7 @@ RMHIP_API int rmhip_complex_real(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf* out);
  * grouping"), input_rows % bps != 0 ("...: bit rows must be a multiple of bits_per_symbol"), shape[0] != input_rows ("...: input_rows
  * must match the input leading dimension"), all RMHIP_ERR_INVALID; bps > 32 RMHIP_ERR_UNSUPPORTED (the CPU's usize shift is no contract
  * there; the wgpu provider caps the order at u32 too); a table of more than 2^32 - 1 points RMHIP_ERR_UNSUPPORTED.  A refused call
- * leaves no buffer behind.  With these two this header serves 228 of the trait's 243 methods. */
+ * leaves no buffer behind. */
 /* @serves modulate_constellation */
 RMHIP_API int rmhip_modulate_constellation(rmhip_ctx* ctx, rmhip_buf input, const double* constellation, size_t n_values, rmhip_buf* out);
 /* @serves modulate_bits_constellation */
@@ -875,6 +875,35 @@ RMHIP_API int rmhip_chol(rmhip_ctx* ctx, rmhip_buf a, int lower, rmhip_buf* fact
  * does not fit in device memory. */
 /* @serves qr */
 RMHIP_API int rmhip_qr(rmhip_ctx* ctx, rmhip_buf a, int economy, int pivot_vector, rmhip_buf out4[4]);
+/* `take_matmul_sources(product)` (lib.rs:2516-2521 -> Option<(lhs, rhs)>): was `product` made by `matmul`, and from which operands?  rmhip_matmul
+ * is the only recording entry point (as in the reference, ops/linalg/matmul.rs:1005,1120): after a successful product it notes
+ * product id -> (lhs id, rhs id) in the context.  This call REMOVES the note (a second call answers *found = 0) and reports *found = 1
+ * with the two ids only if both operands are still live buffers.  Freeing the product drops its note; buffer ids are never reused, so a
+ * stale id cannot alias.  An unknown product id is *found = 0, not an error (the trait returns an Option).  Launches no kernel and
+ * allocates no device memory.  Null pointers: RMHIP_ERR_INVALID. */
+/* @serves take_matmul_sources */
+RMHIP_API int rmhip_take_matmul_sources(rmhip_ctx* ctx, rmhip_buf product, rmhip_buf* lhs, rmhip_buf* rhs, int* found);
+/* `qr_power_iter(product, product_lhs, q_handle, options)` (lib.rs:2522-2531 -> Option<ProviderQrPowerIterResult { q, r, perm_matrix,
+ * perm_vector }> :673-678): the hook `qr` reaches for a tensor that `matmul` produced (qr.rs:436-458) - the `[Q, R] = qr(G*Q, 'econ')` form
+ * of the power-iteration loop.  CholeskyQR2 in f64 (cholqr.hip): two Cholesky-QR passes, no pivoting, no launch chain per column.
+ * Served (*served = 1): economy != 0; `product` a real 2-D buffer, m x k with m >= k and 1 <= k <= 64; `q_handle` of the same shape
+ * (the reference's check, matmul.rs:68-71); every Cholesky pivot finite and > 0 (verdict A: fails on a NaN or Inf entry, on squares that
+ * overflow or underflow, on a numerically rank-deficient product) and ||Q1'Q1 - I||_F <= 1/2 after the first pass (verdict B: cond(Q1) <=
+ * sqrt(3), the condition under which the second pass restores orthogonality to rounding level; holds up to cond(product) of about 1e7).
+ * out4 order as rmhip_qr: Q (m x k), R (k x k, upper triangular with exact zeros below the diagonal and a strictly positive diagonal),
+ * perm_matrix (the k x k identity), perm_vector ([1..k]' as [k, 1]).  `pivot_vector` only selects what the builtin shows, as in rmhip_qr.
+ * The same input gives the same bits (fixed summation order, no float atomics).
+ * Declined (RMHIP_OK with *served = 0 and no buffer left behind - the trait's Ok(None), after which the caller runs `qr`): economy == 0,
+ * m < k, k > 64 or k == 0, more than two dimensions, a shape mismatch with q_handle, a complex-interleaved buffer, either verdict failing.
+ * Null pointers: RMHIP_ERR_INVALID.  Unknown ids (product_lhs == 0 means absent): RMHIP_ERR_NOT_FOUND.
+ * Departures from the wgpu backend (ops/linalg/decomposition.rs:243-421), on purpose: no input is freed or written (the wgpu code frees
+ * `product` and may overwrite q_handle's storage; its caller frees the product itself); no EPS clamps (they return a non-orthogonal Q for a
+ * rank-deficient product); `product_lhs` is validated and otherwise unused (the reference recomputes a zero product from it; here a zero
+ * product declines).  A precision-32 provider runs the f64 kernels on a widened copy and rounds the four outputs to f32 storage.
+ * With these two this header serves 230 of the trait's 243 methods. */
+/* @serves qr_power_iter */
+RMHIP_API int rmhip_qr_power_iter(rmhip_ctx* ctx, rmhip_buf product, rmhip_buf product_lhs, rmhip_buf q_handle, int economy, int pivot_vector,
+                                  rmhip_buf out4[4], int* served);
 /* `eig(a, compute_left)` (lib.rs:2491-2497 -> ProviderEigResult { eigenvalues, diagonal, right, left } :786-791) for a REAL, BITWISE
  * SYMMETRIC matrix (a(i,j) == a(j,i) for every pair, what rmhip_issymmetric(a, 0, 0) answers) of order n <= 4096, finite in every entry;
  * at most two non-unit dimensions.  out4 order: eigenvalues [n, 1] ASCENDING (the reference's Schur order is unpinned, eig.rs:1196-1207),

@@ -69,6 +69,16 @@ struct ProviderQrOptions {
 struct ProviderQrResult {
     GpuTensorHandle q, r, perm_matrix, perm_vector;
 };
+// lib.rs:673-678; `served` is false for the trait's Ok(None) (the four handles are then null: the caller runs qr)
+struct ProviderQrPowerIterResult {
+    bool served = false;
+    GpuTensorHandle q, r, perm_matrix, perm_vector;
+};
+// lib.rs:2516-2521: Option<(lhs, rhs)>; `found` is false for None
+struct MatmulSources {
+    bool found = false;
+    GpuTensorHandle lhs, rhs;
+};
 
 // lib.rs:601-613
 enum class PagefunOp { Mtimes };
@@ -561,6 +571,37 @@ public:
         uint64_t ids[4] = {0, 0, 0, 0};
         check(rmhip_qr(ctx_, own(a), options.economy ? 1 : 0, options.pivot == ProviderQrPivot::Vector ? 1 : 0, ids));
         return {with_shape(ids[0]), with_shape(ids[1]), with_shape(ids[2]), with_shape(ids[3])};
+    }
+    // lib.rs:2516-2521: the operands `matmul` made `product` from - once (the note is removed) and only while both are alive
+    MatmulSources take_matmul_sources(const GpuTensorHandle& product) const {
+        MatmulSources out;
+        if (product.device_id != device_id_) return out;
+        uint64_t lhs = 0, rhs = 0;
+        int found = 0;
+        check(rmhip_take_matmul_sources(ctx_, product.buffer_id, &lhs, &rhs, &found));
+        if (!found) return out;
+        out.found = true;
+        out.lhs = with_shape(lhs);
+        out.rhs = with_shape(rhs);
+        return out;
+    }
+    // lib.rs:2522-2531: CholeskyQR2 of a matmul product (economy, m >= k, k <= 64) with the identity permutation; `served` false is the
+    // trait's Ok(None) - wrong mode or shape, or a product two Cholesky passes cannot factor - after which the caller runs qr.
+    // `product_lhs` may be null (the trait's None).  No input is freed or written.
+    ProviderQrPowerIterResult qr_power_iter(const GpuTensorHandle& product, const GpuTensorHandle* product_lhs, const GpuTensorHandle& q_handle,
+                                            const ProviderQrOptions& options) const {
+        uint64_t ids[4] = {0, 0, 0, 0};
+        int served = 0;
+        check(rmhip_qr_power_iter(ctx_, own(product), product_lhs ? own(*product_lhs) : 0, own(q_handle), options.economy ? 1 : 0,
+                                  options.pivot == ProviderQrPivot::Vector ? 1 : 0, ids, &served));
+        ProviderQrPowerIterResult out;
+        if (!served) return out;
+        out.served = true;
+        out.q = with_shape(ids[0]);
+        out.r = with_shape(ids[1]);
+        out.perm_matrix = with_shape(ids[2]);
+        out.perm_vector = with_shape(ids[3]);
+        return out;
     }
     // lib.rs:2386: batched page products (Mtimes); throws for what the host loop must answer (malformed request, complex input)
     GpuTensorHandle pagefun(const PagefunRequest& request) const {

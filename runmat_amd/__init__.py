@@ -9,9 +9,9 @@ reproduced for tests and bench.py by the request emitter under tests/, outside t
 sharded Monte-Carlo drivers take their two shaders as arguments.
 """
 from .provider import (GpuTensorHandle, HipProvider, ModeResult, ModeTiedSets, PagefunOp, PagefunRequest, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderError, ProviderLinsolveOptions, ProviderLinsolveResult,
-                       ProviderLuResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest,
+                       ProviderLuResult, ProviderQrOptions, ProviderQrPivot, ProviderQrPowerIterResult, ProviderQrResult, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest,
                        ProviderSpectralResult, ReduceDimResult, ReductionFlavor, wgsl_compile_check, wgsl_translate)
 
 __all__ = ["GpuTensorHandle", "HipProvider", "ModeResult", "ModeTiedSets", "PagefunOp", "PagefunRequest", "ProviderEigResult", "ProviderEnvelopeMethod", "ProviderEnvelopeRequest", "ProviderEnvelopeResult", "ProviderError", "ProviderLinsolveOptions", "ProviderLinsolveResult",
-           "ProviderLuResult", "ProviderQrOptions", "ProviderQrPivot", "ProviderQrResult", "ProviderSpectralFrameMode", "ProviderSpectralRange", "ProviderSpectralRequest",
+           "ProviderLuResult", "ProviderQrOptions", "ProviderQrPivot", "ProviderQrPowerIterResult", "ProviderQrResult", "ProviderSpectralFrameMode", "ProviderSpectralRange", "ProviderSpectralRequest",
            "ProviderSpectralResult", "ReduceDimResult", "ReductionFlavor", "wgsl_compile_check", "wgsl_translate"]

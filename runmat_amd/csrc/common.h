@@ -150,6 +150,9 @@ struct Context {
     std::unordered_map<uint64_t, Buffer> table;
     size_t n_lazy = 0;  // records in `table` with lazy() set (guarded by `mu`): lets detach_views_of return at once when there are none
     uint64_t next_id = 1;
+    // `take_matmul_sources` (lib.rs:2516): product id -> (lhs id, rhs id), noted by rmhip_matmul, dropped by the take and by rmhip_free of the
+    // product (guarded by `mu`)
+    std::unordered_map<uint64_t, std::pair<uint64_t, uint64_t>> matmul_sources;
 
     // pool: bucket bytes -> free device pointers
     std::multimap<size_t, double*> pool;

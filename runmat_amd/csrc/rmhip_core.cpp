@@ -589,6 +589,7 @@ int rmhip_free(rmhip_ctx* ctx, rmhip_buf id) {
         if (it->second.rng_lazy) --c->n_rng_lazy;
         victim = std::move(it->second);
         c->table.erase(it);
+        if (!c->matmul_sources.empty()) c->matmul_sources.erase(id);
     }
     return RMHIP_OK;  // `victim` drops the allocation reference outside the lock
 }

@@ -814,6 +814,30 @@ int rmhip_dot(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, int dim, rmhip_buf* out)
     return rc;
 }
 
+// `take_matmul_sources`: rmhip_matmul notes which operands a product came from; the take removes the note
+static void note_matmul_sources(Context* c, rmhip_buf product, rmhip_buf a, rmhip_buf b) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->matmul_sources[product] = {a, b};
+}
+
+int rmhip_take_matmul_sources(rmhip_ctx* ctx, rmhip_buf product, rmhip_buf* lhs, rmhip_buf* rhs, int* found) {
+    CTX_OR_FAIL(ctx);
+    if (!lhs || !rhs || !found) return fail(RMHIP_ERR_INVALID, "take_matmul_sources: null result");
+    *lhs = *rhs = 0;
+    *found = 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    auto it = c->matmul_sources.find(product);
+    if (it == c->matmul_sources.end()) return RMHIP_OK;
+    const std::pair<uint64_t, uint64_t> src = it->second;
+    c->matmul_sources.erase(it);
+    if (c->table.count(product) && c->table.count(src.first) && c->table.count(src.second)) {
+        *lhs = src.first;
+        *rhs = src.second;
+        *found = 1;
+    }
+    return RMHIP_OK;
+}
+
 int rmhip_matmul(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf* out) {
     CTX_OR_FAIL(ctx);
     ScopedTimer timer(&c->tel.matmul_count, &c->tel.matmul_ns);
@@ -847,7 +871,10 @@ int rmhip_matmul(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf* out) {
                 int rc = launch_sgemm_trans(c, ra.tview, rb.tview, m, n, k, ra.data_f32(), ra.tview ? k : m, rb.data_f32(),
                                             rb.tview ? n : k, ob.data_f32(), m);
                 if (rc) rmhip_free(ctx, *out);
-                else c->record_launch("matmul", {{"m", m}, {"n", n}, {"k", k}}, {{"mfma_f32", 1}, {"ta", (uint64_t)ra.tview}, {"tb", (uint64_t)rb.tview}});
+                else {
+                    c->record_launch("matmul", {{"m", m}, {"n", n}, {"k", k}}, {{"mfma_f32", 1}, {"ta", (uint64_t)ra.tview}, {"tb", (uint64_t)rb.tview}});
+                    note_matmul_sources(c, *out, a, b);
+                }
                 return rc;
             }
         }
@@ -868,7 +895,10 @@ int rmhip_matmul(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf* out) {
                                 0.0, ob.data(), m);
     else rc = launch_dgemm(c, m, n, k, 1.0, ab.data(), m, bb.data(), k, 0.0, ob.data(), m);
     if (rc) rmhip_free(ctx, *out);
-    else c->record_launch("matmul", {{"m", m}, {"n", n}, {"k", k}}, {{"mfma_f64", 1}, {"ta", (uint64_t)ab.tview}, {"tb", (uint64_t)bb.tview}});
+    else {
+        c->record_launch("matmul", {{"m", m}, {"n", n}, {"k", k}}, {{"mfma_f64", 1}, {"ta", (uint64_t)ab.tview}, {"tb", (uint64_t)bb.tview}});
+        note_matmul_sources(c, *out, a, b);
+    }
     return rc;
 }
 

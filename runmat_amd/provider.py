@@ -141,6 +141,15 @@ class ProviderQrResult:
     perm_vector: GpuTensorHandle
 
 
+@dataclass
+class ProviderQrPowerIterResult:
+    """`ProviderQrPowerIterResult` (lib.rs:673-678)."""
+    q: GpuTensorHandle
+    r: GpuTensorHandle
+    perm_matrix: GpuTensorHandle
+    perm_vector: GpuTensorHandle
+
+
 class PagefunOp:
     """`PagefunOp` (lib.rs:601-604): the page operation.  Only `Mtimes` exists."""
     Mtimes = "mtimes"
@@ -878,6 +887,34 @@ class HipProvider:
         outs = (C.c_uint64 * 4)()
         self._check(self._lib.rmhip_qr(self._ctx, self._id(a), 1 if opts.economy else 0, 1 if opts.pivot.kind == "vector" else 0, outs))
         return ProviderQrResult(*[self._handle(outs[i]) for i in range(4)])
+
+    def take_matmul_sources(self, product: GpuTensorHandle) -> Optional[Tuple[GpuTensorHandle, GpuTensorHandle]]:
+        """`take_matmul_sources(product)` (lib.rs:2516-2521): the operands `matmul` made `product` from, once - the note is removed by
+        the call - and only while both are still alive; None for any other tensor.  No kernel runs."""
+        if product.device_id != self._device_id:
+            return None
+        lhs, rhs, found = C.c_uint64(), C.c_uint64(), C.c_int()
+        self._check(self._lib.rmhip_take_matmul_sources(self._ctx, product.buffer_id, C.byref(lhs), C.byref(rhs), C.byref(found)))
+        if not found.value:
+            return None
+        return self._handle(lhs.value), self._handle(rhs.value)
+
+    def qr_power_iter(self, product: GpuTensorHandle, product_lhs: Optional[GpuTensorHandle], q_handle: GpuTensorHandle,
+                      options: Optional[ProviderQrOptions] = None) -> Optional[ProviderQrPowerIterResult]:
+        """`qr_power_iter(product, product_lhs, q_handle, options)` (lib.rs:2522-2531): the economy QR of a matmul product inside the
+        power-iteration loop, CholeskyQR2 in f64 with the identity permutation.  None (the trait's Ok(None): the caller runs `qr`) unless
+        options.economy is set, the product is real and m x k with m >= k and 1 <= k <= 64, q_handle has its shape, and the product is
+        conditioned well enough for two Cholesky passes (up to about 1e7; non-finite, rank-deficient, overflowing or underflowing
+        products decline).  No input is freed or written."""
+        opts = options or ProviderQrOptions()
+        outs = (C.c_uint64 * 4)()
+        served = C.c_int()
+        self._check(self._lib.rmhip_qr_power_iter(self._ctx, self._id(product), self._id(product_lhs) if product_lhs is not None else 0,
+                                                  self._id(q_handle), 1 if opts.economy else 0, 1 if opts.pivot.kind == "vector" else 0,
+                                                  outs, C.byref(served)))
+        if not served.value:
+            return None
+        return ProviderQrPowerIterResult(*[self._handle(outs[i]) for i in range(4)])
 
     def pagefun(self, request: PagefunRequest) -> GpuTensorHandle:
         """`pagefun(request)` (lib.rs:2386): for `PagefunOp.Mtimes` every output page is the product of the inputs' pages, an input of

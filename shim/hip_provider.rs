@@ -17,7 +17,7 @@ use runmat_accelerate_api::{
     AccelProvider, AccelProviderFuture, ApiDeviceInfo, CorrcoefNormalization, CorrcoefOptions, CorrcoefRows, CovNormalization, CovRows, CovarianceOptions, FindDirection, GpuTensorHandle, GpuTensorStorage,
     HostLogicalOwned, HostTensorOwned, HostTensorView, IsMemberOptions, IsMemberResult, SetdiffOptions, SetdiffOrder, SetdiffResult, UnionOptions, UnionOrder, UnionResult, UniqueOccurrence, UniqueOptions, UniqueOrder, UniqueResult, ImageNormalizeDescriptor, ImfilterMode, ImfilterOptions, ImfilterPadding, ImfilterShape, KernelAttrTelemetry, MeshgridAxisView, ProviderMeshgridResult, ProviderPolyderQuotient, ProviderPolyvalOptions, KernelLaunchTelemetry, MatmulEpilogue,
     PowerStepEpilogue, ProviderBandwidth, ProviderCovarianceToCorrelationResult, ProviderHilbertRequest, ProviderCondNorm, ProviderPinvOptions, ProviderIirFilterOptions, ProviderIirFilterResult, ProviderInterp1Extrapolation, ProviderInterp1Method, ProviderInterp1Request, ProviderConv1dOptions, ProviderConvMode, ProviderConvOrientation, ProviderCholResult, ProviderCummaxResult, ProviderCumminResult, ProviderDispatchStats, ProviderInvOptions, ProviderFallbackStat, ProviderFindResult, ProviderHermitianKind, ProviderLinsolveOptions,
-    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderModeAxes, ProviderModeRequest, ProviderModeResult, ProviderModeTiedSets, ProviderModulationRequest, ProviderBitModulationRequest, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest, ProviderSpectralResult, ProviderQrOptions, ProviderQrPivot, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
+    ProviderLinsolveResult, ProviderLuResult, ProviderEigResult, ProviderEnvelopeMethod, ProviderEnvelopeRequest, ProviderEnvelopeResult, ProviderModeAxes, ProviderModeRequest, ProviderModeResult, ProviderModeTiedSets, ProviderModulationRequest, ProviderBitModulationRequest, ProviderSpectralFrameMode, ProviderSpectralRange, ProviderSpectralRequest, ProviderSpectralResult, ProviderQrOptions, ProviderQrPivot, ProviderQrPowerIterResult, ProviderQrResult, PagefunOp, PagefunRequest, ProviderMoments2, ProviderMovingWindowEndpoints, ProviderMovingWindowOp, ProviderMovingWindowRequest, ProviderNanMode, ProviderNdgridRequest, ProviderNormOrder, ProviderNdgridResult, ProviderPrecision, ProviderScanDirection,
     ProviderAdamUpdateRequest, ProviderAdamUpdateResult, ProviderBlackScholesPriceRequest, ProviderBlackScholesPriceResult, ProviderCrossentropyMode, ProviderCrossentropyRequest, ProviderCrossentropyResult,
     ProviderStdNormalization, ProviderSymmetryKind, ProviderTelemetry, ProviderTrapezoidSpacing, ReduceDimResult, ReductionFlavor, ScaleOp, SortComparison, SortOrder, SortResult, SortRowsColumnSpec,
 };
@@ -674,6 +674,38 @@ impl AccelProvider for HipProvider {
             check(unsafe { rmhip_qr(self.ctx, self.own(_a)?, _options.economy as c_int, vector as c_int, ids.as_mut_ptr()) })?;
             Ok(ProviderQrResult { q: self.handle(ids[0])?, r: self.handle(ids[1])?, perm_matrix: self.handle(ids[2])?,
                 perm_vector: self.handle(ids[3])? })
+        })
+    }
+    // take_matmul_sources: the operands `matmul` made the product from, once (the library removes its note) and only while both are alive;
+    // qr.rs:436-458 asks this before qr_power_iter.  No kernel runs.
+    fn take_matmul_sources(&self, _product: &GpuTensorHandle) -> Option<(GpuTensorHandle, GpuTensorHandle)> {
+        let id = self.own(_product).ok()?;
+        let (mut lhs, mut rhs, mut found) = (0u64, 0u64, 0 as c_int);
+        check(unsafe { rmhip_take_matmul_sources(self.ctx, id, &mut lhs, &mut rhs, &mut found) }).ok()?;
+        if found == 0 {
+            return None;
+        }
+        Some((self.handle(lhs).ok()?, self.handle(rhs).ok()?))
+    }
+    // qr_power_iter: CholeskyQR2 of a matmul product (economy, m >= k, k <= 64), identity permutation.  Ok(None) - wrong mode or shape, or
+    // a product two Cholesky passes cannot factor (non-finite, rank deficient, cond above ~1e7, squares out of range) - sends the builtin
+    // on to `qr`.  Unlike the wgpu provider this frees and writes no input: the caller frees the product itself.
+    fn qr_power_iter<'a>(&'a self, product: &'a GpuTensorHandle, _product_lhs: Option<&'a GpuTensorHandle>, q_handle: &'a GpuTensorHandle,
+        options: &'a ProviderQrOptions) -> AccelProviderFuture<'a, Option<ProviderQrPowerIterResult>> {
+        Box::pin(async move {
+            let mut ids = [0u64; 4];
+            let mut served: c_int = 0;
+            let lhs = match _product_lhs { Some(h) => self.own(h)?, None => 0 };
+            let vector = matches!(options.pivot, ProviderQrPivot::Vector);
+            check(unsafe {
+                rmhip_qr_power_iter(self.ctx, self.own(product)?, lhs, self.own(q_handle)?, options.economy as c_int, vector as c_int,
+                    ids.as_mut_ptr(), &mut served)
+            })?;
+            if served == 0 {
+                return Ok(None);
+            }
+            Ok(Some(ProviderQrPowerIterResult { q: self.handle(ids[0])?, r: self.handle(ids[1])?, perm_matrix: self.handle(ids[2])?,
+                perm_vector: self.handle(ids[3])? }))
         })
     }
     // eig: real, bitwise symmetric matrices of order <= 4096 (ascending eigenvalues, orthonormal right vectors, `left` a copy of `right`);
