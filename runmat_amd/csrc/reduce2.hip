@@ -13,8 +13,10 @@
 // reduced), every slice is cut into nsplit chunks so that the grid covers the chip several times (reduce_plan.h), a chunk
 // folds into an accumulator, and a final kernel merges the chunks of a slice IN CHUNK ORDER - no atomics, results do not
 // depend on scheduling.  HBM-bound: one 8-byte read per element.
+// Which stage-1 kernel runs on which grid is reduce_plan.h's choice (route_reduction, REDUCE_ACCUMULATOR); run_r2 launches it.
 #include "common.h"
 #include "reduce_plan.h"
+#include "pair_load.h"
 
 namespace rmhip {
 
@@ -236,29 +238,6 @@ __global__ void __launch_bounds__(R2_BLOCK) k_r2_contig(const T* __restrict__ x,
 // ODD: odd `red` or an element-aligned base - the pairs are loaded from 8-byte aligned addresses and the slice's last element is folded
 // by the thread whose walk ends at its pair index (still ascending within the thread).
 // T = storage type: float on a precision-32 provider (widened in registers: exact and order preserving), a pair is then 8 bytes.
-typedef double r2_d2 __attribute__((ext_vector_type(2)));
-template <class T>
-struct R2Pair;
-template <>
-struct R2Pair<double> {
-    typedef double v2 __attribute__((ext_vector_type(2)));
-    typedef v2 v2u __attribute__((aligned(8)));
-};
-template <>
-struct R2Pair<float> {
-    typedef float v2 __attribute__((ext_vector_type(2)));
-    typedef v2 v2u __attribute__((aligned(4)));
-};
-// the pair that starts at element pointer p
-template <class T, bool ODD>
-__device__ __forceinline__ r2_d2 r2_ld2(const T* p) {
-    typedef typename R2Pair<T>::v2 V;
-    typedef typename R2Pair<T>::v2u VU;
-    V v;
-    if constexpr (ODD) v = (V)__builtin_nontemporal_load(reinterpret_cast<const VU*>(p));
-    else v = __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
-    return r2_d2{(double)v.x, (double)v.y};
-}
 template <class Acc, bool ODD = false, class T = double>
 __global__ void __launch_bounds__(R2_BLOCK) k_r2_contig_v2(const T* __restrict__ x, u64 red, u64 nslices, u64 nsplit, Acc* __restrict__ part) {
     __shared__ Acc lds[R2_BLOCK];
@@ -276,12 +255,12 @@ __global__ void __launch_bounds__(R2_BLOCK) k_r2_contig_v2(const T* __restrict__
     u64 r = begin + threadIdx.x;
     constexpr int U = 4;
     if (r + (U - 1) * R2_BLOCK < end) {
-        r2_d2 cur[U], nxt[U];
+        rm_rv2 cur[U], nxt[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) cur[u] = r2_ld2<T, ODD>(xs + 2 * (r + u * R2_BLOCK));
+        for (int u = 0; u < U; ++u) cur[u] = rm_load_pair<!ODD>(xs + 2 * (r + u * R2_BLOCK));
         for (; r + (2 * U - 1) * R2_BLOCK < end; r += U * R2_BLOCK) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) nxt[u] = r2_ld2<T, ODD>(xs + 2 * (r + (U + u) * R2_BLOCK));
+            for (int u = 0; u < U; ++u) nxt[u] = rm_load_pair<!ODD>(xs + 2 * (r + (U + u) * R2_BLOCK));
             {
                 u64 k[8];
                 double w[8];
@@ -312,7 +291,7 @@ __global__ void __launch_bounds__(R2_BLOCK) k_r2_contig_v2(const T* __restrict__
         r += U * R2_BLOCK;
     }
     for (; r < end; r += R2_BLOCK) {
-        const r2_d2 v = r2_ld2<T, ODD>(xs + 2 * r);
+        const rm_rv2 v = rm_load_pair<!ODD>(xs + 2 * r);
         a.add(2 * r, v.x);
         a.add(2 * r + 1, v.y);
     }
@@ -336,11 +315,10 @@ __global__ void __launch_bounds__(R2_BLOCK) k_r2_contig_v2(const T* __restrict__
 // many short contiguous slices (red < 256): a block stages a tile of consecutive slices in LDS with coalesced loads and thread t folds
 // slice t in ascending order (reduce_kernels.hip: k_reduce_short) - one block per slice is half a million blocks for min(x,[],1) of a
 // 32 x 524288 matrix
-static constexpr int R2_SHORT_TILE = 4096;
 __device__ __forceinline__ int r2_short_pad(int i) { return i + (i >> 5); }
 template <class Acc, class T = double>
 __global__ void __launch_bounds__(R2_BLOCK) k_r2_short(const T* __restrict__ x, u64 red, u64 nslices, unsigned per_block, Acc* __restrict__ part) {
-    __shared__ double tile[R2_SHORT_TILE + R2_SHORT_TILE / 32 + 1];
+    __shared__ double tile[REDUCE_SHORT_TILE + REDUCE_SHORT_TILE / 32 + 1];
     const u64 s0 = (u64)blockIdx.x * per_block;
     const u64 ns = nslices - s0 < per_block ? nslices - s0 : per_block;
     const u64 count = ns * red;
@@ -391,12 +369,12 @@ __global__ void __launch_bounds__(R2_BLOCK) k_r2_strided(const T* __restrict__ x
 }
 
 // the same with 16-byte loads: a thread owns two adjacent lines (even `pre`, 16-byte aligned base).  As for sum(x,2)
-// (reduce_kernels.hip) what decides the rate of these lock-step column walks is the number of blocks: three per CU.
+// (reduce_plan.h plan_strided_wide) what decides the rate of these lock-step column walks is the number of blocks: three per CU.
 // ODD: odd `pre` (or an element-aligned base): unaligned pairs, the last line alone in its pair.
 template <class Acc, bool ODD = false, class T = double>
 __global__ void __launch_bounds__(R2_BLOCK) k_r2_strided_v2(const T* __restrict__ x, u64 pre, u64 red, u64 nsplit, unsigned win,
                                                             Acc* __restrict__ part) {
-    const u64 i2 = (u64)blockIdx.x * win + threadIdx.x, pre2 = ODD ? (pre + 1) >> 1 : pre >> 1;  // balanced windows, their number a multiple of the XCD count (run_r2)
+    const u64 i2 = (u64)blockIdx.x * win + threadIdx.x, pre2 = ODD ? (pre + 1) >> 1 : pre >> 1;  // balanced windows, their number a multiple of the XCD count (reduce_plan.h)
     if (threadIdx.x >= win || i2 >= pre2) return;
     const bool single = ODD && 2 * i2 + 1 >= pre;
     const u64 split = blockIdx.y, j = blockIdx.z;
@@ -405,17 +383,17 @@ __global__ void __launch_bounds__(R2_BLOCK) k_r2_strided_v2(const T* __restrict_
     u64 end = begin + chunk;
     if (end > red) end = red;
     const T* const xo = x + 2 * i2 + pre * red * j;  // element offsets: with an odd `pre` the lines alternate between 16- and 8-byte alignment
-    auto ldp = [&](u64 rr) -> r2_d2 {
+    auto ldp = [&](u64 rr) -> rm_rv2 {
         const T* q = xo + pre * rr;
-        if (ODD && single) return r2_d2{(double)__builtin_nontemporal_load(q), 0.0};
-        return r2_ld2<T, ODD>(q);
+        if (ODD && single) return rm_rv2{(double)__builtin_nontemporal_load(q), 0.0};
+        return rm_load_pair<!ODD>(q);
     };
     Acc a0, a1;
     a0.init();
     a1.init();
     u64 r = begin;
     if (r + 8 <= end) {  // two batches in flight: the next one is requested before the current one is folded
-        r2_d2 cur[8], nxt[8];
+        rm_rv2 cur[8], nxt[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) cur[u] = ldp(r + u);
         for (; r + 16 <= end; r += 8) {
@@ -451,7 +429,7 @@ __global__ void __launch_bounds__(R2_BLOCK) k_r2_strided_v2(const T* __restrict_
         r += 8;
     }
     if (r < end) {
-        r2_d2 v[8];
+        rm_rv2 v[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u)
             if (r + u < end) v[u] = ldp(r + u);
@@ -553,60 +531,44 @@ struct TruthFin {
 template <class Acc, class Fin, class T = double>
 static int run_r2(Context* c, const T* x, size_t pre, size_t red, size_t post, const Fin& fin, const char* what) {
     if (pre == 0 || post == 0 || red == 0) return RMHIP_OK;
-    ReducePlan p = plan_reduction(pre, red, post, c->num_cus, (unsigned)sizeof(T));
-    if (!p.valid) return fail(RMHIP_ERR_UNSUPPORTED, "%s: geometry [%zu,%zu,%zu] exceeds launch limits", what, pre, red, post);
-    u64 nsplit = p.nsplit;
-    unsigned gx = p.gx;
-    const bool wide = !p.contiguous && pre >= 512;
-    const bool wide_odd = wide && ((pre & 1) != 0 || (((uintptr_t)x) & (2 * sizeof(T) - 1)) != 0);  // a pair of T
-    unsigned win = R2_BLOCK, threads = R2_BLOCK;
-    if (!p.contiguous) {  // these kernels keep up to 256 threads along `pre`
-        if (wide) {  // as for sum(x,2): a window count that is a multiple of the XCD count pins every window to one XCD (reduce_plan.h)
-            const StridedWidePlan w = plan_strided_wide(pre, red, post, c->num_cus, c->num_xcc, (unsigned)sizeof(T));
-            gx = w.bx;
-            win = w.win;
-            threads = w.threads;
-            nsplit = w.nsplit;
-        } else {
-            gx = (unsigned)ceil_div_u64(pre, R2_BLOCK);
-            u64 want = ceil_div_u64((u64)c->num_cus * 8, (u64)gx * post);
-            u64 max_split = ceil_div_u64(red, 16);
-            nsplit = want < 1 ? 1 : (want > max_split ? max_split : want);
-            nsplit = dealias_nsplit(red, nsplit, pre * sizeof(T), max_split);
-            if (nsplit > 65535) nsplit = 65535;
-        }
-    }
-    const bool short_a = p.contiguous && red < 256 && p.nslices >= 1024;
-    if (short_a) nsplit = 1;
-    const size_t nparts = (size_t)(p.nslices * nsplit);
-    RMHIP_TRY(c->ensure_scratch(nparts * sizeof(Acc)));
+    // which kernel on which grid, how many chunks per slice, which finalize: reduce_plan.h route_reduction (REDUCE_ACCUMULATOR)
+    const ReduceRoute rt = route_reduction(pre, red, post, c->num_cus, c->num_xcc, (unsigned)sizeof(T), (((uintptr_t)x) & (2 * sizeof(T) - 1)) == 0,  // a pair of T
+                                           REDUCE_ACCUMULATOR);
+    if (!rt.valid) return fail(RMHIP_ERR_UNSUPPORTED, "%s: geometry [%zu,%zu,%zu] exceeds launch limits", what, pre, red, post);
+    const u64 nslices = rt.nslices, nsplit = rt.nsplit;
+    RMHIP_TRY(c->ensure_scratch((size_t)(nslices * nsplit) * sizeof(Acc)));
     Acc* part = reinterpret_cast<Acc*>(c->scratch);
-    if (short_a) {
-        unsigned per_block = (unsigned)(R2_SHORT_TILE / red);
-        if (per_block > R2_BLOCK) per_block = R2_BLOCK;
-        hipLaunchKernelGGL((k_r2_short<Acc, T>), dim3((unsigned)ceil_div_u64(p.nslices, per_block)), dim3(R2_BLOCK), 0, c->stream, x, (u64)red, (u64)p.nslices,
-                           per_block, part);
-    } else if (p.contiguous && (red & 1) == 0 && red >= 4 * R2_BLOCK && (((uintptr_t)x) & (2 * sizeof(T) - 1)) == 0)
-        hipLaunchKernelGGL((k_r2_contig_v2<Acc, false, T>), dim3((unsigned)nsplit, p.gy, p.gz), dim3(R2_BLOCK), 0, c->stream, x, (u64)red, (u64)p.nslices, nsplit, part);
-    else if (p.contiguous && red >= 4 * R2_BLOCK)  // odd slice length or element-aligned base
-        hipLaunchKernelGGL((k_r2_contig_v2<Acc, true, T>), dim3((unsigned)nsplit, p.gy, p.gz), dim3(R2_BLOCK), 0, c->stream, x, (u64)red, (u64)p.nslices, nsplit, part);
-    else if (p.contiguous)
-        hipLaunchKernelGGL((k_r2_contig<Acc, T>), dim3((unsigned)nsplit, p.gy, p.gz), dim3(R2_BLOCK), 0, c->stream, x, (u64)red, (u64)p.nslices, nsplit, part);
-    else if (wide_odd)
-        hipLaunchKernelGGL((k_r2_strided_v2<Acc, true, T>), dim3(gx, (unsigned)nsplit, (unsigned)post), dim3(threads), 0, c->stream, x, (u64)pre, (u64)red, nsplit, win, part);
-    else if (wide)
-        hipLaunchKernelGGL((k_r2_strided_v2<Acc, false, T>), dim3(gx, (unsigned)nsplit, (unsigned)post), dim3(threads), 0, c->stream, x, (u64)pre, (u64)red, nsplit, win, part);
-    else
-        hipLaunchKernelGGL((k_r2_strided<Acc, T>), dim3(gx, (unsigned)nsplit, (unsigned)post), dim3(R2_BLOCK), 0, c->stream, x, (u64)pre, (u64)red, nsplit, part);
+    const dim3 grid(rt.gx, rt.gy, rt.gz), block(rt.block);
+    switch (rt.kernel) {
+        case ReduceKernel::SHORT:
+            hipLaunchKernelGGL((k_r2_short<Acc, T>), grid, block, 0, c->stream, x, (u64)red, nslices, rt.span, part);
+            break;
+        case ReduceKernel::CONTIG:
+            hipLaunchKernelGGL((k_r2_contig<Acc, T>), grid, block, 0, c->stream, x, (u64)red, nslices, nsplit, part);
+            break;
+        case ReduceKernel::CONTIG_V2:
+            hipLaunchKernelGGL((k_r2_contig_v2<Acc, false, T>), grid, block, 0, c->stream, x, (u64)red, nslices, nsplit, part);
+            break;
+        case ReduceKernel::CONTIG_V2_ODD:  // odd slice length or element-aligned base
+            hipLaunchKernelGGL((k_r2_contig_v2<Acc, true, T>), grid, block, 0, c->stream, x, (u64)red, nslices, nsplit, part);
+            break;
+        case ReduceKernel::STRIDED:
+            hipLaunchKernelGGL((k_r2_strided<Acc, T>), grid, block, 0, c->stream, x, (u64)pre, (u64)red, nsplit, part);
+            break;
+        case ReduceKernel::STRIDED_V2:
+            hipLaunchKernelGGL((k_r2_strided_v2<Acc, false, T>), grid, block, 0, c->stream, x, (u64)pre, (u64)red, nsplit, rt.span, part);
+            break;
+        case ReduceKernel::STRIDED_V2_ODD:
+            hipLaunchKernelGGL((k_r2_strided_v2<Acc, true, T>), grid, block, 0, c->stream, x, (u64)pre, (u64)red, nsplit, rt.span, part);
+            break;
+    }
     RMHIP_HIP_CHECK(hipGetLastError());
     // many slices with a handful of partials each: one thread per slice (a wave per slice would idle 50 of its lanes; 65536 slices
     // x 14 partials took 37 us that way)
-    if ((nsplit <= 8 && p.nslices >= 1024) || (nsplit <= 32 && p.nslices >= 16384))
-        hipLaunchKernelGGL((k_r2_final_flat<Acc, Fin>), dim3((unsigned)ceil_div_u64(p.nslices, R2_BLOCK)), dim3(R2_BLOCK), 0, c->stream, part,
-                           (u64)p.nslices, nsplit, fin);
+    if (rt.flat_final)
+        hipLaunchKernelGGL((k_r2_final_flat<Acc, Fin>), dim3((unsigned)ceil_div_u64(nslices, R2_BLOCK)), dim3(R2_BLOCK), 0, c->stream, part, nslices, nsplit, fin);
     else
-        hipLaunchKernelGGL((k_r2_final<Acc, Fin>), dim3((unsigned)ceil_div_u64(p.nslices, R2_BLOCK / 64)), dim3(R2_BLOCK), 0, c->stream, part,
-                           (u64)p.nslices, nsplit, fin);
+        hipLaunchKernelGGL((k_r2_final<Acc, Fin>), dim3((unsigned)ceil_div_u64(nslices, R2_BLOCK / 64)), dim3(R2_BLOCK), 0, c->stream, part, nslices, nsplit, fin);
     RMHIP_HIP_CHECK(hipGetLastError());
     c->tel.kernel_launches += 2;
     return RMHIP_OK;

@@ -26,8 +26,8 @@ inline uint64_t ceil_div_u64(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 // Kernel B walks `red` in nsplit chunks of ceil(red / nsplit) columns and the blocks of all chunks run in lockstep.  When a
 // chunk spans a multiple of 256 KiB (power-of-two shapes: 8192 x 8192 f64 in 64 chunks = 8 MiB each) every block is at the
 // same offset of its chunk at the same time; 65 chunks of 127 columns instead measured 112 -> 105 us for sum(x,2) at 8192^2
-// and 115 -> 102 us at 16384 x 4096 (scripts/red_chunk_ab.sh).  The block COUNT matters more (reduce_kernels.hip); this
-// only moves the generic kernel off its worst point.
+// and 115 -> 102 us at 16384 x 4096 (docs/EXPERIMENTS.md section 3.3).  The block COUNT matters
+// more (plan_strided_wide); this only moves the generic kernel off its worst point.
 inline uint64_t dealias_nsplit(uint64_t red, uint64_t nsplit, uint64_t column_stride_bytes, uint64_t max_split) {
     if (nsplit <= 1 || column_stride_bytes == 0) return nsplit;
     for (int tries = 0; tries < 8 && nsplit < max_split; ++tries) {
@@ -89,20 +89,24 @@ inline ReducePlan plan_reduction(uint64_t pre, uint64_t red, uint64_t post, int 
     return p;
 }
 
-// Geometry of kernel B over 16-byte vectors (a thread owns two adjacent lines; reduce_kernels.hip k_reduce_strided_v2, reduce2.hip,
-// generated rm_red_strided2): `bx` windows of `win` pairs along `pre`, their number a multiple of the XCD count - workgroups go to the
-// XCDs round robin in launch order (x fastest), so with bx % xcds == 0 a window is always walked by the same XCD whatever the chunk -,
-// balanced (128-byte granules), a block of as many waves as its window needs, and `blocks_per_cu` blocks per CU over (bx, nsplit, post).
+// Geometry of kernel B over 16-byte vectors (a thread owns two adjacent lines; skel_reduce.h rm_reduce_strided_v2, reduce2.hip
+// k_r2_strided_v2): `bx` windows of `win` <= 256 pairs along `pre`, a block of as many waves as its window needs, THREE blocks per
+// CU over (bx, nsplit, post).  Every block is a strided column walk and the blocks run in lockstep, so the block COUNT decides the
+// rate, and not monotonically: sum(x,2) at 8192^2 took 104 / 100 / 86 / 101 / 93 / 96 us at 1 ... 6 blocks per CU, 113 at 8 (the
+// generic kernel B's count), 130 at 16.  The number of windows is a multiple of the XCD count: workgroups go to the XCDs round robin
+// in launch order (x fastest), so with bx % xcds == 0 a window - the same 4 KiB of every column - is always walked by the same XCD
+// whatever the chunk, otherwise the windows rotate over the XCDs from chunk to chunk (8200 x 8192, 17 -> 24 windows: 109 -> 90 us).
+// The windows are balanced in 128-byte granules, so a row count just above a multiple of 512 leaves no column of nearly empty
+// blocks (8256 rows: 109 -> 86 us).  Tables: docs/EXPERIMENTS.md section 3.3.
 struct StridedWidePlan {
     unsigned bx, win, threads;
     uint64_t nsplit;
 };
-inline StridedWidePlan plan_strided_wide(uint64_t pre, uint64_t red, uint64_t post, int num_cus, int xcds_probed, unsigned elem_bytes,
-                                         int blocks_per_cu = 3, bool pin_xcds = true) {
+inline StridedWidePlan plan_strided_wide(uint64_t pre, uint64_t red, uint64_t post, int num_cus, int xcds_probed, unsigned elem_bytes) {
     StridedWidePlan w{};
     const unsigned xcds = xcds_probed > 0 ? (unsigned)xcds_probed : 8u;
     const uint64_t npairs = (pre + 1) / 2;
-    const bool pin = pin_xcds && pre / 2 >= (uint64_t)xcds * 64;
+    const bool pin = pre / 2 >= (uint64_t)xcds * 64;
     w.bx = (unsigned)ceil_div_u64(npairs, 256);
     if (pin) w.bx = (w.bx + xcds - 1) / xcds * xcds;
     w.win = (unsigned)((ceil_div_u64(npairs, w.bx) + 7) / 8 * 8);
@@ -110,7 +114,7 @@ inline StridedWidePlan plan_strided_wide(uint64_t pre, uint64_t red, uint64_t po
     w.bx = (unsigned)ceil_div_u64(npairs, w.win);
     if (pin) w.bx = (w.bx + xcds - 1) / xcds * xcds;  // (trailing windows may be empty)
     w.threads = (w.win + 63) / 64 * 64;
-    uint64_t want = ceil_div_u64((uint64_t)num_cus * blocks_per_cu, (uint64_t)w.bx * (post ? post : 1));
+    uint64_t want = ceil_div_u64((uint64_t)num_cus * 3, (uint64_t)w.bx * (post ? post : 1));
     const uint64_t max_split = ceil_div_u64(red, 16);
     w.nsplit = want < 1 ? 1 : want;
     if (w.nsplit > max_split) w.nsplit = max_split;
@@ -120,10 +124,11 @@ inline StridedWidePlan plan_strided_wide(uint64_t pre, uint64_t red, uint64_t po
     return w;
 }
 
-// ---- which kernel serves a [pre, red, post] reduction, with how many partials per slice, and which finalize folds them ----
-// The one place where the ahead-of-time reductions (reduce_kernels.hip: run_reduce, reduce_dot_any) choose; a pure function of the
-// shape, the device's CU / XCD counts, the storage width and the base address' alignment, so tests/cpp/reduce_route_check.cpp can
-// pin the choice without a GPU.  The developer knobs (RMHIP_RED_B_*) are overrides the launcher applies on top.
+// ---- which kernel serves a [pre, red, post] reduction, with how many partials per slice, on which grid, and which finalize ----
+// The one place where a reduction launcher chooses: run_reduce (reduce_kernels.hip), run_r2 (reduce2.hip) and rmhip_fused_reduction
+// (rmhip_ops.cpp) switch over the route's kernel and launch what it says.  A pure function of the shape, the device's CU / XCD
+// counts, the storage width, the operands' alignment and the caller's kernel family, so tests/cpp/reduce_route_check.cpp pins every
+// family's choice without a GPU.
 enum class ReduceKernel { SHORT, CONTIG, CONTIG_V2, CONTIG_V2_ODD, STRIDED, STRIDED_V2, STRIDED_V2_ODD };
 inline const char* reduce_kernel_name(ReduceKernel k) {
     switch (k) {
@@ -137,46 +142,86 @@ inline const char* reduce_kernel_name(ReduceKernel k) {
     }
     return "?";
 }
-// Many slices with a handful of partials each: one thread per slice (rm_reduce_finalize_flat) instead of one wave.  The dot
-// launcher has only the first clause.
-inline bool reduce_flat_final(uint64_t nsplit, uint64_t nslices, bool dot = false) {
-    return (nsplit <= 8 && nslices >= 1024) || (!dot && nsplit <= 32 && nslices >= 16384);
+// What a caller's kernel family can do.  The families differ where their kernels were measured apart; the route keeps each as it is.
+struct ReduceFamily {
+    bool short_tile;        // has the SHORT kernel (a tile of short contiguous slices per block)
+    uint64_t wide_a_from;   // kernel A runs over 16-byte vectors from this slice length on
+    bool odd_pairs;         // has the unaligned-pair (ODD) forms; without them such shapes take CONTIG / STRIDED
+    bool wide_b;            // has kernel B over 16-byte vectors
+    bool lanes_256;         // kernel A in 256-thread blocks whatever the slice length (its nsplit still the plan's), and the narrow
+                            // kernel B with 256 lanes along `pre` and no rows along `red`
+    bool flat_many_slices;  // the finalize's second flat clause (<= 32 partials from 16384 slices)
+};
+constexpr ReduceFamily REDUCE_PLAIN{true, 2048, true, true, false, true};         // run_reduce over one tensor
+constexpr ReduceFamily REDUCE_DOT{true, 2048, false, false, false, false};        // run_reduce over the product of two
+constexpr ReduceFamily REDUCE_ACCUMULATOR{true, 1024, true, true, true, true};    // reduce2.hip run_r2
+constexpr ReduceFamily REDUCE_GENERATED{false, 2048, false, true, false, false};  // rmhip_fused_reduction (hipRTC kernels)
+
+static constexpr unsigned REDUCE_SHORT_TILE = 4096;  // elements of a SHORT block's LDS tile
+// Many slices with a handful of partials each: one thread per slice (the flat finalize) instead of one wave.
+inline bool reduce_flat_final(uint64_t nsplit, uint64_t nslices, const ReduceFamily& fam) {
+    return (nsplit <= 8 && nslices >= 1024) || (fam.flat_many_slices && nsplit <= 32 && nslices >= 16384);
 }
 struct ReduceRoute {
-    bool valid;            // false: plan_reduction refused the geometry
+    bool valid;  // false: the geometry exceeds the grid limits (the caller reports UNSUPPORTED)
     ReduceKernel kernel;
-    uint64_t nsplit;       // partials per slice as the kernel and the finalize see them
+    uint64_t nslices;  // pre * post
+    uint64_t nsplit;   // partials per slice as the kernel and the finalize see them
     bool flat_final;
-    ReducePlan plan;       // grid / block of the SHORT-less kernels A and the generic kernel B
-    StridedWidePlan wide;  // geometry of STRIDED_V2 / STRIDED_V2_ODD (zero otherwise)
+    unsigned gx, gy, gz, block;  // stage 1's launch
+    unsigned span;  // the kernel's geometry argument - SHORT: slices per block; STRIDED: lanes along `pre`; STRIDED_V2*: pairs per window
 };
-// `base_16B_aligned`: every operand's base address is a multiple of 16.  `dot`: the two-operand skeletons, which have no
-// unaligned-pair form of kernel A and no 16-byte form of kernel B.
-inline ReduceRoute route_reduction(uint64_t pre, uint64_t red, uint64_t post, int num_cus, int xcds, unsigned elem_bytes,
-                                   bool base_16B_aligned, bool dot = false) {
+// `aligned`: every operand's base address is a multiple of what the family's pair loads need (the caller's test).
+inline ReduceRoute route_reduction(uint64_t pre, uint64_t red, uint64_t post, int num_cus, int xcds, unsigned elem_bytes, bool aligned,
+                                   const ReduceFamily& fam) {
     ReduceRoute r{};
-    r.plan = plan_reduction(pre, red, post, num_cus, elem_bytes);
-    r.valid = r.plan.valid;
+    const ReducePlan p = plan_reduction(pre, red, post, num_cus, elem_bytes);
+    r.valid = p.valid;
     if (!r.valid) return r;
-    const ReducePlan& p = r.plan;
+    r.nslices = p.nslices;
     r.nsplit = p.nsplit;
+    r.gx = p.gx;
+    r.gy = p.gy;
+    r.gz = p.gz;
+    const bool pairs = aligned && ((p.contiguous ? red : pre) & 1) == 0;  // else the ODD form: unaligned pairs, one element left over
     if (p.contiguous) {
-        if (red >= 1 && red < 256 && p.nslices >= 1024) {  // many short contiguous slices: a tile of slices per block
+        r.block = fam.lanes_256 ? 256u : (unsigned)p.tx;
+        if (fam.short_tile && red >= 1 && red < 256 && p.nslices >= 1024) {
             r.kernel = ReduceKernel::SHORT;
             r.nsplit = 1;
-        } else if (red >= 2048 && (red & 1) == 0 && base_16B_aligned)
-            r.kernel = ReduceKernel::CONTIG_V2;
-        else if (red >= 2048 && !dot)  // odd slice length or an element-aligned base: the same kernel on unaligned pairs
-            r.kernel = ReduceKernel::CONTIG_V2_ODD;
+            r.span = REDUCE_SHORT_TILE / (unsigned)red < 256 ? REDUCE_SHORT_TILE / (unsigned)red : 256;
+            r.gx = (unsigned)ceil_div_u64(p.nslices, r.span);
+            r.gy = r.gz = 1;
+            r.block = 256;
+        } else if (red >= fam.wide_a_from && (pairs || fam.odd_pairs))
+            r.kernel = pairs ? ReduceKernel::CONTIG_V2 : ReduceKernel::CONTIG_V2_ODD;
         else
             r.kernel = ReduceKernel::CONTIG;
-    } else if (!dot && pre >= 512 && post <= 65535) {
-        r.wide = plan_strided_wide(pre, red, post, num_cus, xcds, elem_bytes);
-        r.nsplit = r.wide.nsplit;
-        r.kernel = (pre & 1) != 0 || !base_16B_aligned ? ReduceKernel::STRIDED_V2_ODD : ReduceKernel::STRIDED_V2;
-    } else
+    } else if (fam.wide_b && pre >= 512 && post <= 65535 && (pairs || fam.odd_pairs)) {
+        const StridedWidePlan w = plan_strided_wide(pre, red, post, num_cus, xcds, elem_bytes);
+        r.kernel = pairs ? ReduceKernel::STRIDED_V2 : ReduceKernel::STRIDED_V2_ODD;
+        r.nsplit = w.nsplit;
+        r.gx = w.bx;
+        r.gy = (unsigned)w.nsplit;
+        r.gz = (unsigned)post;
+        r.block = w.threads;
+        r.span = w.win;
+    } else {
         r.kernel = ReduceKernel::STRIDED;
-    r.flat_final = reduce_flat_final(r.nsplit, p.nslices, dot);
+        r.block = 256;
+        r.span = (unsigned)p.tx;
+        if (fam.lanes_256) {
+            r.span = 256;
+            r.gx = (unsigned)ceil_div_u64(pre, 256);
+            const uint64_t want = ceil_div_u64((uint64_t)num_cus * 8, (uint64_t)r.gx * post), max_split = ceil_div_u64(red, 16);
+            r.nsplit = want > max_split ? max_split : want;
+            if (r.nsplit < 1) r.nsplit = 1;
+            r.nsplit = dealias_nsplit(red, r.nsplit, pre * elem_bytes, max_split);
+            if (r.nsplit > 65535) r.nsplit = 65535;
+            r.gy = (unsigned)r.nsplit;
+        }
+    }
+    r.flat_final = reduce_flat_final(r.nsplit, r.nslices, fam);
     return r;
 }
 

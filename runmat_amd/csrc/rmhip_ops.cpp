@@ -390,8 +390,6 @@ int rmhip_fused_reduction(rmhip_ctx* ctx, const char* shader, const rmhip_buf* i
     // axis 0: slice s is contiguous (pre=1, red, post=slices); axis 1: element (s, r) at s + r*slices.
     const size_t pre = prog.axis == 0 ? 1 : num_slices;
     const size_t post = prog.axis == 0 ? num_slices : 1;
-    const ReducePlan plan = plan_reduction(pre, reduce_len, post, c->num_cus, f32 ? 4u : 8u);
-    if (!plan.valid) return fail(RMHIP_ERR_UNSUPPORTED, "fused_reduction: geometry exceeds launch limits");
     std::vector<const double*> in_ptr(n_in);
     std::vector<void*> args;
     for (size_t k = 0; k < n_in; ++k) {
@@ -403,13 +401,10 @@ int rmhip_fused_reduction(rmhip_ctx* ctx, const char* shader, const rmhip_buf* i
     bool pairs_ok = true;
     for (size_t k = 0; k < n_in && pairs_ok; ++k)
         if (mult[k] && (((uintptr_t)in_ptr[k]) & (f32 ? 7u : 15u)) != 0) pairs_ok = false;
-    // kernel B over 16-byte vectors (two adjacent slices per thread) with the XCD-pinned window geometry of sum(x,2) (reduce_plan.h):
-    // even `pre` >= 512
-    const bool wide_b = !plan.contiguous && pairs_ok && (pre & 1) == 0 && pre >= 512 && post <= 65535;
-    StridedWidePlan wplan{};
-    if (wide_b) wplan = plan_strided_wide(pre, reduce_len, post, c->num_cus, c->num_xcc, f32 ? 4u : 8u);
-    const unsigned long long nsplit_used = wide_b ? wplan.nsplit : plan.nsplit;
-    const size_t nparts = (size_t)(plan.nslices * nsplit_used);
+    // which generated kernel on which grid, how many partials per slice, which finalize: reduce_plan.h route_reduction
+    const ReduceRoute rt = route_reduction(pre, reduce_len, post, c->num_cus, c->num_xcc, f32 ? 4u : 8u, pairs_ok, REDUCE_GENERATED);
+    if (!rt.valid) return fail(RMHIP_ERR_UNSUPPORTED, "fused_reduction: geometry exceeds launch limits");
+    const size_t nparts = (size_t)(rt.nslices * rt.nsplit);
     RMHIP_TRY(c->ensure_scratch(2 * nparts * sizeof(double)));
     double* pv = c->scratch;
     double* pn = c->scratch + nparts;
@@ -418,39 +413,29 @@ int rmhip_fused_reduction(rmhip_ctx* ctx, const char* shader, const rmhip_buf* i
     rmhip_buf oid = 0;
     RMHIP_TRY(c->new_buffer(out_shape, rank, &oid, &ob));
 
-    unsigned long long u_pre = pre, u_red = reduce_len, u_nsplit = nsplit_used, u_nslices = plan.nslices;
-    int tx = plan.tx;
-    hipError_t e;
-    if (plan.contiguous) {
-        args.push_back(&u_red);
-        args.push_back(&u_nslices);
-        args.push_back(&u_nsplit);
-        args.push_back(&pv);
-        args.push_back(&pn);
-        // 16-byte form (two adjacent elements per call of the value functor): even slices of at least 2048 elements, every full-size
-        // input aligned to its pair - as k_reduce_contig_v2 for plain tensors (+12-18 % there; the Monte-Carlo payoff sum 160 -> us)
-        const bool wide = pairs_ok && (reduce_len & 1) == 0 && reduce_len >= 2048;
-        e = hipModuleLaunchKernel(wide ? kern->fn_contig2 : kern->fn_contig, plan.gx, plan.gy, plan.gz, (unsigned)plan.tx, 1, 1, 0, c->stream,
-                                  args.data(), nullptr);
-    } else if (wide_b) {
-        unsigned win = wplan.win;
-        args.push_back(&u_pre);
-        args.push_back(&u_red);
-        args.push_back(&u_nsplit);
-        args.push_back(&win);
-        args.push_back(&pv);
-        args.push_back(&pn);
-        e = hipModuleLaunchKernel(kern->fn_strided2, wplan.bx, (unsigned)wplan.nsplit, (unsigned)post, wplan.threads, 1, 1, 0, c->stream, args.data(),
-                                  nullptr);
-    } else {
-        args.push_back(&u_pre);
-        args.push_back(&u_red);
-        args.push_back(&u_nsplit);
-        args.push_back(&tx);
-        args.push_back(&pv);
-        args.push_back(&pn);
-        e = hipModuleLaunchKernel(kern->fn_strided, plan.gx, plan.gy, plan.gz, 256, 1, 1, 0, c->stream, args.data(), nullptr);
+    unsigned long long u_pre = pre, u_red = reduce_len, u_nsplit = rt.nsplit, u_nslices = rt.nslices;
+    int tx = (int)rt.span;
+    unsigned win = rt.span;
+    hipFunction_t fn = nullptr;
+    switch (rt.kernel) {
+        case ReduceKernel::CONTIG:
+        case ReduceKernel::CONTIG_V2:  // two adjacent elements per call of the value functor (+12-18 % on plain tensors; the Monte-Carlo payoff sum 160 -> us)
+            fn = rt.kernel == ReduceKernel::CONTIG ? kern->fn_contig : kern->fn_contig2;
+            args.insert(args.end(), {&u_red, &u_nslices, &u_nsplit, &pv, &pn});
+            break;
+        case ReduceKernel::STRIDED:
+            fn = kern->fn_strided;
+            args.insert(args.end(), {&u_pre, &u_red, &u_nsplit, &tx, &pv, &pn});
+            break;
+        case ReduceKernel::STRIDED_V2:  // two adjacent slices per thread
+            fn = kern->fn_strided2;
+            args.insert(args.end(), {&u_pre, &u_red, &u_nsplit, &win, &pv, &pn});
+            break;
+        default:
+            rmhip_free(ctx, oid);
+            return fail(RMHIP_ERR_UNSUPPORTED, "fused_reduction: no generated kernel for route %s", reduce_kernel_name(rt.kernel));
     }
+    hipError_t e = hipModuleLaunchKernel(fn, rt.gx, rt.gy, rt.gz, rt.block, 1, 1, 0, c->stream, args.data(), nullptr);
     if (e == hipSuccess) {
         const double* cpv = pv;
         const double* cpn = pn;
@@ -459,10 +444,10 @@ int rmhip_fused_reduction(rmhip_ctx* ctx, const char* shader, const rmhip_buf* i
         double scale = flavor == RMHIP_FLAVOR_CUSTOM_SCALE ? custom_scale : 1.0;
         double* optr = ob.data();
         void* fargs[] = {&cpv, &cpn, &u_nslices, &u_nsplit, &u_red, &mean, &omit, &scale, &optr};
-        if (nsplit_used <= 8 && plan.nslices >= 1024) {
-            e = hipModuleLaunchKernel(kern->fn_final_flat, (unsigned)ceil_div_u64(plan.nslices, 256), 1, 1, 256, 1, 1, 0, c->stream, fargs, nullptr);
+        if (rt.flat_final) {
+            e = hipModuleLaunchKernel(kern->fn_final_flat, (unsigned)ceil_div_u64(rt.nslices, 256), 1, 1, 256, 1, 1, 0, c->stream, fargs, nullptr);
         } else {
-            const unsigned fb = (unsigned)ceil_div_u64(plan.nslices, 4);
+            const unsigned fb = (unsigned)ceil_div_u64(rt.nslices, 4);
             e = hipModuleLaunchKernel(kern->fn_final, fb, 1, 1, 256, 1, 1, 0, c->stream, fargs, nullptr);
         }
     }
@@ -472,7 +457,7 @@ int rmhip_fused_reduction(rmhip_ctx* ctx, const char* shader, const rmhip_buf* i
     }
     c->tel.kernel_launches += 2;
     c->record_launch("fused_reduction", {{"reduce_len", reduce_len}, {"slices", num_slices}, {"rank", rank}},
-                     {{"wg", (uint64_t)(plan.contiguous ? plan.tx : 256)}, {"flavor", (uint64_t)flavor}});
+                     {{"wg", (uint64_t)(pre == 1 ? rt.block : 256)}, {"flavor", (uint64_t)flavor}});
     *out = oid;
     return RMHIP_OK;
 }
@@ -906,7 +891,7 @@ int rmhip_matmul_power_step(rmhip_ctx* ctx, rmhip_buf lhs, rmhip_buf rhs, double
     CTX_OR_FAIL(ctx);
     if (!out) return fail(RMHIP_ERR_INVALID, "null out");
     // simple_provider.rs:7859-7884 composed from the provider's own ops: P = lhs*rhs; acc_c = sum_r P(r,c)^2 (+ eps);
-    // P(:,c) /= sqrt(acc_c).  The column sums run in the dot kernels (k_dot_*), the division in the broadcast kernel.
+    // P(:,c) /= sqrt(acc_c).  The column sums run in the reduction kernels over the product functor (reduce_kernels.hip), the division in the broadcast kernel.
     rmhip_buf p = 0, sq = 0, sq_eps = 0, norms = 0;
     int rc = rmhip_matmul(ctx, lhs, rhs, &p);
     if (!rc) rc = rmhip_dot(ctx, p, p, 0, &sq);

@@ -1,6 +1,6 @@
 // skel_reduce.h -- reduction kernel skeletons, templated on a value functor F (index -> f64).
-// Used twice: instantiated ahead of time with an identity functor (reduce_kernels.hip:
-// reduce_sum / reduce_sum_dim / reduce_mean / min / max / prod, reference semantics
+// Used twice: instantiated ahead of time with an identity or a product functor (reduce_kernels.hip:
+// reduce_sum / reduce_sum_dim / reduce_mean / min / max / prod and dot, reference semantics
 // crates/runmat-accelerate/src/simple_provider.rs:6728-6806) and embedded as text into the
 // hipRTC source of every fused reduction (the functor is then the folded producer expression of
 // crates/runmat-accelerate/src/fusion.rs:1765-2077).
@@ -304,43 +304,65 @@ __device__ __forceinline__ void rm_reduce_contig_v2(const F2& f2, rm_u64 red, rm
     }
 }
 
-// ---- kernel B over 16-byte vectors for generated fused reductions: a thread owns TWO adjacent slices (pair index along `pre`) and
-// walks its chunk of the reduced extent in ascending order with U vector loads in flight - the per-slice summation order of
-// rm_reduce_strided with ty == 1.  Geometry from reduce_plan.h (plan_strided_wide): blockIdx.x = window of `win` pairs, blockIdx.y =
-// chunk, blockIdx.z = post.  (The plain-tensor kernel k_reduce_strided_v2 in reduce_kernels.hip is the same walk plus the odd-extent form.)
-template <int OP, int U, class F2>
+// ---- kernel B over 16-byte vectors (plain tensors in reduce_kernels.hip: k_reduce_strided_v2 with U = 8; generated fused reductions:
+// rm_red_strided2 with U = 4): a thread owns TWO adjacent slices (pair index along `pre`) and walks its chunk of the reduced extent in
+// ascending order with U vector loads in flight - the per-slice summation order of rm_reduce_strided with ty == 1, at 1 KiB per wave
+// instruction.  Geometry from reduce_plan.h (plan_strided_wide): blockIdx.x = window of `win` <= 256 pairs, blockIdx.y = chunk,
+// blockIdx.z = post.
+// ODD: `pre` is odd (or the base only element-aligned).  Pairs start at even element offsets of every line, which are then only
+// element-aligned in every other line: the functor's unaligned pair_at (the hardware splits the loads that straddle), and the last
+// row - a pair of one - through one_at.  8191 x 8192: 110 us on the generic 8-byte kernel, 94 here.
+template <int OP, int U, bool ODD = false, class F2>
 __device__ __forceinline__ void rm_reduce_strided_v2(const F2& f2, rm_u64 pre, rm_u64 red, rm_u64 nsplit, unsigned win, double* pv, double* pn) {
     const rm_u64 i2 = (rm_u64)blockIdx.x * win + threadIdx.x;
-    const rm_u64 pre2 = pre >> 1;
+    const rm_u64 pre2 = ODD ? (pre + 1) >> 1 : pre >> 1;
     if (threadIdx.x >= win || i2 >= pre2) return;
+    const bool single = ODD && 2 * i2 + 1 >= pre;  // the last row of an odd `pre`
     const rm_u64 split = blockIdx.y, j = blockIdx.z;
     const rm_u64 chunk = (red + nsplit - 1) / nsplit;
     const rm_u64 begin = split * chunk;
     rm_u64 end = begin + chunk;
     if (end > red) end = red;
     RmAcc a0 = rm_acc_init<OP>(), a1 = rm_acc_init<OP>();
-    const rm_u64 base2 = i2 + pre2 * red * j;
+    const rm_u64 base2 = i2 + pre2 * red * j;       // even form: in pairs
+    const rm_u64 ebase = 2 * i2 + pre * red * j;    // odd form: in elements
+    auto ld = [&](rm_u64 rr) -> rm_rv2 {
+        if constexpr (ODD) {
+            if (single) return rm_rv2{f2.one_at(ebase + pre * rr), 0.0};
+            return f2.pair_at(ebase + pre * rr);
+        } else
+            return f2(base2 + pre2 * rr);
+    };
     rm_u64 r = begin;
     for (; r + U <= end; r += U) {
         rm_rv2 v[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = f2(base2 + pre2 * (r + u));
+        for (int u = 0; u < U; ++u) v[u] = ld(r + u);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             rm_acc_add<OP>(a0, v[u].x);
             rm_acc_add<OP>(a1, v[u].y);
         }
     }
-    for (; r < end; ++r) {
-        const rm_rv2 v = f2(base2 + pre2 * r);
-        rm_acc_add<OP>(a0, v.x);
-        rm_acc_add<OP>(a1, v.y);
+    if (r < end) {  // the last, partial group: its loads go out together too (one at a time they cost a memory round trip each)
+        rm_rv2 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (r + u < end) v[u] = ld(r + u);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (r + u < end) {
+                rm_acc_add<OP>(a0, v[u].x);
+                rm_acc_add<OP>(a1, v[u].y);
+            }
     }
     const rm_u64 slice = 2 * i2 + pre * j;
     pv[slice * nsplit + split] = a0.v;
     pn[slice * nsplit + split] = a0.nan;
-    pv[(slice + 1) * nsplit + split] = a1.v;
-    pn[(slice + 1) * nsplit + split] = a1.nan;
+    if (!single) {
+        pv[(slice + 1) * nsplit + split] = a1.v;
+        pn[(slice + 1) * nsplit + split] = a1.nan;
+    }
 }
 
 #endif  // RMHIP_SKEL_REDUCE

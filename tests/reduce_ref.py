@@ -54,6 +54,39 @@ ROUTE_TABLE = [
 ]
 ROUNDED_ROWS = [r for r in ROUTE_TABLE if r[0] * r[1] * r[2] <= ROUNDED_LIMIT]
 
+# The same for the two families whose launchers have kernels of their own: (pre, red, post, kernel, nsplit, flat finalize, grid.x,
+# block).  ACC: the accumulator reductions of reduce2.hip (min / max with indices, std, nnz / any / all, moments); GEN: the generated
+# fused reductions (rmhip_fused_reduction), which reduce axis 0 ([1, red, slices]) or axis 1 ([slices, red, 1]).
+ACC_ROUTE_TABLE = [
+    (1, 3, 1025, "short", 1, True, 5, 256), (1, 255, 1030, "short", 1, True, 65, 256), (1, 255, 1023, "contig", 1, False, 1, 256),
+    (1, 256, 1024, "contig", 1, True, 1, 256), (1, 300, 40, "contig", 1, False, 1, 256), (1, 1023, 3, "contig", 1, False, 1, 256),
+    (1, 1024, 3, "contig_v2", 1, False, 1, 256), (1, 2048, 3, "contig_v2", 1, False, 1, 256),
+    (1, 6000, 1, "contig_v2", 3, False, 3, 256), (1, 70000, 1, "contig_v2", 9, False, 9, 256),
+    (1, 4096, 1030, "contig_v2", 2, True, 2, 256), (1, 1025, 3, "contig_v2_odd", 1, False, 1, 256),
+    (1, 2047, 3, "contig_v2_odd", 1, False, 1, 256), (1, 2049, 3, "contig_v2_odd", 2, False, 2, 256),
+    (1, 6001, 2, "contig_v2_odd", 3, False, 3, 256), (1, 70001, 1, "contig_v2_odd", 9, False, 9, 256),
+    (1, 1025, 1030, "contig_v2_odd", 1, True, 1, 256), (2, 9, 1, "strided", 1, False, 1, 256),
+    (7, 5000, 1, "strided", 313, False, 1, 256), (100, 600, 1, "strided", 38, False, 1, 256),
+    (128, 257, 3, "strided", 17, False, 1, 256), (300, 257, 1, "strided", 17, False, 2, 256),
+    (3, 70000, 1, "strided", 2048, False, 1, 256), (511, 600, 1, "strided", 38, False, 2, 256),
+    (255, 40, 70, "strided", 3, True, 1, 256), (16, 20, 1100, "strided", 2, True, 1, 256),
+    (512, 40, 1, "strided_v2", 3, False, 1, 256), (512, 600, 1, "strided_v2", 38, False, 1, 256),
+    (514, 33, 3, "strided_v2", 3, True, 2, 192), (600, 16, 30, "strided_v2", 1, True, 2, 192),
+    (513, 37, 1, "strided_v2_odd", 3, False, 2, 192), (513, 600, 1, "strided_v2_odd", 38, False, 2, 192),
+    (515, 33, 3, "strided_v2_odd", 3, True, 2, 192), (601, 16, 30, "strided_v2_odd", 1, True, 2, 192),
+]
+GEN_ROUTE_TABLE = [
+    (1, 5, 1, "contig", 1, False, 1, 256), (1, 300, 40, "contig", 1, False, 1, 256), (1, 2049, 3, "contig", 2, False, 2, 256),
+    (1, 6001, 2, "contig", 3, False, 3, 256), (1, 17, 5000, "contig", 1, True, 1, 256), (1, 2048, 3, "contig_v2", 1, False, 1, 256),
+    (1, 6000, 1, "contig_v2", 3, False, 3, 256), (1, 70000, 1, "contig_v2", 9, False, 9, 1024),
+    (1, 4096, 1030, "contig_v2", 2, True, 2, 256), (7, 5000, 1, "strided", 10, False, 1, 256),
+    (300, 257, 1, "strided", 17, False, 2, 256), (511, 600, 1, "strided", 38, False, 2, 256),
+    (513, 600, 1, "strided", 38, False, 3, 256), (1001, 9, 1, "strided", 1, False, 4, 256),
+    (1025, 20, 1, "strided", 2, True, 5, 256), (512, 40, 1, "strided_v2", 3, False, 1, 256),
+    (512, 600, 1, "strided_v2", 38, False, 1, 256), (1100, 20, 1, "strided_v2", 2, True, 8, 128),
+    (8192, 100, 1, "strided_v2", 7, True, 16, 256),
+]
+
 
 def row_id(row) -> str:
     return f"{row[0]}x{row[1]}x{row[2]}-{row[3]}"

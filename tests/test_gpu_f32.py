@@ -15,6 +15,8 @@ builtins/math/elementwise/times.rs:750-760).  Two checks per op:
 import numpy as np
 import pytest
 
+import reduce_ref as R
+
 pytestmark = pytest.mark.gpu
 
 ULP32 = float(np.finfo(np.float32).eps)  # 1.19e-7
@@ -59,6 +61,30 @@ def prov32(built):
     p = HipProvider(int(os.environ.get("RMHIP_TEST_DEVICE", "0")), precision="F32")
     yield p
     p.close()
+
+
+@pytest.mark.parametrize("row", R.GEN_ROUTE_TABLE, ids=R.row_id)
+def test_fused_sum_of_squares_on_every_generated_route(prov32, prov, row):
+    """sum(x .* x) as one generated reduction on every kernel and finalize rmhip_fused_reduction can take (the shapes
+    tests/cpp/reduce_route_check.cpp pins to them), with f64 and with f32 shaders.  Integers with |x| <= 2^10: every partial sum is
+    an integer below 2^37, so any association order gives the same bits - the int64 sum's, narrowed once on the F32 provider."""
+    from planner_requests import FusionGroupPlan
+    from runmat_amd import ReductionFlavor
+
+    pre, red, post = row[:3]
+    axis, slices = (0, post) if pre == 1 else (1, pre)
+    x = np.random.default_rng(pre * red * post).integers(-1024, 1025, size=(red, slices) if axis == 0 else (slices, red)).astype(np.float64)
+    want = (x.astype(np.int64) ** 2).sum(axis=axis)
+    p = FusionGroupPlan()
+    v = p.input()
+    sq = p.primitive("ElemMul", v, v)
+    for pr, ty, narrow in ((prov, "f64", lambda w: w.astype(np.float64)), (prov32, "f32", lambda w: w.astype(np.float32).astype(np.float64))):
+        h = pr.upload(x)
+        out = pr.fused_reduction(p.generate_reduction_wgsl(sq, ty, axis=axis), [h], (slices,), red, slices, 256, ReductionFlavor.Sum())
+        got = pr.download(out)
+        pr.free(out)
+        pr.free(h)
+        assert same_bits(got, narrow(want)), (row, ty)
 
 
 def test_f32_boundary_is_f64_and_rounds_once(prov32, prov):

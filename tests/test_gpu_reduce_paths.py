@@ -264,7 +264,7 @@ def test_empty_reduced_extent(pv):
 
 
 # ---- rmhip_dot ----------------------------------------------------------------------------------------------------------------------
-DOT_ROWS = R.ROUNDED_ROWS + [(1, 17, 5000, "short", 1, True)]  # the extra row reaches k_dot_short; [1, 6000, 1] (k_dot_contig_v2) is in the table
+DOT_ROWS = R.ROUNDED_ROWS + [(1, 17, 5000, "short", 1, True)]  # the extra row reaches the short-tile kernel over the product; [1, 6000, 1] (16-byte kernel A) is in the table
 
 
 @pytest.mark.parametrize("row", DOT_ROWS, ids=R.row_id)

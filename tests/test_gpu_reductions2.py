@@ -4,6 +4,8 @@
 import numpy as np
 import pytest
 
+import reduce_ref as R
+
 pytestmark = pytest.mark.gpu
 
 
@@ -42,6 +44,42 @@ def test_minmax_dim_values_and_indices_bit_exact(prov, oracle, shape):
                     prov.free(r.values)
                     prov.free(r.indices)
         prov.free(h)
+
+
+def _acc_case(row):
+    """(data, dim) of an accumulator-family route row: integers in [-3, 3] with ties, signed zeros, infinities and NaNs"""
+    shape, dim = R.realise(*row[:3])
+    return _special(np.random.default_rng(row[0] * row[1] * row[2]), shape), max(dim, 0)  # [1, n, 1]: dimension 1 of a column
+
+
+@pytest.mark.parametrize("row", R.ACC_ROUTE_TABLE, ids=R.row_id)
+def test_minmax_dim_on_every_accumulator_route(prov, oracle, row):
+    """every stage-1 kernel of reduce2.hip with both finalizes, on the shapes tests/cpp/reduce_route_check.cpp pins to them: values
+    and 1-based indices bit for bit, both NaN modes"""
+    x, dim = _acc_case(row)
+    h = prov.upload(x)
+    for is_max in (False, True):
+        for omit in (False, True):
+            r = (prov.reduce_max_dim if is_max else prov.reduce_min_dim)(h, dim, omitnan=omit)
+            wv, wi = oracle.minmax_dim(x, dim, is_max, omit)
+            gv = prov.download(r.values).reshape(wv.shape, order="F")
+            gi = prov.download(r.indices).reshape(wi.shape, order="F")
+            prov.free(r.values)
+            prov.free(r.indices)
+            assert _same(gv, wv) and _same(gi, wi), (row, is_max, omit)
+    prov.free(h)
+
+
+@pytest.mark.parametrize("row", R.ACC_ROUTE_TABLE, ids=R.row_id)
+def test_nnz_dim_on_every_accumulator_route(prov, oracle, row):
+    x, dim = _acc_case(row)
+    h = prov.upload(x)
+    want = oracle.truth_dim(x, dim, "nnz", False)
+    got = prov.reduce_nnz_dim(h, dim)
+    assert np.array_equal(prov.download(got).reshape(want.shape, order="F"), want), row
+    assert np.array_equal(want.reshape(-1, order="F"), np.count_nonzero(R.slices(x.reshape(-1, order="F"), *row[:3]), axis=1))  # NaN counts, -0 does not
+    prov.free(got)
+    prov.free(h)
 
 
 def test_minmax_dim_edge_slices(prov, oracle):

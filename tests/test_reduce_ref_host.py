@@ -142,3 +142,6 @@ def test_route_table_is_the_host_checks_table(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     rows = [ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith("row ")]
     assert [(int(a), int(b), int(c), k, int(n), f == "flat") for a, b, c, k, n, f in rows] == R.ROUTE_TABLE
+    for tag, table in (("acc", R.ACC_ROUTE_TABLE), ("gen", R.GEN_ROUTE_TABLE)):  # the accumulator and generated families' tables
+        rows = [ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith(tag + " ")]
+        assert [(int(a), int(b), int(c), k, int(n), f == "flat", int(gx), int(bl)) for a, b, c, k, n, f, gx, bl in rows] == table, tag
