@@ -533,10 +533,37 @@ RMHIP_API int rmhip_moving_window(rmhip_ctx* ctx, rmhip_buf a, int dim, size_t b
  * `filter(b, a, x, zi, dim)` in direct form II transposed along zero-based `dim`, every channel an independent recurrence (one thread per
  * channel); coefficients normalised by a(1) as the CPU's complex division rounds them; `zi_or_0`: initial states in the signal's shape with
  * `dim` of extent max(nb, na) - 1.  output: x's shape; final_state: that state shape (`ProviderIirFilterResult`).  Bit-exact.
- * RMHIP_ERR_UNSUPPORTED: order > 64; fewer than 256 channels on more than 4096 samples (a recurrence: the host's one core is faster). */
+ * RMHIP_ERR_UNSUPPORTED: order > 64; fewer than 256 channels on more than 4096 samples (a recurrence: one thread per channel leaves the
+ * chip idle).  rmhip_iir_filter_long serves the shapes declined here, within a tolerance instead of bit for bit. */
 /* @serves iir_filter */
 RMHIP_API int rmhip_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
                                rmhip_buf* final_state);
+/* `iir_filter` on long signals with few channels: the second entry point of the hook, tried when rmhip_iir_filter declines.  Arguments, shapes,
+ * coefficient normalisation and the INVALID / SHAPE refusals are rmhip_iir_filter's; any channel count, any `dim`.  Along the dimension:
+ *   - no states (order 1), an empty signal, or fewer than 512 samples (two chunks of the shortest length): what rmhip_iir_filter computes,
+ *     without its channel-count decline.  Bit-exact.
+ *   - FIR (`unit_denominator`, or every normalised a(i), i >= 2, equal to 0): one thread per output sample forms the CPU's nested sum
+ *     b0 x[n] + (b1 x[n-1] + (b2 x[n-2] + ...)) from the innermost term outwards, the final states likewise.  Equal in VALUE to the CPU's
+ *     result for finite data; the sign of a zero is not promised (the CPU's `- a(i) y` with a(i) = 0 can turn a -0 into +0).
+ *   - recursive: a chunked scan.  With S = order - 1 states and chunks of L samples: tables H (L x S, the zero-input response to each unit
+ *     state) and T_L (S x S, the state after a chunk of zero input) from S runs of the recurrence over zeros; L is the smallest of 256, 512,
+ *     1024, 2048, 4096, 8192 (tried while two chunks fit the signal) whose T_L is finite with largest absolute row sum <= 1; every chunk is
+ *     filtered from a zero state, one thread each; the states that really enter the chunks follow sequentially, s(c+1) = T_L s(c) + sz(c),
+ *     one wavefront per channel; y(cL + k) += sum_i H(k, i) s(c)(i); the samples after the last full chunk are filtered sequentially from
+ *     their true entry state, which also gives the final state.  A signal shorter than two chunks of the first admissible length runs the
+ *     sequential recurrence (bit-exact).
+ *     Accuracy, with `exact` the recurrence in extended precision on the normalised coefficients, `cpu` the CPU's f64 loop, g the impulse
+ *     response and floor = order * 2^-52 * max_n sum_m |g(m)| |x(n - m)|:
+ *         max |y - exact|  <=  8 * max(max |cpu - exact|, floor)
+ *         max |zf - exact| <= 16 * max(max |cpu - exact|, (sum |b| + sum |a|) * floor)
+ * Precision-32 contexts: as rmhip_iir_filter - f64 arithmetic on widened operands, both results rounded to f32 storage on return.
+ * RMHIP_ERR_UNSUPPORTED (outputs freed, both ids 0): order > 64; a complex operand; a non-finite value in x, zi, the normalised
+ * coefficients, the tables or the results (the CPU poisons every later sample once a y is non-finite; neither the per-sample sum nor the
+ * chunked pass reproduces that); a recursive filter with no admissible L - "filter is not contractive over a chunk": unstable filters
+ * and high-order direct forms with clustered poles near the unit circle; more than 2^31 * 256 samples.  The host answers for those. */
+/* @serves iir_filter */
+RMHIP_API int rmhip_iir_filter_long(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator,
+                                    rmhip_buf* output, rmhip_buf* final_state);
 /* `imfilter(image, kernel, options)` (lib.rs:1809-1817; `ImfilterOptions`, :1193-1222; imfilter.rs:476-545, 620-783): N-D correlation (or,
  * convolution != 0, convolution: the kernel read back to front) of up to four dimensions.  padding: 0 constant (`constant_value`), 1 replicate,
  * 2 symmetric, 3 circular; shape_mode: 0 same, 1 full, 2 valid; the kernel's origin is floor(extent / 2) per dimension.  Sums over the kernel's

@@ -1050,6 +1050,13 @@ public:
         check(rmhip_iir_filter(ctx_, own(b), own(a), own(x), (int)dim, zi ? own(*zi) : 0, unit_denominator ? 1 : 0, &out, &fin));
         return {with_shape(out), with_shape(fin)};
     }
+    // the hook's second entry point: long signals with few channels, which iir_filter declines (a chunked scan; rmhip.h has its accuracy contract)
+    IirFilterResult iir_filter_long(const GpuTensorHandle& b, const GpuTensorHandle& a, const GpuTensorHandle& x, size_t dim, const GpuTensorHandle* zi,
+                                    bool unit_denominator) const {
+        uint64_t out = 0, fin = 0;
+        check(rmhip_iir_filter_long(ctx_, own(b), own(a), own(x), (int)dim, zi ? own(*zi) : 0, unit_denominator ? 1 : 0, &out, &fin));
+        return {with_shape(out), with_shape(fin)};
+    }
     // lib.rs:1652-1660; mu == nullptr: no centring / scaling, else {mean, scale}
     GpuTensorHandle polyval(const GpuTensorHandle& coefficients, const GpuTensorHandle& points, const double* mu = nullptr) const {
         uint64_t out = 0;

@@ -358,6 +358,223 @@ __global__ void __launch_bounds__(kB) k_iir(const double* __restrict__ x, const 
         if ((u64)i < state_len) zf[l + (u64)i * leading + t * leading * state_len] = st[i];
 }
 
+// ---- filter on long signals with few channels (rmhip_iir_filter_long) -----------------------------------------------------------------
+// Every kernel below lowers *verdict to 0 when it meets a non-finite value: the CPU poisons every later sample once one appears, which
+// neither the per-sample sum nor the chunked scan reproduces, so the entry point declines the request.
+
+// FIR (every normalised a(i), i >= 2, is 0): the recurrence's states unroll into the nested sum y[n] = b0 x[n] + (b1 x[n-1] + (b2 x[n-2]
+// + ...)), the chain ending in + 0.0 after order - 1 terms or in zi[n] when it reaches the start of the signal first.  One thread per
+// output sample forms it from the innermost term outwards: the CPU's additions in the CPU's order.  `tiles` != 0: the dimension is the
+// contiguous one, a block is one tile of kB samples of one channel and stages them with the order - 1 before them in LDS.
+constexpr int FIRL_WIN = kB + 63;
+__global__ void __launch_bounds__(kB) k_fir_long(const double* __restrict__ x, const double* __restrict__ zi, const double* __restrict__ coef, int order, u64 leading,
+                                                 u64 dim_len, u64 total, u64 tiles, double* __restrict__ y, unsigned* __restrict__ verdict) {
+    __shared__ double win[FIRL_WIN];
+    const int S = order - 1;
+    u64 l, n, t;
+    bool live;
+    if (tiles) {
+        t = (u64)blockIdx.x / tiles, l = 0;
+        const u64 n0 = ((u64)blockIdx.x % tiles) * kB;
+        n = n0 + threadIdx.x;
+        live = n < dim_len;
+        const double* line = x + t * dim_len;
+        for (int j = threadIdx.x; j < kB + S; j += kB) {  // win[j] is sample n0 - S + j
+            const long long m = (long long)n0 - S + j;
+            win[j] = (m >= 0 && (u64)m < dim_len) ? line[m] : 0.0;
+        }
+        __syncthreads();
+    } else {
+        const u64 e = (u64)blockIdx.x * kB + threadIdx.x;
+        live = e < total;
+        l = e % leading, n = (e / leading) % dim_len, t = e / (leading * dim_len);
+    }
+    if (!live) return;
+    const u64 at = t * dim_len * leading + n * leading + l;
+    const int K = n < (u64)S ? (int)n : S;
+    double acc = (zi && n < (u64)S) ? zi[l + n * leading + t * leading * (u64)S] : 0.0;
+    bool bad = !isfinite(acc);
+    if (tiles) {
+        const double* here = win + threadIdx.x + S;
+        for (int k = K; k >= 1; --k) {
+            const double p = coef[k] * *(here - k);
+            acc = p + acc;
+        }
+    } else {
+        const double* here = x + at;
+        for (int k = K; k >= 1; --k) {
+            const double p = coef[k] * *(here - (u64)k * leading);
+            acc = p + acc;
+        }
+    }
+    const double xn = tiles ? win[threadIdx.x + S] : x[at];
+    const double p0 = coef[0] * xn;
+    const double yv = p0 + acc;
+    y[at] = yv;
+    if (bad || !isfinite(xn) || !isfinite(yv)) *verdict = 0;
+}
+
+// its final state, one thread per (channel, state): zf[i] = b[i+1] x[N-1] + (b[i+2] x[N-2] + ...), order - 1 - i terms and + 0.0, or N terms
+// and zi[i + N] when the signal is shorter than that
+__global__ void __launch_bounds__(kB) k_fir_long_state(const double* __restrict__ x, const double* __restrict__ zi, const double* __restrict__ coef, int order,
+                                                       u64 leading, u64 dim_len, u64 total, double* __restrict__ zf, unsigned* __restrict__ verdict) {
+    const u64 w = (u64)blockIdx.x * kB + threadIdx.x;
+    if (w >= total) return;
+    const u64 S = (u64)order - 1;
+    const u64 l = w % leading, i = (w / leading) % S, t = w / (leading * S);
+    const u64 K = dim_len < S - i ? dim_len : S - i;
+    double acc = (zi && i + dim_len < S) ? zi[l + (i + dim_len) * leading + t * leading * S] : 0.0;
+    bool bad = zi && !isfinite(zi[w]);
+    const double* end = x + t * dim_len * leading + dim_len * leading + l;  // one past the channel's last sample
+    for (u64 k = K; k >= 1; --k) {
+        const double p = coef[i + k] * *(end - k * leading);
+        acc = p + acc;
+    }
+    zf[w] = acc;
+    if (bad || !isfinite(acc)) *verdict = 0;
+}
+
+// Recursive filters, by chunks of `count` samples.  k_iir's recurrence, operation for operation, on one chunk per thread:
+//   from_state == 0  the zero-state pass: chunk c of channel ch starts at sample first + c * count from a zero state, writes its y and
+//                    leaves its closing state in states[(ch * slots + c) * S ..];
+//   from_state != 0  the tail (nchunks == 1): it starts from the true entry state the state pass left in the channel's last slot, its y is
+//                    final and its closing state is the filter's final state, written to zf in the signal's layout.
+// Neighbouring threads are neighbouring positions of the leading dimensions, then neighbouring chunks.
+template <int MAXO>
+__global__ void __launch_bounds__(kB) k_iir_chunks(const double* __restrict__ x, const double* __restrict__ coef, int order, u64 leading, u64 dim_len, u64 channels,
+                                                   u64 first, u64 count, u64 nchunks, u64 slots, int from_state, double* __restrict__ states, double* __restrict__ y,
+                                                   double* __restrict__ zf, unsigned* __restrict__ verdict) {
+    const u64 w = (u64)blockIdx.x * kB + threadIdx.x;
+    if (w >= channels * nchunks) return;
+    const u64 l = w % leading, cidx = (w / leading) % nchunks, t = w / (leading * nchunks);
+    const u64 ch = l + t * leading;
+    const u64 state_len = (u64)order - 1;
+    double* slot = states + (ch * slots + (from_state ? slots - 1 : cidx)) * state_len;
+    double bn[MAXO], an[MAXO], st[MAXO];
+#pragma unroll
+    for (int i = 0; i < MAXO; ++i) {
+        bn[i] = i < order ? coef[i] : 0.0;
+        an[i] = i < order ? coef[order + i] : 0.0;
+        st[i] = (from_state && (u64)i < state_len) ? slot[i] : 0.0;
+    }
+    const u64 begin = first + cidx * count;
+    const double* src = x + t * dim_len * leading + begin * leading + l;
+    double* dst = y + t * dim_len * leading + begin * leading + l;
+    bool bad = false;
+    for (u64 s0 = 0; s0 < count; s0 += 8) {
+        double xb[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) xb[u] = s0 + u < count ? src[(s0 + u) * leading] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (s0 + u >= count) break;
+            const double xn = xb[u];
+            const double yv = bn[0] * xn + st[0];
+            dst[(s0 + u) * leading] = yv;
+            bad |= !isfinite(xn) || !isfinite(yv);
+#pragma unroll
+            for (int i = 1; i < MAXO; ++i) {
+                if (i < order) {
+                    const double next = (u64)i < state_len ? st[i] : 0.0;
+                    const double p = bn[i] * xn, q = an[i] * yv;
+                    st[i - 1] = (p + next) - q;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < MAXO; ++i)
+        if ((u64)i < state_len) {
+            bad |= !isfinite(st[i]);
+            if (zf) zf[l + (u64)i * leading + t * leading * state_len] = st[i];
+            else slot[i] = st[i];
+        }
+    if (bad) *verdict = 0;
+}
+
+// The state pass: s(c+1) = T s(c) + sz(c), s(0) = zi, sequentially over a channel's chunks.  One wavefront per channel, lane j holds row j
+// of T (T[j + S i]: state j after a chunk of zero input from unit state i) and state j; slot c holds sz(c) on entry and s(c), the state
+// that really entered chunk c, on return; slot nfull receives the state after the last full chunk.  The loop is bounded by the chunk
+// count and the closing states are fetched four chunks ahead of the products that consume them.
+template <int MAXS>
+__global__ void __launch_bounds__(64) k_iir_states(const double* __restrict__ T, const double* __restrict__ zi, int S, u64 leading, u64 nfull,
+                                                   double* __restrict__ states, unsigned* __restrict__ verdict) {
+    const u64 ch = blockIdx.x, l = ch % leading, t = ch / leading;
+    const int lane = threadIdx.x;
+    const bool mine = lane < S;
+    double row[MAXS];
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < MAXS; ++i) {
+        row[i] = (mine && i < S) ? T[lane + S * i] : 0.0;
+        bad |= !isfinite(row[i]);
+    }
+    double s = (zi && mine) ? zi[l + (u64)lane * leading + t * leading * (u64)S] : 0.0;
+    bad |= !isfinite(s);
+    double* slot = states + ch * (nfull + 1) * (u64)S + (mine ? lane : 0);
+    for (u64 c0 = 0; c0 < nfull; c0 += 4) {
+        double sz[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sz[u] = (mine && c0 + u < nfull) ? slot[(c0 + u) * S] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (c0 + u >= nfull) break;
+            if (mine) slot[(c0 + u) * S] = s;
+            double acc = 0.0;
+#pragma unroll
+            for (int i = 0; i < MAXS; ++i) {
+                if (i < S) {
+                    const double p = row[i] * __shfl(s, i);
+                    acc = acc + p;
+                }
+            }
+            s = acc + sz[u];
+            bad |= !isfinite(s);
+        }
+    }
+    if (mine) slot[nfull * S] = s;
+    if (bad) *verdict = 0;
+}
+
+// The correction: y[c L + k] += sum over i ascending of H[k + L i] * s(c)[i], over every full chunk.  A block owns IIRL_KT samples k of
+// the chunk and stages their H tile (IIRL_KT x S doubles, at most 31.5 KiB) in LDS; each of its waves then walks (channel, chunk) pairs,
+// its lanes on neighbouring samples.
+constexpr int IIRL_KT = 64;
+template <int MAXS>
+__global__ void __launch_bounds__(kB) k_iir_correct(const double* __restrict__ H, int S, u64 L, u64 leading, u64 dim_len, u64 channels, u64 nfull,
+                                                    const double* __restrict__ states, double* __restrict__ y, unsigned* __restrict__ verdict) {
+    __shared__ double h[IIRL_KT * MAXS];
+    const u64 k0 = (u64)blockIdx.x * IIRL_KT;
+    bool bad = false;
+    for (int j = threadIdx.x; j < IIRL_KT * S; j += kB) {
+        const int kk = j % IIRL_KT, i = j / IIRL_KT;
+        const double v = H[k0 + kk + L * (u64)i];
+        h[j] = v;
+        bad |= !isfinite(v);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 pairs = channels * nfull;
+    for (u64 p = (u64)blockIdx.y * (kB / 64) + wave; p < pairs; p += (u64)gridDim.y * (kB / 64)) {
+        const u64 ch = p / nfull, cidx = p % nfull;
+        const u64 l = ch % leading, t = ch / leading;
+        const double* s = states + (ch * (nfull + 1) + cidx) * (u64)S;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < MAXS; ++i) {
+            if (i < S) {
+                const double q = h[i * IIRL_KT + lane] * s[i];
+                acc = acc + q;
+            }
+        }
+        double* at = y + t * dim_len * leading + (cidx * L + k0 + lane) * leading + l;
+        const double v = *at + acc;
+        *at = v;
+        bad |= !isfinite(v);
+    }
+    if (bad) *verdict = 0;
+}
+
 // interp1 (runmat-accelerate/src/simple_provider.rs:1396-1472, 8135-8204): one thread per (series, query) - a binary search of the strictly
 // increasing sample coordinates, then the CPU's four operations (linear) or its nearer-neighbour rule (ties to the left).
 __device__ __forceinline__ long long interp_search(const double* __restrict__ x, u64 n, double q, bool* exact) {  // Rust's binary_search_by on distinct keys
@@ -1099,21 +1316,34 @@ int rmhip_moving_window(rmhip_ctx* ctx, rmhip_buf a, int dim, size_t before, siz
     return RMHIP_OK;
 }
 
-int rmhip_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
-                     rmhip_buf* final_state) {
-    CTX_OR_FAIL(ctx);
-    if (!output || !final_state) return fail(RMHIP_ERR_INVALID, "iir_filter: null output");
-    if (dim < 0) return fail(RMHIP_ERR_INVALID, "iir_filter: dim must be >= 0");
-    *output = *final_state = 0;
-    Buffer bb, ab, xb, zb;
+namespace {
+using namespace rmhip;
+
+// What both filter entry points make of a request: operands, geometry along `dim`, the state shape and the normalised coefficients
+// (coef[0 .. order): b, coef[order .. 2 order): a with a(1) = 1)
+struct IirRequest {
+    Buffer xb, zb;
+    bool has_zi = false;
+    size_t order = 0, state_len = 0;
+    u64 leading = 1, dim_len = 0, channels = 0;
+    std::vector<size_t> zshape;
+    std::vector<double> coef;
+};
+
+// The validation and normalisation of `iir_filter` (filter.rs:1119-1138), shared by rmhip_iir_filter and rmhip_iir_filter_long;
+// `few_channels_ok`: the long form, which keeps the shapes the one-thread-per-channel form declines
+int iir_prepare(Context* c, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, bool few_channels_ok, IirRequest* r) {
+    Buffer bb, ab;
     RMHIP_TRY(c->get(b, &bb));
     RMHIP_TRY(c->get(a, &ab));
-    RMHIP_TRY(c->get(x, &xb));
+    RMHIP_TRY(c->get(x, &r->xb));
+    const Buffer& xb = r->xb;
     const size_t nb = bb.numel, na = unit_denominator ? 1 : ab.numel;
     if (nb == 0) return fail(RMHIP_ERR_INVALID, "iir_filter: numerator coefficients must not be empty");
     if (ab.numel == 0) return fail(RMHIP_ERR_INVALID, "iir_filter: denominator coefficients must not be empty");
     if (unit_denominator && ab.numel != 1) return fail(RMHIP_ERR_INVALID, "iir_filter: unit-denominator FIR path requires scalar denominator");
     const size_t order = std::max(nb, na), state_len = order - 1;
+    r->order = order, r->state_len = state_len;
     if (order > 64) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: order %zu", order);
     std::vector<size_t> shape = xb.shape;
     if ((size_t)dim >= shape.size()) shape.resize(dim + 1, 1);
@@ -1121,19 +1351,25 @@ int rmhip_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int 
     for (int k = 0; k < dim; ++k) leading *= shape[k];
     for (size_t k = dim + 1; k < shape.size(); ++k) trailing *= shape[k];
     const u64 dim_len = shape[dim], channels = leading * trailing;
-    // a recurrence per channel: with few channels the chip idles and the host's one core is faster - the caller keeps those
-    if (state_len > 0 && channels < 256 && xb.numel > 4096) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: %llu channels", channels);
-    std::vector<size_t> zshape = shape;  // filter_state_shape, filter.rs:1311-1319
+    r->leading = leading, r->dim_len = dim_len, r->channels = channels;
+    // a recurrence per channel: one thread per channel leaves the chip idle when there are few - rmhip_iir_filter_long keeps those
+    if (!few_channels_ok && state_len > 0 && channels < 256 && xb.numel > 4096) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: %llu channels", channels);
+    std::vector<size_t>& zshape = r->zshape;  // filter_state_shape, filter.rs:1311-1319
+    zshape = shape;
     zshape[dim] = state_len;
     if (zi_or_0) {
-        RMHIP_TRY(c->get(zi_or_0, &zb));
+        RMHIP_TRY(c->get(zi_or_0, &r->zb));
+        r->has_zi = true;
+        const Buffer& zb = r->zb;
         const size_t rk = std::max(zshape.size(), zb.shape.size());
         for (size_t k = 0; k < rk; ++k)
             if ((k < zshape.size() ? zshape[k] : 1) != (k < zb.shape.size() ? zb.shape[k] : 1))
                 return fail(RMHIP_ERR_SHAPE, "iir_filter: initial conditions are not compatible with the signal shape");
     }
     // coefficients: read back (<= 128 doubles), normalised as the CPU's complex division by (a0 + 0i) rounds them (filter.rs:1119-1138)
-    std::vector<double> hb(nb), ha(ab.numel), coef(2 * order, 0.0);
+    std::vector<double> hb(nb), ha(ab.numel);
+    std::vector<double>& coef = r->coef;
+    coef.assign(2 * order, 0.0);
     RMHIP_HIP_CHECK(hipMemcpyAsync(hb.data(), bb.data(), nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     RMHIP_HIP_CHECK(hipMemcpyAsync(ha.data(), ab.data(), ab.numel * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -1143,29 +1379,179 @@ int rmhip_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int 
     for (size_t i = 0; i < nb; ++i) coef[i] = (hb[i] * a0 + 0.0) / den;
     coef[order] = 1.0;
     for (size_t i = 1; i < na; ++i) coef[order + i] = (ha[i] * a0 + 0.0) / den;
-    Buffer yb, fb;
-    RMHIP_TRY(c->new_buffer(xb.shape.data(), xb.shape.size(), output, &yb));
-    int rc = c->new_buffer(zshape.data(), zshape.size(), final_state, &fb);
-    if (rc == RMHIP_OK && state_len == 0) {
-        if (yb.numel) rc = launch_scalar(c, RMHIP_SMUL, xb.data(), coef[0], yb.data(), yb.numel);  // gain * x (filter.rs:1172-1176)
-    } else if (rc == RMHIP_OK && zi_or_0 && (dim_len == 0 || channels == 0)) {
-        if (fb.numel) RMHIP_HIP_CHECK(hipMemcpyAsync(fb.data(), zb.data(), fb.numel * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    } else if (rc == RMHIP_OK && channels > 0) {
+    return RMHIP_OK;
+}
+
+// k_iir on `channels` lines of `dim_len` samples, `coef_dev` the 2 * order normalised coefficients on the device
+int iir_launch_sequential(Context* c, const double* x, const double* zi, const double* coef_dev, size_t order, u64 leading, u64 dim_len, u64 channels, double* y,
+                          double* zf) {
+    if (order <= 8) hipLaunchKernelGGL(k_iir<8>, dim3(grid_for(channels)), dim3(kB), 0, c->stream, x, zi, coef_dev, (int)order, leading, dim_len, channels, y, zf);
+    else hipLaunchKernelGGL(k_iir<64>, dim3(grid_for(channels)), dim3(kB), 0, c->stream, x, zi, coef_dev, (int)order, leading, dim_len, channels, y, zf);
+    c->tel.kernel_launches++;
+    return hipGetLastError() == hipSuccess ? RMHIP_OK : fail(RMHIP_ERR_HIP, "iir_filter: launch failed");
+}
+
+// The bit-exact forms: the gain kernel without states, the initial states handed on for an empty signal, else k_iir with one thread per
+// channel.  Fills the two output buffers the caller created.
+int iir_run_sequential(Context* c, const IirRequest& r, const Buffer& yb, const Buffer& fb) {
+    const Buffer& xb = r.xb;
+    if (r.state_len == 0) {
+        if (yb.numel) return launch_scalar(c, RMHIP_SMUL, xb.data(), r.coef[0], yb.data(), yb.numel);  // gain * x (filter.rs:1172-1176)
+    } else if (r.has_zi && (r.dim_len == 0 || r.channels == 0)) {
+        if (fb.numel) RMHIP_HIP_CHECK(hipMemcpyAsync(fb.data(), r.zb.data(), fb.numel * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    } else if (r.channels > 0) {
         std::shared_ptr<Allocation> dc;
-        rc = c->alloc_device(2 * order, &dc);
-        if (rc == RMHIP_OK) {
-            // (pageable source: the copy is staged before the call returns, so `coef` may go out of scope)
-            RMHIP_HIP_CHECK(hipMemcpyAsync(dc->ptr, coef.data(), 2 * order * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            const double* zi = zi_or_0 ? zb.data() : nullptr;
-            if (order <= 8)
-                hipLaunchKernelGGL(k_iir<8>, dim3(grid_for(channels)), dim3(kB), 0, c->stream, xb.data(), zi, dc->ptr, (int)order, leading, dim_len, channels, yb.data(), fb.data());
-            else
-                hipLaunchKernelGGL(k_iir<64>, dim3(grid_for(channels)), dim3(kB), 0, c->stream, xb.data(), zi, dc->ptr, (int)order, leading, dim_len, channels, yb.data(), fb.data());
-            c->tel.kernel_launches++;
-            if (hipGetLastError() != hipSuccess) rc = fail(RMHIP_ERR_HIP, "iir_filter: launch failed");
-            RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // the coefficient block is released on return
+        RMHIP_TRY(c->alloc_device(2 * r.order, &dc));
+        // (pageable source: the copy is staged before the call returns, so `coef` may go out of scope)
+        RMHIP_HIP_CHECK(hipMemcpyAsync(dc->ptr, r.coef.data(), 2 * r.order * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        const int rc = iir_launch_sequential(c, xb.data(), r.has_zi ? r.zb.data() : nullptr, dc->ptr, r.order, r.leading, r.dim_len, r.channels, yb.data(), fb.data());
+        RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // the coefficient block is released on return
+        return rc;
+    }
+    return RMHIP_OK;
+}
+
+constexpr u64 IIRL_CHUNKS[] = {256, 512, 1024, 2048, 4096, 8192};
+
+// FIR: the nested sum per output sample and per final state
+int iir_run_fir(Context* c, const IirRequest& r, const double* coef_dev, const Buffer& yb, const Buffer& fb) {
+    const double* zi = r.has_zi ? r.zb.data() : nullptr;
+    const u64 tiles = r.leading == 1 ? (r.dim_len + kB - 1) / kB : 0;  // the contiguous dimension: a block per tile of a channel
+    const u64 blocks = tiles ? tiles * r.channels : grid_for(yb.numel);
+    hipLaunchKernelGGL(k_fir_long, dim3(blocks), dim3(kB), 0, c->stream, r.xb.data(), zi, coef_dev, (int)r.order, r.leading, r.dim_len, (u64)yb.numel, tiles,
+                       yb.data(), c->verdict_word);
+    hipLaunchKernelGGL(k_fir_long_state, dim3(grid_for(fb.numel)), dim3(kB), 0, c->stream, r.xb.data(), zi, coef_dev, (int)r.order, r.leading, r.dim_len,
+                       (u64)fb.numel, fb.data(), c->verdict_word);
+    c->tel.kernel_launches += 2;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
+}
+
+// Recursive: the chunked scan.  *declined: no chunk length is admissible.  *sequential: the signal is too short for two chunks of the
+// first admissible length, nothing was launched on the outputs.
+int iir_run_chunked(Context* c, const IirRequest& r, const double* coef_dev, const Buffer& yb, const Buffer& fb, bool* declined, bool* sequential) {
+    const u64 S = r.state_len, N = r.dim_len;
+    *declined = *sequential = false;
+    u64 lmax = 0;
+    for (u64 cand : IIRL_CHUNKS)
+        if (2 * cand <= N) lmax = cand;
+    // tables: S runs of the recurrence over `L` zeros from the unit states - their outputs are H (H[k + L i]), their final states T_L
+    std::shared_ptr<Allocation> zeros, eye, H, T;
+    RMHIP_TRY(c->alloc_device(lmax * S, &zeros));
+    RMHIP_TRY(c->alloc_device(lmax * S, &H));
+    RMHIP_TRY(c->alloc_device(S * S, &eye));
+    RMHIP_TRY(c->alloc_device(S * S, &T));
+    std::vector<double> host(S * S, 0.0);
+    for (u64 i = 0; i < S; ++i) host[i + S * i] = 1.0;
+    RMHIP_HIP_CHECK(hipMemsetAsync(zeros->ptr, 0, lmax * S * sizeof(double), c->stream));
+    RMHIP_HIP_CHECK(hipMemcpyAsync(eye->ptr, host.data(), S * S * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // `host` is reused for T below
+    u64 L = 0;
+    for (u64 cand : IIRL_CHUNKS) {
+        if (cand > lmax) break;
+        RMHIP_TRY(iir_launch_sequential(c, zeros->ptr, eye->ptr, coef_dev, r.order, 1, cand, S, H->ptr, T->ptr));
+        RMHIP_HIP_CHECK(hipMemcpyAsync(host.data(), T->ptr, S * S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
+        // admissible: T_L finite and contractive in the infinity norm of |T_L| - a state error is not amplified from chunk to chunk
+        double worst = 0.0;
+        for (u64 j = 0; j < S; ++j) {
+            double sum = 0.0;
+            for (u64 i = 0; i < S; ++i) sum += std::fabs(host[j + S * i]);
+            worst = std::isfinite(sum) ? std::max(worst, sum) : INFINITY;
+        }
+        if (worst <= 1.0) {
+            L = cand;
+            break;
         }
     }
+    if (L == 0) {
+        if (lmax == IIRL_CHUNKS[5]) *declined = true;
+        else *sequential = true;
+        return RMHIP_OK;
+    }
+    const u64 nfull = N / L, tail = N - nfull * L, slots = nfull + 1;
+    std::shared_ptr<Allocation> states;
+    RMHIP_TRY(c->alloc_device(r.channels * slots * S, &states));
+    const double* zi = r.has_zi ? r.zb.data() : nullptr;
+    const double* x = r.xb.data();
+    const u64 pairs = r.channels * nfull, ktiles = L / IIRL_KT;
+    const u64 wave_rows = (pairs + kB / 64 - 1) / (kB / 64);
+    const unsigned gy = (unsigned)std::min<u64>(wave_rows, std::max<u64>(1, 4096 / ktiles));
+    auto launch = [&](auto maxo) {  // the four phases, states and coefficients in registers up to order 8
+        constexpr int MAXO = decltype(maxo)::value;
+        hipLaunchKernelGGL(k_iir_chunks<MAXO>, dim3(grid_for(pairs)), dim3(kB), 0, c->stream, x, coef_dev, (int)r.order, r.leading, N, r.channels, (u64)0, L, nfull,
+                           slots, 0, states->ptr, yb.data(), (double*)nullptr, c->verdict_word);
+        hipLaunchKernelGGL(k_iir_states<MAXO - 1>, dim3(r.channels), dim3(64), 0, c->stream, T->ptr, zi, (int)S, r.leading, nfull, states->ptr, c->verdict_word);
+        hipLaunchKernelGGL(k_iir_correct<MAXO - 1>, dim3(ktiles, gy), dim3(kB), 0, c->stream, H->ptr, (int)S, L, r.leading, N, r.channels, nfull, states->ptr,
+                           yb.data(), c->verdict_word);
+        hipLaunchKernelGGL(k_iir_chunks<MAXO>, dim3(grid_for(r.channels)), dim3(kB), 0, c->stream, x, coef_dev, (int)r.order, r.leading, N, r.channels, nfull * L,
+                           tail, (u64)1, slots, 1, states->ptr, yb.data(), fb.data(), c->verdict_word);
+    };
+    if (r.order <= 8) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 64>{});
+    c->tel.kernel_launches += 4;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // the tables and the states are released on return
+    return RMHIP_OK;
+}
+}  // namespace
+
+int rmhip_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
+                     rmhip_buf* final_state) {
+    CTX_OR_FAIL(ctx);
+    if (!output || !final_state) return fail(RMHIP_ERR_INVALID, "iir_filter: null output");
+    if (dim < 0) return fail(RMHIP_ERR_INVALID, "iir_filter: dim must be >= 0");
+    *output = *final_state = 0;
+    IirRequest r;
+    RMHIP_TRY(iir_prepare(c, b, a, x, dim, zi_or_0, unit_denominator, false, &r));
+    Buffer yb, fb;
+    RMHIP_TRY(c->new_buffer(r.xb.shape.data(), r.xb.shape.size(), output, &yb));
+    int rc = c->new_buffer(r.zshape.data(), r.zshape.size(), final_state, &fb);
+    if (rc == RMHIP_OK) rc = iir_run_sequential(c, r, yb, fb);
+    if (rc != RMHIP_OK) {
+        rmhip_free(ctx, *output);
+        if (*final_state) rmhip_free(ctx, *final_state);
+        *output = *final_state = 0;
+    }
+    return rc;
+}
+
+int rmhip_iir_filter_long(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
+                          rmhip_buf* final_state) {
+    CTX_OR_FAIL(ctx);
+    if (!output || !final_state) return fail(RMHIP_ERR_INVALID, "iir_filter: null output");
+    if (dim < 0) return fail(RMHIP_ERR_INVALID, "iir_filter: dim must be >= 0");
+    *output = *final_state = 0;
+    IirRequest r;
+    RMHIP_TRY(iir_prepare(c, b, a, x, dim, zi_or_0, unit_denominator, true, &r));
+    if (r.xb.numel > 0x7fffffffull * kB) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: %zu samples", r.xb.numel);
+    bool fir = true, finite = true;
+    for (size_t i = 0; i < 2 * r.order; ++i) finite = finite && std::isfinite(r.coef[i]);
+    for (size_t i = 1; i < r.order; ++i) fir = fir && r.coef[r.order + i] == 0.0;
+    // too short to form two chunks of the shortest length, no states, nothing to filter: the bit-exact forms
+    const bool plain = r.state_len == 0 || r.channels == 0 || r.dim_len < 2 * IIRL_CHUNKS[0];
+    if (!plain && !finite) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: non-finite coefficients");
+    Buffer yb, fb;
+    RMHIP_TRY(c->new_buffer(r.xb.shape.data(), r.xb.shape.size(), output, &yb));
+    int rc = c->new_buffer(r.zshape.data(), r.zshape.size(), final_state, &fb);
+    auto chunked = [&]() -> int {
+        if (!c->verdict_word) RMHIP_HIP_CHECK(hipMalloc((void**)&c->verdict_word, sizeof(unsigned)));
+        RMHIP_HIP_CHECK(hipMemsetAsync(c->verdict_word, 0xff, sizeof(unsigned), c->stream));
+        std::shared_ptr<Allocation> dc;
+        RMHIP_TRY(c->alloc_device(2 * r.order, &dc));
+        RMHIP_HIP_CHECK(hipMemcpyAsync(dc->ptr, r.coef.data(), 2 * r.order * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        bool declined = false, sequential = false;
+        if (fir) RMHIP_TRY(iir_run_fir(c, r, dc->ptr, yb, fb));
+        else RMHIP_TRY(iir_run_chunked(c, r, dc->ptr, yb, fb, &declined, &sequential));
+        unsigned code = 0;
+        RMHIP_HIP_CHECK(hipMemcpyAsync(&code, c->verdict_word, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // the verdict is part of the answer; the coefficient block is released on return
+        if (declined) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: filter is not contractive over a chunk");
+        if (sequential) return iir_run_sequential(c, r, yb, fb);
+        if (code == 0) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: a non-finite value in the signal, the initial states or the result");
+        return RMHIP_OK;
+    };
+    if (rc == RMHIP_OK) rc = plain ? iir_run_sequential(c, r, yb, fb) : chunked();
     if (rc != RMHIP_OK) {
         rmhip_free(ctx, *output);
         if (*final_state) rmhip_free(ctx, *final_state);

@@ -1586,6 +1586,14 @@ class HipProvider:
                                                1 if unit_denominator else 0, C.byref(out), C.byref(fin)))
         return self._handle(out.value), self._handle(fin.value)
 
+    def iir_filter_long(self, b, a, x, dim: int, zi=None, unit_denominator: bool = False):
+        """The hook's second entry point, for the long signals with few channels that `iir_filter` declines: a nested sum per sample for an
+        FIR filter, a chunked scan for a recursive one (within the accuracy contract of rmhip.h, not bit for bit).  Same result pair."""
+        out, fin = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.rmhip_iir_filter_long(self._ctx, self._id(b), self._id(a), self._id(x), int(dim), self._id(zi) if zi is not None else 0,
+                                                    1 if unit_denominator else 0, C.byref(out), C.byref(fin)))
+        return self._handle(out.value), self._handle(fin.value)
+
     def imfilter(self, image, kernel, padding="constant", shape: str = "same", mode: str = "correlation") -> GpuTensorHandle:
         """lib.rs:1809-1817 (`ImfilterOptions`, :1193-1222); padding: a number (constant fill) | "replicate" | "symmetric" | "circular" ("constant": 0)."""
         pads = {"constant": (0, 0.0), "replicate": (1, 0.0), "symmetric": (2, 0.0), "circular": (3, 0.0)}

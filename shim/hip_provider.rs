@@ -1011,9 +1011,13 @@ impl AccelProvider for HipProvider {
         Box::pin(async move {
             let (mut out, mut fin) = (0u64, 0u64);
             let zi = match &options.zi { Some(h) => self.own(h)?, None => 0 };
-            check(unsafe {
-                rmhip_iir_filter(self.ctx, self.own(b)?, self.own(a)?, self.own(x)?, options.dim as c_int, zi, options.unit_denominator as c_int, &mut out, &mut fin)
-            })?;
+            let (hb, ha, hx) = (self.own(b)?, self.own(a)?, self.own(x)?);
+            let mut rc = unsafe { rmhip_iir_filter(self.ctx, hb, ha, hx, options.dim as c_int, zi, options.unit_denominator as c_int, &mut out, &mut fin) };
+            if rc == RMHIP_ERR_UNSUPPORTED {
+                // long signals with few channels: the nested FIR sum / the chunked scan; its own declines go back to the caller as Err
+                rc = unsafe { rmhip_iir_filter_long(self.ctx, hb, ha, hx, options.dim as c_int, zi, options.unit_denominator as c_int, &mut out, &mut fin) };
+            }
+            check(rc)?;
             Ok(ProviderIirFilterResult { output: self.handle(out)?, final_state: Some(self.handle(fin)?) })
         })
     }
