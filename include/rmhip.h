@@ -460,7 +460,8 @@ RMHIP_API int rmhip_pow2_scale(rmhip_ctx* ctx, rmhip_buf mantissa, rmhip_buf exp
 RMHIP_API int rmhip_round_digits(rmhip_ctx* ctx, rmhip_buf a, int digits, int significant, rmhip_buf* out);
 /* `unary_real / unary_imag / unary_conj / unary_angle` on REAL storage (lib.rs:2217-2240; simple_provider.rs:5482-5640): part 0 real = the
  * operand, 1 imag = zeros, 2 conj = the operand, 3 angle = atan2(+0, x): +0 for x > 0 and +0, pi for x < 0 and -0, NaN for NaN.
- * `logical_isreal` (lib.rs:2055; simple_provider.rs:4786): always 1 here - this library has no complex-interleaved storage. */
+ * A complex-interleaved operand is refused here; `rmhip_complex_unary` (RMHIP_CREAL / CIMAG / CCONJ / CANGLE) serves it.
+ * `logical_isreal` (lib.rs:2055; simple_provider.rs:4786): 1 for real storage, 0 for a complex-interleaved tensor. */
 /* @serves unary_real unary_imag unary_conj unary_angle */
 RMHIP_API int rmhip_real_part(rmhip_ctx* ctx, int part, rmhip_buf a, rmhip_buf* out);
 /* @serves logical_isreal */
@@ -604,9 +605,11 @@ RMHIP_API int rmhip_window(rmhip_ctx* ctx, int kind, size_t len, int periodic, r
 /* ---- discrete Fourier transforms and complex-interleaved storage (fft.hip) --------------------------------------------------------
  * A transform's result is a COMPLEX-INTERLEAVED tensor (`GpuTensorStorage::ComplexInterleaved`, lib.rs:247-251): its shape is the
  * logical one, its storage 2 * numel doubles (re, im, re, im, ...).  `rmhip_download` hands such a tensor back as 2 * numel doubles
- * (what `HostTensorOwned { data, shape, storage }` carries, lib.rs:3362-3366); `rmhip_storage` tells which kind an id is.  Only the
- * entry points of this section accept complex tensors; every other one returns RMHIP_ERR_UNSUPPORTED for them (the caller gathers,
- * as for any `Err`).  A precision-32 context rounds the values of a complex result through f32 (storage stays 2 x f64). */
+ * (what `HostTensorOwned { data, shape, storage }` carries, lib.rs:3362-3366); `rmhip_storage` tells which kind an id is.  Complex
+ * tensors are accepted by the entry points of this section - the transforms, `rmhip_spectral_estimate`, `rmhip_complex_real` and the
+ * elementwise arithmetic `rmhip_complex_unary` / `rmhip_complex_binary` / `rmhip_complex_scalar` - and by the plumbing (download, shape,
+ * storage, isreal, free); every other entry point returns RMHIP_ERR_UNSUPPORTED for them (the caller gathers, as for any `Err`):
+ * fused elementwise, reductions, transpose, matmul, round_digits, pow and the comparisons among them.  A precision-32 context rounds the values of a complex result through f32 (storage stays 2 x f64). */
 /* @serves - */
 RMHIP_API int rmhip_storage(rmhip_ctx* ctx, rmhip_buf id, int* complex_interleaved);
 /* `fft_dim(handle, len, dim)` / `ifft_dim` (lib.rs:2622-2638; semantics of the wgpu provider's host form, ops/fft/fallback.rs:4-150):
@@ -701,6 +704,47 @@ RMHIP_API int rmhip_zeros_complex(rmhip_ctx* ctx, const size_t* shape, size_t ra
  * same shape (a real input is copied: the caller frees the handle it passed). */
 /* @serves fft_extract_real */
 RMHIP_API int rmhip_complex_real(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf* out);
+
+/* ---- elementwise arithmetic on complex operands (complex_ew.hip): the second entry points of hooks `rmhip_unary`, `rmhip_binary`,
+ * `rmhip_scalar` and `rmhip_real_part` serve for real operands.  Those four keep refusing complex storage; a caller chooses by the
+ * operand's storage kind (`rmhip_storage`), as the wgpu provider's `unary_*_exec` / `elem_*` do with `handle_storage`
+ * (backend/wgpu/provider/ops/elementwise.rs:163-330, 948-1000, 1106-1420).  The CPU builtins are the semantics - every part a chain of
+ * separately rounded f64 operations (sources under crates/runmat-runtime/src/builtins/math/):
+ *   add  (ar+br, ai+bi)               z + s: (ar+s, ai)          s + z: (s+br, bi)            elementwise/plus.rs:696-751
+ *   sub  (ar-br, ai-bi)               z - s: (ar-s, ai)          s - z: (s-br, -bi)           minus.rs:724-779 (a negation: +0 -> -0)
+ *   mul  (ar*br - ai*bi, ar*bi + ai*br)      z * s: (ar*s, ai*s)        s * z: (s*br, s*bi)          times.rs:702-784
+ *   div  d = br*br + bi*bi; ((ar*br + ai*bi)/d, (ai*br - ar*bi)/d); a real operand enters as (s, 0.0) with every term kept
+ *        (num-complex Div, rdivide.rs:633-690); division by zero is what the formula yields
+ *   abs hypot(re, im) (abs.rs:181; an infinite part beside a NaN part gives inf) | angle atan2(im, re) (angle.rs:192) | real re | imag im
+ *   conj (re, -im) | sign: sign.rs:248-278 branch for branch (zero, NaN, infinite parts, then scale by max(|re|, |im|), norm, divide)
+ *   sin (sin re cosh im, cos re sinh im) | cos (cos re cosh im, (-sin re) sinh im) | sinh (sinh re cos im, cosh re sin im)
+ *   cosh (cosh re cos im, sinh re sin im)                                          trigonometry/sin.rs, cos.rs, sinh.rs, cosh.rs
+ *   tan  ic = 1/cosh(2 im); d = 1 + cos(2 re)*ic; (sin(2 re)*ic/d, tanh(2 im)/d)   tan.rs:283-291
+ *   sinc the real rule and a zero imaginary part when im == 0, otherwise sin(pi z) / (pi z) as the quotient above with the denominator
+ *        fma(pi re, pi re, (pi im)*(pi im))                                        signal/sinc.rs:301-327
+ * Bit-exact: add, sub, mul, div, every scalar form, real, imag, conj, sign (only + - * / sqrt, comparisons, negation).  The others call
+ * the device library's sin / cos / sinh / cosh / tanh / hypot / atan2, the functions the real hooks use: tests/test_gpu_complex_ew.py
+ * states the first-order bound per op.
+ * Precision-32 context: complex results follow this header's rule (2 x f64 storage, each part rounded through f32 once on store); real
+ * results (abs, angle, real, imag) are f32 buffers rounded once; f32 real operands are widened.
+ * Errors, for all three: RMHIP_ERR_NOT_FOUND an unknown id; RMHIP_ERR_UNSUPPORTED any other op (pow, max, min, hypot, atan2,
+ * comparisons, scalar max / min: the wgpu provider refuses them the same way), only real operands (the real entry points serve
+ * those), more than 8 dimensions after collapsing; RMHIP_ERR_SHAPE non-conforming extents.  A zero-extent result is an empty tensor of
+ * the right storage kind.  Nothing is allocated or left behind on an error path; no host synchronisation. */
+enum rmhip_complex_unary_op { RMHIP_CABS = 0, RMHIP_CANGLE, RMHIP_CREAL, RMHIP_CIMAG,      /* real results    */
+                              RMHIP_CCONJ, RMHIP_CSIGN, RMHIP_CSIN, RMHIP_CCOS, RMHIP_CTAN,
+                              RMHIP_CSINH, RMHIP_CCOSH, RMHIP_CSINC,                        /* complex results */
+                              RMHIP_COMPLEX_UNARY_OP_COUNT };
+/* `a` complex-interleaved; the result has its shape. */
+/* @serves unary_abs unary_angle unary_real unary_imag unary_conj unary_sign unary_sin unary_cos unary_tan unary_sinh unary_cosh unary_sinc */
+RMHIP_API int rmhip_complex_unary(rmhip_ctx* ctx, int op, rmhip_buf a, rmhip_buf* out);
+/* `op`: RMHIP_ADD .. RMHIP_DIV.  At least one operand complex-interleaved, the other may be a real tensor (a lazy view of it is
+ * materialised first); operands broadcast under MATLAB implicit expansion as in `rmhip_binary`; the result is complex. */
+/* @serves elem_add elem_sub elem_mul elem_div */
+RMHIP_API int rmhip_complex_binary(rmhip_ctx* ctx, int op, rmhip_buf a, rmhip_buf b, rmhip_buf* out);
+/* `op`: RMHIP_SADD .. RMHIP_SRDIV, the real scalar `s` in the kernel's arguments; `a` complex-interleaved; the result is complex. */
+/* @serves scalar_add scalar_sub scalar_mul scalar_div scalar_rsub scalar_rdiv */
+RMHIP_API int rmhip_complex_scalar(rmhip_ctx* ctx, int op, rmhip_buf a, double s, rmhip_buf* out);
 
 /* ---- modulation: symbols and bits to constellation points (comms_ops.hip) -------------------------------------------------------------
  * The two hooks `qammod` and `pskmod` call on a resident tensor (builtins/comms/qammod.rs:71-119, pskmod.rs:73-121).  Request structs:

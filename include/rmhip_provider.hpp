@@ -400,6 +400,23 @@ public:
         check(rmhip_scalar(ctx_, op, own(a), s, &out));
         return make(out, a.shape);
     }
+    // Complex operands of the same hooks (rmhip.h, "elementwise arithmetic on complex operands"): binary(), unary() and scalar() above keep
+    // refusing complex storage; a caller picks the entry point by rmhip_storage.
+    GpuTensorHandle complex_unary(rmhip_complex_unary_op op, const GpuTensorHandle& z) const {  // abs / angle / real / imag give real tensors
+        uint64_t out = 0;
+        check(rmhip_complex_unary(ctx_, op, own(z), &out));
+        return make(out, z.shape);
+    }
+    GpuTensorHandle complex_binary(rmhip_binary_op op, const GpuTensorHandle& a, const GpuTensorHandle& b) const {  // RMHIP_ADD .. RMHIP_DIV
+        uint64_t out = 0;
+        check(rmhip_complex_binary(ctx_, op, own(a), own(b), &out));
+        return with_shape(out);
+    }
+    GpuTensorHandle complex_scalar(rmhip_scalar_op op, const GpuTensorHandle& z, double s) const {  // RMHIP_SADD .. RMHIP_SRDIV
+        uint64_t out = 0;
+        check(rmhip_complex_scalar(ctx_, op, own(z), s, &out));
+        return make(out, z.shape);
+    }
     GpuTensorHandle scalar_add(const GpuTensorHandle& a, double s) const { return scalar(RMHIP_SADD, a, s); }
     GpuTensorHandle scalar_sub(const GpuTensorHandle& a, double s) const { return scalar(RMHIP_SSUB, a, s); }
     GpuTensorHandle scalar_mul(const GpuTensorHandle& a, double s) const { return scalar(RMHIP_SMUL, a, s); }

@@ -332,6 +332,16 @@ int launch_binary_bcast(Context* c, int op, const double* a, const double* b, do
                         size_t n, const BroadcastDesc& d);
 int launch_binary_bcast_f32(Context* c, int op, const float* a, const float* b, float* out, size_t n,
                             const BroadcastDesc& d);
+unsigned stream_grid(const Context* c, size_t nvec);  // blocks of a streaming launch: one 1024-thread block per 1024 work items, capped per CU
+// complex operands (complex_ew.hip).  `kind`: 0 complex o complex, 1 complex o real, 2 real o complex; a complex operand is interleaved
+// (re, im) f64 pairs, a real one f64.  An operand that does not stream is one element read from its pointer or, pointer null, the real `s`.
+int launch_complex_binary_same(Context* c, int op, int kind, const double* a, bool a_streams, const double* b, bool b_streams, double s, double* out,
+                               size_t n);
+// strides of `d` count elements of each operand's own kind (a complex element is one unit)
+int launch_complex_binary_bcast(Context* c, int op, int kind, const double* a, const double* b, double* out, size_t n, const BroadcastDesc& d);
+bool complex_unary_is_real(int op);  // abs, angle, real, imag
+// `out`: 2 n doubles for a complex result; n doubles, or n floats when `out_f32`, for a real one
+int launch_complex_unary(Context* c, int op, const double* a, void* out, bool out_f32, size_t n);
 
 // tensor_ops.hip: out[idx] = src[sum_d map_d(c_d) * stride[d]] with (c_0, c_1, ...) the column-major coordinates of idx in
 // `shape`; map_d(c) = (off[d] + c) % mod[d], or off[d] - c when rev[d] (flip).  One kernel family behind repmat

@@ -39,7 +39,7 @@ static constexpr int kStream = 1024;  // streaming kernels: 1024-thread blocks m
                                       // A/B on the generated kernels, scripts/tune_ew_ab.py; same skeleton here)
 static constexpr int kUnroll = 1;  // one 16-byte vector per stream per thread (interleaved A/B: unrolling never helped)
 
-static inline unsigned stream_grid(const Context* c, size_t nvec) {
+unsigned stream_grid(const Context* c, size_t nvec) {  // (declared in common.h: complex_ew.hip sizes its grids by the same rule)
     size_t want = (nvec + (size_t)kStream * kUnroll - 1) / ((size_t)kStream * kUnroll);
     size_t cap = (size_t)c->num_cus * 16;
     if (want < 1) want = 1;

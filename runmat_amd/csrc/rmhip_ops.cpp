@@ -560,6 +560,90 @@ int rmhip_binary(rmhip_ctx* ctx, int op, rmhip_buf a, rmhip_buf b, rmhip_buf* ou
     return rc;
 }
 
+// ---- complex operands of the same hooks (complex_ew.hip).  Everything that can refuse does so before the output is created. ----------
+int rmhip_complex_unary(rmhip_ctx* ctx, int op, rmhip_buf a, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "null out");
+    if (op < 0 || op >= RMHIP_COMPLEX_UNARY_OP_COUNT) return fail(RMHIP_ERR_UNSUPPORTED, "complex unary op %d not supported by provider", op);
+    Buffer ab, ob;
+    RMHIP_TRY(c->lookup(a, &ab));
+    if (!ab.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_unary: tensor %llu is real (rmhip_unary / rmhip_real_part serve it)", (unsigned long long)a);
+    const bool real_result = complex_unary_is_real(op), f32 = real_result && c->precision == 32;
+    if (!real_result) RMHIP_TRY(c->new_buffer_complex(ab.shape.data(), ab.shape.size(), out, &ob));
+    else if (f32) RMHIP_TRY(c->new_buffer_f32(ab.shape.data(), ab.shape.size(), out, &ob));
+    else RMHIP_TRY(c->new_buffer(ab.shape.data(), ab.shape.size(), out, &ob));
+    const int rc = launch_complex_unary(c, op, ab.data(), ob.data(), f32, ab.numel);
+    if (rc) rmhip_free(ctx, *out);
+    return rc;
+}
+
+int rmhip_complex_scalar(rmhip_ctx* ctx, int op, rmhip_buf a, double s, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "null out");
+    if (op < RMHIP_SADD || op > RMHIP_SRDIV) return fail(RMHIP_ERR_UNSUPPORTED, "scalar op %d is not served for complex operands", op);
+    Buffer ab, ob;
+    RMHIP_TRY(c->lookup(a, &ab));
+    if (!ab.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_scalar: tensor %llu is real (rmhip_scalar serves it)", (unsigned long long)a);
+    RMHIP_TRY(c->new_buffer_complex(ab.shape.data(), ab.shape.size(), out, &ob));
+    static const int kBinary[6] = {RMHIP_ADD, RMHIP_SUB, RMHIP_MUL, RMHIP_DIV, RMHIP_SUB, RMHIP_DIV};
+    const bool reversed = op == RMHIP_SRSUB || op == RMHIP_SRDIV;  // s - z, s ./ z: the scalar is the left operand
+    const int rc = reversed ? launch_complex_binary_same(c, kBinary[op], 2, nullptr, false, ab.data(), true, s, ob.data(), ob.numel)
+                            : launch_complex_binary_same(c, kBinary[op], 1, ab.data(), true, nullptr, false, s, ob.data(), ob.numel);
+    if (rc) rmhip_free(ctx, *out);
+    return rc;
+}
+
+int rmhip_complex_binary(rmhip_ctx* ctx, int op, rmhip_buf a, rmhip_buf b, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "null out");
+    if (op < RMHIP_ADD || op > RMHIP_DIV) return fail(RMHIP_ERR_UNSUPPORTED, "binary op %d is not served for complex operands", op);
+    Buffer ab, bb, ob;
+    RMHIP_TRY(c->lookup(a, &ab));
+    RMHIP_TRY(c->lookup(b, &bb));
+    if (!ab.cplx && !bb.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_binary: both operands are real (rmhip_binary serves them)");
+    // a real operand as plain f64: a lazy view is materialised, f32 storage widened
+    if (!ab.cplx) RMHIP_TRY(c->get(a, &ab));
+    if (!bb.cplx) RMHIP_TRY(c->get(b, &bb));
+    const int kind = ab.cplx && bb.cplx ? 0 : (ab.cplx ? 1 : 2);
+    // broadcast_shapes (broadcast.rs:8-47), as rmhip_binary
+    const size_t rank = std::max(ab.shape.size(), bb.shape.size());
+    if (rank > 16) return fail(RMHIP_ERR_UNSUPPORTED, "binary: rank too large");
+    std::vector<size_t> oshape(rank);
+    for (size_t d = 0; d < rank; ++d) {
+        const size_t ea = d < rank - ab.shape.size() ? 1 : ab.shape[d - (rank - ab.shape.size())];
+        const size_t eb = d < rank - bb.shape.size() ? 1 : bb.shape[d - (rank - bb.shape.size())];
+        if (ea == eb) oshape[d] = ea;
+        else if (ea == 1) oshape[d] = eb;
+        else if (eb == 1) oshape[d] = ea;
+        else
+            return fail(RMHIP_ERR_SHAPE, "size mismatch between inputs (dimension %zu has lengths %zu and %zu)", d + 1, ea, eb);
+    }
+    const size_t on = shape_numel(oshape.data(), rank);
+    const bool fast = (ab.numel == on || ab.numel == 1) && (bb.numel == on || bb.numel == 1);
+    BroadcastDesc d{};
+    if (!fast && on) {
+        std::vector<std::vector<uint64_t>> strides;
+        std::vector<uint64_t> os;
+        const rmhip_buf ids[2] = {a, b};
+        std::vector<Buffer> in = {ab, bb};
+        RMHIP_TRY(bcast_prepare(c, ids, &in, false, oshape.data(), rank, &os, &strides, "complex_binary"));
+        collapse(&os, &strides);
+        if (os.size() > 8) return fail(RMHIP_ERR_UNSUPPORTED, "complex_binary: broadcast rank %zu > 8 after collapsing", os.size());
+        d.rank = (int)os.size();
+        for (size_t i = 0; i < os.size(); ++i) {
+            d.out_shape[i] = os[i];
+            d.stride_a[i] = strides[0][i];
+            d.stride_b[i] = strides[1][i];
+        }
+    }
+    RMHIP_TRY(c->new_buffer_complex(oshape.data(), rank, out, &ob));
+    if (on == 0) return RMHIP_OK;
+    const int rc = fast ? launch_complex_binary_same(c, op, kind, ab.data(), ab.numel == on, bb.data(), bb.numel == on, 0.0, ob.data(), on)
+                        : launch_complex_binary_bcast(c, op, kind, ab.data(), bb.data(), ob.data(), on, d);
+    if (rc) rmhip_free(ctx, *out);
+    return rc;
+}
+
 int rmhip_reduce(rmhip_ctx* ctx, int op, rmhip_buf a, int dim, int nan_mode, rmhip_buf* out) {
     CTX_OR_FAIL(ctx);
     if (!out) return fail(RMHIP_ERR_INVALID, "null out");

@@ -30,6 +30,7 @@ BINARY_OPS = _ops("rmhip_binary_op", "RMHIP_")
 UNARY_OPS = _ops("rmhip_unary_op", "RMHIP_")
 SCALAR_OPS = _ops("rmhip_scalar_op", "RMHIP_S")
 REDUCE_OPS = _ops("rmhip_reduce_op", "RMHIP_R")
+COMPLEX_UNARY_OPS = _ops("rmhip_complex_unary_op", "RMHIP_C")  # abs, angle, real, imag | conj, sign, sin, cos, tan, sinh, cosh, sinc
 # trait method -> unary op code name (lib.rs:2077-2331, 2053-2068, 2980-2988)
 UNARY_HOOKS = {f"unary_{n}": n for n in UNARY_OPS}  # unary_sin ... (plus unary_<op> for every op code without a trait method of that name)
 UNARY_HOOKS.update({"unary_pow2": "exp2", "logical_not": "not", "logical_isnan": "isnan", "logical_isinf": "isinf",
@@ -539,6 +540,27 @@ class HipProvider:
         out = C.c_uint64()
         self._check(self._lib.rmhip_scalar(self._ctx, SCALAR_OPS[op], self._id(a), float(s), C.byref(out)))
         return self._handle(out.value, a.shape)
+
+    # Complex operands of the same hooks (complex_ew.hip).  The methods above and the unary_* / scalar_* ones keep refusing complex
+    # storage; the Rust shim dispatches on `handle_storage`, this mirror keeps the two entry points apart.  An op is a name ("mul",
+    # "rsub", "abs") or the C enum's code.
+    def complex_unary(self, op, z: GpuTensorHandle) -> GpuTensorHandle:
+        """unary_abs / angle / real / imag (real results) and unary_conj / sign / sin / cos / tan / sinh / cosh / sinc of a complex tensor."""
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_complex_unary(self._ctx, COMPLEX_UNARY_OPS[op] if isinstance(op, str) else int(op), self._id(z), C.byref(out)))
+        return self._handle(out.value)
+
+    def complex_binary(self, op, a: GpuTensorHandle, b: GpuTensorHandle) -> GpuTensorHandle:
+        """elem_add / sub / mul / div with at least one complex operand (the other may be real), broadcasting -> complex tensor."""
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_complex_binary(self._ctx, BINARY_OPS[op] if isinstance(op, str) else int(op), self._id(a), self._id(b), C.byref(out)))
+        return self._handle(out.value)
+
+    def complex_scalar(self, op, z: GpuTensorHandle, s: float) -> GpuTensorHandle:
+        """scalar_add / sub / mul / div / rsub / rdiv of a complex tensor and a real scalar -> complex tensor."""
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_complex_scalar(self._ctx, SCALAR_OPS[op] if isinstance(op, str) else int(op), self._id(z), float(s), C.byref(out)))
+        return self._handle(out.value)
 
     def elem_add(self, a, b): return self._binary("add", a, b)
     def elem_sub(self, a, b): return self._binary("sub", a, b)

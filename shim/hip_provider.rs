@@ -53,6 +53,9 @@ fn check(rc: c_int) -> Result<()> {
 
 impl HipProvider {
     fn real_part(&self, part: c_int, a: &GpuTensorHandle) -> Result<GpuTensorHandle> {
+        if Self::is_complex(a) {
+            return self.complex_unary([RMHIP_CREAL, RMHIP_CIMAG, RMHIP_CCONJ, RMHIP_CANGLE][part as usize], a);
+        }
         let mut out = 0u64;
         check(unsafe { rmhip_real_part(self.ctx, part, self.own(a)?, &mut out) })?;
         self.handle(out)
@@ -117,14 +120,48 @@ impl HipProvider {
         }
         Ok(h.buffer_id)
     }
+    // Complex operands: the named hooks choose the entry point by `handle_storage`, as the wgpu provider's `unary_*_exec` / `elem_*` do
+    // (ops/elementwise.rs:163-330, 1106-1420).  An op the complex entry points do not serve goes to the real one, which refuses the operand.
+    fn is_complex(h: &GpuTensorHandle) -> bool {
+        matches!(runmat_accelerate_api::handle_storage(h), GpuTensorStorage::ComplexInterleaved)
+    }
+    fn complex_unary(&self, op: c_int, a: &GpuTensorHandle) -> Result<GpuTensorHandle> {
+        let mut out = 0u64;
+        check(unsafe { rmhip_complex_unary(self.ctx, op, self.own(a)?, &mut out) })?;
+        // abs, angle, real, imag give real tensors
+        if op == RMHIP_CABS || op == RMHIP_CANGLE || op == RMHIP_CREAL || op == RMHIP_CIMAG { self.handle(out) } else { self.complex_handle(out) }
+    }
     fn unary(&self, op: c_int, a: &GpuTensorHandle) -> Result<GpuTensorHandle> {
+        if Self::is_complex(a) {
+            let complex_op = match op {
+                RMHIP_ABS => Some(RMHIP_CABS), RMHIP_SIGN => Some(RMHIP_CSIGN), RMHIP_SIN => Some(RMHIP_CSIN), RMHIP_COS => Some(RMHIP_CCOS),
+                RMHIP_TAN => Some(RMHIP_CTAN), RMHIP_SINH => Some(RMHIP_CSINH), RMHIP_COSH => Some(RMHIP_CCOSH), RMHIP_SINC => Some(RMHIP_CSINC),
+                _ => None,
+            };
+            if let Some(cop) = complex_op {
+                return self.complex_unary(cop, a);
+            }
+        }
         let mut out = 0u64;
         check(unsafe { rmhip_unary(self.ctx, op, self.own(a)?, &mut out) })?;
         self.handle(out)
     }
     fn binary(&self, op: c_int, a: &GpuTensorHandle, b: &GpuTensorHandle) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
+        if (Self::is_complex(a) || Self::is_complex(b)) && (RMHIP_ADD..=RMHIP_DIV).contains(&op) {
+            check(unsafe { rmhip_complex_binary(self.ctx, op, self.own(a)?, self.own(b)?, &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_binary(self.ctx, op, self.own(a)?, self.own(b)?, &mut out) })?;
+        self.handle(out)
+    }
+    fn scalar(&self, op: c_int, a: &GpuTensorHandle, scalar: f64) -> Result<GpuTensorHandle> {
+        let mut out = 0u64;
+        if Self::is_complex(a) && (RMHIP_SADD..=RMHIP_SRDIV).contains(&op) {
+            check(unsafe { rmhip_complex_scalar(self.ctx, op, self.own(a)?, scalar, &mut out) })?;
+            return self.complex_handle(out);
+        }
+        check(unsafe { rmhip_scalar(self.ctx, op, self.own(a)?, scalar, &mut out) })?;
         self.handle(out)
     }
 }
@@ -150,11 +187,7 @@ macro_rules! logical_hooks { ($($name:ident => $op:expr),* $(,)?) => { $(
     fn $name(&self, a: &GpuTensorHandle, b: &GpuTensorHandle) -> Result<GpuTensorHandle> { self.binary($op, a, b) }
 )* } }
 macro_rules! scalar_hooks { ($($name:ident => $op:expr),* $(,)?) => { $(
-    fn $name(&self, a: &GpuTensorHandle, scalar: f64) -> Result<GpuTensorHandle> {
-        let mut out = 0u64;
-        check(unsafe { rmhip_scalar(self.ctx, $op, self.own(a)?, scalar, &mut out) })?;
-        self.handle(out)
-    }
+    fn $name(&self, a: &GpuTensorHandle, scalar: f64) -> Result<GpuTensorHandle> { self.scalar($op, a, scalar) }
 )* } }
 macro_rules! reduce_all_hooks { ($($name:ident => $op:expr),* $(,)?) => { $(
     fn $name<'a>(&'a self, a: &'a GpuTensorHandle) -> AccelProviderFuture<'a, GpuTensorHandle> {
