@@ -11,6 +11,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from fft_ref import bound   # the tolerance stated above, shared with test_gpu_fft_paths.py
+
 pytestmark = pytest.mark.gpu
 
 K = json.loads((Path(__file__).parent / "golden" / "fft_kats.json").read_text())
@@ -26,16 +28,6 @@ def upload_any(prov, x):
     if np.iscomplexobj(x):
         return prov.complex_from_real_imag(up(x.real), up(x.imag))
     return up(x)
-
-
-def bound(x, n, dim, inverse):
-    """Per-line error bound, broadcastable against the result."""
-    xs = x.reshape(x.shape + (1,) * max(0, dim + 1 - x.ndim))
-    pow2 = n & (n - 1) == 0
-    work = n if pow2 else 1 << math.ceil(math.log2(2 * n - 1))
-    c = 4.0 if pow2 else 8.0
-    norm = np.sqrt(np.sum(np.abs(np.take(xs, range(min(n, xs.shape[dim])), axis=dim)) ** 2, axis=dim, keepdims=True))
-    return c * EPS * max(1.0, math.log2(work)) * norm / (n if inverse else 1) + 1e-300
 
 
 def check(prov, x, length, dim, inverse, want):
