@@ -606,10 +606,14 @@ RMHIP_API int rmhip_window(rmhip_ctx* ctx, int kind, size_t len, int periodic, r
  * A transform's result is a COMPLEX-INTERLEAVED tensor (`GpuTensorStorage::ComplexInterleaved`, lib.rs:247-251): its shape is the
  * logical one, its storage 2 * numel doubles (re, im, re, im, ...).  `rmhip_download` hands such a tensor back as 2 * numel doubles
  * (what `HostTensorOwned { data, shape, storage }` carries, lib.rs:3362-3366); `rmhip_storage` tells which kind an id is.  Complex
- * tensors are accepted by the entry points of this section - the transforms, `rmhip_spectral_estimate`, `rmhip_complex_real` and the
- * elementwise arithmetic `rmhip_complex_unary` / `rmhip_complex_binary` / `rmhip_complex_scalar` - and by the plumbing (download, shape,
- * storage, isreal, free); every other entry point returns RMHIP_ERR_UNSUPPORTED for them (the caller gathers, as for any `Err`):
- * fused elementwise, reductions, transpose, matmul, round_digits, pow and the comparisons among them.  A precision-32 context rounds the values of a complex result through f32 (storage stays 2 x f64). */
+ * tensors are accepted by the entry points of this section - the transforms, `rmhip_spectral_estimate`, `rmhip_complex_real`, the
+ * elementwise arithmetic `rmhip_complex_unary` / `rmhip_complex_binary` / `rmhip_complex_scalar` and the shape and indexing hooks
+ * `rmhip_complex_reshape` / `_transpose` / `_permute` / `_repmat` / `_gather_linear` / `_scatter_linear` / `_circshift` / `_flip` /
+ * `_cat` - and by the plumbing (download, shape, storage, isreal, free).  Every other entry point returns RMHIP_ERR_UNSUPPORTED for
+ * them (the caller gathers, as for any `Err`): fused elementwise, reductions, matmul, round_digits, pow, the comparisons, tril / triu
+ * and read_scalar among them, and so do the real forms of the hooks just named (`rmhip_transpose`, `rmhip_permute`, ...): a caller
+ * chooses the entry point by the operand's storage kind.  A precision-32 context rounds the values a complex result COMPUTES through
+ * f32 (storage stays 2 x f64); the shape and indexing hooks move bits and round nothing. */
 /* @serves - */
 RMHIP_API int rmhip_storage(rmhip_ctx* ctx, rmhip_buf id, int* complex_interleaved);
 /* `fft_dim(handle, len, dim)` / `ifft_dim` (lib.rs:2622-2638; semantics of the wgpu provider's host form, ops/fft/fallback.rs:4-150):
@@ -745,6 +749,45 @@ RMHIP_API int rmhip_complex_binary(rmhip_ctx* ctx, int op, rmhip_buf a, rmhip_bu
 /* `op`: RMHIP_SADD .. RMHIP_SRDIV, the real scalar `s` in the kernel's arguments; `a` complex-interleaved; the result is complex. */
 /* @serves scalar_add scalar_sub scalar_mul scalar_div scalar_rsub scalar_rdiv */
 RMHIP_API int rmhip_complex_scalar(rmhip_ctx* ctx, int op, rmhip_buf a, double s, rmhip_buf* out);
+
+/* ---- shape and indexing hooks on complex operands (tensor_ops.hip, move_kernels.h): the second entry points of `rmhip_reshape`,
+ * `rmhip_transpose`, `rmhip_permute`, `rmhip_repmat`, `rmhip_gather_linear`, `rmhip_scatter_linear`, `rmhip_circshift`, `rmhip_flip`
+ * and `rmhip_cat`, which keep refusing complex storage.  The reference serves complex storage in these places in both providers
+ * (wgpu: ops/tensor.rs reshape_exec / repmat_exec / transpose_exec / permute_exec, ops/indexing.rs gather_linear_exec /
+ * scatter_linear_exec; simple_provider.rs transpose, permute, repmat, gather_linear, scatter_linear), and fftshift / ifftshift /
+ * circshift / flip / cat hand whatever handle they hold to the provider.  Each entry point has its sibling's signature, shape rules,
+ * argument checks, messages and error codes - one host function serves both.  An element is one logical (re, im) pair of 16 bytes;
+ * indices, extents and shifts count logical elements (the reference's lane_factor 2).  Every result is complex-interleaved, a
+ * zero-extent one included, and a bit-for-bit copy in either precision mode.  What differs from the siblings:
+ *   - a real operand is RMHIP_ERR_UNSUPPORTED, the message naming the sibling that serves it; for `cat` every input must be complex
+ *     (a mixed list: the caller gathers);
+ *   - `scatter_linear`: target and values both complex, else RMHIP_ERR_UNSUPPORTED "scatter_linear: storage mismatch target=...
+ *     values=..." with Real / ComplexInterleaved (indexing.rs:781-786); a count mismatch reports the raw length 2 * numel and
+ *     "lane factor 2";
+ *   - `transpose` and `repmat` return materialised tensors (the lazy views are read in place by real kernels only); `transpose` is
+ *     `permute` with order [1, 0] and takes what `rmhip_transpose` takes (at most two dimensions).
+ * Nothing is allocated or left behind on an error path; host synchronisation as in the siblings (gather / scatter wait for the
+ * caller's index slice to be read). */
+/* @serves reshape */
+RMHIP_API int rmhip_complex_reshape(rmhip_ctx* ctx, rmhip_buf id, const size_t* shape, size_t rank,
+                            rmhip_buf* out);
+/* @serves transpose */
+RMHIP_API int rmhip_complex_transpose(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf* out);
+/* @serves permute */
+RMHIP_API int rmhip_complex_permute(rmhip_ctx* ctx, rmhip_buf a, const size_t* order, size_t n_order, rmhip_buf* out);
+/* @serves repmat */
+RMHIP_API int rmhip_complex_repmat(rmhip_ctx* ctx, rmhip_buf a, const size_t* reps, size_t n_reps, rmhip_buf* out);
+/* @serves gather_linear */
+RMHIP_API int rmhip_complex_gather_linear(rmhip_ctx* ctx, rmhip_buf source, const uint32_t* indices, size_t n_indices,
+                                  const size_t* out_shape, size_t rank, rmhip_buf* out);
+/* @serves scatter_linear */
+RMHIP_API int rmhip_complex_scatter_linear(rmhip_ctx* ctx, rmhip_buf target, const uint32_t* indices, size_t n_indices, rmhip_buf values);
+/* @serves circshift */
+RMHIP_API int rmhip_complex_circshift(rmhip_ctx* ctx, rmhip_buf a, const long long* shifts, size_t n_shifts, rmhip_buf* out);
+/* @serves flip */
+RMHIP_API int rmhip_complex_flip(rmhip_ctx* ctx, rmhip_buf a, const size_t* axes, size_t n_axes, rmhip_buf* out);
+/* @serves cat */
+RMHIP_API int rmhip_complex_cat(rmhip_ctx* ctx, size_t dim_one_based, const rmhip_buf* inputs, size_t n_inputs, rmhip_buf* out);
 
 /* ---- modulation: symbols and bits to constellation points (comms_ops.hip) -------------------------------------------------------------
  * The two hooks `qammod` and `pskmod` call on a resident tensor (builtins/comms/qammod.rs:71-119, pskmod.rs:73-121).  Request structs:

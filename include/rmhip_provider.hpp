@@ -417,6 +417,52 @@ public:
         check(rmhip_complex_scalar(ctx_, op, own(z), s, &out));
         return make(out, z.shape);
     }
+    // the shape and indexing hooks on complex-interleaved operands: the arguments of the real methods (which keep refusing complex
+    // storage), counted in logical (re, im) elements; complex results, transpose / repmat materialised
+    GpuTensorHandle complex_reshape(const GpuTensorHandle& h, const std::vector<size_t>& shape) const {
+        uint64_t id = 0;
+        check(rmhip_complex_reshape(ctx_, own(h), shape.data(), shape.size(), &id));
+        return make(id, shape);
+    }
+    GpuTensorHandle complex_transpose(const GpuTensorHandle& a) const {
+        uint64_t id = 0;
+        check(rmhip_complex_transpose(ctx_, own(a), &id));
+        return with_shape(id);
+    }
+    GpuTensorHandle complex_permute(const GpuTensorHandle& a, const std::vector<size_t>& order_zero_based) const {
+        uint64_t id = 0;
+        check(rmhip_complex_permute(ctx_, own(a), order_zero_based.data(), order_zero_based.size(), &id));
+        return with_shape(id);
+    }
+    GpuTensorHandle complex_repmat(const GpuTensorHandle& a, const std::vector<size_t>& reps) const {
+        uint64_t id = 0;
+        check(rmhip_complex_repmat(ctx_, own(a), reps.data(), reps.size(), &id));
+        return with_shape(id);
+    }
+    GpuTensorHandle complex_gather_linear(const GpuTensorHandle& source, const std::vector<uint32_t>& indices, const std::vector<size_t>& output_shape) const {
+        uint64_t id = 0;
+        check(rmhip_complex_gather_linear(ctx_, own(source), indices.data(), indices.size(), output_shape.data(), output_shape.size(), &id));
+        return make(id, output_shape);
+    }
+    void complex_scatter_linear(const GpuTensorHandle& target, const std::vector<uint32_t>& indices, const GpuTensorHandle& values) const {
+        check(rmhip_complex_scatter_linear(ctx_, own(target), indices.data(), indices.size(), own(values)));
+    }
+    GpuTensorHandle complex_circshift(const GpuTensorHandle& a, const std::vector<long long>& shifts) const {
+        uint64_t id = 0;
+        check(rmhip_complex_circshift(ctx_, own(a), shifts.data(), shifts.size(), &id));
+        return make(id, a.shape);
+    }
+    GpuTensorHandle complex_flip(const GpuTensorHandle& a, const std::vector<size_t>& axes_zero_based) const {
+        uint64_t id = 0;
+        check(rmhip_complex_flip(ctx_, own(a), axes_zero_based.data(), axes_zero_based.size(), &id));
+        return make(id, a.shape);
+    }
+    GpuTensorHandle complex_cat(size_t dim_one_based, const std::vector<GpuTensorHandle>& inputs) const {
+        std::vector<uint64_t> ids = ids_of(inputs);
+        uint64_t id = 0;
+        check(rmhip_complex_cat(ctx_, dim_one_based, ids.data(), ids.size(), &id));
+        return with_shape(id);
+    }
     GpuTensorHandle scalar_add(const GpuTensorHandle& a, double s) const { return scalar(RMHIP_SADD, a, s); }
     GpuTensorHandle scalar_sub(const GpuTensorHandle& a, double s) const { return scalar(RMHIP_SSUB, a, s); }
     GpuTensorHandle scalar_mul(const GpuTensorHandle& a, double s) const { return scalar(RMHIP_SMUL, a, s); }

@@ -353,6 +353,7 @@ struct IndexMap {
 };
 int launch_index_copy(Context* c, const double* src, double* dst, size_t n, const IndexMap& m);
 int launch_index_copy_f32(Context* c, const float* src, float* dst, size_t n, const IndexMap& m);
+int launch_index_copy_like(Context* c, const Buffer& like, const void* src, void* dst, size_t n, const IndexMap& m);  // f64, f32 or complex (16-byte elements), as `like` is stored
 int materialize_repmat(Context* c, const Buffer& view, void* dst);  // tile a repmat view's base into dst (the view's storage type)
 
 // reductions (reduce_kernels.hip)

@@ -644,11 +644,16 @@ int rmhip_fill_uniform(rmhip_ctx* ctx, uint64_t seed, double lo, double hi, cons
     return rc;
 }
 
-int rmhip_reshape(rmhip_ctx* ctx, rmhip_buf id, const size_t* shape, size_t rank, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+// `cplx`: the call came through rmhip_complex_reshape, which takes complex-interleaved storage only (extents count logical elements)
+static int reshape_any(Context* c, bool cplx, rmhip_buf id, const size_t* shape, size_t rank, rmhip_buf* out) {
     if (!out || (rank && !shape)) return fail(RMHIP_ERR_INVALID, "reshape: null argument");
     Buffer b;
-    RMHIP_TRY(c->get_raw(id, &b));
+    if (cplx) {
+        RMHIP_TRY(c->lookup(id, &b));
+        if (!b.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_reshape: tensor %llu is real (rmhip_reshape serves it)", (unsigned long long)id);
+    } else {
+        RMHIP_TRY(c->get_raw(id, &b));
+    }
     if (shape_numel(shape, rank) != b.numel)
         return fail(RMHIP_ERR_SHAPE, "reshape: element count mismatch (%zu vs %zu)", shape_numel(shape, rank), b.numel);
     // Same buffer, new shape: the trait default (lib.rs:2676-2684) and the wgpu provider (ops/tensor.rs reshape_exec)
@@ -664,6 +669,14 @@ int rmhip_reshape(rmhip_ctx* ctx, rmhip_buf id, const size_t* shape, size_t rank
     }
     *out = id;
     return RMHIP_OK;
+}
+int rmhip_reshape(rmhip_ctx* ctx, rmhip_buf id, const size_t* shape, size_t rank, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return reshape_any(c, false, id, shape, rank, out);
+}
+int rmhip_complex_reshape(rmhip_ctx* ctx, rmhip_buf id, const size_t* shape, size_t rank, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return reshape_any(c, true, id, shape, rank, out);
 }
 
 int rmhip_wrap_external(rmhip_ctx* ctx, void* device_ptr, const size_t* shape, size_t rank, rmhip_buf* out) {

@@ -9,77 +9,32 @@
 // family (IndexMap, common.h): the output is walked contiguously - dim 0 along the threads, the outer coordinates
 // decoded once per block with scalar arithmetic - and the source index is rebuilt from per-dimension maps.  A permutation
 // that moves source dim 0 away from output dim 0 goes through a 64 x 64 LDS tile so that both sides stay coalesced.
+// The kernels are in move_kernels.h.
+//
+// Complex-interleaved operands come in through second entry points (rmhip_complex_permute, ... _cat; rmhip_complex_reshape is in
+// rmhip_core.cpp): the same host code with `cplx` set - shape rules, checks and messages are written once - and the kernels
+// instantiated for v2d, one 16-byte element per load.  The real entry points keep refusing complex storage (Context::get_raw).
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "common.h"
+#include "move_kernels.h"
 
 using namespace rmhip;
 
 namespace rmhip {
 
 namespace {
-constexpr int kBlock = 256;
+// tile of the 16-byte permutation: 32 (output dim 0) x 64 (source dim 0), 33 280 bytes of LDS (docs/EXPERIMENTS.md has the candidates)
+constexpr int kTileI16 = 32, kTileJ16 = 64;
 
-struct MapParams {
-    unsigned long long d0, nchunks;
-    int rank;
-    int id0;  // dim 0 is the identity map (off 0, mod >= extent, not reversed): no modulo per element
-    unsigned long long shape[8], stride[8], off[8], mod[8];
-    unsigned char rev[8];
-};
-
-__device__ __forceinline__ unsigned long long map_coord(const MapParams& p, int d, unsigned long long cd) {
-    if (p.rev[d]) return p.off[d] - cd;
-    unsigned long long t = p.off[d] + cd;
-    if (t >= p.mod[d]) t = (t | p.mod[d]) >> 32 ? t % p.mod[d] : (unsigned long long)((unsigned)t % (unsigned)p.mod[d]);
-    return t;
-}
-
-// One block: kBlock * E consecutive elements of dim 0 at one outer coordinate (E = 4, or less when dim 0 is short: a 512-element
-// dim 0 on the four-element form leaves half of every block idle).
-template <class T, int E>
-__global__ void __launch_bounds__(kBlock) k_index_copy(const T* __restrict__ src, T* __restrict__ dst, MapParams p) {
-    const unsigned long long blk = blockIdx.x + (unsigned long long)gridDim.x * blockIdx.y;
-    const unsigned long long chunk = blk % p.nchunks;
-    const unsigned long long outer = blk / p.nchunks;
-    unsigned long long base = 0, rem = outer;
-    for (int d = 1; d < p.rank; ++d) {
-        const unsigned long long cd = rem % p.shape[d];
-        rem /= p.shape[d];
-        base += map_coord(p, d, cd) * p.stride[d];
-    }
-    if (rem != 0) return;
-    const unsigned long long obase = outer * p.d0;
-    const unsigned long long i0 = chunk * (unsigned long long)(kBlock * E) + threadIdx.x;
-    T v[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const unsigned long long i = i0 + (unsigned long long)e * kBlock;
-        if (i < p.d0) v[e] = src[base + (p.id0 ? i : map_coord(p, 0, i)) * p.stride[0]];
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const unsigned long long i = i0 + (unsigned long long)e * kBlock;
-        if (i < p.d0) dst[obase + i] = v[e];
-    }
-}
-
-// Short dim 0 with many outer coordinates (repmat of a 1 x N row to 8 x N): flat threads over the output, 32-bit decode.
+// per-lane elements of k_index_copy by the length of dim 0.  16-byte elements stop at two: two 16-byte loads in flight per lane carry the
+// bytes of the four 8-byte ones, and four measured no better (docs/EXPERIMENTS.md)
 template <class T>
-__global__ void __launch_bounds__(kBlock) k_index_copy_flat(const T* __restrict__ src, T* __restrict__ dst, MapParams p, unsigned n) {
-    const unsigned stride = gridDim.x * kBlock;
-    for (unsigned idx = blockIdx.x * kBlock + threadIdx.x; idx < n; idx += stride) {
-        unsigned rem = idx;
-        unsigned long long s = 0;
-        for (int d = 0; d < p.rank; ++d) {
-            const unsigned sd = (unsigned)p.shape[d];
-            const unsigned q = rem / sd, cd = rem - q * sd;
-            rem = q;
-            s += map_coord(p, d, cd) * p.stride[d];
-        }
-        dst[idx] = src[s];
-    }
+int index_copy_elems(unsigned long long d0) {
+    if (sizeof(T) == 16) return d0 > (unsigned long long)kBlock ? 2 : 1;
+    return d0 > 2ull * kBlock ? 4 : (d0 > (unsigned long long)kBlock ? 2 : 1);
 }
 
 template <class T>
@@ -89,7 +44,7 @@ int index_copy(Context* c, const T* src, T* dst, size_t n, const IndexMap& m) {
     MapParams p;
     p.rank = m.rank;
     p.d0 = m.shape[0];
-    const int elems = p.d0 > 2ull * kBlock ? 4 : (p.d0 > (unsigned long long)kBlock ? 2 : 1);
+    const int elems = index_copy_elems<T>(p.d0);
     p.nchunks = (p.d0 + (unsigned long long)kBlock * elems - 1) / ((unsigned long long)kBlock * elems);
     unsigned long long outer = 1;
     for (int i = 0; i < 8; ++i) {
@@ -117,61 +72,6 @@ int index_copy(Context* c, const T* src, T* dst, size_t n, const IndexMap& m) {
     c->tel.kernel_launches++;
     RMHIP_HIP_CHECK(hipGetLastError());
     return RMHIP_OK;
-}
-
-// ---- permutation that moves source dim 0 to output dim j > 0 -----------------------------------------------------------
-// Tile = 64 (output dim 0; source stride s0) x 64 (output dim j = source dim 0, stride 1).  Loads run along the source's
-// contiguous dimension, stores along the output's; the transposition happens in LDS (row padding: no bank conflicts).
-struct PermParams {
-    int rank, j;
-    unsigned long long shape[8];    // output extents
-    unsigned long long sstride[8];  // source stride of every output dim (sstride[j] == 1)
-    unsigned long long ostride[8];  // output strides
-    unsigned long long t0, tj;      // tiles along dim 0 / dim j
-};
-template <class T>
-__global__ void __launch_bounds__(256) k_permute_tiled(const T* __restrict__ src, T* __restrict__ dst, PermParams p) {
-    __shared__ T tile[64][65];
-    unsigned long long blk = blockIdx.x + (unsigned long long)gridDim.x * blockIdx.y;
-    // consecutive workgroups advance along the SOURCE's contiguous dimension (output dim j): their loads continue each other's 512-byte
-    // row pieces (the other order - along the output's contiguous dimension - measured 275 us against 225 for 8192^2)
-    const unsigned long long bj = blk % p.tj;
-    blk /= p.tj;
-    const unsigned long long b0 = blk % p.t0;
-    unsigned long long rem = blk / p.t0;
-    unsigned long long sbase = 0, obase = 0;
-    for (int d = 1; d < p.rank; ++d) {
-        if (d == p.j) continue;
-        const unsigned long long cd = rem % p.shape[d];
-        rem /= p.shape[d];
-        sbase += cd * p.sstride[d];
-        obase += cd * p.ostride[d];
-    }
-    if (rem != 0) return;
-    const unsigned long long i0 = b0 * 64, j0 = bj * 64;  // tile origin: output dim 0, output dim j
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // 64 x 4
-    // load: tx runs along source dim 0 (= output dim j).  All 16 loads are issued before the first one is used (indices clamped into
-    // the tensor instead of a branch per load - a guarded loop waits for every load before it issues the next: 268 us against 225 for
-    // 8192^2), the stores are guarded.
-    const unsigned long long jj = j0 + tx;
-    const unsigned long long jc = jj < p.shape[p.j] ? jj : p.shape[p.j] - 1;
-    T v[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const unsigned long long ii = i0 + ty + 4 * q;
-        const unsigned long long ic = ii < p.shape[0] ? ii : p.shape[0] - 1;
-        v[q] = src[sbase + jc + ic * p.sstride[0]];
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) tile[ty + 4 * q][tx] = v[q];
-    __syncthreads();
-    // store: tx runs along output dim 0
-    const unsigned long long io = i0 + tx;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const unsigned long long jo = j0 + ty + 4 * q;
-        if (io < p.shape[0] && jo < p.shape[p.j]) dst[obase + io + jo * p.ostride[p.j]] = tile[tx][ty + 4 * q];
-    }
 }
 
 template <class T>
@@ -270,6 +170,11 @@ unsigned flat_grid(const Context* c, size_t n) {
 
 int launch_index_copy(Context* c, const double* src, double* dst, size_t n, const IndexMap& m) { return index_copy(c, src, dst, n, m); }
 int launch_index_copy_f32(Context* c, const float* src, float* dst, size_t n, const IndexMap& m) { return index_copy(c, src, dst, n, m); }
+// the copy in the storage kind of `like` (n counts logical elements: a complex one is 16 bytes)
+int launch_index_copy_like(Context* c, const Buffer& like, const void* src, void* dst, size_t n, const IndexMap& m) {
+    if (like.cplx) return index_copy(c, (const v2d*)src, (v2d*)dst, n, m);
+    return like.dtype == DT_F32 ? launch_index_copy_f32(c, (const float*)src, (float*)dst, n, m) : launch_index_copy(c, (const double*)src, (double*)dst, n, m);
+}
 
 int materialize_repmat(Context* c, const Buffer& v, void* dst) {
     // collapse runs of dimensions the view does not tile (rep == 1 ... rep == 1) into one: rank 8 covers 4 tiled N-d axes and more
@@ -307,8 +212,7 @@ int materialize_repmat(Context* c, const Buffer& v, void* dst) {
         m.off[d] = 0;
         m.rev[d] = 0;
     }
-    return v.dtype == DT_F32 ? launch_index_copy_f32(c, v.data_f32(), (float*)dst, v.numel, m)
-                             : launch_index_copy(c, v.data(), (double*)dst, v.numel, m);
+    return launch_index_copy_like(c, v, v.data(), dst, v.numel, m);
 }
 
 }  // namespace rmhip
@@ -325,9 +229,28 @@ int get_settled(Context* c, rmhip_buf id, Buffer* out) {
     return RMHIP_OK;
 }
 
-// a new buffer of the operand's storage type (f32 results of a precision-32 context are not narrowed again)
+// The operand of an entry point that moves elements.  `cplx`: the call came through the rmhip_complex_* form of hook `op`, which takes
+// complex-interleaved storage only - the record as it is, which is all Context::get_any does for one: complex tensors have no views
+// and no f32 storage - and refuses a real tensor before anything is created; the real form refuses complex storage in get_raw.
+int fetch(Context* c, rmhip_buf id, bool cplx, const char* op, Buffer* out) {
+    if (!cplx) return get_settled(c, id, out);
+    RMHIP_TRY(c->lookup(id, out));
+    if (!out->cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_%s: tensor %llu is real (rmhip_%s serves it)", op, (unsigned long long)id, op);
+    return RMHIP_OK;
+}
+
+// a new buffer of the operand's storage type (f32 results of a precision-32 context are not narrowed again; complex results are 2 x f64)
 int new_like(Context* c, const Buffer& like, const size_t* shape, size_t rank, rmhip_buf* id, Buffer* out) {
+    if (like.cplx) return c->new_buffer_complex(shape, rank, id, out);
     return like.dtype == DT_F32 ? c->new_buffer_f32(shape, rank, id, out) : c->new_buffer(shape, rank, id, out);
+}
+
+// f(T*) with T the operand's element type: float, double, or v2d for one complex-interleaved element
+template <class F>
+void by_elem(const Buffer& b, F&& f) {
+    if (b.cplx) f((v2d*)nullptr);
+    else if (b.dtype == DT_F32) f((float*)nullptr);
+    else f((double*)nullptr);
 }
 
 // device copy of host u32 indices; the caller keeps `hold` alive until the kernel is enqueued (stream ordered pool)
@@ -342,12 +265,13 @@ int upload_indices(Context* c, const uint32_t* idx, size_t n, std::shared_ptr<Al
 
 extern "C" {
 
-int rmhip_repmat(rmhip_ctx* ctx, rmhip_buf a, const size_t* reps, size_t n_reps, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+// repmat, both storage kinds.  A real operand gives a lazy view; a complex one is tiled at once (views are read in place only by real kernels).
+static int repmat_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf a, const size_t* reps, size_t n_reps, rmhip_buf* out) {
     if (!out || !reps) return fail(RMHIP_ERR_INVALID, "repmat: null argument");
     if (n_reps == 0) return fail(RMHIP_ERR_INVALID, "repmat: replication factors must be specified");  // simple_provider.rs:2175-2178
     Buffer ab;
-    RMHIP_TRY(c->get_raw(a, &ab));
+    if (cplx) RMHIP_TRY(fetch(c, a, true, "repmat", &ab));
+    else RMHIP_TRY(c->get_raw(a, &ab));
     if (ab.tview) {  // a view of a transpose view: the base first, in its own storage type
         RMHIP_TRY(c->settle_view(a));
         RMHIP_TRY(c->get_raw(a, &ab));
@@ -371,6 +295,16 @@ int rmhip_repmat(rmhip_ctx* ctx, rmhip_buf a, const size_t* reps, size_t n_reps,
         Buffer ob;
         return new_like(c, ab, shape.data(), rank, out, &ob);
     }
+    if (cplx) {
+        Buffer ob, view = ab;  // the view the real form would register, tiled into the output instead
+        view.shape = shape;
+        view.numel = total;
+        view.rep_base = base;
+        RMHIP_TRY(new_like(c, ab, shape.data(), rank, out, &ob));
+        const int rc = materialize_repmat(c, view, ob.data());
+        if (rc) rmhip_free(ctx, *out);
+        return rc;
+    }
     Buffer r;
     r.alloc = ab.alloc;
     r.shape = shape;
@@ -392,13 +326,20 @@ int rmhip_repmat(rmhip_ctx* ctx, rmhip_buf a, const size_t* reps, size_t n_reps,
         if (e[0] == '1') RMHIP_TRY(c->settle_view(*out));
     return RMHIP_OK;
 }
-
-int rmhip_permute(rmhip_ctx* ctx, rmhip_buf a, const size_t* order, size_t n_order, rmhip_buf* out) {
+int rmhip_repmat(rmhip_ctx* ctx, rmhip_buf a, const size_t* reps, size_t n_reps, rmhip_buf* out) {
     CTX_OR_FAIL(ctx);
+    return repmat_any(ctx, c, false, a, reps, n_reps, out);
+}
+int rmhip_complex_repmat(rmhip_ctx* ctx, rmhip_buf a, const size_t* reps, size_t n_reps, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return repmat_any(ctx, c, true, a, reps, n_reps, out);
+}
+
+static int permute_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf a, const size_t* order, size_t n_order, rmhip_buf* out) {
     if (!out || (n_order && !order)) return fail(RMHIP_ERR_INVALID, "permute: null argument");
     if (n_order == 0) return fail(RMHIP_ERR_INVALID, "permute: order must not be empty");  // simple_provider.rs:1651
     Buffer ab, ob;
-    RMHIP_TRY(get_settled(c, a, &ab));
+    RMHIP_TRY(fetch(c, a, cplx, "permute", &ab));
     const size_t rank = n_order;
     if (ab.shape.size() > rank) return fail(RMHIP_ERR_INVALID, "permute: order length must be at least the number of dimensions");
     std::vector<char> seen(rank, 0);
@@ -456,15 +397,17 @@ int rmhip_permute(rmhip_ctx* ctx, rmhip_buf a, const size_t* order, size_t n_ord
             if (on) os *= shape[d];
             if (on && d != 0 && d != j) others *= shape[d];
         }
-        p.t0 = (shape[0] + 63) / 64;
-        p.tj = (shape[j] + 63) / 64;
+        const uint64_t ti = ab.cplx ? kTileI16 : 64, tj = ab.cplx ? kTileJ16 : 64;
+        p.t0 = (shape[0] + ti - 1) / ti;
+        p.tj = (shape[j] + tj - 1) / tj;
         const unsigned long long blocks = p.t0 * p.tj * others;
         const unsigned long long gx = std::min<unsigned long long>(blocks, 1048576ULL), gy = (blocks + gx - 1) / gx;
         if (gy > 65535ULL) {
             rmhip_free(ctx, *out);
             return fail(RMHIP_ERR_UNSUPPORTED, "permute: grid too large");
         }
-        if (ab.dtype == DT_F32) hipLaunchKernelGGL((k_permute_tiled<float>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, c->stream, ab.data_f32(), ob.data_f32(), p);
+        if (ab.cplx) hipLaunchKernelGGL((k_permute_tiled16<kTileI16, kTileJ16>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, c->stream, (const v2d*)ab.data(), (v2d*)ob.data(), p);
+        else if (ab.dtype == DT_F32) hipLaunchKernelGGL((k_permute_tiled<float>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, c->stream, ab.data_f32(), ob.data_f32(), p);
         else hipLaunchKernelGGL((k_permute_tiled<double>), dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, c->stream, ab.data(), ob.data(), p);
         c->tel.kernel_launches++;
         hipError_t e = hipGetLastError();
@@ -479,11 +422,29 @@ int rmhip_permute(rmhip_ctx* ctx, rmhip_buf a, const size_t* order, size_t n_ord
             m.mod[d] = shape[d];
             m.rev[d] = 0;
         }
-        rc = ab.dtype == DT_F32 ? launch_index_copy_f32(c, ab.data_f32(), ob.data_f32(), ab.numel, m)
-                                : launch_index_copy(c, ab.data(), ob.data(), ab.numel, m);
+        rc = launch_index_copy_like(c, ab, ab.data(), ob.data(), ab.numel, m);
     }
     if (rc) rmhip_free(ctx, *out);
     return rc;
+}
+int rmhip_permute(rmhip_ctx* ctx, rmhip_buf a, const size_t* order, size_t n_order, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return permute_any(ctx, c, false, a, order, n_order, out);
+}
+int rmhip_complex_permute(rmhip_ctx* ctx, rmhip_buf a, const size_t* order, size_t n_order, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return permute_any(ctx, c, true, a, order, n_order, out);
+}
+// `transpose` of a complex matrix: the materialised permutation [1, 0] (a lazy transpose view is read in place only by real kernels);
+// takes what rmhip_transpose takes
+int rmhip_complex_transpose(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "null out");
+    Buffer ab;
+    RMHIP_TRY(fetch(c, a, true, "transpose", &ab));
+    if (ab.shape.size() > 2) return fail(RMHIP_ERR_UNSUPPORTED, "transpose: only 2D supported");
+    const size_t order[2] = {1, 0};
+    return permute_any(ctx, c, true, a, order, 2, out);
 }
 
 int rmhip_fill_like(rmhip_ctx* ctx, rmhip_buf prototype, double value, rmhip_buf* out) {
@@ -529,14 +490,13 @@ int rmhip_read_scalar(rmhip_ctx* ctx, rmhip_buf a, size_t linear_index, double* 
     return RMHIP_OK;
 }
 
-int rmhip_gather_linear(rmhip_ctx* ctx, rmhip_buf source, const uint32_t* indices, size_t n_indices, const size_t* out_shape, size_t rank,
-                        rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+static int gather_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf source, const uint32_t* indices, size_t n_indices, const size_t* out_shape,
+                      size_t rank, rmhip_buf* out) {
     if (!out || (n_indices && !indices) || (rank && !out_shape)) return fail(RMHIP_ERR_INVALID, "gather_linear: null argument");
     if (shape_numel(out_shape, rank) != n_indices)
         return fail(RMHIP_ERR_SHAPE, "gather_linear: output shape holds %zu elements, %zu indices given", shape_numel(out_shape, rank), n_indices);
     Buffer sb, ob;
-    RMHIP_TRY(get_settled(c, source, &sb));
+    RMHIP_TRY(fetch(c, source, cplx, "gather_linear", &sb));
     static const size_t device_min = std::getenv("RMHIP_SCATTER_DEVICE_MIN") ? (size_t)std::atol(std::getenv("RMHIP_SCATTER_DEVICE_MIN")) : 4096;
     const bool on_device = device_min && n_indices >= device_min;  // the bounds check inside the gather kernel instead of a host loop
     if (!on_device)
@@ -554,8 +514,10 @@ int rmhip_gather_linear(rmhip_ctx* ctx, rmhip_buf source, const uint32_t* indice
         unsigned long long first_bad = ~0ULL;
         hipError_t e = hipMemsetAsync(bad, 0xff, sizeof(unsigned long long), c->stream);
         if (e == hipSuccess) {
-            if (sb.dtype == DT_F32) hipLaunchKernelGGL((k_gather_checked<float>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, sb.data_f32(), di, ob.data_f32(), n_indices, sb.numel, bad);
-            else hipLaunchKernelGGL((k_gather_checked<double>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, sb.data(), di, ob.data(), n_indices, sb.numel, bad);
+            by_elem(sb, [&](auto* t) {
+                using T = std::remove_pointer_t<decltype(t)>;
+                hipLaunchKernelGGL((k_gather_checked<T>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, (const T*)sb.data(), di, (T*)ob.data(), n_indices, sb.numel, bad);
+            });
             c->tel.kernel_launches++;
             e = hipGetLastError();
         }
@@ -567,8 +529,10 @@ int rmhip_gather_linear(rmhip_ctx* ctx, rmhip_buf source, const uint32_t* indice
                       (size_t)first_bad, (unsigned long long)source, sb.numel);
     } else if (rc == RMHIP_OK) {
         const unsigned* di = reinterpret_cast<const unsigned*>(didx->ptr);
-        if (sb.dtype == DT_F32) hipLaunchKernelGGL((k_gather<float>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, sb.data_f32(), di, ob.data_f32(), n_indices);
-        else hipLaunchKernelGGL((k_gather<double>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, sb.data(), di, ob.data(), n_indices);
+        by_elem(sb, [&](auto* t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            hipLaunchKernelGGL((k_gather<T>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, (const T*)sb.data(), di, (T*)ob.data(), n_indices);
+        });
         c->tel.kernel_launches++;
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the caller's index slice (pageable host memory) may go away on return
@@ -577,18 +541,40 @@ int rmhip_gather_linear(rmhip_ctx* ctx, rmhip_buf source, const uint32_t* indice
     if (rc) rmhip_free(ctx, *out);
     return rc;
 }
-
-int rmhip_scatter_linear(rmhip_ctx* ctx, rmhip_buf target, const uint32_t* indices, size_t n_indices, rmhip_buf values) {
+int rmhip_gather_linear(rmhip_ctx* ctx, rmhip_buf source, const uint32_t* indices, size_t n_indices, const size_t* out_shape, size_t rank,
+                        rmhip_buf* out) {
     CTX_OR_FAIL(ctx);
+    return gather_any(ctx, c, false, source, indices, n_indices, out_shape, rank, out);
+}
+int rmhip_complex_gather_linear(rmhip_ctx* ctx, rmhip_buf source, const uint32_t* indices, size_t n_indices, const size_t* out_shape, size_t rank,
+                                rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return gather_any(ctx, c, true, source, indices, n_indices, out_shape, rank, out);
+}
+
+static int scatter_any(Context* c, bool cplx, rmhip_buf target, const uint32_t* indices, size_t n_indices, rmhip_buf values) {
     if (n_indices && !indices) return fail(RMHIP_ERR_INVALID, "scatter_linear: null indices");
     Buffer tb, vb;
-    RMHIP_TRY(get_settled(c, target, &tb));
-    RMHIP_TRY(c->detach_views_of(target));  // written in place: a repmat / transpose view of the target keeps the values it was made from
-    RMHIP_TRY(get_settled(c, values, &vb));
+    if (cplx) {  // both complex-interleaved (indexing.rs:781-786); two real tensors are the real entry point's
+        RMHIP_TRY(c->lookup(target, &tb));
+        RMHIP_TRY(c->lookup(values, &vb));
+        if (!tb.cplx && !vb.cplx)
+            return fail(RMHIP_ERR_UNSUPPORTED, "complex_scatter_linear: tensors %llu and %llu are real (rmhip_scatter_linear serves them)", (unsigned long long)target,
+                        (unsigned long long)values);
+        if (tb.cplx != vb.cplx)
+            return fail(RMHIP_ERR_UNSUPPORTED, "scatter_linear: storage mismatch target=%s values=%s", tb.cplx ? "ComplexInterleaved" : "Real",
+                        vb.cplx ? "ComplexInterleaved" : "Real");
+        RMHIP_TRY(c->detach_views_of(target));  // (complex tensors have no views today)
+    } else {
+        RMHIP_TRY(get_settled(c, target, &tb));
+        RMHIP_TRY(c->detach_views_of(target));  // written in place: a repmat / transpose view of the target keeps the values it was made from
+        RMHIP_TRY(get_settled(c, values, &vb));
+    }
     if (tb.dtype != vb.dtype)  // simple_provider.rs:2663-2669 (storage mismatch)
         return fail(RMHIP_ERR_UNSUPPORTED, "scatter_linear: storage mismatch target=%s values=%s", tb.dtype == DT_F32 ? "f32" : "f64", vb.dtype == DT_F32 ? "f32" : "f64");
-    if (vb.numel != n_indices)
-        return fail(RMHIP_ERR_SHAPE, "scatter_linear: values raw length %zu does not match index count %zu for lane factor 1", vb.numel, n_indices);
+    if (vb.numel != n_indices)  // the raw length counts doubles: two per complex element
+        return fail(RMHIP_ERR_SHAPE, "scatter_linear: values raw length %zu does not match index count %zu for lane factor %d", (cplx ? 2 : 1) * vb.numel, n_indices,
+                    cplx ? 2 : 1);
     if (n_indices == 0) return RMHIP_OK;
     // From kScatterDeviceMin indices on (and fewer than 2^32 - 1 of them) the host does nothing per index: an O(n) bounds loop, a sort
     // and a hash map per call were the cost of a large `A(idx) = v` (1e7 indices: seconds on the host against two short kernels).
@@ -612,8 +598,10 @@ int rmhip_scatter_linear(rmhip_ctx* ctx, rmhip_buf target, const uint32_t* indic
         if (first_bad != ~0ULL)  // nothing was stored (the reference's loop stores the positions before the offending one, then fails: simple_provider.rs:2698-2706; both paths here validate first)
             return fail(RMHIP_ERR_INVALID, "scatter_linear: index %u (position %zu) out of bounds for target (logical_len=%zu)", indices[first_bad],
                         (size_t)first_bad, tb.numel);
-        if (tb.dtype == DT_F32) hipLaunchKernelGGL((k_scatter_owned<float>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, tb.data_f32(), di, own, vb.data_f32(), n_indices);
-        else hipLaunchKernelGGL((k_scatter_owned<double>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, tb.data(), di, own, vb.data(), n_indices);
+        by_elem(tb, [&](auto* t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            hipLaunchKernelGGL((k_scatter_owned<T>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, (T*)tb.data(), di, own, (const T*)vb.data(), n_indices);
+        });
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
         return RMHIP_OK;  // (didx / owner return to the pool in stream order)
@@ -642,12 +630,22 @@ int rmhip_scatter_linear(rmhip_ctx* ctx, rmhip_buf target, const uint32_t* indic
         dw = reinterpret_cast<const unsigned char*>(didx->ptr) + n_indices * sizeof(uint32_t);
         RMHIP_HIP_CHECK(hipMemcpyAsync((void*)dw, winner.data(), winner.size(), hipMemcpyHostToDevice, c->stream));
     }
-    if (tb.dtype == DT_F32) hipLaunchKernelGGL((k_scatter<float>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, tb.data_f32(), di, dw, vb.data_f32(), n_indices);
-    else hipLaunchKernelGGL((k_scatter<double>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, tb.data(), di, dw, vb.data(), n_indices);
+    by_elem(tb, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        hipLaunchKernelGGL((k_scatter<T>), dim3(flat_grid(c, n_indices)), dim3(kBlock), 0, c->stream, (T*)tb.data(), di, dw, (const T*)vb.data(), n_indices);
+    });
     c->tel.kernel_launches++;
     RMHIP_HIP_CHECK(hipGetLastError());
     RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));  // host index / winner arrays go out of scope
     return RMHIP_OK;
+}
+int rmhip_scatter_linear(rmhip_ctx* ctx, rmhip_buf target, const uint32_t* indices, size_t n_indices, rmhip_buf values) {
+    CTX_OR_FAIL(ctx);
+    return scatter_any(c, false, target, indices, n_indices, values);
+}
+int rmhip_complex_scatter_linear(rmhip_ctx* ctx, rmhip_buf target, const uint32_t* indices, size_t n_indices, rmhip_buf values) {
+    CTX_OR_FAIL(ctx);
+    return scatter_any(c, true, target, indices, n_indices, values);
 }
 
 int rmhip_linspace(rmhip_ctx* ctx, double start, double stop, size_t count, rmhip_buf* out) {
@@ -738,18 +736,16 @@ int mapped_copy(rmhip_ctx* ctx, Context* c, const Buffer& ab, const std::vector<
         m.mod[0] = 1;
         m.rev[0] = 0;
     }
-    const int rc = ab.dtype == DT_F32 ? launch_index_copy_f32(c, ab.data_f32(), ob.data_f32(), ab.numel, m)
-                                      : launch_index_copy(c, ab.data(), ob.data(), ab.numel, m);
+    const int rc = launch_index_copy_like(c, ab, ab.data(), ob.data(), ab.numel, m);
     if (rc) rmhip_free(ctx, *out);
     return rc;
 }
 }  // namespace
 
-int rmhip_flip(rmhip_ctx* ctx, rmhip_buf a, const size_t* axes, size_t n_axes, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+static int flip_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf a, const size_t* axes, size_t n_axes, rmhip_buf* out) {
     if (!out || (n_axes && !axes)) return fail(RMHIP_ERR_INVALID, "flip: null argument");
     Buffer ab;
-    RMHIP_TRY(get_settled(c, a, &ab));
+    RMHIP_TRY(fetch(c, a, cplx, "flip", &ab));
     std::vector<size_t> shape = ab.shape;
     for (size_t k = 0; k < n_axes; ++k)
         if (axes[k] >= shape.size()) shape.resize(axes[k] + 1, 1);  // flip_data: axes beyond the rank are extent-1 dimensions
@@ -762,12 +758,19 @@ int rmhip_flip(rmhip_ctx* ctx, rmhip_buf a, const size_t* axes, size_t n_axes, r
     }
     return mapped_copy(ctx, c, ab, shape, off, rev, out);
 }
-
-int rmhip_circshift(rmhip_ctx* ctx, rmhip_buf a, const long long* shifts, size_t n_shifts, rmhip_buf* out) {
+int rmhip_flip(rmhip_ctx* ctx, rmhip_buf a, const size_t* axes, size_t n_axes, rmhip_buf* out) {
     CTX_OR_FAIL(ctx);
+    return flip_any(ctx, c, false, a, axes, n_axes, out);
+}
+int rmhip_complex_flip(rmhip_ctx* ctx, rmhip_buf a, const size_t* axes, size_t n_axes, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return flip_any(ctx, c, true, a, axes, n_axes, out);
+}
+
+static int circshift_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf a, const long long* shifts, size_t n_shifts, rmhip_buf* out) {
     if (!out || (n_shifts && !shifts)) return fail(RMHIP_ERR_INVALID, "circshift: null argument");
     Buffer ab;
-    RMHIP_TRY(get_settled(c, a, &ab));
+    RMHIP_TRY(fetch(c, a, cplx, "circshift", &ab));
     std::vector<size_t> shape = ab.shape;
     if (n_shifts > shape.size()) shape.resize(n_shifts, 1);  // simple_provider.rs:6439-6442
     std::vector<uint8_t> rev(shape.size(), 0);
@@ -780,6 +783,14 @@ int rmhip_circshift(rmhip_ctx* ctx, rmhip_buf a, const long long* shifts, size_t
         off[d] = (uint64_t)((len - v) % len);  // src = (coord + len - shift) % len
     }
     return mapped_copy(ctx, c, ab, shape, off, rev, out);
+}
+int rmhip_circshift(rmhip_ctx* ctx, rmhip_buf a, const long long* shifts, size_t n_shifts, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return circshift_any(ctx, c, false, a, shifts, n_shifts, out);
+}
+int rmhip_complex_circshift(rmhip_ctx* ctx, rmhip_buf a, const long long* shifts, size_t n_shifts, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return circshift_any(ctx, c, true, a, shifts, n_shifts, out);
 }
 
 int rmhip_tri(rmhip_ctx* ctx, rmhip_buf a, int upper, long long offset, rmhip_buf* out) {
@@ -806,8 +817,8 @@ int rmhip_tri(rmhip_ctx* ctx, rmhip_buf a, int upper, long long offset, rmhip_bu
     return RMHIP_OK;
 }
 
-int rmhip_cat(rmhip_ctx* ctx, size_t dim, const rmhip_buf* inputs, size_t n_inputs, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+// `cplx`: every input complex-interleaved; a list that mixes the kinds is refused and the caller gathers
+static int cat_any(rmhip_ctx* ctx, Context* c, bool cplx, size_t dim, const rmhip_buf* inputs, size_t n_inputs, rmhip_buf* out) {
     if (!out || !inputs) return fail(RMHIP_ERR_INVALID, "cat: null argument");
     if (n_inputs < 2) return fail(RMHIP_ERR_INVALID, "cat: at least two input arrays are required");  // tensor.rs:462-465
     if (dim < 1) return fail(RMHIP_ERR_INVALID, "cat: dimension must be >= 1");
@@ -815,7 +826,13 @@ int rmhip_cat(rmhip_ctx* ctx, size_t dim, const rmhip_buf* inputs, size_t n_inpu
     std::vector<Buffer> in(n_inputs);
     size_t rank = dz + 1;
     for (size_t k = 0; k < n_inputs; ++k) {
-        RMHIP_TRY(get_settled(c, inputs[k], &in[k]));
+        if (cplx) {
+            RMHIP_TRY(c->lookup(inputs[k], &in[k]));
+            if (!in[k].cplx)
+                return fail(RMHIP_ERR_UNSUPPORTED, "complex_cat: input %zu is real: every input must be complex-interleaved (rmhip_cat serves a list of real tensors)", k + 1);
+        } else {
+            RMHIP_TRY(get_settled(c, inputs[k], &in[k]));
+        }
         if (in[k].dtype != in[0].dtype) return fail(RMHIP_ERR_UNSUPPORTED, "cat: input precision mismatch");
         rank = std::max(rank, in[k].shape.size());
     }
@@ -845,7 +862,7 @@ int rmhip_cat(rmhip_ctx* ctx, size_t dim, const rmhip_buf* inputs, size_t n_inpu
     Buffer ob;
     RMHIP_TRY(new_like(c, in[0], nshape.data(), nshape.size(), out, &ob));
     if (ob.numel == 0) return RMHIP_OK;
-    const size_t esz = in[0].dtype == DT_F32 ? sizeof(float) : sizeof(double);
+    const size_t esz = cplx ? 2 * sizeof(double) : (in[0].dtype == DT_F32 ? sizeof(float) : sizeof(double));
     size_t at = 0;  // offset along the concatenated dimension
     for (size_t k = 0; k < n_inputs; ++k) {
         const size_t w = inner * shapes[k][dz];  // contiguous elements per outer index
@@ -860,6 +877,14 @@ int rmhip_cat(rmhip_ctx* ctx, size_t dim, const rmhip_buf* inputs, size_t n_inpu
         at += shapes[k][dz];
     }
     return RMHIP_OK;
+}
+int rmhip_cat(rmhip_ctx* ctx, size_t dim, const rmhip_buf* inputs, size_t n_inputs, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return cat_any(ctx, c, false, dim, inputs, n_inputs, out);
+}
+int rmhip_complex_cat(rmhip_ctx* ctx, size_t dim, const rmhip_buf* inputs, size_t n_inputs, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return cat_any(ctx, c, true, dim, inputs, n_inputs, out);
 }
 
 }  // extern "C"

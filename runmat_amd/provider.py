@@ -478,12 +478,12 @@ class HipProvider:
         self._check(self._lib.rmhip_fill_uniform(self._ctx, int(seed), float(lo), float(hi), sh, rank, C.byref(out)))
         return self._handle(out.value, shape)
 
-    def reshape(self, h: GpuTensorHandle, shape: Sequence[int]) -> GpuTensorHandle:
+    def reshape(self, h: GpuTensorHandle, shape: Sequence[int], *, entry: str = "rmhip_reshape") -> GpuTensorHandle:
         """`reshape` (lib.rs:2676-2684): the SAME buffer with a new shape - the returned handle carries `h`'s
         buffer_id, and one `free` releases the storage (a transpose view is materialised first)."""
         sh, rank = _shape_array(shape)
         out = C.c_uint64()
-        self._check(self._lib.rmhip_reshape(self._ctx, self._id(h), sh, rank, C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(h), sh, rank, C.byref(out)))
         return self._handle(out.value, shape)
 
     def wrap_external(self, device_ptr: int, shape: Sequence[int]) -> GpuTensorHandle:
@@ -562,6 +562,18 @@ class HipProvider:
         self._check(self._lib.rmhip_complex_scalar(self._ctx, SCALAR_OPS[op] if isinstance(op, str) else int(op), self._id(z), float(s), C.byref(out)))
         return self._handle(out.value)
 
+    # The shape and indexing hooks on complex-interleaved operands (include/rmhip.h): the arguments of the real methods, which keep refusing
+    # complex storage; indices, extents and shifts count logical (re, im) elements; every result is complex, transpose / repmat materialised.
+    def complex_reshape(self, h, shape): return self.reshape(h, shape, entry="rmhip_complex_reshape")
+    def complex_transpose(self, a): return self.transpose(a, entry="rmhip_complex_transpose")
+    def complex_permute(self, a, order): return self.permute(a, order, entry="rmhip_complex_permute")
+    def complex_repmat(self, a, reps): return self.repmat(a, reps, entry="rmhip_complex_repmat")
+    def complex_gather_linear(self, source, indices, output_shape): return self.gather_linear(source, indices, output_shape, entry="rmhip_complex_gather_linear")
+    def complex_scatter_linear(self, target, indices, values): return self.scatter_linear(target, indices, values, entry="rmhip_complex_scatter_linear")
+    def complex_circshift(self, a, shifts): return self.circshift(a, shifts, entry="rmhip_complex_circshift")
+    def complex_flip(self, a, axes): return self.flip(a, axes, entry="rmhip_complex_flip")
+    def complex_cat(self, dim, inputs): return self.cat(dim, inputs, entry="rmhip_complex_cat")
+
     def elem_add(self, a, b): return self._binary("add", a, b)
     def elem_sub(self, a, b): return self._binary("sub", a, b)
     def elem_mul(self, a, b): return self._binary("mul", a, b)
@@ -595,19 +607,19 @@ class HipProvider:
     # 2980-2988) are attached below the class from UNARY_HOOKS: one method per trait hook, all through rmhip_unary.
 
     # -- shape / indexing hooks -------------------------------------------------------------------
-    def repmat(self, a: GpuTensorHandle, reps: Sequence[int]) -> GpuTensorHandle:
+    def repmat(self, a: GpuTensorHandle, reps: Sequence[int], *, entry: str = "rmhip_repmat") -> GpuTensorHandle:
         """`repmat` (lib.rs:2689-2695).  The result is a view of `a`'s storage; elem_* / fused_elementwise read it in
         place, anything else materialises it on first use (include/rmhip.h)."""
         arr, n = _shape_array(reps)
         out = C.c_uint64()
-        self._check(self._lib.rmhip_repmat(self._ctx, self._id(a), arr, n, C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(a), arr, n, C.byref(out)))
         return self._handle(out.value)
 
-    def permute(self, a: GpuTensorHandle, order: Sequence[int]) -> GpuTensorHandle:
+    def permute(self, a: GpuTensorHandle, order: Sequence[int], *, entry: str = "rmhip_permute") -> GpuTensorHandle:
         """`permute` (lib.rs:2579-2585): `order` is zero-based."""
         arr, n = _shape_array(order)
         out = C.c_uint64()
-        self._check(self._lib.rmhip_permute(self._ctx, self._id(a), arr, n, C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(a), arr, n, C.byref(out)))
         return self._handle(out.value)
 
     def fill_like(self, prototype: GpuTensorHandle, value: float) -> GpuTensorHandle:
@@ -627,20 +639,19 @@ class HipProvider:
         self._check(self._lib.rmhip_read_scalar(self._ctx, self._id(h), int(linear_index), C.byref(out)))
         return out.value
 
-    def gather_linear(self, source: GpuTensorHandle, indices: Sequence[int], output_shape: Sequence[int]) -> GpuTensorHandle:
+    def gather_linear(self, source: GpuTensorHandle, indices: Sequence[int], output_shape: Sequence[int], *,
+                      entry: str = "rmhip_gather_linear") -> GpuTensorHandle:
         """`gather_linear` (lib.rs:1423-1430): zero-based u32 linear indices."""
         idx = np.ascontiguousarray(indices, dtype=np.uint32)
         sh, rank = _shape_array(output_shape)
         out = C.c_uint64()
-        self._check(self._lib.rmhip_gather_linear(self._ctx, self._id(source), idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size, sh,
-                                                  rank, C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(source), idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size, sh, rank, C.byref(out)))
         return self._handle(out.value, output_shape)
 
-    def scatter_linear(self, target: GpuTensorHandle, indices: Sequence[int], values: GpuTensorHandle) -> None:
+    def scatter_linear(self, target: GpuTensorHandle, indices: Sequence[int], values: GpuTensorHandle, *, entry: str = "rmhip_scatter_linear") -> None:
         """`scatter_linear` (lib.rs:1438-1445): updates `target` in place."""
         idx = np.ascontiguousarray(indices, dtype=np.uint32)
-        self._check(self._lib.rmhip_scatter_linear(self._ctx, self._id(target), idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size,
-                                                   self._id(values)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(target), idx.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size, self._id(values)))
 
     def eye(self, shape: Sequence[int]) -> GpuTensorHandle:
         """`eye` (lib.rs:1552): identity on the first two dimensions of every page; [n] means [n, n]."""
@@ -652,18 +663,18 @@ class HipProvider:
     def eye_like(self, prototype: GpuTensorHandle) -> GpuTensorHandle:
         return self.eye(prototype.shape)  # lib.rs:1557
 
-    def flip(self, a: GpuTensorHandle, axes: Sequence[int]) -> GpuTensorHandle:
+    def flip(self, a: GpuTensorHandle, axes: Sequence[int], *, entry: str = "rmhip_flip") -> GpuTensorHandle:
         """`flip` (lib.rs:2586): zero-based axes."""
         arr, n = _shape_array(axes)
         out = C.c_uint64()
-        self._check(self._lib.rmhip_flip(self._ctx, self._id(a), arr, n, C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(a), arr, n, C.byref(out)))
         return self._handle(out.value, a.shape)
 
-    def circshift(self, a: GpuTensorHandle, shifts: Sequence[int]) -> GpuTensorHandle:
+    def circshift(self, a: GpuTensorHandle, shifts: Sequence[int], *, entry: str = "rmhip_circshift") -> GpuTensorHandle:
         """`circshift` (lib.rs:2589-2595): signed shifts per dimension."""
         arr = (C.c_longlong * max(len(shifts), 1))(*[int(v) for v in shifts])
         out = C.c_uint64()
-        self._check(self._lib.rmhip_circshift(self._ctx, self._id(a), arr, len(shifts), C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(a), arr, len(shifts), C.byref(out)))
         return self._handle(out.value, a.shape)
 
     def _tri(self, a: GpuTensorHandle, upper: bool, offset: int) -> GpuTensorHandle:
@@ -674,11 +685,11 @@ class HipProvider:
     def tril(self, a, offset: int = 0): return self._tri(a, False, offset)  # lib.rs:1635
     def triu(self, a, offset: int = 0): return self._tri(a, True, offset)   # lib.rs:1644
 
-    def cat(self, dim: int, inputs: Sequence[GpuTensorHandle]) -> GpuTensorHandle:
+    def cat(self, dim: int, inputs: Sequence[GpuTensorHandle], *, entry: str = "rmhip_cat") -> GpuTensorHandle:
         """`cat` (lib.rs:2686): ONE-based dimension."""
         ids = (C.c_uint64 * max(len(inputs), 1))(*[self._id(h) for h in inputs])
         out = C.c_uint64()
-        self._check(self._lib.rmhip_cat(self._ctx, int(dim), ids, len(inputs), C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, int(dim), ids, len(inputs), C.byref(out)))
         return self._handle(out.value)
 
     def linspace(self, start: float, stop: float, count: int) -> GpuTensorHandle:
@@ -1010,10 +1021,10 @@ class HipProvider:
         self._check(self._lib.rmhip_linsolve(self._ctx, self._id(lhs), self._id(rhs), C.byref(co), C.byref(out), C.byref(rc)))
         return ProviderLinsolveResult(self._handle(out.value), rc.value)
 
-    def transpose(self, a: GpuTensorHandle) -> GpuTensorHandle:
+    def transpose(self, a: GpuTensorHandle, *, entry: str = "rmhip_transpose") -> GpuTensorHandle:
         """lib.rs:2532: a view aliasing `a` (consumed in place by matmul / syrk, materialised on any other use)."""
         out = C.c_uint64()
-        self._check(self._lib.rmhip_transpose(self._ctx, self._id(a), C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(a), C.byref(out)))
         return self._handle(out.value)
 
     def matmul_power_step(self, lhs: GpuTensorHandle, rhs: GpuTensorHandle, epsilon: float = 0.0) -> GpuTensorHandle:

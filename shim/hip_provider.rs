@@ -300,6 +300,12 @@ impl AccelProvider for HipProvider {
     // buffer id (`out == handle.buffer_id`), so the consumed source handle needs no separate free.
     fn reshape(&self, handle: &GpuTensorHandle, new_shape: &[usize]) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
+        if Self::is_complex(handle) { // the same id comes back: its storage kind stays recorded
+            check(unsafe { rmhip_complex_reshape(self.ctx, self.own(handle)?, new_shape.as_ptr(), new_shape.len(), &mut out) })?;
+            let h = GpuTensorHandle { shape: new_shape.to_vec(), device_id: self.device_id, buffer_id: out };
+            runmat_accelerate_api::set_handle_storage(&h, GpuTensorStorage::ComplexInterleaved);
+            return Ok(h);
+        }
         check(unsafe { rmhip_reshape(self.ctx, self.own(handle)?, new_shape.as_ptr(), new_shape.len(), &mut out) })?;
         Ok(GpuTensorHandle { shape: new_shape.to_vec(), device_id: self.device_id, buffer_id: out })
     }
@@ -687,6 +693,10 @@ impl AccelProvider for HipProvider {
     }
     fn transpose(&self, a: &GpuTensorHandle) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
+        if Self::is_complex(a) { // materialised: the lazy view is read in place by real kernels only
+            check(unsafe { rmhip_complex_transpose(self.ctx, self.own(a)?, &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_transpose(self.ctx, self.own(a)?, &mut out) })?;
         self.handle(out)
     }
@@ -1351,14 +1361,25 @@ impl AccelProvider for HipProvider {
         })
     }
 
-    // shape / indexing hooks the hot-path builtins call around the kernels (include/rmhip.h "shape / indexing hooks")
+    // shape / indexing hooks the hot-path builtins call around the kernels (include/rmhip.h "shape / indexing hooks").  repmat, permute,
+    // gather_linear, scatter_linear, flip, circshift and cat (like reshape and transpose above) choose the entry point by `handle_storage`,
+    // as the wgpu provider's ops/tensor.rs and ops/indexing.rs do: a complex-interleaved operand goes to rmhip_complex_*, whose result is
+    // marked ComplexInterleaved.
     fn repmat(&self, handle: &GpuTensorHandle, reps: &[usize]) -> Result<GpuTensorHandle> {
         let mut out = 0u64; // a view: elem_* / fused_elementwise read it in place (times.rs:501-543)
+        if Self::is_complex(handle) { // tiled at once
+            check(unsafe { rmhip_complex_repmat(self.ctx, self.own(handle)?, reps.as_ptr(), reps.len(), &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_repmat(self.ctx, self.own(handle)?, reps.as_ptr(), reps.len(), &mut out) })?;
         self.handle(out)
     }
     fn permute(&self, handle: &GpuTensorHandle, order: &[usize]) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
+        if Self::is_complex(handle) {
+            check(unsafe { rmhip_complex_permute(self.ctx, self.own(handle)?, order.as_ptr(), order.len(), &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_permute(self.ctx, self.own(handle)?, order.as_ptr(), order.len(), &mut out) })?;
         self.handle(out)
     }
@@ -1376,11 +1397,21 @@ impl AccelProvider for HipProvider {
     }
     fn gather_linear(&self, source: &GpuTensorHandle, indices: &[u32], output_shape: &[usize]) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
+        if Self::is_complex(source) { // indices count logical (re, im) elements
+            check(unsafe { rmhip_complex_gather_linear(self.ctx, self.own(source)?, indices.as_ptr(), indices.len(), output_shape.as_ptr(),
+                output_shape.len(), &mut out) })?;
+            let h = GpuTensorHandle { shape: output_shape.to_vec(), device_id: self.device_id, buffer_id: out };
+            runmat_accelerate_api::set_handle_storage(&h, GpuTensorStorage::ComplexInterleaved);
+            return Ok(h);
+        }
         check(unsafe { rmhip_gather_linear(self.ctx, self.own(source)?, indices.as_ptr(), indices.len(), output_shape.as_ptr(),
             output_shape.len(), &mut out) })?;
         Ok(GpuTensorHandle { shape: output_shape.to_vec(), device_id: self.device_id, buffer_id: out })
     }
     fn scatter_linear(&self, target: &GpuTensorHandle, indices: &[u32], values: &GpuTensorHandle) -> Result<()> {
+        if Self::is_complex(target) || Self::is_complex(values) { // a real tensor beside a complex one: the library's "storage mismatch"
+            return check(unsafe { rmhip_complex_scatter_linear(self.ctx, self.own(target)?, indices.as_ptr(), indices.len(), self.own(values)?) });
+        }
         check(unsafe { rmhip_scatter_linear(self.ctx, self.own(target)?, indices.as_ptr(), indices.len(), self.own(values)?) })
     }
     fn linspace(&self, start: f64, stop: f64, count: usize) -> Result<GpuTensorHandle> {
@@ -1396,12 +1427,20 @@ impl AccelProvider for HipProvider {
     fn eye_like(&self, prototype: &GpuTensorHandle) -> Result<GpuTensorHandle> { self.eye(&prototype.shape) }
     fn flip(&self, handle: &GpuTensorHandle, axes: &[usize]) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
+        if Self::is_complex(handle) {
+            check(unsafe { rmhip_complex_flip(self.ctx, self.own(handle)?, axes.as_ptr(), axes.len(), &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_flip(self.ctx, self.own(handle)?, axes.as_ptr(), axes.len(), &mut out) })?;
         Ok(GpuTensorHandle { shape: handle.shape.clone(), device_id: self.device_id, buffer_id: out })
     }
     fn circshift(&self, handle: &GpuTensorHandle, shifts: &[isize]) -> Result<GpuTensorHandle> {
         let s: Vec<std::ffi::c_longlong> = shifts.iter().map(|&v| v as std::ffi::c_longlong).collect();
         let mut out = 0u64;
+        if Self::is_complex(handle) { // fftshift / ifftshift of a spectrum stay resident
+            check(unsafe { rmhip_complex_circshift(self.ctx, self.own(handle)?, s.as_ptr(), s.len(), &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_circshift(self.ctx, self.own(handle)?, s.as_ptr(), s.len(), &mut out) })?;
         Ok(GpuTensorHandle { shape: handle.shape.clone(), device_id: self.device_id, buffer_id: out })
     }
@@ -1422,6 +1461,10 @@ impl AccelProvider for HipProvider {
     fn cat(&self, dim: usize, inputs: &[GpuTensorHandle]) -> Result<GpuTensorHandle> {
         let ids = inputs.iter().map(|h| self.own(h)).collect::<Result<Vec<_>>>()?;
         let mut out = 0u64;
+        if inputs.iter().any(Self::is_complex) { // every input complex: served; a mixed list: the library's refusal, and the caller gathers
+            check(unsafe { rmhip_complex_cat(self.ctx, dim, ids.as_ptr(), ids.len(), &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_cat(self.ctx, dim, ids.as_ptr(), ids.len(), &mut out) })?;
         self.handle(out)
     }
