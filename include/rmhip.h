@@ -1397,6 +1397,25 @@ typedef struct rmhip_lu_stats {
 /* @serves - */
 RMHIP_API int rmhip_lu_stats(rmhip_ctx* ctx, rmhip_lu_stats_t* out);
 
+/* Which kernel the last GEMM ran (no counterpart in the reference).  Every launch site of the f64 products (matmul, matmul_epilogue,
+ * syrk, blk_gemm, transpose views, the LU's updates), of pagefun's large-page tier and of the f32 matrix-core products records what
+ * it launched - a few host stores - so that tests can attest the route a shape took through the dispatch, not only its result.
+ * The routing itself is not affected.  kernel: "small" (64 x 64 tiles), "w8" (eight-wave 128 x 128 tile), "w8g" (its guarded form),
+ * "w8p" (persistent, look-ahead LU only), "w4" (four-wave tile), "pgemm" (paged guarded eight-wave tile), "s_w8" / "s_w8g" / "s_w4" (the
+ * f32 kernels); empty before the first product. */
+typedef struct rmhip_gemm_route {
+    char kernel[8];
+    int guard;      /* the bounds-checking form: GUARD of small / w8g / pgemm / s_w8g, EDGE of w4 / s_w4 */
+    int pre;        /* C <- C - A*B with C preloaded into the accumulators */
+    int ta, tb;     /* operand consumed transposed in place */
+    int epi;        /* 0 plain store, 1 matmul_epilogue without pow, 2 with pow */
+    int yield_word; /* the form that checks the LU's yield word */
+    uint32_t splits;  /* split-K slices (1: none; > 1 is followed by the reduction over the slices; 0: no product yet) */
+    uint32_t k_chunk; /* k per slice (k itself without split-K) */
+} rmhip_gemm_route_t;
+/* @serves - */
+RMHIP_API int rmhip_gemm_last_route(rmhip_ctx* ctx, rmhip_gemm_route_t* out);
+
 /* HIP-event timing on the context stream (for bench.py's roofline leg): begin records an event,
  * end records another, synchronizes and returns the elapsed milliseconds between them. */
 /* @serves - */

@@ -207,6 +207,11 @@ public:
         check(rmhip_lu_stats(ctx_, &st));
         return st;
     }
+    rmhip_gemm_route_t gemm_last_route() const {  // which GEMM kernel the last product ran, its flags and split-K slices
+        rmhip_gemm_route_t r;
+        check(rmhip_gemm_last_route(ctx_, &r));
+        return r;
+    }
 
     // ---- memory (lib.rs:1387-1389, 1468-1522) ----
     GpuTensorHandle upload(const HostTensorView& host) const {

@@ -22,7 +22,7 @@ ERR_COMPILE, ERR_SINGULAR, ERR_OOM, ERR_NO_DEVICE, ERR_GROWTH = 6, 7, 8, 9, 10
 
 # Structures, signatures and constants are GENERATED from include/rmhip.h (scripts/gen_bindings.py -> _abi.py); the table is
 # used both to bind and by the CPU-side test that checks the library exports the full ABI.
-from ._abi import (CONSTANTS, ENUMS, SERVES, SIGNATURES, DeviceInfo, ImageNormalize, KernelAttr, KernelLaunch,  # noqa: E402,F401
+from ._abi import (CONSTANTS, ENUMS, SERVES, SIGNATURES, DeviceInfo, GemmRoute, ImageNormalize, KernelAttr, KernelLaunch,  # noqa: E402,F401
                    LinsolveOptions, LuStats, MatmulEpilogue, Telemetry, View)
 
 _lib = None

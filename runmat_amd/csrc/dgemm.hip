@@ -137,7 +137,7 @@ __device__ __forceinline__ void tile_of_block(const GemmArgs& g, unsigned& tm, u
 //   pattern K: k contiguous in memory,            LDS [y][k] with row stride SB   (B plain, A transposed)
 // PRE (only with EDGE = EPI = TA = TB = false): C <- C - A*B, the rank-k update of the blocked LU.  The C tile is loaded into
 // the accumulators (negated) BEFORE the k loop, where its latency hides behind the first operand tiles, and the epilogue
-// is stores only (-acc).  The plain beta path reads C at the end: four dependent load -> store round trips with the
+// is stores only (0 - acc: the subtraction, not a sign flip, so that C == A*B leaves +0 and not -0).  The plain beta path reads C at the end: four dependent load -> store round trips with the
 // matrix pipe idle - 10-25 % of a k = 256..512 tile when one block per CU runs (the look-ahead's update stream).
 template <bool EDGE, bool EPI, bool TA, bool TB, bool PRE = false>
 __global__ void __launch_bounds__(256, 2) k_dgemm(const GemmArgs g) {
@@ -410,7 +410,7 @@ __global__ void __launch_bounds__(256, 2) k_dgemm(const GemmArgs g) {
                     const unsigned nn = n0 + wn * 64 + j * 16 + row;
                     v = ok[e] ? apply_epilogue(g.ep, acc[j][i][r], mm, nn) : 0.0;
                 } else if (PRE) {
-                    v = -acc[j][i][r];
+                    v = 0.0 - acc[j][i][r];  // (not -acc: an exactly cancelling C - A*B is +0 as in the forms that read C at the end)
                 } else {
                     v = g.alpha * acc[j][i][r];
                     if (g.beta != 0.0) v = g.beta * prev[e] + v;
@@ -554,7 +554,7 @@ __global__ void __launch_bounds__(256) k_dgemm_small(const GemmArgs g) {
                 const int e = (j * 2 + i) * 4 + r;
                 double v;
                 if (PRE) {
-                    v = -acc[j][i][r];
+                    v = 0.0 - acc[j][i][r];  // (not -acc: an exactly cancelling C - A*B is +0 as in the forms that read C at the end)
                 } else {
                     v = g.alpha * acc[j][i][r];
                     if (g.beta != 0.0) v = g.beta * prev[e] + v;
@@ -794,7 +794,7 @@ __device__ __forceinline__ void w8_tile(const GemmArgs& g, const unsigned tm, co
                 const int e = i * 4 + r;
                 double v;
                 if (PRE) {
-                    v = -acc[j][i][r];
+                    v = 0.0 - acc[j][i][r];  // (not -acc: an exactly cancelling C - A*B is +0 as in the forms that read C at the end)
                 } else if (EPI) {
                     const unsigned mm = m0 + wm * 64 + i * 16 + l15;
                     const unsigned row = g.rowmap ? (4 * lq + r) : (4 * r + lq);
@@ -917,6 +917,26 @@ template <bool EDGE, bool EPI, bool TA, bool TB, bool PRE = false>
 static void launch_variant(Context* c, unsigned blocks, unsigned splits, size_t lds_bytes, size_t max_lds, const GemmArgs& g) {
     c->ensure_max_lds((const void*)k_dgemm<EDGE, EPI, TA, TB, PRE>, max_lds);
     hipLaunchKernelGGL((k_dgemm<EDGE, EPI, TA, TB, PRE>), dim3(blocks, splits), dim3(256), lds_bytes, c->stream, g);
+    c->note_gemm_route("w4", EDGE, PRE, TA, TB, EPI ? ((g.ep.flags & EP_POW) ? 2 : 1) : 0, false, splits, g.k_chunk);
+}
+
+// One helper per kernel: the launch and the route note (Context::note_gemm_route) take their flags from the same template arguments.
+template <bool PRE, bool GUARD>
+static void launch_small(Context* c, dim3 grid, size_t lds_bytes, const GemmArgs& g) {
+    hipLaunchKernelGGL((k_dgemm_small<PRE, GUARD>), grid, dim3(256), lds_bytes, c->stream, g);
+    c->note_gemm_route("small", GUARD, PRE, false, false, 0, false, 1, g.k_chunk);
+}
+template <bool PRE, bool TA = false, bool TB = false, int EPI = 0, bool YIELD = false>
+static void launch_w8(Context* c, unsigned blocks, unsigned splits, size_t lds_bytes, size_t max_lds, const GemmArgs& g) {
+    c->ensure_max_lds((const void*)k_dgemm_w8<PRE, TA, TB, EPI, YIELD>, max_lds);
+    hipLaunchKernelGGL((k_dgemm_w8<PRE, TA, TB, EPI, YIELD>), dim3(blocks, splits), dim3(512), lds_bytes, c->stream, g);
+    c->note_gemm_route("w8", false, PRE, TA, TB, EPI, YIELD, splits, g.k_chunk);
+}
+template <bool PRE, bool TA, int EPI>
+static void launch_w8g(Context* c, unsigned blocks, unsigned splits, size_t lds_bytes, size_t max_lds, const GemmArgs& g) {
+    c->ensure_max_lds((const void*)k_dgemm_w8g<PRE, TA, EPI>, max_lds);
+    hipLaunchKernelGGL((k_dgemm_w8g<PRE, TA, EPI>), dim3(blocks, splits), dim3(512), lds_bytes, c->stream, g);
+    c->note_gemm_route("w8g", true, PRE, TA, false, EPI, false, splits, g.k_chunk);
 }
 
 // C = alpha * (P_0 + P_1 + ... + P_{S-1}) + beta * C, partials m x n dense (ld m), summed in split order
@@ -1049,11 +1069,11 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
         g.tiles_n = (unsigned)((n + SN - 1) / SN);
         const dim3 sgrid(g.tiles_m * g.tiles_n);
         if (small_whole) {
-            if (preload) hipLaunchKernelGGL(k_dgemm_small<true>, sgrid, dim3(256), (size_t)small_pad, c->stream, g);
-            else hipLaunchKernelGGL(k_dgemm_small<false>, sgrid, dim3(256), (size_t)small_pad, c->stream, g);
+            if (preload) launch_small<true, false>(c, sgrid, (size_t)small_pad, g);
+            else launch_small<false, false>(c, sgrid, (size_t)small_pad, g);
         } else {
-            if (preload) hipLaunchKernelGGL((k_dgemm_small<true, true>), sgrid, dim3(256), (size_t)small_pad, c->stream, g);
-            else hipLaunchKernelGGL((k_dgemm_small<false, true>), sgrid, dim3(256), (size_t)small_pad, c->stream, g);
+            if (preload) launch_small<true, true>(c, sgrid, (size_t)small_pad, g);
+            else launch_small<false, true>(c, sgrid, (size_t)small_pad, g);
         }
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
@@ -1080,6 +1100,7 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
         if (grid_cap > 0 && grid > (unsigned)grid_cap) grid = (unsigned)grid_cap;
         c->ensure_max_lds((const void*)k_dgemm_w8p, kMaxLds);
         hipLaunchKernelGGL(k_dgemm_w8p, dim3(grid), dim3(512), lds_bytes, c->stream, g);
+        c->note_gemm_route("w8p", false, false, false, false, 0, false, 1, g.k_chunk);
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
         return RMHIP_OK;
@@ -1097,13 +1118,8 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
     };
     if (w8_fast && ep && !ta && !tb && w8_mode != 0 && !c->in_lookahead && c->gemm_lds_pad == 0) {
         // matmul_epilogue on the eight-wave tile (splits == 1 whenever there is an epilogue)
-        if (g.ep.flags & EP_POW) {
-            c->ensure_max_lds((const void*)k_dgemm_w8<false, false, false, 2>, kMaxLds);
-            hipLaunchKernelGGL((k_dgemm_w8<false, false, false, 2>), dim3(blocks), dim3(512), lds_bytes, c->stream, g);
-        } else {
-            c->ensure_max_lds((const void*)k_dgemm_w8<false, false, false, 1>, kMaxLds);
-            hipLaunchKernelGGL((k_dgemm_w8<false, false, false, 1>), dim3(blocks), dim3(512), lds_bytes, c->stream, g);
-        }
+        if (g.ep.flags & EP_POW) launch_w8<false, false, false, 2>(c, blocks, 1, lds_bytes, kMaxLds, g);
+        else launch_w8<false, false, false, 1>(c, blocks, 1, lds_bytes, kMaxLds, g);
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
         return RMHIP_OK;
@@ -1112,15 +1128,13 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
         // A' * B (transpose views, syrk, the Gram matrices of covariance and least squares): 70.7 -> 72.5 TFLOP/s at 8192^3 as
         // well.  (A * B' measured 69.8 against 70.2 in this form and stays on k_dgemm.)
         // Split-K (tall A'*A: few output tiles, long k) runs the same kernel with blockIdx.y over the k slices.
-        c->ensure_max_lds((const void*)k_dgemm_w8<false, true, false>, kMaxLds);
-        hipLaunchKernelGGL((k_dgemm_w8<false, true, false>), dim3(blocks, splits), dim3(512), lds_bytes, c->stream, g);
+        launch_w8<false, true, false>(c, blocks, splits, lds_bytes, kMaxLds, g);
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
         return reduce_splits();
     }
     if (w8_fast && splits > 1 && !ep && !ta && !tb && w8_mode != 0 && !c->in_lookahead && c->gemm_lds_pad == 0) {
-        c->ensure_max_lds((const void*)k_dgemm_w8<false>, kMaxLds);
-        hipLaunchKernelGGL(k_dgemm_w8<false>, dim3(blocks, splits), dim3(512), lds_bytes, c->stream, g);
+        launch_w8<false>(c, blocks, splits, lds_bytes, kMaxLds, g);
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
         return reduce_splits();
@@ -1128,14 +1142,11 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
     if (fast_k && splits == 1 && !ep && !ta && !tb &&
         ((w8_mode == 1 && (c->gemm_lds_pad != 0 || !c->in_lookahead)) || w8_mode == 2)) {
         if (preload && g.yield_word) {  // the two-level LU's update streams: the variant that checks the yield word
-            c->ensure_max_lds((const void*)k_dgemm_w8<true, false, false, 0, true>, kMaxLds);
-            hipLaunchKernelGGL((k_dgemm_w8<true, false, false, 0, true>), dim3(blocks), dim3(512), lds_bytes, c->stream, g);
+            launch_w8<true, false, false, 0, true>(c, blocks, 1, lds_bytes, kMaxLds, g);
         } else if (preload) {
-            c->ensure_max_lds((const void*)k_dgemm_w8<true>, kMaxLds);
-            hipLaunchKernelGGL(k_dgemm_w8<true>, dim3(blocks), dim3(512), lds_bytes, c->stream, g);
+            launch_w8<true>(c, blocks, 1, lds_bytes, kMaxLds, g);
         } else {
-            c->ensure_max_lds((const void*)k_dgemm_w8<false>, kMaxLds);
-            hipLaunchKernelGGL(k_dgemm_w8<false>, dim3(blocks), dim3(512), lds_bytes, c->stream, g);
+            launch_w8<false>(c, blocks, 1, lds_bytes, kMaxLds, g);
         }
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
@@ -1144,23 +1155,16 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
     // (inside the look-ahead LU only the update stream - the one with the LDS pad - runs eight-wave blocks, as for whole tiles)
     if (!fast && guard_ok && w8_mode != 0 && (splits == 1 || g.k_chunk % BK == 0) && !(ep && ta) && (c->gemm_lds_pad != 0 || !c->in_lookahead)) {
         // guarded eight-wave tile (plain or transposed A; plain, preloaded-C or epilogue store; split-K slices are whole tiles except the last)
-        const dim3 ggrid(blocks, splits);
-#define RMHIP_W8G(...)                                                                         \
-    do {                                                                                       \
-        c->ensure_max_lds((const void*)k_dgemm_w8g<__VA_ARGS__>, kMaxLds);                     \
-        hipLaunchKernelGGL((k_dgemm_w8g<__VA_ARGS__>), ggrid, dim3(512), lds_bytes, c->stream, g); \
-    } while (0)
         if (ep) {
-            if (g.ep.flags & EP_POW) RMHIP_W8G(false, false, 2);
-            else RMHIP_W8G(false, false, 1);
+            if (g.ep.flags & EP_POW) launch_w8g<false, false, 2>(c, blocks, splits, lds_bytes, kMaxLds, g);
+            else launch_w8g<false, false, 1>(c, blocks, splits, lds_bytes, kMaxLds, g);
         } else if (ta) {
-            RMHIP_W8G(false, true, 0);
+            launch_w8g<false, true, 0>(c, blocks, splits, lds_bytes, kMaxLds, g);
         } else if (preload) {
-            RMHIP_W8G(true, false, 0);
+            launch_w8g<true, false, 0>(c, blocks, splits, lds_bytes, kMaxLds, g);
         } else {
-            RMHIP_W8G(false, false, 0);
+            launch_w8g<false, false, 0>(c, blocks, splits, lds_bytes, kMaxLds, g);
         }
-#undef RMHIP_W8G
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
         return reduce_splits();
@@ -1215,6 +1219,7 @@ int launch_pgemm_w8(Context* c, const double* A, const double* B, double* C, uns
     const unsigned grid = (unsigned)(work < (1ull << 20) ? work : (1ull << 20));
     c->ensure_max_lds((const void*)k_pgemm_w8, lds_bytes);
     hipLaunchKernelGGL(k_pgemm_w8, dim3(grid), dim3(512), lds_bytes, c->stream, g, pm, pages);
+    c->note_gemm_route("pgemm", true, false, false, false, 0, false, 1, g.k_chunk);
     c->tel.kernel_launches++;
     RMHIP_HIP_CHECK(hipGetLastError());
     return RMHIP_OK;

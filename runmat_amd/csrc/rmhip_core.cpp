@@ -780,6 +780,23 @@ int rmhip_lu_stats(rmhip_ctx* ctx, rmhip_lu_stats_t* out) {
     return RMHIP_OK;
 }
 
+int rmhip_gemm_last_route(rmhip_ctx* ctx, rmhip_gemm_route_t* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "null out");
+    std::memset(out, 0, sizeof *out);
+    const GemmRoute& r = c->gemm_route;
+    std::snprintf(out->kernel, sizeof out->kernel, "%s", r.kernel);
+    out->guard = r.guard;
+    out->pre = r.pre;
+    out->ta = r.ta;
+    out->tb = r.tb;
+    out->epi = r.epi;
+    out->yield_word = r.yield;
+    out->splits = r.splits;
+    out->k_chunk = r.k_chunk;
+    return RMHIP_OK;
+}
+
 int rmhip_reset_telemetry(rmhip_ctx* ctx) {
     CTX_OR_FAIL(ctx);
     Telemetry& t = c->tel;

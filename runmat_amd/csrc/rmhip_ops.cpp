@@ -913,8 +913,9 @@ int rmhip_matmul(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf* out) {
     if (!out) return fail(RMHIP_ERR_INVALID, "null out");
     Buffer ab, bb, ob;
     // Precision 32: both operands in f32 storage run on the f32 matrix cores (sgemm.hip; f32 accumulation like the
-    // reference's F32 backend).  RMHIP_F32_MATMUL=f64 keeps the widen -> dgemm -> round-once path (the CPU's `single`
-    // result exactly); it is also what mixed operands, k == 0 and few-tile / long-k shapes (split-K) use.
+    // reference's F32 backend), whatever m and n are: few-tile / long-k shapes included, which launch_sgemm_trans splits
+    // along k itself (f32 partials, summed in f64 and rounded once).  RMHIP_F32_MATMUL=f64 keeps the widen -> dgemm ->
+    // round-once path (the CPU's `single` result exactly); it is also what mixed operands and k == 0 use.
     if (c->precision == 32) {
         Buffer ra, rb;
         RMHIP_TRY(c->get_raw(a, &ra));

@@ -379,6 +379,18 @@ __global__ void __launch_bounds__(512, 4) k_sgemm_w8g(const SgemmArgs g) {  // f
 template <bool EDGE, bool TA, bool TB>
 static void sg_launch(Context* c, unsigned blocks, unsigned splits, const SgemmArgs& g) {
     hipLaunchKernelGGL((k_sgemm<EDGE, TA, TB>), dim3(blocks, splits), dim3(256), 0, c->stream, g);
+    c->note_gemm_route("s_w4", EDGE, false, TA, TB, 0, false, splits, g.k_chunk);
+}
+
+template <bool TA>
+static void sg_launch_w8(Context* c, unsigned blocks, const SgemmArgs& g) {
+    hipLaunchKernelGGL(k_sgemm_w8<TA>, dim3(blocks), dim3(512), 0, c->stream, g);
+    c->note_gemm_route("s_w8", false, false, TA, false, 0, false, 1, g.k_chunk);
+}
+template <bool TA>
+static void sg_launch_w8g(Context* c, unsigned blocks, const SgemmArgs& g) {
+    hipLaunchKernelGGL(k_sgemm_w8g<TA>, dim3(blocks), dim3(512), 0, c->stream, g);
+    c->note_gemm_route("s_w8g", true, false, TA, false, 0, false, 1, g.k_chunk);
 }
 
 // C = P_0 + P_1 + ... + P_{S-1} (partials m x n dense, ld m), summed in split order in f64 and rounded once
@@ -441,15 +453,14 @@ int launch_sgemm_trans(Context* c, bool ta, bool tb, size_t m, size_t n, size_t 
     static const int guard_on = std::getenv("RMHIP_GEMM_GUARD") ? std::atoi(std::getenv("RMHIP_GEMM_GUARD")) : 1;
     const bool w8_env_off = std::getenv("RMHIP_SGEMM_W8") && *std::getenv("RMHIP_SGEMM_W8") == '0';
     if (!fast && guard_on && !w8_env_off && !tb && splits == 1 && k >= 1) {
-        if (ta) hipLaunchKernelGGL(k_sgemm_w8g<true>, dim3(blocks), dim3(512), 0, c->stream, g);
-        else hipLaunchKernelGGL(k_sgemm_w8g<false>, dim3(blocks), dim3(512), 0, c->stream, g);
+        if (ta) sg_launch_w8g<true>(c, blocks, g);
+        else sg_launch_w8g<false>(c, blocks, g);
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
         return RMHIP_OK;
     }
     if (ta) {
-        if (fast_k && splits == 1 && !w8_env_off)
-            hipLaunchKernelGGL(k_sgemm_w8<true>, dim3(blocks), dim3(512), 0, c->stream, g);  // A' * B (syrk, covariance, transpose views)
+        if (fast_k && splits == 1 && !w8_env_off) sg_launch_w8<true>(c, blocks, g);  // A' * B (syrk, covariance, transpose views)
         else if (fast_k) sg_launch<false, true, false>(c, blocks, splits, g);
         else sg_launch<true, true, false>(c, blocks, splits, g);
     } else if (tb) {
@@ -461,7 +472,7 @@ int launch_sgemm_trans(Context* c, bool ta, bool tb, size_t m, size_t n, size_t 
             const char* v = std::getenv("RMHIP_SGEMM_W8");
             w8_mode = (v && *v == '0') ? 0 : 1;
         }
-        if (fast_k && splits == 1 && w8_mode) hipLaunchKernelGGL(k_sgemm_w8<false>, dim3(blocks), dim3(512), 0, c->stream, g);
+        if (fast_k && splits == 1 && w8_mode) sg_launch_w8<false>(c, blocks, g);
         else if (fast_k) sg_launch<false, false, false>(c, blocks, splits, g);
         else sg_launch<true, false, false>(c, blocks, splits, g);
     }

@@ -1905,6 +1905,17 @@ class HipProvider:
         self._check(self._lib.rmhip_lu_stats(self._ctx, C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    def gemm_last_route(self) -> dict:
+        """`rmhip_gemm_last_route`: which GEMM kernel the last product of this provider ran - `kernel` ("small", "w8", "w8g", "w8p",
+        "w4", "pgemm", "s_w8", "s_w8g", "s_w4"; "" before the first), its template flags (`guard`, `pre`, `ta`, `tb`, `epi` 0/1/2,
+        `yield`), `splits` (0 before the first product) and `k_chunk`."""
+        st = _lib.GemmRoute()
+        self._check(self._lib.rmhip_gemm_last_route(self._ctx, C.byref(st)))
+        out = {f: getattr(st, f) for f, _ in st._fields_}
+        out["kernel"] = out["kernel"].decode()
+        out["yield"] = out.pop("yield_word")
+        return out
+
     def reset_telemetry(self) -> None:
         self._check(self._lib.rmhip_reset_telemetry(self._ctx))
 

@@ -534,7 +534,9 @@ def test_matmul_ragged_shapes(prov, oracle, m, k, n):
 
 def test_matmul_random_shapes_fuzz(prov):
     """120 random shapes (1 .. 700 in every dimension, biased towards tile boundaries) through matmul, A' * B, syrk and the update
-    form on a view: every dispatch decision of dgemm.hip (whole tiles, guarded tiles, 64 x 64 kernel, split-K) against numpy."""
+    form on a view, against numpy within the k eps bound: a sweep over shapes, not over kernels.  Nothing here records which kernel a
+    shape took; the dispatch of dgemm.hip is walked variant by variant, with the route attested and exact integer products, in
+    tests/test_gpu_gemm_paths.py."""
     rng = np.random.default_rng(20260927)
     edges = np.array([1, 2, 3, 15, 16, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257, 383, 384, 511, 512, 513])
 
