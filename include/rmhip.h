@@ -594,7 +594,7 @@ RMHIP_API int rmhip_polyval(rmhip_ctx* ctx, rmhip_buf coefficients, rmhip_buf po
 /* @serves polyder_single polyder_product polyder_quotient */
 RMHIP_API int rmhip_polyder(rmhip_ctx* ctx, rmhip_buf p, rmhip_buf q_or_0, int quotient, rmhip_buf* out, rmhip_buf* denominator_or_null);
 /* `polyint(polynomial, constant)` (lib.rs:1704-1710; simple_provider.rs:374-390, 3190-3215): coefficient i divided by its new power, the
- * constant appended; real polynomials (a complex-interleaved one is RMHIP_ERR_UNSUPPORTED).  Bit-exact. */
+ * constant appended; real polynomials (a complex-interleaved one is RMHIP_ERR_UNSUPPORTED here: rmhip_complex_polyint serves it).  Bit-exact. */
 /* @serves polyint */
 RMHIP_API int rmhip_polyint(rmhip_ctx* ctx, rmhip_buf p, double constant, rmhip_buf* out);
 /* `hann_window / hamming_window / blackman_window(len, periodic)` (lib.rs:1797-1807; simple_provider.rs:95-120) -> [len, 1]; kind 0 / 1 / 2.
@@ -609,7 +609,8 @@ RMHIP_API int rmhip_window(rmhip_ctx* ctx, int kind, size_t len, int periodic, r
  * tensors are accepted by the entry points of this section - the transforms, `rmhip_spectral_estimate`, `rmhip_complex_real`, the
  * elementwise arithmetic `rmhip_complex_unary` / `rmhip_complex_binary` / `rmhip_complex_scalar` and the shape and indexing hooks
  * `rmhip_complex_reshape` / `_transpose` / `_permute` / `_repmat` / `_gather_linear` / `_scatter_linear` / `_circshift` / `_flip` /
- * `_cat` - and by the plumbing (download, shape, storage, isreal, free).  Every other entry point returns RMHIP_ERR_UNSUPPORTED for
+ * `_cat`, and the calculus and filter hooks `rmhip_complex_gradient_dim` / `_trapz_dim` / `_polyint` / `_iir_filter` /
+ * `_iir_filter_long` - and by the plumbing (download, shape, storage, isreal, free).  Every other entry point returns RMHIP_ERR_UNSUPPORTED for
  * them (the caller gathers, as for any `Err`): fused elementwise, reductions, matmul, round_digits, pow, the comparisons, tril / triu
  * and read_scalar among them, and so do the real forms of the hooks just named (`rmhip_transpose`, `rmhip_permute`, ...): a caller
  * chooses the entry point by the operand's storage kind.  A precision-32 context rounds the values a complex result COMPUTES through
@@ -788,6 +789,65 @@ RMHIP_API int rmhip_complex_circshift(rmhip_ctx* ctx, rmhip_buf a, const long lo
 RMHIP_API int rmhip_complex_flip(rmhip_ctx* ctx, rmhip_buf a, const size_t* axes, size_t n_axes, rmhip_buf* out);
 /* @serves cat */
 RMHIP_API int rmhip_complex_cat(rmhip_ctx* ctx, size_t dim_one_based, const rmhip_buf* inputs, size_t n_inputs, rmhip_buf* out);
+
+/* ---- calculus and filter hooks on complex operands (misc_ops.hip, signal_ops.hip): the second entry points of `rmhip_gradient_dim`,
+ * `rmhip_trapz_dim`, `rmhip_polyint`, `rmhip_iir_filter` and `rmhip_iir_filter_long`, which keep refusing complex storage.  These are
+ * the remaining hooks for which the reference's providers take `GpuTensorStorage::ComplexInterleaved` (simple_provider.rs:6498-6611 ->
+ * gradient.rs:741-841; :2421-2598; :391-409, 3190-3220; :6155-6399; wgpu ops/signal.rs): with them every hook that takes complex
+ * storage in the reference takes it here.  Each entry point has its sibling's argument list; one host function serves both, so shape
+ * rules, argument checks, messages and error codes are the sibling's unless stated.  Common to all five:
+ *   - the principal operand (`a`, `p`, `x`) must be complex-interleaved; a real one is RMHIP_ERR_UNSUPPORTED, the message naming the
+ *     sibling that serves it;
+ *   - shapes, extents, `dim` and strides count logical (re, im) elements;
+ *   - every tensor result is complex-interleaved, a zero-extent one included;
+ *   - the two parts of an element are independent lanes: a NaN, an Inf or the sign of a zero in one part never reaches the other;
+ *   - a precision-32 context follows the rule for complex results: 2 x f64 storage, each part rounded through f32 once, on the final
+ *     store; no intermediate (the trapezoid terms, their sums, the filter's states and chunk tables) is rounded through f32;
+ *   - lazy views and f32 storage of the real side operands (coordinates, spacing, coefficients) are materialised / widened as the
+ *     siblings do;
+ *   - on any error nothing is left behind and the output ids are 0.
+ *
+ * `rmhip_complex_gradient_dim`: per element and per part (x[k+1] - x[k-1]) * (1.0 / den), den exactly the sibling's (`spacing` at the two
+ * ends, 2.0 * spacing inside, or the matching coordinate differences): the reciprocal is rounded once and multiplied into both parts
+ * (`scale_complex`, gradient.rs:839-841) - NOT the sibling's quotient num / den, from which it differs in the last bit.  Bit-exact.
+ * `coordinates` must be real: a complex vector is RMHIP_ERR_UNSUPPORTED "gradient_dim_with_coordinates: coordinates must be real".
+ *
+ * `rmhip_complex_trapz_dim`: per part t = (0.5 * w) * (x[k] + x[k+1]), w indexed by the logical element exactly as in the sibling; the
+ * terms are bit-exact and are summed per part by the library's reduction (trapz) or cumulative scan (cumtrapz) over the real view
+ * [2, shape...] of the interleaved terms along dim + 1.  Accuracy is the sibling's, per part: against the strictly sequential sum of the
+ * same terms |err| <= n eps sum|t| (cumtrapz: at every prefix), n the extent along `dim`.  Spacing must be real: a complex operand is
+ * RMHIP_ERR_UNSUPPORTED "trapezoid: spacing vector must be real" (kind 3) / "trapezoid: spacing tensor must be real" (kinds 2, 4).
+ *
+ * `rmhip_complex_polyint`: both parts of coefficient idx divided by power = logical_len - idx (a true division), the appended element
+ * (constant, +0); the sibling's orientation rule on the logical length (row [1, n + 1], column [n + 1, 1], scalar [1, 2], no elements
+ * [1, 1]).  Bit-exact.
+ *
+ * `rmhip_complex_iir_filter` / `rmhip_complex_iir_filter_long`: `b` and `a` real (complex ones: RMHIP_ERR_UNSUPPORTED "iir_filter:
+ * complex filter coefficients are not supported"); `zi`, when given, complex like `x` (else RMHIP_ERR_UNSUPPORTED "iir_filter: initial
+ * conditions storage must match the signal"); `output` has x's shape, `final_state` the state shape, both complex.  THE CONTRACT: every
+ * part of every channel runs the real recurrence of rmhip_iir_filter, y = b0 x + s0, s[i-1] = (b[i] x + s[i]) - a[i] y, with the
+ * normalised real coefficients, and the two parts never meet (simple_provider.rs:6367-6379) - so the result equals, bit for bit, what
+ * the real entry point gives on the real parts and on the imaginary parts.  This equals the CPU builtin's complex arithmetic
+ * (filter.rs:1199-1219) in value for finite data, because every product with the coefficients' zero imaginary parts vanishes; the sign
+ * of a zero and the propagation of a non-finite part follow this lane rule, not `num-complex`'s cross terms.  A complex tensor of shape
+ * S filtered along `dim` is, byte for byte, a real tensor [2, S...] filtered along dim + 1, and the kernels of the real entry points run
+ * on that view.  The few-channels decline of rmhip_complex_iir_filter counts logical channels and logical elements, so "try the first,
+ * on RMHIP_ERR_UNSUPPORTED the long one" is the same sequence for both storages.  The long form keeps its sibling's three regimes, its
+ * accuracy contract (per part) and its declines; "fewer than 512 samples" and the chunk lengths count logical samples; a non-finite
+ * value in either part declines the request. */
+/* @serves gradient_dim gradient_dim_with_coordinates */
+RMHIP_API int rmhip_complex_gradient_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, double spacing, rmhip_buf coordinates_or_0, rmhip_buf* out);
+/* @serves trapz_dim cumtrapz_dim */
+RMHIP_API int rmhip_complex_trapz_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, int cumulative, int spacing_kind, double scalar, rmhip_buf spacing_or_0,
+                                      rmhip_buf* out);
+/* @serves polyint */
+RMHIP_API int rmhip_complex_polyint(rmhip_ctx* ctx, rmhip_buf p, double constant, rmhip_buf* out);
+/* @serves iir_filter */
+RMHIP_API int rmhip_complex_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator,
+                                       rmhip_buf* output, rmhip_buf* final_state);
+/* @serves iir_filter */
+RMHIP_API int rmhip_complex_iir_filter_long(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator,
+                                            rmhip_buf* output, rmhip_buf* final_state);
 
 /* ---- modulation: symbols and bits to constellation points (comms_ops.hip) -------------------------------------------------------------
  * The two hooks `qammod` and `pskmod` call on a resident tensor (builtins/comms/qammod.rs:71-119, pskmod.rs:73-121).  Request structs:

@@ -468,6 +468,33 @@ public:
         check(rmhip_complex_cat(ctx_, dim_one_based, ids.data(), ids.size(), &id));
         return with_shape(id);
     }
+    // the calculus and filter hooks on complex-interleaved operands: the arguments of the real methods (which keep refusing complex
+    // storage), counted in logical (re, im) elements; the two parts are independent lanes, every result is complex
+    GpuTensorHandle complex_gradient_dim(const GpuTensorHandle& a, size_t dim, double spacing) const {
+        uint64_t out = 0;
+        check(rmhip_complex_gradient_dim(ctx_, own(a), (int)dim, spacing, 0, &out));
+        return with_shape(out);
+    }
+    GpuTensorHandle complex_gradient_dim_with_coordinates(const GpuTensorHandle& a, size_t dim, const GpuTensorHandle& coordinates) const {
+        uint64_t out = 0;
+        check(rmhip_complex_gradient_dim(ctx_, own(a), (int)dim, 1.0, own(coordinates), &out));
+        return with_shape(out);
+    }
+    GpuTensorHandle complex_trapz_dim(const GpuTensorHandle& a, size_t dim, int spacing_kind = 0, double scalar = 1.0, const GpuTensorHandle* spacing = nullptr) const {
+        uint64_t out = 0;
+        check(rmhip_complex_trapz_dim(ctx_, own(a), (int)dim, 0, spacing_kind, scalar, spacing ? own(*spacing) : 0, &out));
+        return with_shape(out);
+    }
+    GpuTensorHandle complex_cumtrapz_dim(const GpuTensorHandle& a, size_t dim, int spacing_kind = 0, double scalar = 1.0, const GpuTensorHandle* spacing = nullptr) const {
+        uint64_t out = 0;
+        check(rmhip_complex_trapz_dim(ctx_, own(a), (int)dim, 1, spacing_kind, scalar, spacing ? own(*spacing) : 0, &out));
+        return with_shape(out);
+    }
+    GpuTensorHandle complex_polyint(const GpuTensorHandle& polynomial, double constant) const {
+        uint64_t out = 0;
+        check(rmhip_complex_polyint(ctx_, own(polynomial), constant, &out));
+        return with_shape(out);
+    }
     GpuTensorHandle scalar_add(const GpuTensorHandle& a, double s) const { return scalar(RMHIP_SADD, a, s); }
     GpuTensorHandle scalar_sub(const GpuTensorHandle& a, double s) const { return scalar(RMHIP_SSUB, a, s); }
     GpuTensorHandle scalar_mul(const GpuTensorHandle& a, double s) const { return scalar(RMHIP_SMUL, a, s); }
@@ -1123,6 +1150,19 @@ public:
                                     bool unit_denominator) const {
         uint64_t out = 0, fin = 0;
         check(rmhip_iir_filter_long(ctx_, own(b), own(a), own(x), (int)dim, zi ? own(*zi) : 0, unit_denominator ? 1 : 0, &out, &fin));
+        return {with_shape(out), with_shape(fin)};
+    }
+    // the same pair for a complex-interleaved signal (and zi): real coefficients, every part of every channel its own real recurrence
+    IirFilterResult complex_iir_filter(const GpuTensorHandle& b, const GpuTensorHandle& a, const GpuTensorHandle& x, size_t dim, const GpuTensorHandle* zi,
+                                       bool unit_denominator) const {
+        uint64_t out = 0, fin = 0;
+        check(rmhip_complex_iir_filter(ctx_, own(b), own(a), own(x), (int)dim, zi ? own(*zi) : 0, unit_denominator ? 1 : 0, &out, &fin));
+        return {with_shape(out), with_shape(fin)};
+    }
+    IirFilterResult complex_iir_filter_long(const GpuTensorHandle& b, const GpuTensorHandle& a, const GpuTensorHandle& x, size_t dim, const GpuTensorHandle* zi,
+                                            bool unit_denominator) const {
+        uint64_t out = 0, fin = 0;
+        check(rmhip_complex_iir_filter_long(ctx_, own(b), own(a), own(x), (int)dim, zi ? own(*zi) : 0, unit_denominator ? 1 : 0, &out, &fin));
         return {with_shape(out), with_shape(fin)};
     }
     // lib.rs:1652-1660; mu == nullptr: no centring / scaling, else {mean, scale}

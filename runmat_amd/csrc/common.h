@@ -364,6 +364,9 @@ int launch_complex_binary_bcast(Context* c, int op, int kind, const double* a, c
 bool complex_unary_is_real(int op);  // abs, angle, real, imag
 // `out`: 2 n doubles for a complex result; n doubles, or n floats when `out_f32`, for a real one
 int launch_complex_unary(Context* c, int op, const double* a, void* out, bool out_f32, size_t n);
+// p[i] = f32(p[i]) in place (misc_ops.hip): the one rounding a precision-32 context applies to the parts of a complex result whose kernels
+// store f64 (the sums behind complex trapz / cumtrapz, the filter kernels run on the two lanes)
+int launch_round_f32(Context* c, double* p, size_t n);
 
 // tensor_ops.hip: out[idx] = src[sum_d map_d(c_d) * stride[d]] with (c_0, c_1, ...) the column-major coordinates of idx in
 // `shape`; map_d(c) = (off[d] + c) % mod[d], or off[d] - c when rev[d] (flip).  One kernel family behind repmat

@@ -11,6 +11,7 @@
 #include <limits>
 
 #include "common.h"
+#include "move_kernels.h"
 
 using namespace rmhip;
 
@@ -85,6 +86,34 @@ __global__ void __launch_bounds__(kB) k_gradient(const double* __restrict__ x, u
         den = coords ? coords[k + 1] - coords[k - 1] : 2.0 * spacing;
     }
     __builtin_nontemporal_store(num / den, out + o);
+}
+
+// The same differences on complex-interleaved elements (gradient.rs:741-841): both neighbours come in as one 16-byte load each, the
+// denominator is the real kernel's, and the result is (x[k+1] - x[k-1]) * (1.0 / den) - the reciprocal rounded once and multiplied into
+// both parts (scale_complex), which is not the real kernel's quotient.  The parts never meet.  `r32`: a precision-32 context rounds
+// each part through f32 on the store.
+__global__ void __launch_bounds__(kB) k_gradient_cx(const v2d* __restrict__ x, u64 pre, u64 len, u64 total, double spacing, const double* __restrict__ coords, int r32,
+                                                    v2d* __restrict__ out) {
+    const u64 o = (u64)blockIdx.x * kB + threadIdx.x;
+    if (o >= total) return;
+    const u64 k = (o / pre) % len;
+    u64 hi, lo;
+    double den;
+    if (k == 0) {
+        hi = o + pre, lo = o;
+        den = coords ? coords[1] - coords[0] : spacing;
+    } else if (k + 1 == len) {
+        hi = o, lo = o - pre;
+        den = coords ? coords[len - 1] - coords[len - 2] : spacing;
+    } else {
+        hi = o + pre, lo = o - pre;
+        den = coords ? coords[k + 1] - coords[k - 1] : 2.0 * spacing;
+    }
+    const v2d a = x[hi], b = x[lo];
+    const double scale = 1.0 / den;
+    v2d r = (a - b) * scale;
+    if (r32) r.x = (double)(float)r.x, r.y = (double)(float)r.y;
+    __builtin_nontemporal_store(r, out + o);
 }
 
 // One workgroup per pair of 32 x 32 tiles (ti <= tj): tile (ti, tj) and its mirror (tj, ti) are both read along their columns
@@ -287,6 +316,35 @@ __global__ void __launch_bounds__(kB) k_trapz_terms(const double* __restrict__ x
     __builtin_nontemporal_store(v, t + o);
 }
 
+// The terms of a complex-interleaved operand (simple_provider.rs:2551-2563, lane_factor 2): the width is indexed by the logical element,
+// exactly as above, and multiplies both parts; one 16-byte element per thread.  The terms are laid out as the interleaved array they
+// are - bitwise a real f64 array [2, shape...] - which the library's sum and scan take along the next dimension.
+template <int KIND>
+__global__ void __launch_bounds__(kB) k_trapz_terms_cx(const v2d* __restrict__ x, u64 pre, u64 len, u64 total, double scalar, const double* __restrict__ sp,
+                                                       v2d* __restrict__ t) {
+    const u64 o = (u64)blockIdx.x * kB + threadIdx.x;
+    if (o >= total) return;
+    const u64 k1 = (o / pre) % len;
+    v2d v = {0.0, 0.0};
+    if (k1 > 0) {
+        const u64 i0 = o - pre;
+        double w = 1.0;
+        if (KIND == 1) w = scalar;
+        if (KIND == 3) w = sp[k1] - sp[k1 - 1];
+        if (KIND == 4) w = sp[o] - sp[i0];
+        const double hw = 0.5 * w;
+        v = (x[i0] + x[o]) * hw;
+    }
+    __builtin_nontemporal_store(v, t + o);
+}
+
+// p[i] = f32(p[i]) in place: what a precision-32 context does to the parts of a complex result that kernels without a rounding store
+// computed (the sums of the terms above, the filter's outputs) - once, after the last f64 operation
+__global__ void __launch_bounds__(kB) k_round_f32(double* __restrict__ p, u64 n) {
+    const u64 i = (u64)blockIdx.x * kB + threadIdx.x;
+    if (i < n) p[i] = (double)(float)p[i];
+}
+
 // norm: one sweep leaves per-workgroup partials - sum |x| (NaN iff the operand holds one), and what the order needs of max |x|, min |x|,
 // the count of nonzeros, the sum of squares, sum |x|^p - and a one-workgroup kernel folds them and writes the [1, 1] result: no read-back.
 // Two / Fro square the values as they are; when the largest magnitude turns out to lie beyond 2^+-500 the fold asks a second sweep for
@@ -472,6 +530,14 @@ int vector_operand(const Buffer& b, const char* what) {
 }
 
 }  // namespace
+
+int launch_round_f32(Context* c, double* p, size_t n) {
+    if (n == 0) return RMHIP_OK;
+    hipLaunchKernelGGL(k_round_f32, dim3(grid_for(n)), dim3(kB), 0, c->stream, p, (u64)n);
+    c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
+}
 }  // namespace rmhip
 
 int rmhip_diag_from_vector(rmhip_ctx* ctx, rmhip_buf vector, long long offset, long long rows_or_neg, long long cols_or_neg, rmhip_buf* out) {
@@ -557,29 +623,74 @@ int rmhip_cross(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, int dim_one_based_or_0
     return RMHIP_OK;
 }
 
-int rmhip_gradient_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, double spacing, rmhip_buf coordinates_or_0, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+// The principal operand of an rmhip_complex_* entry point of the calculus hooks: complex-interleaved, or the refusal that names the sibling
+static int complex_operand(Context* c, const char* who, const char* sibling, rmhip_buf id, Buffer* b) {
+    RMHIP_TRY(c->lookup(id, b));
+    if (!b->cplx) return fail(RMHIP_ERR_UNSUPPORTED, "%s: tensor %llu is real (%s serves it)", who, (unsigned long long)id, sibling);
+    return RMHIP_OK;
+}
+// A real side operand (coordinates, spacing) of either form: complex storage is `refusal`, a lazy view is materialised, f32 storage widened
+static int real_side_operand(Context* c, bool cplx_entry, const char* refusal, rmhip_buf id, Buffer* b) {
+    if (cplx_entry) {
+        RMHIP_TRY(c->lookup(id, b));
+        if (b->cplx) return fail(RMHIP_ERR_UNSUPPORTED, "%s", refusal);
+    }
+    return c->get(id, b);
+}
+
+// `cplx`: the call came through rmhip_complex_gradient_dim, which takes complex-interleaved storage only (extents count logical elements)
+static int gradient_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf a, int dim, double spacing, rmhip_buf coordinates_or_0, rmhip_buf* out) {
     if (!out) return fail(RMHIP_ERR_INVALID, "null out");
     if (dim < 0) return fail(RMHIP_ERR_INVALID, "gradient_dim: dim must be >= 0");
     Buffer ab, cb, ob;
-    RMHIP_TRY(c->get(a, &ab));
+    if (cplx) {
+        *out = 0;
+        RMHIP_TRY(complex_operand(c, "complex_gradient_dim", "rmhip_gradient_dim", a, &ab));
+    } else {
+        RMHIP_TRY(c->get(a, &ab));
+    }
     const std::vector<size_t> shape = matrix_shape(ab.shape);
     u64 pre = 1, len = 1;
     for (size_t k = 0; k < shape.size() && k < (size_t)dim; ++k) pre *= shape[k];
     if ((size_t)dim < shape.size()) len = shape[dim];
     const double* coords = nullptr;
     if (coordinates_or_0) {
-        RMHIP_TRY(c->get(coordinates_or_0, &cb));
+        RMHIP_TRY(real_side_operand(c, cplx, "gradient_dim_with_coordinates: coordinates must be real", coordinates_or_0, &cb));
         if (cb.numel != len) return fail(RMHIP_ERR_SHAPE, "gradient: coordinate vector length must match the dimension (%zu vs %llu)", cb.numel, len);
         coords = cb.data();
     }
-    RMHIP_TRY(c->new_buffer(shape.data(), shape.size(), out, &ob));
+    if (cplx) RMHIP_TRY(c->new_buffer_complex(shape.data(), shape.size(), out, &ob));
+    else RMHIP_TRY(c->new_buffer(shape.data(), shape.size(), out, &ob));
     if (ob.numel == 0) return RMHIP_OK;
-    if (len <= 1) return launch_fill(c, ob.data(), ob.numel, 0.0);  // gradient.rs:691-692: nothing to difference
-    hipLaunchKernelGGL(k_gradient, dim3(grid_for(ob.numel)), dim3(kB), 0, c->stream, ab.data(), pre, len, (u64)ob.numel, spacing, coords, ob.data());
-    c->tel.kernel_launches++;
-    RMHIP_HIP_CHECK(hipGetLastError());
-    return RMHIP_OK;
+    if (!cplx) {
+        if (len <= 1) return launch_fill(c, ob.data(), ob.numel, 0.0);  // gradient.rs:691-692: nothing to difference
+        hipLaunchKernelGGL(k_gradient, dim3(grid_for(ob.numel)), dim3(kB), 0, c->stream, ab.data(), pre, len, (u64)ob.numel, spacing, coords, ob.data());
+        c->tel.kernel_launches++;
+        RMHIP_HIP_CHECK(hipGetLastError());
+        return RMHIP_OK;
+    }
+    int rc = RMHIP_OK;
+    if (len <= 1) {  // gradient.rs:778-779
+        rc = launch_fill(c, ob.data(), 2 * ob.numel, 0.0);
+    } else {
+        hipLaunchKernelGGL(k_gradient_cx, dim3(grid_for(ob.numel)), dim3(kB), 0, c->stream, reinterpret_cast<const v2d*>(ab.data()), pre, len, (u64)ob.numel, spacing,
+                           coords, c->precision == 32 ? 1 : 0, reinterpret_cast<v2d*>(ob.data()));
+        c->tel.kernel_launches++;
+        if (hipGetLastError() != hipSuccess) rc = fail(RMHIP_ERR_HIP, "complex_gradient_dim: launch failed");
+    }
+    if (rc != RMHIP_OK) {
+        rmhip_free(ctx, *out);
+        *out = 0;
+    }
+    return rc;
+}
+int rmhip_gradient_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, double spacing, rmhip_buf coordinates_or_0, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return gradient_any(ctx, c, false, a, dim, spacing, coordinates_or_0, out);
+}
+int rmhip_complex_gradient_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, double spacing, rmhip_buf coordinates_or_0, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return gradient_any(ctx, c, true, a, dim, spacing, coordinates_or_0, out);
 }
 
 static int symmetry_test(Context* c, const char* who, rmhip_buf a, int mode, double tolerance, int* result) {
@@ -737,12 +848,18 @@ int rmhip_corrcoef(rmhip_ctx* ctx, rmhip_buf matrix, int biased, int rows_mode, 
     return rc;
 }
 
-int rmhip_trapz_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, int cumulative, int spacing_kind, double scalar, rmhip_buf spacing_or_0, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+// `cplx`: the call came through rmhip_complex_trapz_dim, which takes complex-interleaved storage only (extents count logical elements)
+static int trapz_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf a, int dim, int cumulative, int spacing_kind, double scalar, rmhip_buf spacing_or_0,
+                     rmhip_buf* out) {
     if (!out) return fail(RMHIP_ERR_INVALID, "null out");
     if (dim < 0) return fail(RMHIP_ERR_INVALID, "trapezoid: dim must be >= 0");
     Buffer ab, sb;
-    RMHIP_TRY(c->get(a, &ab));
+    if (cplx) {
+        *out = 0;
+        RMHIP_TRY(complex_operand(c, "complex_trapz_dim", "rmhip_trapz_dim", a, &ab));
+    } else {
+        RMHIP_TRY(c->get(a, &ab));
+    }
     std::vector<size_t> shape = matrix_shape(ab.shape);
     while (shape.size() <= (size_t)dim) shape.push_back(1);  // simple_provider.rs:2497-2499
     u64 pre = 1;
@@ -751,13 +868,13 @@ int rmhip_trapz_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, int cumulative, int sp
     const double* sp = nullptr;
     int kind = spacing_kind;
     if (kind == 2) {  // ScalarHandle: the first element of a resident tensor
-        RMHIP_TRY(c->get(spacing_or_0, &sb));
+        RMHIP_TRY(real_side_operand(c, cplx, "trapezoid: spacing tensor must be real", spacing_or_0, &sb));
         if (sb.numel == 0) return fail(RMHIP_ERR_INVALID, "trapezoid: scalar spacing is empty");
         RMHIP_HIP_CHECK(hipMemcpyAsync(&scalar, sb.data(), sizeof(double), hipMemcpyDeviceToHost, c->stream));
         RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
         kind = 1;
     } else if (kind == 3 || kind == 4) {
-        RMHIP_TRY(c->get(spacing_or_0, &sb));
+        RMHIP_TRY(real_side_operand(c, cplx, kind == 3 ? "trapezoid: spacing vector must be real" : "trapezoid: spacing tensor must be real", spacing_or_0, &sb));
         if (kind == 3 && sb.numel < len) return fail(RMHIP_ERR_SHAPE, "trapezoid: spacing vector is shorter than integration dimension");
         if (kind == 4 && sb.numel < ab.numel) return fail(RMHIP_ERR_SHAPE, "trapezoid: spacing tensor is smaller than input");
         sp = sb.data();
@@ -766,6 +883,44 @@ int rmhip_trapz_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, int cumulative, int sp
     }
     std::vector<size_t> oshape = shape;
     if (!cumulative) oshape[dim] = 1;
+    if (cplx) {
+        // The terms as the interleaved array they are, in storage of their own (f64 in either precision mode: nothing on the way to the
+        // sums is rounded through f32), summed along the middle extent of the real view [2 * pre, len, post] by the library's reduction and
+        // scan launchers straight into the complex result.
+        Buffer ob;
+        RMHIP_TRY(c->new_buffer_complex(oshape.data(), oshape.size(), out, &ob));
+        if (ob.numel == 0) return RMHIP_OK;
+        int rc = RMHIP_OK;
+        if (ab.numel == 0 || len <= 1) {  // simple_provider.rs:2545-2546, 2576-2577
+            rc = launch_fill(c, ob.data(), 2 * ob.numel, 0.0);
+        } else {
+            std::shared_ptr<Allocation> terms;
+            rc = c->alloc_device(2 * ab.numel, &terms);
+            if (rc == RMHIP_OK) {
+                const unsigned grid = grid_for(ab.numel);
+                const v2d* x = reinterpret_cast<const v2d*>(ab.data());
+                v2d* t = reinterpret_cast<v2d*>(terms->ptr);
+                switch (kind) {
+                    case 0: hipLaunchKernelGGL(k_trapz_terms_cx<0>, dim3(grid), dim3(kB), 0, c->stream, x, pre, len, (u64)ab.numel, scalar, sp, t); break;
+                    case 1: hipLaunchKernelGGL(k_trapz_terms_cx<1>, dim3(grid), dim3(kB), 0, c->stream, x, pre, len, (u64)ab.numel, scalar, sp, t); break;
+                    case 3: hipLaunchKernelGGL(k_trapz_terms_cx<3>, dim3(grid), dim3(kB), 0, c->stream, x, pre, len, (u64)ab.numel, scalar, sp, t); break;
+                    default: hipLaunchKernelGGL(k_trapz_terms_cx<4>, dim3(grid), dim3(kB), 0, c->stream, x, pre, len, (u64)ab.numel, scalar, sp, t); break;
+                }
+                c->tel.kernel_launches++;
+                if (hipGetLastError() != hipSuccess) rc = fail(RMHIP_ERR_HIP, "trapezoid: launch failed");
+            }
+            const size_t post = ab.numel / (size_t)(pre * len);
+            if (rc == RMHIP_OK)
+                rc = cumulative ? launch_cumulative(c, 0, 0, 0, terms->ptr, 2 * pre, len, post, ob.data())
+                                : launch_reduce_mid(c, RMHIP_RSUM, 0, terms->ptr, 2 * pre, len, post, ob.data());
+            if (rc == RMHIP_OK && c->precision == 32) rc = launch_round_f32(c, ob.data(), 2 * ob.numel);
+        }
+        if (rc != RMHIP_OK) {
+            rmhip_free(ctx, *out);
+            *out = 0;
+        }
+        return rc;
+    }
     if (ab.numel == 0 || len <= 1) {  // nothing to integrate: zeros of the output's shape (simple_provider.rs:2544-2546, 2576-2577)
         Buffer ob;
         RMHIP_TRY(c->new_buffer(oshape.data(), oshape.size(), out, &ob));
@@ -786,6 +941,14 @@ int rmhip_trapz_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, int cumulative, int sp
     if (!rc) rc = cumulative ? rmhip_cumulative(ctx, 0, tid, dim, 0, 0, out) : rmhip_reduce(ctx, RMHIP_RSUM, tid, dim, 0, out);
     rmhip_free(ctx, tid);
     return rc;
+}
+int rmhip_trapz_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, int cumulative, int spacing_kind, double scalar, rmhip_buf spacing_or_0, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return trapz_any(ctx, c, false, a, dim, cumulative, spacing_kind, scalar, spacing_or_0, out);
+}
+int rmhip_complex_trapz_dim(rmhip_ctx* ctx, rmhip_buf a, int dim, int cumulative, int spacing_kind, double scalar, rmhip_buf spacing_or_0, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return trapz_any(ctx, c, true, a, dim, cumulative, spacing_kind, scalar, spacing_or_0, out);
 }
 
 // order: 1 One, 2 Two, 3 Inf, 4 NegInf, 5 Zero, 6 Fro, 7 Nuc, 8 P(p)  (ProviderNormOrder, lib.rs:745-754)

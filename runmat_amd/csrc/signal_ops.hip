@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "move_kernels.h"
 
 using namespace rmhip;
 
@@ -836,6 +837,21 @@ __global__ void __launch_bounds__(kB) k_poly(PolyVec p, PolyVec q, int mode, dou
     out[k] = r;
 }
 
+// polyint of a complex-interleaved polynomial (simple_provider.rs:391-409): both parts of coefficient k over the power n - k, a true
+// division each; the appended element is (constant, +0).  `r32`: a precision-32 context rounds each part through f32 on the store.
+__global__ void __launch_bounds__(kB) k_polyint_cx(const v2d* __restrict__ p, u64 n, double constant, u64 len, int r32, v2d* __restrict__ out) {
+    const u64 k = (u64)blockIdx.x * kB + threadIdx.x;
+    if (k >= len) return;
+    v2d r = {constant, 0.0};
+    if (k < n) {
+        const double power = (double)(n - k);
+        const v2d cf = p[k];
+        r.x = cf.x / power, r.y = cf.y / power;
+    }
+    if (r32) r.x = (double)(float)r.x, r.y = (double)(float)r.y;
+    out[k] = r;
+}
+
 // poly_trim_slice: the first coefficient with |c| > 1e-12 (a NaN does not count), or len if there is none
 __global__ void __launch_bounds__(kB) k_poly_first(const double* __restrict__ x, u64 len, unsigned long long* __restrict__ first) {
     __shared__ unsigned long long best;
@@ -1325,18 +1341,36 @@ struct IirRequest {
     Buffer xb, zb;
     bool has_zi = false;
     size_t order = 0, state_len = 0;
+    // 2 for a complex-interleaved signal: a complex tensor of shape S filtered along `dim` is, byte for byte, the real tensor [2, S...]
+    // filtered along dim + 1 (and so are zi and zf), so `leading` and `channels` are twice the logical ones and every kernel below runs
+    // the real recurrence on each part - the parts never meet (simple_provider.rs:6367-6379)
+    size_t lanes = 1;
     u64 leading = 1, dim_len = 0, channels = 0;
+    size_t raw(const Buffer& b) const { return lanes * b.numel; }  // doubles in a signal-shaped or state-shaped tensor
     std::vector<size_t> zshape;
     std::vector<double> coef;
 };
 
 // The validation and normalisation of `iir_filter` (filter.rs:1119-1138), shared by rmhip_iir_filter and rmhip_iir_filter_long;
-// `few_channels_ok`: the long form, which keeps the shapes the one-thread-per-channel form declines
-int iir_prepare(Context* c, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, bool few_channels_ok, IirRequest* r) {
+// `few_channels_ok`: the long form, which keeps the shapes the one-thread-per-channel form declines.  `cplx`: the call came through
+// rmhip_complex_iir_filter(_long): the signal and the initial states are complex-interleaved, the coefficients real.
+int iir_prepare(Context* c, bool cplx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, bool few_channels_ok, IirRequest* r) {
     Buffer bb, ab;
+    if (cplx) {
+        RMHIP_TRY(c->lookup(x, &r->xb));
+        if (!r->xb.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_iir_filter: tensor %llu is real (rmhip_iir_filter serves it)", (unsigned long long)x);
+        RMHIP_TRY(c->lookup(b, &bb));
+        RMHIP_TRY(c->lookup(a, &ab));
+        if (bb.cplx || ab.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: complex filter coefficients are not supported");
+        if (zi_or_0) {
+            RMHIP_TRY(c->lookup(zi_or_0, &r->zb));
+            if (!r->zb.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: initial conditions storage must match the signal");
+        }
+        r->lanes = 2;
+    }
     RMHIP_TRY(c->get(b, &bb));
     RMHIP_TRY(c->get(a, &ab));
-    RMHIP_TRY(c->get(x, &r->xb));
+    if (!cplx) RMHIP_TRY(c->get(x, &r->xb));
     const Buffer& xb = r->xb;
     const size_t nb = bb.numel, na = unit_denominator ? 1 : ab.numel;
     if (nb == 0) return fail(RMHIP_ERR_INVALID, "iir_filter: numerator coefficients must not be empty");
@@ -1358,7 +1392,7 @@ int iir_prepare(Context* c, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhi
     zshape = shape;
     zshape[dim] = state_len;
     if (zi_or_0) {
-        RMHIP_TRY(c->get(zi_or_0, &r->zb));
+        if (!cplx) RMHIP_TRY(c->get(zi_or_0, &r->zb));
         r->has_zi = true;
         const Buffer& zb = r->zb;
         const size_t rk = std::max(zshape.size(), zb.shape.size());
@@ -1379,6 +1413,7 @@ int iir_prepare(Context* c, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhi
     for (size_t i = 0; i < nb; ++i) coef[i] = (hb[i] * a0 + 0.0) / den;
     coef[order] = 1.0;
     for (size_t i = 1; i < na; ++i) coef[order + i] = (ha[i] * a0 + 0.0) / den;
+    r->leading *= r->lanes, r->channels *= r->lanes;  // (the few-channels decline above counted logical channels and elements)
     return RMHIP_OK;
 }
 
@@ -1396,9 +1431,9 @@ int iir_launch_sequential(Context* c, const double* x, const double* zi, const d
 int iir_run_sequential(Context* c, const IirRequest& r, const Buffer& yb, const Buffer& fb) {
     const Buffer& xb = r.xb;
     if (r.state_len == 0) {
-        if (yb.numel) return launch_scalar(c, RMHIP_SMUL, xb.data(), r.coef[0], yb.data(), yb.numel);  // gain * x (filter.rs:1172-1176)
+        if (yb.numel) return launch_scalar(c, RMHIP_SMUL, xb.data(), r.coef[0], yb.data(), r.raw(yb));  // gain * x (filter.rs:1172-1176)
     } else if (r.has_zi && (r.dim_len == 0 || r.channels == 0)) {
-        if (fb.numel) RMHIP_HIP_CHECK(hipMemcpyAsync(fb.data(), r.zb.data(), fb.numel * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (fb.numel) RMHIP_HIP_CHECK(hipMemcpyAsync(fb.data(), r.zb.data(), r.raw(fb) * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     } else if (r.channels > 0) {
         std::shared_ptr<Allocation> dc;
         RMHIP_TRY(c->alloc_device(2 * r.order, &dc));
@@ -1417,11 +1452,11 @@ constexpr u64 IIRL_CHUNKS[] = {256, 512, 1024, 2048, 4096, 8192};
 int iir_run_fir(Context* c, const IirRequest& r, const double* coef_dev, const Buffer& yb, const Buffer& fb) {
     const double* zi = r.has_zi ? r.zb.data() : nullptr;
     const u64 tiles = r.leading == 1 ? (r.dim_len + kB - 1) / kB : 0;  // the contiguous dimension: a block per tile of a channel
-    const u64 blocks = tiles ? tiles * r.channels : grid_for(yb.numel);
-    hipLaunchKernelGGL(k_fir_long, dim3(blocks), dim3(kB), 0, c->stream, r.xb.data(), zi, coef_dev, (int)r.order, r.leading, r.dim_len, (u64)yb.numel, tiles,
+    const u64 blocks = tiles ? tiles * r.channels : grid_for(r.raw(yb));
+    hipLaunchKernelGGL(k_fir_long, dim3(blocks), dim3(kB), 0, c->stream, r.xb.data(), zi, coef_dev, (int)r.order, r.leading, r.dim_len, (u64)r.raw(yb), tiles,
                        yb.data(), c->verdict_word);
-    hipLaunchKernelGGL(k_fir_long_state, dim3(grid_for(fb.numel)), dim3(kB), 0, c->stream, r.xb.data(), zi, coef_dev, (int)r.order, r.leading, r.dim_len,
-                       (u64)fb.numel, fb.data(), c->verdict_word);
+    hipLaunchKernelGGL(k_fir_long_state, dim3(grid_for(r.raw(fb))), dim3(kB), 0, c->stream, r.xb.data(), zi, coef_dev, (int)r.order, r.leading, r.dim_len,
+                       (u64)r.raw(fb), fb.data(), c->verdict_word);
     c->tel.kernel_launches += 2;
     RMHIP_HIP_CHECK(hipGetLastError());
     return RMHIP_OK;
@@ -1496,18 +1531,32 @@ int iir_run_chunked(Context* c, const IirRequest& r, const double* coef_dev, con
 }
 }  // namespace
 
-int rmhip_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
-                     rmhip_buf* final_state) {
-    CTX_OR_FAIL(ctx);
+namespace {
+// A signal-shaped or state-shaped result: real, or complex-interleaved when the signal is
+int iir_new_result(Context* c, const IirRequest& r, const std::vector<size_t>& shape, rmhip_buf* id, Buffer* out) {
+    return r.lanes == 2 ? c->new_buffer_complex(shape.data(), shape.size(), id, out) : c->new_buffer(shape.data(), shape.size(), id, out);
+}
+// A precision-32 context rounds the parts of a complex result through f32 once, after the last f64 operation (real results are narrowed
+// by the entry point's scope)
+int iir_round_results(Context* c, const IirRequest& r, const Buffer& yb, const Buffer& fb) {
+    if (r.lanes != 2 || c->precision != 32) return RMHIP_OK;
+    RMHIP_TRY(launch_round_f32(c, yb.data(), r.raw(yb)));
+    return launch_round_f32(c, fb.data(), r.raw(fb));
+}
+
+// `cplx`: the call came through rmhip_complex_iir_filter
+int iir_filter_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
+                   rmhip_buf* final_state) {
     if (!output || !final_state) return fail(RMHIP_ERR_INVALID, "iir_filter: null output");
     if (dim < 0) return fail(RMHIP_ERR_INVALID, "iir_filter: dim must be >= 0");
     *output = *final_state = 0;
     IirRequest r;
-    RMHIP_TRY(iir_prepare(c, b, a, x, dim, zi_or_0, unit_denominator, false, &r));
+    RMHIP_TRY(iir_prepare(c, cplx, b, a, x, dim, zi_or_0, unit_denominator, false, &r));
     Buffer yb, fb;
-    RMHIP_TRY(c->new_buffer(r.xb.shape.data(), r.xb.shape.size(), output, &yb));
-    int rc = c->new_buffer(r.zshape.data(), r.zshape.size(), final_state, &fb);
+    RMHIP_TRY(iir_new_result(c, r, r.xb.shape, output, &yb));
+    int rc = iir_new_result(c, r, r.zshape, final_state, &fb);
     if (rc == RMHIP_OK) rc = iir_run_sequential(c, r, yb, fb);
+    if (rc == RMHIP_OK) rc = iir_round_results(c, r, yb, fb);
     if (rc != RMHIP_OK) {
         rmhip_free(ctx, *output);
         if (*final_state) rmhip_free(ctx, *final_state);
@@ -1516,15 +1565,15 @@ int rmhip_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int 
     return rc;
 }
 
-int rmhip_iir_filter_long(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
-                          rmhip_buf* final_state) {
-    CTX_OR_FAIL(ctx);
+// `cplx`: the call came through rmhip_complex_iir_filter_long
+int iir_filter_long_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator,
+                        rmhip_buf* output, rmhip_buf* final_state) {
     if (!output || !final_state) return fail(RMHIP_ERR_INVALID, "iir_filter: null output");
     if (dim < 0) return fail(RMHIP_ERR_INVALID, "iir_filter: dim must be >= 0");
     *output = *final_state = 0;
     IirRequest r;
-    RMHIP_TRY(iir_prepare(c, b, a, x, dim, zi_or_0, unit_denominator, true, &r));
-    if (r.xb.numel > 0x7fffffffull * kB) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: %zu samples", r.xb.numel);
+    RMHIP_TRY(iir_prepare(c, cplx, b, a, x, dim, zi_or_0, unit_denominator, true, &r));
+    if (r.raw(r.xb) > 0x7fffffffull * kB) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: %zu samples", r.xb.numel);
     bool fir = true, finite = true;
     for (size_t i = 0; i < 2 * r.order; ++i) finite = finite && std::isfinite(r.coef[i]);
     for (size_t i = 1; i < r.order; ++i) fir = fir && r.coef[r.order + i] == 0.0;
@@ -1532,8 +1581,8 @@ int rmhip_iir_filter_long(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x,
     const bool plain = r.state_len == 0 || r.channels == 0 || r.dim_len < 2 * IIRL_CHUNKS[0];
     if (!plain && !finite) return fail(RMHIP_ERR_UNSUPPORTED, "iir_filter: non-finite coefficients");
     Buffer yb, fb;
-    RMHIP_TRY(c->new_buffer(r.xb.shape.data(), r.xb.shape.size(), output, &yb));
-    int rc = c->new_buffer(r.zshape.data(), r.zshape.size(), final_state, &fb);
+    RMHIP_TRY(iir_new_result(c, r, r.xb.shape, output, &yb));
+    int rc = iir_new_result(c, r, r.zshape, final_state, &fb);
     auto chunked = [&]() -> int {
         if (!c->verdict_word) RMHIP_HIP_CHECK(hipMalloc((void**)&c->verdict_word, sizeof(unsigned)));
         RMHIP_HIP_CHECK(hipMemsetAsync(c->verdict_word, 0xff, sizeof(unsigned), c->stream));
@@ -1552,12 +1601,35 @@ int rmhip_iir_filter_long(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x,
         return RMHIP_OK;
     };
     if (rc == RMHIP_OK) rc = plain ? iir_run_sequential(c, r, yb, fb) : chunked();
+    if (rc == RMHIP_OK) rc = iir_round_results(c, r, yb, fb);
     if (rc != RMHIP_OK) {
         rmhip_free(ctx, *output);
         if (*final_state) rmhip_free(ctx, *final_state);
         *output = *final_state = 0;
     }
     return rc;
+}
+}  // namespace
+
+int rmhip_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
+                     rmhip_buf* final_state) {
+    CTX_OR_FAIL(ctx);
+    return iir_filter_any(ctx, c, false, b, a, x, dim, zi_or_0, unit_denominator, output, final_state);
+}
+int rmhip_complex_iir_filter(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
+                             rmhip_buf* final_state) {
+    CTX_OR_FAIL(ctx);
+    return iir_filter_any(ctx, c, true, b, a, x, dim, zi_or_0, unit_denominator, output, final_state);
+}
+int rmhip_iir_filter_long(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
+                          rmhip_buf* final_state) {
+    CTX_OR_FAIL(ctx);
+    return iir_filter_long_any(ctx, c, false, b, a, x, dim, zi_or_0, unit_denominator, output, final_state);
+}
+int rmhip_complex_iir_filter_long(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf x, int dim, rmhip_buf zi_or_0, int unit_denominator, rmhip_buf* output,
+                                  rmhip_buf* final_state) {
+    CTX_OR_FAIL(ctx);
+    return iir_filter_long_any(ctx, c, true, b, a, x, dim, zi_or_0, unit_denominator, output, final_state);
 }
 
 int rmhip_imfilter(rmhip_ctx* ctx, rmhip_buf image, rmhip_buf kernel, int padding, double constant_value, int shape_mode, int convolution, rmhip_buf* out) {
@@ -1745,23 +1817,49 @@ int rmhip_polyder(rmhip_ctx* ctx, rmhip_buf p, rmhip_buf q_or_0, int quotient, r
     return rc;
 }
 
-int rmhip_polyint(rmhip_ctx* ctx, rmhip_buf p, double constant, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+// `cplx`: the call came through rmhip_complex_polyint, which takes complex-interleaved storage only (lengths count logical coefficients)
+static int polyint_any(rmhip_ctx* ctx, Context* c, bool cplx, rmhip_buf p, double constant, rmhip_buf* out) {
     if (!out) return fail(RMHIP_ERR_INVALID, "null out");
     Buffer pb;
-    RMHIP_TRY(c->get(p, &pb));
+    if (cplx) {
+        *out = 0;
+        RMHIP_TRY(c->lookup(p, &pb));
+        if (!pb.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_polyint: tensor %llu is real (rmhip_polyint serves it)", (unsigned long long)p);
+    } else {
+        RMHIP_TRY(c->get(p, &pb));
+    }
     int orientation = 0;
     RMHIP_TRY(poly_orientation(pb.shape, &orientation));
     const u64 len = (u64)pb.numel + 1;
     if (len > 0x7fffffffull * kB) return fail(RMHIP_ERR_UNSUPPORTED, "polyint: %zu coefficients", pb.numel);
     const size_t shape[2] = {orientation == 2 && len > 1 ? (size_t)len : 1, orientation == 2 || len <= 1 ? 1 : (size_t)len};
     Buffer ob;
+    if (cplx) {  // (simple_provider.rs:3205-3217: the same orientation rule on the logical length)
+        RMHIP_TRY(c->new_buffer_complex(shape, 2, out, &ob));
+        hipLaunchKernelGGL(k_polyint_cx, dim3(grid_for(len)), dim3(kB), 0, c->stream, reinterpret_cast<const v2d*>(pb.data()), (u64)pb.numel, constant, len,
+                           c->precision == 32 ? 1 : 0, reinterpret_cast<v2d*>(ob.data()));
+        c->tel.kernel_launches++;
+        if (hipGetLastError() != hipSuccess) {
+            rmhip_free(ctx, *out);
+            *out = 0;
+            return fail(RMHIP_ERR_HIP, "complex_polyint: launch failed");
+        }
+        return RMHIP_OK;
+    }
     RMHIP_TRY(c->new_buffer(shape, 2, out, &ob));
     const PolyVec pv{pb.numel ? pb.data() : nullptr, (u64)pb.numel};
     hipLaunchKernelGGL(k_poly, dim3(grid_for(len)), dim3(kB), 0, c->stream, pv, pv, 4, constant, len, ob.data());
     c->tel.kernel_launches++;
     RMHIP_HIP_CHECK(hipGetLastError());
     return RMHIP_OK;
+}
+int rmhip_polyint(rmhip_ctx* ctx, rmhip_buf p, double constant, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return polyint_any(ctx, c, false, p, constant, out);
+}
+int rmhip_complex_polyint(rmhip_ctx* ctx, rmhip_buf p, double constant, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    return polyint_any(ctx, c, true, p, constant, out);
 }
 
 int rmhip_window(rmhip_ctx* ctx, int kind, size_t len, int periodic, rmhip_buf* out) {

@@ -574,6 +574,19 @@ class HipProvider:
     def complex_flip(self, a, axes): return self.flip(a, axes, entry="rmhip_complex_flip")
     def complex_cat(self, dim, inputs): return self.cat(dim, inputs, entry="rmhip_complex_cat")
 
+    # The calculus and filter hooks on complex-interleaved operands (include/rmhip.h): the arguments of the real methods, which keep refusing
+    # complex storage; extents and `dim` count logical (re, im) elements, the two parts are independent lanes, every result is complex.
+    def complex_gradient_dim(self, a, dim, spacing=1.0): return self.gradient_dim(a, dim, spacing, entry="rmhip_complex_gradient_dim")
+    def complex_gradient_dim_with_coordinates(self, a, dim, coordinates):
+        return self.gradient_dim_with_coordinates(a, dim, coordinates, entry="rmhip_complex_gradient_dim")
+    def complex_trapz_dim(self, a, dim, spacing=None): return self.trapz_dim(a, dim, spacing, entry="rmhip_complex_trapz_dim")
+    def complex_cumtrapz_dim(self, a, dim, spacing=None): return self.cumtrapz_dim(a, dim, spacing, entry="rmhip_complex_trapz_dim")
+    def complex_polyint(self, polynomial, constant=0.0): return self.polyint(polynomial, constant, entry="rmhip_complex_polyint")
+    def complex_iir_filter(self, b, a, x, dim, zi=None, unit_denominator=False):
+        return self.iir_filter(b, a, x, dim, zi, unit_denominator, entry="rmhip_complex_iir_filter")
+    def complex_iir_filter_long(self, b, a, x, dim, zi=None, unit_denominator=False):
+        return self.iir_filter_long(b, a, x, dim, zi, unit_denominator, entry="rmhip_complex_iir_filter_long")
+
     def elem_add(self, a, b): return self._binary("add", a, b)
     def elem_sub(self, a, b): return self._binary("sub", a, b)
     def elem_mul(self, a, b): return self._binary("mul", a, b)
@@ -1454,19 +1467,19 @@ class HipProvider:
         self._check(self._lib.rmhip_cross(self._ctx, self._id(lhs), self._id(rhs), 0 if dim is None else int(dim), C.byref(out)))
         return self._handle(out.value)
 
-    def gradient_dim(self, a, dim: int, spacing: float = 1.0) -> GpuTensorHandle:
+    def gradient_dim(self, a, dim: int, spacing: float = 1.0, *, entry: str = "rmhip_gradient_dim") -> GpuTensorHandle:
         """lib.rs:2604-2611: zero-based dim, scalar spacing (gradient.rs:650-720)."""
         out = C.c_uint64()
-        self._check(self._lib.rmhip_gradient_dim(self._ctx, self._id(a), int(dim), float(spacing), 0, C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(a), int(dim), float(spacing), 0, C.byref(out)))
         return self._handle(out.value)
 
-    def gradient_dim_with_coordinates(self, a, dim: int, coordinates) -> GpuTensorHandle:
+    def gradient_dim_with_coordinates(self, a, dim: int, coordinates, *, entry: str = "rmhip_gradient_dim") -> GpuTensorHandle:
         """lib.rs:2612-2620: denominators from a resident coordinate vector of the dimension's extent."""
         out = C.c_uint64()
-        self._check(self._lib.rmhip_gradient_dim(self._ctx, self._id(a), int(dim), 1.0, self._id(coordinates), C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(a), int(dim), 1.0, self._id(coordinates), C.byref(out)))
         return self._handle(out.value)
 
-    def _trapz(self, a, dim: int, spacing, cumulative: bool) -> GpuTensorHandle:
+    def _trapz(self, a, dim: int, spacing, cumulative: bool, entry: str = "rmhip_trapz_dim") -> GpuTensorHandle:
         kind, scalar, sid = 0, 0.0, 0
         if spacing is None:
             pass
@@ -1477,17 +1490,17 @@ class HipProvider:
             kind = {"scalar_handle": 2, "vector": 3, "tensor": 4}[name]
             sid = self._id(h)
         out = C.c_uint64()
-        self._check(self._lib.rmhip_trapz_dim(self._ctx, self._id(a), int(dim), 1 if cumulative else 0, kind, scalar, sid, C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(a), int(dim), 1 if cumulative else 0, kind, scalar, sid, C.byref(out)))
         return self._handle(out.value)
 
-    def trapz_dim(self, a, dim: int, spacing=None) -> GpuTensorHandle:
+    def trapz_dim(self, a, dim: int, spacing=None, *, entry: str = "rmhip_trapz_dim") -> GpuTensorHandle:
         """lib.rs:2893-2900; `ProviderTrapezoidSpacing` (:1060-1066) as None (Unit), a float (Scalar) or ("scalar_handle" | "vector" |
         "tensor", handle)."""
-        return self._trapz(a, dim, spacing, False)
+        return self._trapz(a, dim, spacing, False, entry)
 
-    def cumtrapz_dim(self, a, dim: int, spacing=None) -> GpuTensorHandle:
+    def cumtrapz_dim(self, a, dim: int, spacing=None, *, entry: str = "rmhip_trapz_dim") -> GpuTensorHandle:
         """lib.rs:2901-2908."""
-        return self._trapz(a, dim, spacing, True)
+        return self._trapz(a, dim, spacing, True, entry)
 
     def norm(self, tensor, order="two", p: float = 2.0) -> GpuTensorHandle:
         """lib.rs:2451-2457; `ProviderNormOrder` (:745-754) as "one" | "two" | "inf" | "-inf" | "zero" | "fro" | "nuc" | "p" (with `p`) -> [1, 1]."""
@@ -1612,19 +1625,19 @@ class HipProvider:
         self._check(self._lib.rmhip_ismember_rows(self._ctx, self._id(a), self._id(b), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), loc.ctypes.data_as(C.POINTER(C.c_double))))
         return mask[:ra].reshape(ra, 1).copy(), loc[:ra].reshape(ra, 1).copy()
 
-    def iir_filter(self, b, a, x, dim: int, zi=None, unit_denominator: bool = False):
+    def iir_filter(self, b, a, x, dim: int, zi=None, unit_denominator: bool = False, *, entry: str = "rmhip_iir_filter"):
         """lib.rs:2551-2559 -> `ProviderIirFilterResult { output, final_state }` as a pair of handles."""
         out, fin = C.c_uint64(), C.c_uint64()
-        self._check(self._lib.rmhip_iir_filter(self._ctx, self._id(b), self._id(a), self._id(x), int(dim), self._id(zi) if zi is not None else 0,
-                                               1 if unit_denominator else 0, C.byref(out), C.byref(fin)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(b), self._id(a), self._id(x), int(dim), self._id(zi) if zi is not None else 0,
+                                              1 if unit_denominator else 0, C.byref(out), C.byref(fin)))
         return self._handle(out.value), self._handle(fin.value)
 
-    def iir_filter_long(self, b, a, x, dim: int, zi=None, unit_denominator: bool = False):
+    def iir_filter_long(self, b, a, x, dim: int, zi=None, unit_denominator: bool = False, *, entry: str = "rmhip_iir_filter_long"):
         """The hook's second entry point, for the long signals with few channels that `iir_filter` declines: a nested sum per sample for an
         FIR filter, a chunked scan for a recursive one (within the accuracy contract of rmhip.h, not bit for bit).  Same result pair."""
         out, fin = C.c_uint64(), C.c_uint64()
-        self._check(self._lib.rmhip_iir_filter_long(self._ctx, self._id(b), self._id(a), self._id(x), int(dim), self._id(zi) if zi is not None else 0,
-                                                    1 if unit_denominator else 0, C.byref(out), C.byref(fin)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(b), self._id(a), self._id(x), int(dim), self._id(zi) if zi is not None else 0,
+                                              1 if unit_denominator else 0, C.byref(out), C.byref(fin)))
         return self._handle(out.value), self._handle(fin.value)
 
     def imfilter(self, image, kernel, padding="constant", shape: str = "same", mode: str = "correlation") -> GpuTensorHandle:
@@ -1674,10 +1687,10 @@ class HipProvider:
         """lib.rs:1691-1701 (`ProviderPolyderQuotient { numerator, denominator }`): u' v - u v' and v v."""
         return self._polyder(u, v, True)
 
-    def polyint(self, polynomial, constant: float = 0.0) -> GpuTensorHandle:
+    def polyint(self, polynomial, constant: float = 0.0, *, entry: str = "rmhip_polyint") -> GpuTensorHandle:
         """lib.rs:1704-1710."""
         out = C.c_uint64()
-        self._check(self._lib.rmhip_polyint(self._ctx, self._id(polynomial), float(constant), C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, self._id(polynomial), float(constant), C.byref(out)))
         return self._handle(out.value)
 
     def meshgrid(self, axes: Sequence[Sequence[float]]) -> List[GpuTensorHandle]:

@@ -70,6 +70,10 @@ impl HipProvider {
             ProviderTrapezoidSpacing::Tensor(h) => (4, 0.0, self.own(h)?),
         };
         let mut out = 0u64;
+        if Self::is_complex(input) { // both parts integrated as independent lanes; spacing stays real (a complex one: the library's refusal)
+            check(unsafe { rmhip_complex_trapz_dim(self.ctx, self.own(input)?, dim as c_int, cumulative, kind, scalar, handle, &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_trapz_dim(self.ctx, self.own(input)?, dim as c_int, cumulative, kind, scalar, handle, &mut out) })?;
         self.handle(out)
     }
@@ -866,13 +870,24 @@ impl AccelProvider for HipProvider {
         check(unsafe { rmhip_cross(self.ctx, self.own(lhs)?, self.own(rhs)?, dim.unwrap_or(0) as c_int, &mut out) })?;
         self.handle(out)
     }
+    // gradient_dim, gradient_dim_with_coordinates, trapz_dim, cumtrapz_dim, polyint and iir_filter choose the entry point by `handle_storage`
+    // of the principal operand, as the in-process provider does (simple_provider.rs lane_factor): a complex-interleaved one goes to
+    // rmhip_complex_*, whose results are marked ComplexInterleaved.
     fn gradient_dim(&self, handle: &GpuTensorHandle, dim: usize, spacing: f64) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
+        if Self::is_complex(handle) { // (x[k+1] - x[k-1]) * (1 / den) on both parts (gradient.rs:839-841)
+            check(unsafe { rmhip_complex_gradient_dim(self.ctx, self.own(handle)?, dim as c_int, spacing, 0, &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_gradient_dim(self.ctx, self.own(handle)?, dim as c_int, spacing, 0, &mut out) })?;
         self.handle(out)
     }
     fn gradient_dim_with_coordinates(&self, handle: &GpuTensorHandle, dim: usize, coordinates: &GpuTensorHandle) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
+        if Self::is_complex(handle) {
+            check(unsafe { rmhip_complex_gradient_dim(self.ctx, self.own(handle)?, dim as c_int, 1.0, self.own(coordinates)?, &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_gradient_dim(self.ctx, self.own(handle)?, dim as c_int, 1.0, self.own(coordinates)?, &mut out) })?;
         self.handle(out)
     }
@@ -1055,6 +1070,14 @@ impl AccelProvider for HipProvider {
             let (mut out, mut fin) = (0u64, 0u64);
             let zi = match &options.zi { Some(h) => self.own(h)?, None => 0 };
             let (hb, ha, hx) = (self.own(b)?, self.own(a)?, self.own(x)?);
+            if Self::is_complex(x) { // the same two-step sequence with the complex pair: every part of every channel its own real recurrence
+                let mut rc = unsafe { rmhip_complex_iir_filter(self.ctx, hb, ha, hx, options.dim as c_int, zi, options.unit_denominator as c_int, &mut out, &mut fin) };
+                if rc == RMHIP_ERR_UNSUPPORTED {
+                    rc = unsafe { rmhip_complex_iir_filter_long(self.ctx, hb, ha, hx, options.dim as c_int, zi, options.unit_denominator as c_int, &mut out, &mut fin) };
+                }
+                check(rc)?;
+                return Ok(ProviderIirFilterResult { output: self.complex_handle(out)?, final_state: Some(self.complex_handle(fin)?) });
+            }
             let mut rc = unsafe { rmhip_iir_filter(self.ctx, hb, ha, hx, options.dim as c_int, zi, options.unit_denominator as c_int, &mut out, &mut fin) };
             if rc == RMHIP_ERR_UNSUPPORTED {
                 // long signals with few channels: the nested FIR sum / the chunked scan; its own declines go back to the caller as Err
@@ -1093,6 +1116,10 @@ impl AccelProvider for HipProvider {
     }
     fn polyint(&self, polynomial: &GpuTensorHandle, constant: f64) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
+        if Self::is_complex(polynomial) { // the appended element is (constant, 0)
+            check(unsafe { rmhip_complex_polyint(self.ctx, self.own(polynomial)?, constant, &mut out) })?;
+            return self.complex_handle(out);
+        }
         check(unsafe { rmhip_polyint(self.ctx, self.own(polynomial)?, constant, &mut out) })?;
         self.handle(out)
     }
