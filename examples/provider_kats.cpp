@@ -43,6 +43,13 @@ int main() {
         ok = ok && eq(p.download(p.transpose(a)).data, {1, 3, 2, 4});
         // syrk: accelerate/tests/syrk.rs (A' * A), here on [1 3; 2 4]
         ok = ok && near(p.download(p.syrk(a)).data, {5, 11, 11, 25}, 1e-12);
+        // cov(x, y) and cov(x, w) through the general entry point (cov.rs:901-1003): x = [1 2 4]', y = [2 1 5]', w = [1 2 1]'
+        {
+            auto cx = p.upload({1, 2, 4}, {3, 1}), cy = p.upload({2, 1, 5}, {3, 1}), cw = p.upload({1, 2, 1}, {3, 1});
+            ok = ok && near(p.download(p.covariance_general(cx, &cy, nullptr, false)).data, {7.0 / 3, 8.0 / 3, 8.0 / 3, 13.0 / 3}, 1e-12);
+            ok = ok && near(p.download(p.covariance_general(cx, nullptr, &cw, false)).data, {19.0 / 12}, 1e-12);
+            ok = ok && p.download(p.covariance_general(cx, nullptr, nullptr, true)).data == p.download(p.covariance(cx, true)).data;
+        }
         // linsolve LT hint: linsolve.rs:1224-1247
         rmhip_linsolve_options_t lt{};
         lt.lower = 1;

@@ -939,6 +939,28 @@ RMHIP_API int rmhip_image_normalize(rmhip_ctx* ctx, rmhip_buf input, const rmhip
  * rows - 1 <= 0 gives the all-NaN matrix the CPU returns.  The centred product runs as A'*A on the MFMA path. */
 /* @serves covariance */
 RMHIP_API int rmhip_covariance(rmhip_ctx* ctx, rmhip_buf matrix, int biased, rmhip_buf* out);
+/* `covariance(matrix, second, weights, options)` with rows == All in its general form: `cov(x, y)` and `cov(x, w)` as `cov_try_gpu` issues them
+ * (cov.rs:479-555).  Semantics of `cov_from_tensors(left, right, CovRows::All, weight)`, that is `combine_tensors` followed by `covariance_dense`
+ * (cov.rs:362-385, 901-1003, 1080-1126, 1218-1236): M = [matrix | second] column-wise, rows x (c1 + c2), each operand at most 2-D and normalised
+ * as rmhip_covariance normalises its operand (`second` may be the id of `matrix`); the result is cols x cols with cols = c1 + c2.
+ *   No weights: denom = rows - 1 (rows when `biased`), mean_c = sum(M[:, c]) / rows, C_ij = sum_r (M_ri - mean_i)(M_rj - mean_j) / denom.
+ *   Weights (one per row): `biased` is ignored (cov.rs:958-972); sum_w = sum(w), denom = sum_w - 1, mean_c = sum_r w_r M_rc / sum_w,
+ *   C_ij = sum_r w_r (M_ri - mean_i)(M_rj - mean_j) / denom.  sum_w <= 0 or denom <= 0 gives the all-NaN matrix: that decision is taken on the
+ *   device's sum_w, summed in a fixed tree and so within rounding of the CPU's sequential sum.
+ * cols == 0 gives an empty [0, 0] (before the weights are looked at), denom <= 0 the all-NaN matrix.  A column holding a non-finite value makes
+ * its row and column of the result NaN (IEEE arithmetic; a zero weight does not shield such a row: the CPU's mean has already refused the
+ * column).  A finite diagonal entry in (-1e-12, 0) becomes 0 (sanitize_covariance); the result is exactly symmetric.  Parity by tolerance with
+ * finite data, as for rmhip_covariance; bitwise reproducible from run to run (fixed-order trees, no float atomics).  At precision 32 the
+ * operands and the weights are read in place as f32, sums and products are f64, the result rounds once on store.
+ * With second_or_0 == weights_or_0 == 0 the call is rmhip_covariance.  Where gram_skinny_applies(rows, cols): the tall-skinny VALU Gram kernel
+ * (weighted form: j side w_r (x - mu_j)); every other shape: one centring pass sqrt(w_r) (M - 1 mu) and the A'*A product on the MFMA path.
+ * Refusals, in this order, with nothing allocated or left behind: null out INVALID; unknown id NOT_FOUND; a complex-interleaved operand
+ * UNSUPPORTED; more than two dimensions UNSUPPORTED; differing row counts SHAPE; weights with more than two dimensions or neither extent 1
+ * SHAPE; weight count != rows SHAPE; weights with rows == 0 INVALID; a negative or non-finite weight INVALID (found by the pass that sums the
+ * weights: one 16-byte read-back of (sum_w, verdict) is the call's only synchronisation; the unweighted form has none).  The rows modes
+ * OmitRows / PartialRows never reach a provider (cov.rs:480-482). */
+/* @serves covariance */
+RMHIP_API int rmhip_covariance_general(rmhip_ctx* ctx, rmhip_buf matrix, rmhip_buf second_or_0, rmhip_buf weights_or_0, int biased, rmhip_buf* out);
 /* `rank(matrix, tolerance)` (lib.rs:2464-2470; rank.rs:280-295), `cond(matrix, norm)` for the 2-norm (norm == 0; lib.rs:2444-2450; cond.rs:276-330,
  * 448-467; the other norms: RMHIP_ERR_UNSUPPORTED) and `pinv(matrix, options)` (lib.rs:2437-2443; pinv.rs:242-285) from the one-sided Jacobi SVD of
  * svdsolve.hip (min(rows, cols) <= 4096, finite data; else RMHIP_ERR_UNSUPPORTED): rank = singular values above the tolerance (default max(m, n) *

@@ -762,6 +762,12 @@ public:
         check(rmhip_covariance(ctx_, own(matrix), biased ? 1 : 0, &out));
         return with_shape(out);
     }
+    // lib.rs:1857 with rows == All: cov(x, y) / weighted cov; null second and weights: covariance(matrix, biased)
+    GpuTensorHandle covariance_general(const GpuTensorHandle& matrix, const GpuTensorHandle* second, const GpuTensorHandle* weights, bool biased) const {
+        uint64_t out = 0;
+        check(rmhip_covariance_general(ctx_, own(matrix), second ? own(*second) : 0, weights ? own(*weights) : 0, biased ? 1 : 0, &out));
+        return with_shape(out);
+    }
     std::pair<GpuTensorHandle, GpuTensorHandle> covariance_to_correlation(const GpuTensorHandle& m) const {  // lib.rs:1876: (correlation, sigma)
         uint64_t corr = 0, sig = 0;
         check(rmhip_covariance_to_correlation(ctx_, own(m), &corr, &sig));

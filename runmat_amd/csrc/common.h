@@ -487,7 +487,22 @@ bool gram_skinny_applies(size_t rows, size_t cols);
 int gram_skinny_device(Context* c, const double* x, size_t rows, size_t cols, const double* mu, double denom, bool sanitize, double* g,
                        const double* x2 = nullptr, size_t cols2 = 0);
 // f32 storage read in place, f64 products and sums (a precision-32 provider's covariance / syrk of such shapes)
-int gram_skinny_device_f32(Context* c, const float* x, size_t rows, size_t cols, const double* mu, double denom, bool sanitize, double* g);
+int gram_skinny_device_f32(Context* c, const float* x, size_t rows, size_t cols, const double* mu, double denom, bool sanitize, double* g,
+                           const float* x2 = nullptr, size_t cols2 = 0);
+// cov(x, y) / weighted cov (rmhip_covariance_general; special.hip), M = [x | x2] with cols = cols1 + the second operand's columns (x2 may be
+// null when cols1 == cols), w = one weight per row or null.  cov_wsums: stat[0 .. cols) = the (weighted) column means, stat[cols] = sum_w
+// (the row count without weights), stat[cols + 1] = the number of negative or non-finite weights; two launches, fixed-order sums.
+int cov_wsums_device(Context* c, const double* x, const double* x2, size_t cols1, size_t rows, size_t cols, const double* w, double* stat);
+int cov_wsums_device_f32(Context* c, const float* x, const float* x2, size_t cols1, size_t rows, size_t cols, const float* w, double* stat);
+// weighted tall-skinny Gram matrix (M - 1 mu)' diag(w) (M - 1 mu) / denom with the diagonal rule, where gram_skinny_applies(rows, cols)
+int gram_skinny_w_device(Context* c, const double* x, const double* x2, size_t cols1, size_t rows, size_t cols, const double* w, const double* mu,
+                         double denom, double* g);
+int gram_skinny_w_device_f32(Context* c, const float* x, const float* x2, size_t cols1, size_t rows, size_t cols, const float* w, const double* mu,
+                             double denom, double* g);
+// y [rows, cols] f64 = sqrt(w_r) (M - 1 mu) (w null: M - 1 mu); then out = lower triangle of `gram` / denom mirrored, diagonal rule applied
+int cov_centre_device(Context* c, const double* x, const double* x2, size_t cols1, size_t rows, size_t cols, const double* w, const double* mu, double* y);
+int cov_centre_device_f32(Context* c, const float* x, const float* x2, size_t cols1, size_t rows, size_t cols, const float* w, const double* mu, double* y);
+int cov_finish_device(Context* c, const double* gram, size_t n, double denom, double* out);
 int launch_stochastic_evolution(Context* c, uint64_t state, const double* in, double* out, size_t n, double drift,
                                 double scale, unsigned steps, uint64_t draws_per_step);
 

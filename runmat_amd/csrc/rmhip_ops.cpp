@@ -1162,6 +1162,101 @@ int rmhip_covariance(rmhip_ctx* ctx, rmhip_buf matrix, int biased, rmhip_buf* ou
     return rc;
 }
 
+int rmhip_covariance_general(rmhip_ctx* ctx, rmhip_buf matrix, rmhip_buf second_or_0, rmhip_buf weights_or_0, int biased, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "null out");
+    if (!second_or_0 && !weights_or_0) return rmhip_covariance(ctx, matrix, biased, out);
+    *out = 0;
+    Buffer mb, sb, wb;
+    RMHIP_TRY(c->lookup(matrix, &mb));  // every id is known before any operand is judged
+    if (second_or_0) RMHIP_TRY(c->lookup(second_or_0, &sb));
+    if (weights_or_0) RMHIP_TRY(c->lookup(weights_or_0, &wb));
+    RMHIP_TRY(c->get_raw(matrix, &mb));  // shape only; refuses complex-interleaved storage
+    if (second_or_0) RMHIP_TRY(c->get_raw(second_or_0, &sb));
+    if (weights_or_0) RMHIP_TRY(c->get_raw(weights_or_0, &wb));
+    if (mb.shape.size() > 2 || sb.shape.size() > 2) return fail(RMHIP_ERR_UNSUPPORTED, "covariance: only 2D supported");
+    const std::vector<size_t> ms = normalize_matrix_shape(mb.shape);
+    const size_t rows = ms[0], cols1 = ms[1];
+    size_t cols2 = 0;
+    if (second_or_0) {  // combine_tensors, cov.rs:901-914
+        const std::vector<size_t> ss = normalize_matrix_shape(sb.shape);
+        if (ss[0] != rows) return fail(RMHIP_ERR_SHAPE, "covariance: inputs must have the same number of rows (got %zu and %zu)", rows, ss[0]);
+        cols2 = ss[1];
+    }
+    const size_t cols = cols1 + cols2;
+    if (weights_or_0) {
+        const std::vector<size_t> ws = normalize_matrix_shape(wb.shape);
+        if (wb.shape.size() > 2 || (ws[0] != 1 && ws[1] != 1)) return fail(RMHIP_ERR_SHAPE, "covariance: weight vector must be 1-D");
+        if (wb.numel != rows) return fail(RMHIP_ERR_SHAPE, "covariance: weight vector length mismatch (expected %zu elements)", rows);
+        if (rows == 0) return fail(RMHIP_ERR_INVALID, "covariance: weight vector cannot be empty");
+    }
+    const size_t oshape[2] = {cols, cols};
+    auto all_nan = [&]() {  // cov.rs:920-934, 966-972: empty, or the all-NaN matrix
+        Buffer ob;
+        RMHIP_TRY(c->new_buffer(oshape, 2, out, &ob));
+        const int rc0 = launch_fill(c, ob.data(), ob.numel, std::numeric_limits<double>::quiet_NaN());
+        if (rc0) {
+            rmhip_free(ctx, *out);
+            *out = 0;
+        }
+        return rc0;
+    };
+    if (cols == 0) return all_nan();
+    double denom = biased ? (double)rows : (double)rows - 1.0;
+    if (!weights_or_0 && denom <= 0.0) return all_nan();
+    // f32 storage is read in place when every operand holds it; otherwise all of them are read as f64 (widened / materialised copies)
+    bool native = c->precision == 32;
+    Buffer xb, x2b, wgt;
+    for (int pass = 0; pass < 2; ++pass) {
+        bool n1 = native, n2 = native, n3 = native;
+        RMHIP_TRY(get_operand(c, matrix, &xb, &n1));
+        if (second_or_0) RMHIP_TRY(get_operand(c, second_or_0, &x2b, &n2));
+        if (weights_or_0) RMHIP_TRY(get_operand(c, weights_or_0, &wgt, &n3));
+        if (n1 == native && (!second_or_0 || n2 == native) && (!weights_or_0 || n3 == native)) break;
+        native = false;
+    }
+    const bool f32 = native;
+    std::shared_ptr<Allocation> stat;  // means, sum_w, bad-weight count
+    RMHIP_TRY(c->alloc_device(cols + 2, &stat));
+    const void *xp = xb.data(), *x2p = second_or_0 ? x2b.data() : nullptr, *wp = weights_or_0 ? wgt.data() : nullptr;
+    RMHIP_TRY(f32 ? cov_wsums_device_f32(c, (const float*)xp, (const float*)x2p, cols1, rows, cols, (const float*)wp, stat->ptr)
+                  : cov_wsums_device(c, (const double*)xp, (const double*)x2p, cols1, rows, cols, (const double*)wp, stat->ptr));
+    if (weights_or_0) {  // the call's only synchronisation: (sum_w, bad count)
+        double host[2] = {0.0, 0.0};
+        RMHIP_HIP_CHECK(hipMemcpyAsync(host, stat->ptr + cols, sizeof host, hipMemcpyDeviceToHost, c->stream));
+        RMHIP_HIP_CHECK(hipStreamSynchronize(c->stream));
+        if (host[1] != 0.0) return fail(RMHIP_ERR_INVALID, "covariance: weights must be non-negative finite values");
+        denom = host[0] - 1.0;  // `biased` is ignored, cov.rs:958-972
+        if (host[0] <= 0.0 || denom <= 0.0) return all_nan();
+    }
+    Buffer ob;
+    int rc = RMHIP_OK;
+    if (gram_skinny_applies(rows, cols) && solve_knobs().gram_skinny) {
+        RMHIP_TRY(c->new_buffer(oshape, 2, out, &ob));
+        if (weights_or_0)
+            rc = f32 ? gram_skinny_w_device_f32(c, (const float*)xp, (const float*)x2p, cols1, rows, cols, (const float*)wp, stat->ptr, denom, ob.data())
+                     : gram_skinny_w_device(c, (const double*)xp, (const double*)x2p, cols1, rows, cols, (const double*)wp, stat->ptr, denom, ob.data());
+        else
+            rc = f32 ? gram_skinny_device_f32(c, (const float*)xp, rows, cols1, stat->ptr, denom, true, ob.data(), (const float*)x2p, cols2)
+                     : gram_skinny_device(c, (const double*)xp, rows, cols1, stat->ptr, denom, true, ob.data(), (const double*)x2p, cols2);
+    } else {
+        // every other shape: one centring pass writes sqrt(w) (M - 1 mu) for both operands, the MFMA path multiplies Y' Y
+        std::shared_ptr<Allocation> centred, gram;
+        RMHIP_TRY(c->alloc_device(rows * cols, &centred));
+        RMHIP_TRY(c->alloc_device(cols * cols, &gram));
+        RMHIP_TRY(f32 ? cov_centre_device_f32(c, (const float*)xp, (const float*)x2p, cols1, rows, cols, (const float*)wp, stat->ptr, centred->ptr)
+                      : cov_centre_device(c, (const double*)xp, (const double*)x2p, cols1, rows, cols, (const double*)wp, stat->ptr, centred->ptr));
+        RMHIP_TRY(launch_dgemm_trans(c, true, false, cols, cols, rows, 1.0, centred->ptr, rows, centred->ptr, rows, 0.0, gram->ptr, cols));
+        RMHIP_TRY(c->new_buffer(oshape, 2, out, &ob));
+        rc = cov_finish_device(c, gram->ptr, cols, denom, ob.data());
+    }
+    if (rc) {
+        rmhip_free(ctx, *out);
+        *out = 0;
+    }
+    return rc;
+}
+
 int rmhip_diag_extract(rmhip_ctx* ctx, rmhip_buf matrix, long long offset, rmhip_buf* out) {
     CTX_OR_FAIL(ctx);
     if (!out) return fail(RMHIP_ERR_INVALID, "null out");

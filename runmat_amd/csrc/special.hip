@@ -541,8 +541,280 @@ int gram_skinny_device(Context* c, const double* x, size_t rows, size_t cols, co
                        const double* x2, size_t cols2) {
     return gram_skinny_any(c, x, rows, cols, mu, denom, sanitize, g, x2, cols2);
 }
-int gram_skinny_device_f32(Context* c, const float* x, size_t rows, size_t cols, const double* mu, double denom, bool sanitize, double* g) {
-    return gram_skinny_any<float>(c, x, rows, cols, mu, denom, sanitize, g, nullptr, 0);
+int gram_skinny_device_f32(Context* c, const float* x, size_t rows, size_t cols, const double* mu, double denom, bool sanitize, double* g,
+                           const float* x2, size_t cols2) {
+    return gram_skinny_any<float>(c, x, rows, cols, mu, denom, sanitize, g, x2, cols2);
+}
+
+// ---- cov(x, y) and weighted cov (rmhip_covariance_general): M = [x | x2], rows x cols, each operand column-major and read in place -----
+// Weighted column sums: one pass over M and w gives sum_r w_r M_rc for every column, sum_w and the count of weights that are negative
+// or not finite (w == null: weight 1).  A workgroup takes a chunk of rows and eight columns (grid.y), a thread keeps the eight sums in
+// registers with two rows' loads in flight, the workgroup folds them on the DPP network and in LDS, and a second kernel sums the chunks
+// in a fixed tree: deterministic, no atomics.  The weights are read once per eight columns (from L2 after the first group).
+static constexpr int CW_BLOCK = 256;
+template <class T>
+__global__ void __launch_bounds__(CW_BLOCK) k_cov_wsums(const T* __restrict__ x, const T* __restrict__ x2, int cols1, size_t rows, int cols,
+                                                        const T* __restrict__ w, double* __restrict__ partial) {
+    __shared__ double lds[CW_BLOCK / 64][10];
+    const int c0 = (int)blockIdx.y * 8;
+    const T* cp[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {  // columns past the last one read the last one (no load under a condition); their sums are not stored
+        const int cc = c0 + u < cols ? c0 + u : cols - 1;
+        cp[u] = cc < cols1 ? x + (size_t)cc * rows : x2 + (size_t)(cc - cols1) * rows;
+    }
+    double acc[8], sw = 0.0, bad = 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = 0.0;
+    size_t chunk = (rows + gridDim.x - 1) / gridDim.x;
+    chunk = (chunk + CW_BLOCK - 1) / CW_BLOCK * CW_BLOCK;
+    const size_t begin = (size_t)blockIdx.x * chunk;
+    size_t end = begin + chunk;
+    if (end > rows) end = rows;
+    auto load_row = [&](size_t r, double (&v)[8], double* wv) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = (double)cp[u][r];
+        *wv = w ? (double)w[r] : 1.0;
+    };
+    auto fold_row = [&](const double (&v)[8], double wv) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc[u] += wv * v[u];
+        sw += wv;
+        if (!(wv >= 0.0) || fabs(wv) == __builtin_inf()) bad += 1.0;
+    };
+    size_t r = begin + threadIdx.x;
+    for (; r + CW_BLOCK < end; r += 2 * CW_BLOCK) {
+        double v0[8], v1[8], w0, w1;
+        load_row(r, v0, &w0);
+        load_row(r + CW_BLOCK, v1, &w1);
+        fold_row(v0, w0);
+        fold_row(v1, w1);
+    }
+    if (r < end) {
+        double v0[8], w0;
+        load_row(r, v0, &w0);
+        fold_row(v0, w0);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const double s = gs_wave_sum63(acc[u]);
+        if (lane == 63) lds[wave][u] = s;
+    }
+    sw = gs_wave_sum63(sw);
+    bad = gs_wave_sum63(bad);
+    if (lane == 63) lds[wave][8] = sw, lds[wave][9] = bad;
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < 10) {
+        const double s = ((lds[0][t] + lds[1][t]) + lds[2][t]) + lds[3][t];
+        double* row = partial + (size_t)blockIdx.x * (size_t)(cols + 2);
+        if (t < 8) {
+            if (c0 + t < cols) row[c0 + t] = s;
+        } else if (blockIdx.y == 0) row[cols + (t - 8)] = s;  // sum_w, bad count: the first column group's copy
+    }
+}
+// stat[c] = mean of column c (block c < cols), stat[cols] = sum_w, stat[cols + 1] = bad count.  Every block sums the chunks of its own
+// entry and of sum_w in the same fixed order (thread t: chunks t, t + 256, ...; then a halving tree), so all blocks divide by the same
+// sum_w bits.  count > 0: the unweighted form, the divisor is the row count.
+__global__ void __launch_bounds__(CW_BLOCK) k_cov_wsums_final(const double* __restrict__ partial, int nchunks, int cols, double count,
+                                                              double* __restrict__ stat) {
+    __shared__ double ls[CW_BLOCK], lw[CW_BLOCK];
+    const int e = (int)blockIdx.x, t = threadIdx.x;
+    double s = 0.0, sw = 0.0;
+    for (int q = t; q < nchunks; q += CW_BLOCK) {
+        s += partial[(size_t)q * (size_t)(cols + 2) + e];
+        sw += partial[(size_t)q * (size_t)(cols + 2) + cols];
+    }
+    ls[t] = s, lw[t] = sw;
+    __syncthreads();
+    for (int h = CW_BLOCK / 2; h > 0; h >>= 1) {
+        if (t < h) ls[t] += ls[t + h], lw[t] += lw[t + h];
+        __syncthreads();
+    }
+    if (t == 0) stat[e] = e < cols ? ls[0] / (count > 0.0 ? count : lw[0]) : ls[0];
+}
+template <class T>
+static int cov_wsums_any(Context* c, const T* x, const T* x2, size_t cols1, size_t rows, size_t cols, const T* w, double* stat) {
+    const size_t ngroups = (cols + 7) / 8;
+    size_t nchunks = (rows + (size_t)CW_BLOCK * 8 - 1) / ((size_t)CW_BLOCK * 8);  // >= 8 rows per thread
+    const size_t cap = (size_t)c->num_cus * 4 / ngroups;
+    if (nchunks > cap) nchunks = cap;
+    if (nchunks < 1) nchunks = 1;
+    RMHIP_TRY(c->ensure_scratch(sizeof(double) * nchunks * (cols + 2)));
+    double* partial = c->scratch;
+    hipLaunchKernelGGL(k_cov_wsums<T>, dim3((unsigned)nchunks, (unsigned)ngroups), dim3(CW_BLOCK), 0, c->stream, x, x2 ? x2 : x, (int)cols1, rows, (int)cols, w,
+                       partial);
+    hipLaunchKernelGGL(k_cov_wsums_final, dim3((unsigned)(cols + 2)), dim3(CW_BLOCK), 0, c->stream, (const double*)partial, (int)nchunks, (int)cols,
+                       w ? 0.0 : (double)rows, stat);
+    c->tel.kernel_launches += 2;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
+}
+int cov_wsums_device(Context* c, const double* x, const double* x2, size_t cols1, size_t rows, size_t cols, const double* w, double* stat) {
+    return cov_wsums_any(c, x, x2, cols1, rows, cols, w, stat);
+}
+int cov_wsums_device_f32(Context* c, const float* x, const float* x2, size_t cols1, size_t rows, size_t cols, const float* w, double* stat) {
+    return cov_wsums_any(c, x, x2, cols1, rows, cols, w, stat);
+}
+
+// The weighted form of k_gram_skinny: G = (M - 1 mu)' diag(w) (M - 1 mu).  The j side of a product is w_r (x - mu_j), the k side the plain
+// centred value, so a diagonal block pair keeps a k side of its own (from the j side's loaded values: no second read); the weight loads
+// coalesced with the rows.  Same partial layout: k_gram_skinny_final sums the chunks, keeps the lower triangle of the diagonal blocks and
+// mirrors it, so the result is exactly symmetric.
+template <class T>
+__global__ void __launch_bounds__(GS_BLOCK) k_gram_skinny_w(const T* __restrict__ x, const T* __restrict__ x2, int cols1, size_t rows, int cols,
+                                                            const T* __restrict__ w, const double* __restrict__ mu, double* __restrict__ partial) {
+    __shared__ double lds[GS_BLOCK / 64][64];
+    int jb, kb;
+    gs_pair((int)blockIdx.y, &jb, &kb);
+    const int j0 = jb * 8, k0 = kb * 8;
+    const bool diag = jb == kb;
+    double mj[8], mk[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        mj[u] = j0 + u < cols ? mu[j0 + u] : 0.0;
+        mk[u] = k0 + u < cols ? mu[k0 + u] : 0.0;
+    }
+    double acc[8][8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int v = 0; v < 8; ++v) acc[u][v] = 0.0;
+    size_t chunk = (rows + gridDim.x - 1) / gridDim.x;
+    chunk = (chunk + GS_BLOCK - 1) / GS_BLOCK * GS_BLOCK;
+    const size_t begin = (size_t)blockIdx.x * chunk;
+    size_t end = begin + chunk;
+    if (end > rows) end = rows;
+    const T* cj[8];
+    const T* ck[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {  // columns past the last one are loaded from the last one and zeroed afterwards, as in k_gram_skinny
+        const int jc = j0 + u < cols ? j0 + u : cols - 1, kc = k0 + u < cols ? k0 + u : cols - 1;
+        cj[u] = jc < cols1 ? x + (size_t)jc * rows : x2 + (size_t)(jc - cols1) * rows;
+        ck[u] = kc < cols1 ? x + (size_t)kc * rows : x2 + (size_t)(kc - cols1) * rows;
+    }
+    auto load_row = [&](size_t r, double (&a)[8], double (&b)[8]) {
+        double ra[8], rb[8];
+        const double wv = (double)w[r];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) ra[u] = (double)cj[u][r];
+        if (!diag) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) rb[u] = (double)ck[u][r];
+        } else {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) rb[u] = ra[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) a[u] = j0 + u < cols ? wv * (ra[u] - mj[u]) : 0.0;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) b[u] = k0 + u < cols ? rb[u] - mk[u] : 0.0;
+    };
+    auto fold_row = [&](const double (&a)[8], const double (&b)[8]) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int v = 0; v < 8; ++v) acc[u][v] = __builtin_fma(a[u], b[v], acc[u][v]);
+    };
+    size_t r = begin + threadIdx.x;
+    for (; r + GS_BLOCK < end; r += 2 * GS_BLOCK) {  // two rows' loads in flight before the first product
+        double a0[8], b0[8], a1[8], b1[8];
+        load_row(r, a0, b0);
+        load_row(r + GS_BLOCK, a1, b1);
+        fold_row(a0, b0);
+        fold_row(a1, b1);
+    }
+    if (r < end) {
+        double a0[8], b0[8];
+        load_row(r, a0, b0);
+        fold_row(a0, b0);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+            const double s = gs_wave_sum63(acc[u][v]);
+            if (lane == 63) lds[wave][u * 8 + v] = s;
+        }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int t = threadIdx.x;
+        partial[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 64 + t] = ((lds[0][t] + lds[1][t]) + lds[2][t]) + lds[3][t];
+    }
+}
+template <class T>
+static int gram_skinny_w_any(Context* c, const T* x, const T* x2, size_t cols1, size_t rows, size_t cols, const T* w, const double* mu, double denom,
+                             double* g) {
+    const int nb = (int)((cols + 7) / 8), npairs = nb * (nb + 1) / 2;
+    size_t nchunks = (rows + (size_t)GS_BLOCK * 8 - 1) / ((size_t)GS_BLOCK * 8);  // the chunking of gram_skinny_any
+    const size_t cap = (size_t)c->num_cus * 2 / (size_t)npairs;
+    if (nchunks > cap) nchunks = cap ? cap : 1;
+    if (nchunks < 1) nchunks = 1;
+    RMHIP_TRY(c->ensure_scratch(sizeof(double) * nchunks * (size_t)npairs * 64));
+    double* partial = c->scratch;
+    hipLaunchKernelGGL(k_gram_skinny_w<T>, dim3((unsigned)nchunks, (unsigned)npairs), dim3(GS_BLOCK), 0, c->stream, x, x2 ? x2 : x, (int)cols1, rows, (int)cols, w,
+                       mu, partial);
+    hipLaunchKernelGGL(k_gram_skinny_final, dim3((unsigned)npairs), dim3(64 * GS_FGROUPS), 0, c->stream, (const double*)partial, (int)nchunks, npairs, (int)cols, denom,
+                       1, g);
+    c->tel.kernel_launches += 2;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
+}
+int gram_skinny_w_device(Context* c, const double* x, const double* x2, size_t cols1, size_t rows, size_t cols, const double* w, const double* mu,
+                         double denom, double* g) {
+    return gram_skinny_w_any(c, x, x2, cols1, rows, cols, w, mu, denom, g);
+}
+int gram_skinny_w_device_f32(Context* c, const float* x, const float* x2, size_t cols1, size_t rows, size_t cols, const float* w, const double* mu,
+                             double denom, double* g) {
+    return gram_skinny_w_any(c, x, x2, cols1, rows, cols, w, mu, denom, g);
+}
+
+// MFMA route, before the product: Y[r, c] = sqrt(w_r) (M[r, c] - mu_c) for both operands into one [rows, cols] f64 matrix (w == null: the
+// plain centring), so that Y' Y is the weighted centred Gram matrix - symmetric by construction.  grid.y walks the columns.
+template <class T>
+__global__ void __launch_bounds__(256) k_cov_centre(const T* __restrict__ x, const T* __restrict__ x2, int cols1, size_t rows, int cols,
+                                                    const T* __restrict__ w, const double* __restrict__ mu, double* __restrict__ y) {
+    const size_t r = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const double s = w ? sqrt((double)w[r]) : 1.0;
+    for (int col = (int)blockIdx.y; col < cols; col += (int)gridDim.y) {
+        const T* src = col < cols1 ? x + (size_t)col * rows : x2 + (size_t)(col - cols1) * rows;
+        y[(size_t)col * rows + r] = s * ((double)src[r] - mu[col]);
+    }
+}
+template <class T>
+static int cov_centre_any(Context* c, const T* x, const T* x2, size_t cols1, size_t rows, size_t cols, const T* w, const double* mu, double* y) {
+    const size_t gy = cols < 32768 ? cols : 32768;
+    hipLaunchKernelGGL(k_cov_centre<T>, dim3((unsigned)((rows + 255) / 256), (unsigned)gy), dim3(256), 0, c->stream, x, x2 ? x2 : x, (int)cols1, rows, (int)cols, w, mu,
+                       y);
+    c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
+}
+int cov_centre_device(Context* c, const double* x, const double* x2, size_t cols1, size_t rows, size_t cols, const double* w, const double* mu, double* y) {
+    return cov_centre_any(c, x, x2, cols1, rows, cols, w, mu, y);
+}
+int cov_centre_device_f32(Context* c, const float* x, const float* x2, size_t cols1, size_t rows, size_t cols, const float* w, const double* mu, double* y) {
+    return cov_centre_any(c, x, x2, cols1, rows, cols, w, mu, y);
+}
+// MFMA route, after the product: out = gram / denom from the LOWER triangle of the product, written to both triangles (exactly symmetric
+// whatever the product's tile order), with sanitize_covariance's diagonal rule (cov.rs:1218-1227)
+__global__ void __launch_bounds__(256) k_cov_finish(const double* __restrict__ gram, size_t n, double denom, double* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n * n) return;
+    const size_t j = i % n, k = i / n;
+    double v = gram[j >= k ? j + k * n : k + j * n] / denom;
+    if (j == k && v == v && fabs(v) != __builtin_inf() && v < 0.0 && v > -1.0e-12) v = 0.0;
+    out[i] = v;
+}
+int cov_finish_device(Context* c, const double* gram, size_t n, double denom, double* out) {
+    if (n == 0) return RMHIP_OK;
+    hipLaunchKernelGGL(k_cov_finish, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, c->stream, gram, n, denom, out);
+    c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
 }
 
 // sanitize_covariance (cov.rs:1218-1227): a finite diagonal entry in (-1e-12, 0) is rounding noise -> 0

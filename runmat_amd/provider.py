@@ -1065,6 +1065,15 @@ class HipProvider:
         self._check(self._lib.rmhip_covariance(self._ctx, self._id(matrix), int(bool(biased)), C.byref(out)))
         return self._handle(out.value)
 
+    def covariance_general(self, matrix: GpuTensorHandle, second: Optional[GpuTensorHandle] = None, weights: Optional[GpuTensorHandle] = None,
+                           biased: bool = False) -> GpuTensorHandle:
+        """lib.rs:1857-1865 with rows == All: `cov(x, y)` ([matrix | second] column-wise) and the weighted form (one weight per row; `biased`
+        is then ignored), as `cov_from_tensors` computes them (cov.rs:362-385, 901-1003).  With neither it is `covariance(matrix)`."""
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_covariance_general(self._ctx, self._id(matrix), self._id(second) if second is not None else 0,
+                                                       self._id(weights) if weights is not None else 0, int(bool(biased)), C.byref(out)))
+        return self._handle(out.value)
+
     def covariance_to_correlation(self, matrix):
         """lib.rs:1876-1884 -> `ProviderCovarianceToCorrelationResult { correlation, sigma }` as a pair of handles."""
         corr, sig = C.c_uint64(), C.c_uint64()

@@ -564,12 +564,21 @@ impl AccelProvider for HipProvider {
     fn covariance<'a>(&'a self, matrix: &'a GpuTensorHandle, second: Option<&'a GpuTensorHandle>, weights: Option<&'a GpuTensorHandle>,
                       options: &'a CovarianceOptions) -> AccelProviderFuture<'a, GpuTensorHandle> {
         Box::pin(async move {
-            if second.is_some() || weights.is_some() || options.has_weight_vector || options.rows != CovRows::All {
-                return Err(anyhow!("covariance: only the dense unweighted form is offloaded"));  // callers use the CPU path
+            if options.rows != CovRows::All {
+                return Err(anyhow!("covariance: only rows == All is offloaded"));  // cov_try_gpu never issues the others (cov.rs:480-482)
+            }
+            if options.has_weight_vector && weights.is_none() {
+                return Err(anyhow!("covariance: a weight vector that is not resident uses the CPU path"));
             }
             let mut out = 0u64;
             let biased = matches!(options.normalization, CovNormalization::Biased) as c_int;
-            check(unsafe { rmhip_covariance(self.ctx, self.own(matrix)?, biased, &mut out) })?;
+            if second.is_some() || weights.is_some() {  // cov(x, y) / cov(x, w): the general entry point
+                let second_id = match second { Some(h) => self.own(h)?, None => 0 };
+                let weights_id = match weights { Some(h) => self.own(h)?, None => 0 };
+                check(unsafe { rmhip_covariance_general(self.ctx, self.own(matrix)?, second_id, weights_id, biased, &mut out) })?;
+            } else {
+                check(unsafe { rmhip_covariance(self.ctx, self.own(matrix)?, biased, &mut out) })?;
+            }
             self.handle(out)
         })
     }
