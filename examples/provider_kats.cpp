@@ -4,6 +4,7 @@
 // widened entry point (transpose view, syrk, linsolve, mldivide, stochastic_evolution, comparisons).
 // Build: g++ -std=c++17 -Iinclude examples/provider_kats.cpp -Lrunmat_amd/csrc -lrmhip -Wl,-rpath,$PWD/runmat_amd/csrc
 // Exit code 0 = all KATs pass; 2 = no gfx950 device (the provider has no CPU fallback); 1 = mismatch.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <string>
@@ -158,6 +159,28 @@ int main() {
                 ok = false;
             } catch (const rmhip::ProviderError& e) {
                 ok = ok && e.code == RMHIP_ERR_INVALID && std::string(e.what()).find("symbols must be in range") != std::string::npos;
+            }
+        }
+        {
+            // moving_window's second entry point: the 101-point median (shrinking at the ends) of the ramp 0 .. 199 with a spike at 100, which
+            // moving_window itself declines; against the middle of each sorted window
+            std::vector<double> ramp(200);
+            for (size_t i = 0; i < ramp.size(); ++i) ramp[i] = (double)i;
+            ramp[100] = 1e6;
+            auto h = p.upload(ramp, {200, 1});
+            try {
+                p.moving_window(h, {200, 1}, 0, 50, 50, 5, 0, 0.0, false, false);
+                ok = false;
+            } catch (const rmhip::ProviderError& e) {
+                ok = ok && e.code == RMHIP_ERR_UNSUPPORTED;
+            }
+            auto med = p.download(p.moving_window_long(h, {200, 1}, 0, 50, 50, 5, 0, 0.0, false, false)).data;
+            ok = ok && med.size() == ramp.size();
+            for (size_t i = 0; ok && i < ramp.size(); ++i) {
+                std::vector<double> w(ramp.begin() + (i < 50 ? 0 : i - 50), ramp.begin() + (i + 51 > ramp.size() ? ramp.size() : i + 51));
+                std::sort(w.begin(), w.end());
+                const size_t mid = w.size() / 2;
+                ok = med[i] == (w.size() % 2 ? w[mid] : (w[mid - 1] + w[mid]) / 2.0);
             }
         }
         {

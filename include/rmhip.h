@@ -526,10 +526,30 @@ RMHIP_API int rmhip_conv2d(rmhip_ctx* ctx, rmhip_buf signal, rmhip_buf kernel, i
  * op: 0 sum 1 mean 2 prod 3 min 4 max 5 median 6 std 7 var (`ProviderMovingWindowOp`); endpoints: 0 shrink, 1 discard, 2 fill(`fill`);
  * nan_omit / population: `ProviderNanMode::Omit` / `ProviderStdNormalization::Population`.  out_shape: the request's output shape (checked).
  * Bit-exact (the CPU's accumulation order).  RMHIP_ERR_UNSUPPORTED: a median window of more than 64 points; a product padded with a
- * value other than 0, 1 or NaN (the CPU multiplies by `powf(fill, count)`). */
+ * value other than 0, 1 or NaN (the CPU multiplies by `powf(fill, count)`).  `rmhip_moving_window_long` serves the median windows declined here. */
 /* @serves moving_window */
 RMHIP_API int rmhip_moving_window(rmhip_ctx* ctx, rmhip_buf a, int dim, size_t before, size_t after, int op, int endpoints, double fill, int nan_omit,
                                   int population, const size_t* out_shape, size_t out_rank, rmhip_buf* out);
+/* The median over long windows: the second entry point of the hook, tried when rmhip_moving_window declines.  Arguments, output shape and the
+ * refusals - INVALID (a null `out`, a null `out_shape` with a nonzero rank, dim < 0, an unknown op or endpoints value, dim >= out_rank),
+ * NOT_FOUND, SHAPE, a complex operand - are rmhip_moving_window's, in its order, all before anything is allocated.  It serves op 5 (median)
+ * only; `population` is accepted and ignored.  With W_eff = min(extent of dim, before + after + 1) it serves 1 <= W_eff <= 4096, the short
+ * windows of rmhip_moving_window included.  Semantics are that entry point's median (moving.rs:1282-1323): window placement and fill count of
+ * shrink / discard / fill; `nan_omit` drops NaNs, otherwise one NaN in the window gives NaN; NaN padding gives NaN unless omitted, when the
+ * values alone are reduced; a window with no value and no fill gives NaN; with total = values + fill count and mid = total / 2 the result is
+ * sorted[mid] for an odd total and (sorted[mid - 1] + sorted[mid]) / 2.0 for an even one, an element that falls among padding or values equal
+ * to the fill being the fill itself.  "Sorted" is the CPU's stable sort under `partial_cmp`: -0.0 and 0.0 compare equal and keep window order,
+ * so the element is the k-th under (value, position in the window) and comes back with its own bits.  Found by a radix select over keys staged
+ * in LDS, an order statistic: bit-exact, the same bits on every run.  An empty output is RMHIP_OK with an empty tensor; a dimension beyond the
+ * rank has extent 1.  Precision-32 contexts: as rmhip_moving_window - the f64 result of the widened operand, rounded once to f32 storage.
+ * RMHIP_ERR_UNSUPPORTED: an op other than 5 (rmhip_moving_window serves those for every window); W_eff > 4096 - a design limit, not a
+ * measured crossover: a tile of 1024 outputs with such a window is 5119 keys, 44 KiB with the counters, of the 64 KiB of LDS a workgroup
+ * gets; more than 2^36 window points (outputs x W_eff) in one request - a cap, not a measurement, that keeps a request to well under a
+ * second of selection work by the LDS rate; more workgroups than one launch takes (2^31 - 1).  Launches are split so that none covers more
+ * than 2^32 window points. */
+/* @serves moving_window */
+RMHIP_API int rmhip_moving_window_long(rmhip_ctx* ctx, rmhip_buf a, int dim, size_t before, size_t after, int op, int endpoints, double fill, int nan_omit,
+                                       int population, const size_t* out_shape, size_t out_rank, rmhip_buf* out);
 /* `iir_filter(b, a, x, options)` (lib.rs:2551-2559; `ProviderIirFilterOptions { dim, zi, unit_denominator }`, :1295-1306; filter.rs:1119-1222):
  * `filter(b, a, x, zi, dim)` in direct form II transposed along zero-based `dim`, every channel an independent recurrence (one thread per
  * channel); coefficients normalised by a(1) as the CPU's complex division rounds them; `zi_or_0`: initial states in the signal's shape with

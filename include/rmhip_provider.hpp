@@ -1234,6 +1234,14 @@ public:
                                   output_shape.size(), &out));
         return with_shape(out);
     }
+    // the hook's second entry point: the median (op 5) over windows of up to 4096 points, tried when moving_window declines
+    GpuTensorHandle moving_window_long(const GpuTensorHandle& input, const std::vector<size_t>& output_shape, size_t dim, size_t before, size_t after, int op,
+                                       int endpoints, double fill, bool nan_omit, bool population) const {
+        uint64_t out = 0;
+        check(rmhip_moving_window_long(ctx_, own(input), (int)dim, before, after, op, endpoints, fill, nan_omit ? 1 : 0, population ? 1 : 0, output_shape.data(),
+                                       output_shape.size(), &out));
+        return with_shape(out);
+    }
     // lib.rs:1797-1807
     GpuTensorHandle hann_window(size_t len, bool periodic) const { return window(0, len, periodic); }
     GpuTensorHandle hamming_window(size_t len, bool periodic) const { return window(1, len, periodic); }

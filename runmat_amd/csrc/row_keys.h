@@ -3,6 +3,7 @@
 //   key(x)          the canonical sort key: orders as `compare_f64` (unique.rs:1357-1369: NaN after every number, the zeros equal) and
 //                   equates as `canonicalize_f64` (:1347-1355: every NaN one key, both zeros one key, anything else its bit pattern) -
 //                   exactly what order_ops.hip's sort_key(x, 0, 0) gives
+//   value_of_key    the number a non-NaN key came from (the zeros' shared key: +0.0)
 //   compare_rows    `compare_numeric_rows` (:1371-1379) over two rows of column-major matrices, column 0 first
 //   rows_differ     row equality (`NumericRowKey`), early exit on the first differing column
 //   lower_bound     the first rank of a sorted permutation of b's rows that does not order before a probe row
@@ -24,6 +25,16 @@ RMHIP_ROWKEY_FN uint64_t key(double x) {
     uint64_t u;
     __builtin_memcpy(&u, &x, sizeof u);
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+// The key of a number back to that number.  Exact for every key but KEY_ZERO, the one both zeros share, which comes back as +0.0: a caller
+// that needs the sign reads the element itself (the moving median of signal_ops.hip does).
+constexpr uint64_t KEY_ZERO = 0x8000000000000000ull;
+RMHIP_ROWKEY_FN double value_of_key(uint64_t k) {
+    const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double x;
+    __builtin_memcpy(&x, &u, sizeof x);
+    return x;
 }
 
 // row ra of a (leading dimension lda) against row rb of b (ldb): -1, 0 or 1

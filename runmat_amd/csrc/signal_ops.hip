@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "move_kernels.h"
+#include "row_keys.h"
 
 using namespace rmhip;
 
@@ -280,6 +281,203 @@ __global__ void __launch_bounds__(kB) k_moving(const double* __restrict__ x, Mov
         }
     }
     out[e] = res;
+}
+
+// ---- median over long windows (rmhip_moving_window_long) ---------------------------------------------------------------------------------
+// The same result as k_moving<5> (moving.rs:1282-1323), found by selection instead of a per-thread sorted array.  One workgroup takes one
+// line and a tile of up to MEDL_T consecutive outputs: the samples those windows cover are staged in LDS once as order-preserving keys
+// (row_keys.h, the key map of k_sort_keys: both zeros one key, NaN the largest key).  Each wave then takes every fourth output and finds
+// the key of the wanted rank by a most-significant-digit radix select over the window's keys: per level an 8-bit digit histogram in the
+// wave's own 256 LDS counters (integer adds: the same bits on every run), a scan across the wave for the digit that holds the rank, a
+// narrower prefix; it stops as soon as one candidate is left.  Level 0 reads every key, so it also counts the NaNs and, with padding, the values below / equal to the fill.  A walk
+// over the window in window order then gives the POSITION of the rank's element among the candidates - the CPU's stable sort keeps equal
+// values in window order - and the element's own bits: the key's inverse, or the sample itself for the one key two values share (+-0).
+// For an even count the upper middle element is the next equal key in window order or else the first least key above.
+constexpr unsigned MEDL_T = 1024;  // most outputs per tile
+constexpr u64 MEDL_W = 4096;       // longest window: MEDL_T + MEDL_W - 1 keys and the counters are 44 KiB of a workgroup's 64 KiB of LDS
+constexpr unsigned MEDL_HIST = 4 * 256 * sizeof(unsigned);  // bytes of the four waves' counters, ahead of the keys
+struct MedLongArgs {
+    u64 pre, len, out_len, before, after, tiles;
+    unsigned T;
+    int endpoints, nan_omit;
+    double fill;
+};
+
+// position in window order of the k-th (from 0) key whose bits above `sh` equal `prefix`; every lane gets it
+__device__ __forceinline__ unsigned medl_walk(const u64* wk, unsigned wlen, int sh, u64 prefix, unsigned k, int lane) {
+    for (unsigned base = 0; base < wlen; base += 64) {
+        const unsigned idx = base + lane;
+        const bool m = idx < wlen && (wk[idx] >> sh) == prefix;
+        const u64 mask = __ballot(m);
+        const unsigned cnt = (unsigned)__popcll(mask);
+        if (k < cnt) {
+            const unsigned rank = (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
+            return base + (unsigned)(__ffsll((long long)__ballot(m && rank == k)) - 1);
+        }
+        k -= cnt;
+    }
+    return 0;  // (not reached: the caller's k is below the number of such keys)
+}
+
+__global__ void __launch_bounds__(kB) k_movmed_long(const double* __restrict__ x, MedLongArgs A, u64 block0, double* __restrict__ out) {
+    extern __shared__ u64 medl_lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned* hist = (unsigned*)medl_lds + wave * 256;
+    u64* keys = medl_lds + MEDL_HIST / sizeof(u64);
+    // neighbouring workgroups are neighbouring lines (the strided samples of a line along a later dimension share their cache lines with the
+    // next lines'), then the tiles of a line, then the outer index
+    const u64 b = block0 + blockIdx.x;
+    const u64 i = b % A.pre, r = b / A.pre, tile = r % A.tiles, o = r / A.tiles;
+    const u64 p0 = tile * A.T;
+    const unsigned nout = (unsigned)(A.out_len - p0 < A.T ? A.out_len - p0 : A.T);
+    const long long len = (long long)A.len, shift = A.endpoints == 1 ? (long long)A.before : 0;
+    // the samples this tile's windows cover: [lo, hi) of the line
+    long long lo = (long long)p0 + shift - (long long)A.before, hi = (long long)p0 + shift + (long long)(nout - 1) + (long long)A.after + 1;
+    lo = lo < 0 ? 0 : (lo > len ? len : lo);
+    hi = hi < lo ? lo : (hi > len ? len : hi);
+    const double* src = x + i + o * A.pre * A.len;
+    const unsigned span = (unsigned)(hi - lo);
+    for (unsigned j = threadIdx.x; j < span; j += kB) keys[j] = rowkeys::key(src[((u64)lo + j) * A.pre]);
+    ((uint4*)hist)[lane] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    const u64 fkey = rowkeys::key(A.fill);
+    const bool fill_nan = A.fill != A.fill;
+    for (unsigned q = wave; q < nout; q += kB / 64) {
+        const u64 p = p0 + q;
+        const long long start = (long long)p + shift - (long long)A.before, end = (long long)p + shift + (long long)A.after;
+        long long s0 = start < 0 ? 0 : start, e0 = end + 1;
+        if (s0 > len) s0 = len;
+        if (e0 < 0) e0 = 0;
+        if (e0 > len) e0 = len;
+        if (e0 < s0) e0 = s0;
+        unsigned fc = 0;  // (a window has at most 2^31 points: checked by the entry point)
+        if (A.endpoints == 2) fc = (unsigned)(start < 0 ? -start : 0) + (unsigned)(end >= len ? end - len + 1 : 0);
+        const u64* wk = keys + (s0 - lo);
+        const unsigned wlen = (unsigned)(e0 - s0);
+        double* dst = out + i + A.pre * (p + A.out_len * o);
+        // level 0: every key
+        unsigned nn = 0, less_f = 0, eq_f = 0;
+        for (unsigned base = 0; base < wlen; base += 64) {
+            const unsigned idx = base + lane;
+            const bool in = idx < wlen;
+            const u64 key = in ? wk[idx] : 0ull;
+            const unsigned digit = (unsigned)(key >> 56);
+            nn += (unsigned)__popcll(__ballot(in && key == ~0ull));
+            if (fc) {
+                less_f += (unsigned)__popcll(__ballot(in && key < fkey));
+                eq_f += (unsigned)__popcll(__ballot(in && key == fkey));
+            }
+            // the lanes that share the first lane's digit add as one (a window's top digits are mostly one value), the others singly
+            const unsigned lead = (unsigned)__shfl((int)digit, 0);
+            const u64 grp = __ballot(in && digit == lead);
+            if (lane == 0) atomicAdd(&hist[lead], (unsigned)__popcll(grp));
+            if (in && digit != lead) atomicAdd(&hist[digit], 1u);
+        }
+        const unsigned n = wlen - nn;
+        bool nan_res = !A.nan_omit && (nn > 0 || (fc > 0 && fill_nan));
+        if (fc && fill_nan) fc = 0;  // omitted NaN padding: the values alone
+        if (n == 0 && fc == 0) nan_res = true;
+        // the ranks wanted of the values (`sel`, and the one after it when `two`), the rest of the middle being the fill (kth_fill above)
+        const unsigned total = n + fc, mid = total / 2;
+        const bool even = !(total & 1);
+        bool fill_a = false, fill_b = false;
+        unsigned ja = even ? mid - 1 : mid, jb = mid;
+        if (fc) {
+            fill_a = ja >= less_f && ja < less_f + eq_f + fc;
+            fill_b = jb >= less_f && jb < less_f + eq_f + fc;
+            if (ja >= less_f + eq_f + fc) ja -= fc;
+            if (jb >= less_f + eq_f + fc) jb -= fc;
+        }
+        const bool need_a = !fill_a, need_b = even && !fill_b;
+        if (nan_res || !(need_a || need_b)) {
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            ((uint4*)hist)[lane] = make_uint4(0, 0, 0, 0);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            if (lane == 0) *dst = nan_res ? NAN : (even ? (A.fill + A.fill) / 2.0 : A.fill);
+            continue;
+        }
+        const bool two = need_a && need_b;
+        unsigned k = need_a ? ja : jb, cand = wlen;
+        u64 prefix = 0;
+        int sh = 56;
+        for (int level = 0;; ++level, sh -= 8) {
+            if (level > 0) {
+                for (unsigned base = 0; base < wlen; base += 64) {
+                    const unsigned idx = base + lane;
+                    const u64 key = idx < wlen ? wk[idx] : 0ull;
+                    const bool m = idx < wlen && (key >> (sh + 8)) == prefix;
+                    const unsigned digit = (unsigned)(key >> sh) & 255u;
+                    const u64 todo = __ballot(m);
+                    if (todo) {
+                        const int leader = __ffsll((long long)todo) - 1;
+                        const unsigned lead = (unsigned)__shfl((int)digit, leader);
+                        const u64 grp = __ballot(m && digit == lead);
+                        if (lane == leader) atomicAdd(&hist[lead], (unsigned)__popcll(grp));
+                        if (m && digit != lead) atomicAdd(&hist[digit], 1u);
+                    }
+                }
+            }
+            // the digit whose bin holds rank k: four bins per lane, their sums scanned across the wave
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            const uint4 c4 = ((const uint4*)hist)[lane];
+            ((uint4*)hist)[lane] = make_uint4(0, 0, 0, 0);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            const unsigned s4 = c4.x + c4.y + c4.z + c4.w;
+            unsigned incl = s4;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const unsigned up = (unsigned)__shfl_up((int)incl, d);
+                if (lane >= d) incl += up;
+            }
+            const unsigned excl = incl - s4;
+            const int who = __ffsll((long long)__ballot(k >= excl && k < incl)) - 1;
+            const unsigned rk = k - excl;  // (meaningful in lane `who`)
+            unsigned bin = 0, below = excl, cnt = c4.x;
+            if (rk >= c4.x) bin = 1, below = excl + c4.x, cnt = c4.y;
+            if (rk >= c4.x + c4.y) bin = 2, below = excl + c4.x + c4.y, cnt = c4.z;
+            if (rk >= c4.x + c4.y + c4.z) bin = 3, below = excl + c4.x + c4.y + c4.z, cnt = c4.w;
+            const unsigned digit = (unsigned)__shfl((int)(4 * lane + bin), who);
+            k -= (unsigned)__shfl((int)below, who);
+            cand = (unsigned)__shfl((int)cnt, who);
+            prefix = (prefix << 8) | digit;
+            if (cand == 1 || level == 7) break;
+        }
+        // the element of that rank and its bits
+        const unsigned pa = medl_walk(wk, wlen, sh, prefix, k, lane);
+        const u64 key_a = wk[pa];
+        double va = key_a == rowkeys::KEY_ZERO ? src[((u64)s0 + pa) * A.pre] : rowkeys::value_of_key(key_a);
+        double vb = va;
+        if (two) {
+            unsigned pb;
+            u64 key_b;
+            if (k + 1 < cand) {  // the next equal key in window order
+                pb = medl_walk(wk, wlen, sh, prefix, k + 1, lane);
+                key_b = key_a;
+            } else {  // the least key above, at its first position
+                u64 best = ~0ull;
+                unsigned at = 0;
+                for (unsigned idx = lane; idx < wlen; idx += 64) {
+                    const u64 key = wk[idx];
+                    if (key > key_a && key < best) best = key, at = idx;
+                }
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) {
+                    const u64 ok = (u64)__shfl_xor((long long)best, d);
+                    const unsigned oa = (unsigned)__shfl_xor((int)at, d);
+                    if (ok < best || (ok == best && oa < at)) best = ok, at = oa;
+                }
+                pb = at, key_b = best;
+            }
+            vb = key_b == rowkeys::KEY_ZERO ? src[((u64)s0 + pb) * A.pre] : rowkeys::value_of_key(key_b);
+        }
+        if (lane == 0) {
+            double res;
+            if (!even) res = va;
+            else if (two) res = (va + vb) / 2.0;
+            else res = need_a ? (va + A.fill) / 2.0 : (A.fill + va) / 2.0;
+            *dst = res;
+        }
+    }
 }
 
 // polyval (builtins/math/poly/polyval.rs:886-905): Horner's rule acc = acc * x + c over the coefficients, product rounded before the sum;
@@ -1277,14 +1475,15 @@ int rmhip_conv2d(rmhip_ctx* ctx, rmhip_buf signal, rmhip_buf kernel, int mode, r
     return RMHIP_OK;
 }
 
-int rmhip_moving_window(rmhip_ctx* ctx, rmhip_buf a, int dim, size_t before, size_t after, int op, int endpoints, double fill, int nan_omit, int population,
-                        const size_t* out_shape, size_t out_rank, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
+namespace rmhip {
+namespace {
+// What both moving_window entry points make of a request: the operand, the geometry along `dim`, and the refusals they share, in one order
+int moving_prepare(Context* c, rmhip_buf a, int dim, size_t before, size_t after, int op, int endpoints, double fill, int nan_omit, int population,
+                   const size_t* out_shape, size_t out_rank, rmhip_buf* out, Buffer* ab, MovingArgs* args) {
     if (!out || (out_rank && !out_shape)) return fail(RMHIP_ERR_INVALID, "moving_window: null argument");
     if (dim < 0 || op < 0 || op > 7 || endpoints < 0 || endpoints > 2) return fail(RMHIP_ERR_INVALID, "moving_window: dim %d, op %d, endpoints %d", dim, op, endpoints);
-    Buffer ab;
-    RMHIP_TRY(c->get(a, &ab));
-    std::vector<size_t> shape = ab.shape;
+    RMHIP_TRY(c->get(a, ab));
+    std::vector<size_t> shape = ab->shape;
     if ((size_t)dim >= shape.size()) shape.resize(dim + 1, 1);  // simple_provider.rs:1266-1269
     if ((size_t)dim >= out_rank) return fail(RMHIP_ERR_INVALID, "moving_window: dimension exceeds tensor rank");
     // the caller's output shape (moving.rs:1545-1570): the input's, the dimension trimmed by before + after for 'discard'
@@ -1294,13 +1493,25 @@ int rmhip_moving_window(rmhip_ctx* ctx, rmhip_buf a, int dim, size_t before, siz
     while (given.size() > (size_t)dim + 1 && given.back() == 1) given.pop_back();
     while (wanted.size() > (size_t)dim + 1 && wanted.back() == 1) wanted.pop_back();
     if (given != wanted) return fail(RMHIP_ERR_SHAPE, "moving_window: output shape does not match the request");
-    MovingArgs A{};
+    MovingArgs& A = *args;
+    A = MovingArgs{};
     A.pre = 1, A.post = 1;
     for (int k = 0; k < dim; ++k) A.pre *= shape[k];
     for (size_t k = dim + 1; k < shape.size(); ++k) A.post *= shape[k];
     A.len = shape[dim], A.out_len = want[dim], A.before = before, A.after = after;
     A.op = op, A.endpoints = endpoints, A.nan_omit = nan_omit ? 1 : 0, A.population = population ? 1 : 0, A.fill = fill;
     if (before > (1ull << 30) || after > (1ull << 30)) return fail(RMHIP_ERR_UNSUPPORTED, "moving_window: window %zu + %zu", before, after);
+    return RMHIP_OK;
+}
+}  // namespace
+}  // namespace rmhip
+
+int rmhip_moving_window(rmhip_ctx* ctx, rmhip_buf a, int dim, size_t before, size_t after, int op, int endpoints, double fill, int nan_omit, int population,
+                        const size_t* out_shape, size_t out_rank, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    Buffer ab;
+    MovingArgs A;
+    RMHIP_TRY(moving_prepare(c, a, dim, before, after, op, endpoints, fill, nan_omit, population, out_shape, out_rank, out, &ab, &A));
     if (op == 5 && std::min<u64>(A.len, before + after + 1) > (u64)MED_MAX)
         return fail(RMHIP_ERR_UNSUPPORTED, "moving_window: median over windows of more than %d points", MED_MAX);
     // prod with padding multiplies by fill^count (`powf`, moving.rs:991): only fills whose every power is the fill itself stay exact
@@ -1328,6 +1539,41 @@ int rmhip_moving_window(rmhip_ctx* ctx, rmhip_buf a, int dim, size_t before, siz
         default: hipLaunchKernelGGL(k_moving<7>, grid, block, 0, c->stream, ab.data(), A, ob.data()); break;
     }
     c->tel.kernel_launches++;
+    RMHIP_HIP_CHECK(hipGetLastError());
+    return RMHIP_OK;
+}
+
+int rmhip_moving_window_long(rmhip_ctx* ctx, rmhip_buf a, int dim, size_t before, size_t after, int op, int endpoints, double fill, int nan_omit, int population,
+                             const size_t* out_shape, size_t out_rank, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    Buffer ab;
+    MovingArgs A;
+    RMHIP_TRY(moving_prepare(c, a, dim, before, after, op, endpoints, fill, nan_omit, population, out_shape, out_rank, out, &ab, &A));
+    if (op != 5) return fail(RMHIP_ERR_UNSUPPORTED, "moving_window_long: the median only; rmhip_moving_window serves op %d for every window", op);
+    const u64 weff = std::min<u64>(A.len, before + after + 1);
+    if (weff > MEDL_W) return fail(RMHIP_ERR_UNSUPPORTED, "moving_window_long: median over windows of more than %llu points", MEDL_W);
+    const u64 lines = A.pre * A.post, outputs = lines * A.out_len;
+    if (weff && outputs > (1ull << 36) / weff) return fail(RMHIP_ERR_UNSUPPORTED, "moving_window_long: %llu outputs of %llu window points", outputs, weff);
+    // tiles of MEDL_T outputs, shorter ones while they would leave compute units without a workgroup
+    MedLongArgs M{};
+    M.T = MEDL_T;
+    while (M.T > 64 && lines * ((A.out_len + M.T - 1) / M.T) < 1024) M.T /= 2;
+    M.tiles = (A.out_len + M.T - 1) / M.T;
+    const u64 blocks = lines * M.tiles;
+    if (blocks > 0x7fffffffull) return fail(RMHIP_ERR_UNSUPPORTED, "moving_window_long: %llu workgroups", blocks);
+    Buffer ob;
+    RMHIP_TRY(c->new_buffer(out_shape, out_rank, out, &ob));
+    if (ob.numel == 0) return RMHIP_OK;
+    M.pre = A.pre, M.len = A.len, M.out_len = A.out_len, M.before = before, M.after = after;
+    M.endpoints = endpoints, M.nan_omit = A.nan_omit, M.fill = fill;
+    const u64 span = std::min<u64>(A.len, (u64)M.T + before + after);  // the most samples a tile's windows cover
+    const size_t lds = MEDL_HIST + span * sizeof(u64);
+    // launches of at most 2^32 window points each, so that no single launch runs long
+    const u64 per = std::max<u64>(1, (1ull << 32) / (std::min<u64>(M.T, A.out_len) * weff));
+    for (u64 b0 = 0; b0 < blocks; b0 += per) {
+        hipLaunchKernelGGL(k_movmed_long, dim3((unsigned)std::min<u64>(per, blocks - b0)), dim3(kB), lds, c->stream, ab.data(), M, b0, ob.data());
+        c->tel.kernel_launches++;
+    }
     RMHIP_HIP_CHECK(hipGetLastError());
     return RMHIP_OK;
 }

@@ -1164,10 +1164,19 @@ impl AccelProvider for HipProvider {
             let omit = matches!(request.nan_mode, ProviderNanMode::Omit) as c_int;
             let population = matches!(request.normalization, ProviderStdNormalization::Population) as c_int;
             let mut out = 0u64;
-            check(unsafe {
-                rmhip_moving_window(self.ctx, self.own(request.input)?, request.dim as c_int, request.before, request.after, op, endpoints, fill, omit, population,
+            let input = self.own(request.input)?;
+            let mut rc = unsafe {
+                rmhip_moving_window(self.ctx, input, request.dim as c_int, request.before, request.after, op, endpoints, fill, omit, population,
                                     request.output_shape.as_ptr(), request.output_shape.len(), &mut out)
-            })?;
+            };
+            if rc == RMHIP_ERR_UNSUPPORTED && matches!(request.op, ProviderMovingWindowOp::Median) {
+                // a median window of more than 64 points: the radix select; its own declines go back to the caller as Err
+                rc = unsafe {
+                    rmhip_moving_window_long(self.ctx, input, request.dim as c_int, request.before, request.after, op, endpoints, fill, omit, population,
+                                             request.output_shape.as_ptr(), request.output_shape.len(), &mut out)
+                };
+            }
+            check(rc)?;
             self.handle(out)
         })
     }
