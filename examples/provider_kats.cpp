@@ -184,6 +184,21 @@ int main() {
             }
         }
         {
+            // chol's second entry point on the reference's chol_gpu_failure_flag (chol.rs:1008-1021): [1 2; 2 1] fails its second pivot, so
+            // info = 2 and the factor keeps row 1, [1 2; 0 0] (column-major below) - lower: its transpose; chol itself declines the matrix
+            auto h = p.upload({1, 2, 2, 1}, {2, 2});
+            try {
+                p.chol(h, false);
+                ok = false;
+            } catch (const rmhip::ProviderError& e) {
+                ok = ok && e.code == RMHIP_ERR_UNSUPPORTED;
+            }
+            auto up = p.chol_info(h, false), low = p.chol_info(h, true);
+            ok = ok && up.info == 2 && eq(p.download(up.factor).data, {1, 0, 2, 0}) && low.info == 2 && eq(p.download(low.factor).data, {1, 2, 0, 0});
+            auto spd = p.chol_info(p.upload({4, 12, -16, 12, 37, -43, -16, -43, 98}, {3, 3}), false);
+            ok = ok && spd.info == 0 && eq(p.download(spd.factor).data, {2, 0, 0, 6, 1, 0, -8, 5, 3});
+        }
+        {
             // ProviderPrecision::F32 (lib.rs:815-818): host views stay f64, storage is f32, results round once
             rmhip::HipProvider q(0, 32);
             ok = ok && std::string(q.precision()) == "F32";

@@ -1079,9 +1079,30 @@ RMHIP_API int rmhip_mrdivide(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf
  * Cholesky-Crout with a symmetry check of every pair to 1e-12 relative): the upper factor R (A = R'R) or, lower != 0, L = R'.  The SUCCESS
  * path only - a recursive blocked factorisation (deep MFMA products, 64 x 64 leaves in LDS), *info = 0, forward error ~ cond * eps against
  * the host's in-order sums.  A matrix that fails the symmetry check or has a pivot that is not positive and finite is
- * RMHIP_ERR_UNSUPPORTED: the builtin falls back (chol.rs:331-342) and its host code produces `info` and the partial factor. */
+ * RMHIP_ERR_UNSUPPORTED: the builtin falls back (chol.rs:331-342) and its host code produces `info` and the partial factor.
+ * `rmhip_chol_info` answers those matrices on the device.  A positive pivot whose root is <= 1e-12 is not looked for here: such a matrix
+ * gets info = 0 and the factor the divisions give, where the CPU's denominator test reports that pivot (info = its 1-based column) unless
+ * it is the last one. */
 /* @serves chol */
 RMHIP_API int rmhip_chol(rmhip_ctx* ctx, rmhip_buf a, int lower, rmhip_buf* factor, unsigned* info);
+/* `[R, p] = chol(A)` with its failure forms: the second entry point of the hook, which answers everything rmhip_chol answers - the same
+ * factor bit for bit, *info = 0 - and does not need it tried first.  Arguments, the refusals for null outputs, non-square, higher-rank
+ * operands, the empty result and the precision-32 handling are rmhip_chol's.  Columns are judged left to right as chol.rs:374-433 does:
+ *   - column j (0-based) holds a pair (i, j), i < j, that fails the symmetry check (a NaN in the pair or Inf - Inf fails it): RMHIP_OK,
+ *     *info = j + 1, the factor holds columns < j of R and exact zeros elsewhere; column j is not formed.  Checked before j's pivot.
+ *   - the pivot a_jj - sum_k r_kj^2 is not finite or <= 0: RMHIP_OK, *info = j + 1, the factor holds columns < j of R and rows < j of
+ *     column j (the reference has formed them by then), exact zeros elsewhere.
+ * Only the upper triangle of `a` enters the sums.  lower != 0 returns the transpose of that partial upper factor (from_components,
+ * chol.rs:276-287).  No NaN or Inf of the steps after the event reaches the result.  Kept entries are those of the blocked factorisation:
+ * forward error ~ cond * eps of the leading block against the host's in-order sums.  The event is decided on the device (first asymmetric
+ * column, first bad pivot, first tiny pivot; one 24-byte read-back is the call's only synchronisation) and one kernel writes the factor
+ * from the workspace; a failing call costs what a successful one costs.
+ * RMHIP_ERR_UNSUPPORTED, nothing left behind: a positive pivot with a root <= 1e-12 in column t, before any event above and not the last
+ * column.  The reference then fails its denominator test in column t + 1 (info = t + 1) and keeps entries that were divided by that root;
+ * a matrix of condition >~ 1e24 stays with the host.  (Slightly conservative: an event in column t + 1 itself would precede that test.)
+ * A tiny LAST pivot is a success, as on the CPU. */
+/* @serves chol */
+RMHIP_API int rmhip_chol_info(rmhip_ctx* ctx, rmhip_buf a, int lower, rmhip_buf* factor, unsigned* info);
 /* `qr(a, options)` (lib.rs:2509-2515 -> ProviderQrResult { q, r, perm_matrix, perm_vector } :665-670) with the CPU builtin's contract
  * (qr.rs:576-870): column pivoting always on (squared norms recomputed before every step, ties to the last index), the builtin's
  * reflector quirks, Q and R cleaned at |x| <= 1e-12.  economy != 0 with rows >= cols: Q is rows x cols and R cols x cols; otherwise Q is

@@ -660,6 +660,14 @@ public:
         check(rmhip_chol(ctx_, own(a), lower ? 1 : 0, &out, &info));
         return {with_shape(out), info};
     }
+    // the hook's second entry point: what chol answers, bit for bit, and for an asymmetric or not positive definite matrix the reference's
+    // info and partial factor (chol.rs:374-433); throws only for a pivot whose root is <= 1e-12 before the last column
+    CholResult chol_info(const GpuTensorHandle& a, bool lower) const {
+        uint64_t out = 0;
+        unsigned info = 0;
+        check(rmhip_chol_info(ctx_, own(a), lower ? 1 : 0, &out, &info));
+        return {with_shape(out), info};
+    }
     // lib.rs:2509-2515: column-pivoted QR with the CPU builtin's contract; both permutations are returned whatever options.pivot says.
     // Throws for what the host path must answer (non-finite input, max |a| >= 1e150, more than two dimensions, a full Q that does not fit)
     ProviderQrResult qr(const GpuTensorHandle& a, const ProviderQrOptions& options = ProviderQrOptions()) const {

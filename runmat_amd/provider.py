@@ -1008,6 +1008,14 @@ class HipProvider:
         self._check(self._lib.rmhip_chol(self._ctx, self._id(a), 1 if lower else 0, C.byref(out), C.byref(info)))
         return ProviderCholResult(self._handle(out.value), int(info.value))
 
+    def chol_info(self, a: GpuTensorHandle, lower: bool = False) -> "ProviderCholResult":
+        """The hook's second entry point: everything `chol` answers, bit for bit, and the failure forms of `[R, p] = chol(A)` - for a
+        matrix that is asymmetric or has a pivot that is not positive and finite, the reference's `info` and partial factor
+        (chol.rs:374-433), resident.  Raises (UNSUPPORTED) only for a pivot whose root is <= 1e-12 before the last column."""
+        out, info = C.c_uint64(), C.c_uint()
+        self._check(self._lib.rmhip_chol_info(self._ctx, self._id(a), 1 if lower else 0, C.byref(out), C.byref(info)))
+        return ProviderCholResult(self._handle(out.value), int(info.value))
+
     def inv(self, matrix: GpuTensorHandle, options=None) -> GpuTensorHandle:
         """`inv` (lib.rs:2430-2436; `ProviderInvOptions {}`): X = A \\ I on the LU path; SINGULAR -> the caller's CPU path (inv.rs:225-227)."""
         out = C.c_uint64()

@@ -508,11 +508,13 @@ impl AccelProvider for HipProvider {
             self.handle(out)
         })
     }
-    // chol: the device's success path (info = 0); Err for a matrix that is not symmetric positive definite -> chol.rs:331-342 host path
+    // chol: the hook's second entry point ALONE.  It answers everything the first one answers, bit for bit, and the failure forms too (info
+    // and the resident partial factor for an asymmetric or not positive definite matrix); trying the first entry point before it would
+    // factor every failing matrix twice.  Err only for a pivot whose root is <= 1e-12 before the last column -> chol.rs:331-342 host path
     fn chol<'a>(&'a self, a: &'a GpuTensorHandle, lower: bool) -> AccelProviderFuture<'a, ProviderCholResult> {
         Box::pin(async move {
             let (mut out, mut info) = (0u64, 0u32);
-            check(unsafe { rmhip_chol(self.ctx, self.own(a)?, lower as c_int, &mut out, &mut info) })?;
+            check(unsafe { rmhip_chol_info(self.ctx, self.own(a)?, lower as c_int, &mut out, &mut info) })?;
             Ok(ProviderCholResult { factor: self.handle(out)?, info })
         })
     }
