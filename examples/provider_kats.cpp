@@ -57,6 +57,25 @@ int main() {
         lt.need_rcond = 1;
         auto sol = p.linsolve(p.upload({3, -1, 4, 0, 2, 1, 0, 0, 5}, {3, 3}), p.upload({9, 1, 19}, {3, 1}), lt);
         ok = ok && near(p.download(sol.solution).data, {3, 2, 1}, 1e-12) && sol.reciprocal_condition == 2.0 / 5.0;
+        {
+            // linsolve's second entry point: 2 I \ [1; 1] = [0.5; 0.5] with rcond 1, which linsolve itself declines once rcond is asked for
+            rmhip_linsolve_options_t rq{};
+            rq.need_rcond = 1;
+            auto two_i = p.upload({2, 0, 0, 2}, {2, 2}), ones = p.upload({1, 1}, {2, 1});
+            try {
+                p.linsolve(two_i, ones, rq);
+                ok = false;
+            } catch (const rmhip::ProviderError& e) {
+                ok = ok && e.code == RMHIP_ERR_UNSUPPORTED;
+            }
+            auto r = p.linsolve_rcond(two_i, ones, rq);
+            ok = ok && eq(p.download(r.solution).data, {0.5, 0.5}) && r.reciprocal_condition == 1.0;
+            // cond's second entry point on the reference's KATs (cond.rs:661-690): [4 -1; 2 3] is 15/7 in One and Inf, diag(5, 2) 2.9 in Fro
+            auto m = p.upload({4, 2, -1, 3}, {2, 2});
+            ok = ok && near(p.download(p.cond_norm(m, 1)).data, {15.0 / 7.0}, 1e-12) && near(p.download(p.cond_norm(m, 2)).data, {15.0 / 7.0}, 1e-12);
+            ok = ok && near(p.download(p.cond_norm(p.upload({5, 0, 0, 2}, {2, 2}), 3)).data, {2.9}, 1e-12);
+            ok = ok && std::isinf(p.download(p.cond_norm(p.upload({1, 2, 2, 4}, {2, 2}), 1)).data[0]);
+        }
         // mldivide: mldivide.rs:662-680 ([1 2; 3 4] \ [5; 6] = [-4; 4.5])
         ok = ok && near(p.download(p.mldivide(p.upload({1, 3, 2, 4}, {2, 2}), p.upload({5, 6}, {2, 1}))).data, {-4, 4.5}, 1e-12);
         // stochastic_evolution with zero scale: accelerate/tests/stochastic_evolution.rs:17-47

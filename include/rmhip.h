@@ -985,11 +985,26 @@ RMHIP_API int rmhip_covariance_general(rmhip_ctx* ctx, rmhip_buf matrix, rmhip_b
  * 448-467; the other norms: RMHIP_ERR_UNSUPPORTED) and `pinv(matrix, options)` (lib.rs:2437-2443; pinv.rs:242-285) from the one-sided Jacobi SVD of
  * svdsolve.hip (min(rows, cols) <= 4096, finite data; else RMHIP_ERR_UNSUPPORTED): rank = singular values above the tolerance (default max(m, n) *
  * eps(s_max), common/linalg.rs:209-228), cond = s_max / s_min (inf when s_min == 0; 0 for an empty matrix), pinv = V diag(1 / s_i, s_i > tol) U' as
- * [cols, rows].  rank and cond return [1, 1] tensors.  The CPU decomposes with nalgebra: parity by tolerance (singular values to relative accuracy). */
+ * [cols, rows].  rank and cond return [1, 1] tensors.  The CPU decomposes with nalgebra: parity by tolerance (singular values to relative accuracy).
+ * The norms rmhip_cond declines (1 One, 2 Inf, 3 Fro) are served by its sibling rmhip_cond_norm. */
 /* @serves rank */
 RMHIP_API int rmhip_rank(rmhip_ctx* ctx, rmhip_buf matrix, int has_tolerance, double tolerance, rmhip_buf* out);
 /* @serves cond */
 RMHIP_API int rmhip_cond(rmhip_ctx* ctx, rmhip_buf matrix, int norm, rmhip_buf* out);
+/* `cond(matrix, norm)` for norm = 1 One, 2 Inf, 3 Fro (cond.rs:276-300, 343-357, 384-414): the second entry point of the hook, a [1, 1] tensor.
+ * In this order: a null `out` or an unknown norm code is RMHIP_ERR_INVALID; norm == 0 RMHIP_ERR_UNSUPPORTED (rmhip_cond serves the 2-norm); a
+ * complex tensor UNSUPPORTED; more than two non-unit dimensions INVALID; rows == 0 or cols == 0 gives 0; one element gives a == 0 ? Inf : 1
+ * (NaN: 1), evaluated on the device; rows != cols is INVALID ("cond: matrix must be square for the requested norm."); a non-finite entry
+ * UNSUPPORTED (the CPU's f64::max drops NaN sums there); otherwise norm(A) * norm(inv(A)) - One the largest column sum of |a|, Inf the
+ * largest row sum of |a| (columns added in ascending order, as on the CPU), Fro sqrt(sum a^2) without scaling - and a product that is not
+ * finite is Inf.  The inverse is the LU inverse with the reference's pivot rule, formed in column slabs and folded into the norms slab by
+ * slab (cond_norm.hip): memory beyond the operand is n^2 + n W + O(n) doubles, W = 1024.  The first pivot at the LU's cut-off decides: exactly
+ * zero gives Inf (nalgebra's try_inverse returns None, cond.rs:354-356), nonzero and <= 1e-12 is UNSUPPORTED (the host's LU answers with
+ * its own rounding noise).  One 12-byte verdict is read back; a refused call leaves nothing behind; the operand is not modified; fixed
+ * summation order, so equal operands give equal bits.  Forward error within n eps cond_p of the CPU's value (first order, LU inverse).
+ * A precision-32 context runs the same path on a widened copy and stores the result as f32. */
+/* @serves cond */
+RMHIP_API int rmhip_cond_norm(rmhip_ctx* ctx, rmhip_buf matrix, int norm, rmhip_buf* out);
 /* `rcond(matrix)` (lib.rs:2471-2476; rcond.rs:304-320): s_min / s_max of a square matrix from the same decomposition (0 when s_max == 0, inf for the
  * empty matrix; a non-square input is RMHIP_ERR_INVALID). */
 /* @serves rcond */
@@ -1181,7 +1196,7 @@ RMHIP_API int rmhip_inv(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf* out);
  *   - lower / upper : triangular solve on the device, *rcond as the reference computes it.
  *   - general square: LU solve as rmhip_mldivide; *rcond = NaN.  With need_rcond or has_rcond the
  *     reference reports sigma_min/sigma_max of an SVD (linsolve.rs:933-944): UNSUPPORTED here so the
- *     caller takes its CPU path (linsolve.rs:414-417 `.ok()`).
+ *     caller takes its CPU path (linsolve.rs:414-417 `.ok()`).  Its sibling rmhip_linsolve_rcond serves that form on the device.
  *   - general rectangular (no rcond requested): full-rank least squares / minimum norm as rmhip_mldivide; *rcond = NaN.
  *   - conjugate / symmetric / posdef are accepted and, as in the reference's real path, have no effect. */
 typedef struct rmhip_linsolve_options {
@@ -1192,6 +1207,17 @@ typedef struct rmhip_linsolve_options {
 /* @serves linsolve */
 RMHIP_API int rmhip_linsolve(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, const rmhip_linsolve_options_t* opts,
                              rmhip_buf* out, double* reciprocal_condition);
+/* `[x, r] = linsolve(A, b)` / `opts.RCOND` for a general matrix, square or rectangular: the second entry point of the hook, with
+ * rmhip_linsolve's arguments, serving what that one declines.  A request with the lower or upper hint, or with neither need_rcond nor
+ * has_rcond, is RMHIP_ERR_UNSUPPORTED here (rmhip_linsolve serves it).  *reciprocal_condition = sigma_min / sigma_max over the Jacobi
+ * singular values of the (TRANSA: transposed) matrix, 0 when a value is not finite or sigma_max == 0 (singular_value_rcond,
+ * common/linalg.rs:241-259; linsolve.rs:933-944).  has_rcond and rcond < opts->rcond: RMHIP_ERR_SINGULAR, "linsolve: matrix is singular
+ * to working precision." (linsolve.rs:1000-1009), decided before any solve, nothing left behind.  Otherwise status and solution are
+ * exactly rmhip_linsolve's for the same operands with need_rcond = has_rcond = 0, bit for bit - LU, least squares or the SVD fallback.
+ * min(rows, cols) > 4096 (RMHIP_SVD_MAX_COLS), non-finite data, scalar operands and empty systems are UNSUPPORTED. */
+/* @serves linsolve */
+RMHIP_API int rmhip_linsolve_rcond(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, const rmhip_linsolve_options_t* opts,
+                                   rmhip_buf* out, double* reciprocal_condition);
 /* `transpose` (lib.rs:2532): out[j,i] = a[i,j] for a 2-D tensor, shape [cols, rows].  Like the reference's wgpu
  * provider (ops/tensor.rs:828-846, `record_handle_transpose` lib.rs:218-245) the result is a VIEW that aliases the
  * operand's storage: rmhip_matmul / rmhip_syrk read it in place through transposed-operand MFMA kernels (`A'*B`,

@@ -755,6 +755,14 @@ public:
         check(rmhip_linsolve(ctx_, own(lhs), own(rhs), &opts, &out, &rcond));
         return {with_shape(out), rcond};
     }
+    // the hook's second entry point: a general matrix with need_rcond / has_rcond, which linsolve declines - linsolve's solution bit for
+    // bit and sigma_min / sigma_max (linsolve.rs:933-944); throws SINGULAR below opts.rcond, UNSUPPORTED for the triangular hints
+    LinsolveResult linsolve_rcond(const GpuTensorHandle& lhs, const GpuTensorHandle& rhs, const rmhip_linsolve_options_t& opts) const {
+        uint64_t out = 0;
+        double rcond = 0.0;
+        check(rmhip_linsolve_rcond(ctx_, own(lhs), own(rhs), &opts, &out, &rcond));
+        return {with_shape(out), rcond};
+    }
     GpuTensorHandle matmul_power_step(const GpuTensorHandle& lhs, const GpuTensorHandle& rhs, double epsilon) const {  // lib.rs:2414
         uint64_t out = 0;
         check(rmhip_matmul_power_step(ctx_, own(lhs), own(rhs), epsilon, &out));
@@ -790,6 +798,13 @@ public:
     GpuTensorHandle cond(const GpuTensorHandle& m, int norm = 0) const {
         uint64_t out = 0;
         check(rmhip_cond(ctx_, own(m), norm, &out));
+        return with_shape(out);
+    }
+    // the hook's second entry point: norm 1 One, 2 Inf, 3 Fro (cond.rs:343-357, 384-414) from the LU inverse, formed and folded into the
+    // norms slab by slab; Inf for an exactly singular matrix, throws for non-finite data and a nonzero pivot at the LU's cut-off
+    GpuTensorHandle cond_norm(const GpuTensorHandle& m, int norm) const {
+        uint64_t out = 0;
+        check(rmhip_cond_norm(ctx_, own(m), norm, &out));
         return with_shape(out);
     }
     GpuTensorHandle rcond(const GpuTensorHandle& m) const {  // lib.rs:2471

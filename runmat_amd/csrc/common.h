@@ -529,6 +529,14 @@ int lu_solve_device(Context* c, const double* LU, size_t n, size_t lda, const in
                     const double* B, size_t nrhs, size_t ldb, double* X, size_t ldx);
 int lu_extract_device(Context* c, const double* LU, size_t rows, size_t cols, const int* perm_dev,
                       double* L, double* U, double* P, double* piv);
+// The substitutions of lu_solve_device alone: X (n x nrhs, ld ldx) holds P B on entry and U^-1 L^-1 P B on return.  RMHIP_SUBST_RETRY:
+// the chain kernel timed out and X is clobbered - the caller writes P B again and calls once more (the pair form then runs).
+int lu_substitute_device(Context* c, const double* LU, size_t n, size_t lda, double* X, size_t nrhs, size_t ldx);
+// solve.cpp: copy `src` into the padded workspace (leading dimension lu_padded_ld(rows)) and factor it, again on a fresh copy when the
+// panel kernels ask for it; solve_path / pad_n as described there
+size_t lu_padded_ld(size_t rows);
+int lu_copy_and_factor(Context* c, const double* src, size_t rows, size_t cols, double* work, size_t ldw, int* perm, int* info,
+                       bool solve_path = false, size_t pad_n = 0);
 // The RMHIP_LU_* environment knobs (docs/KNOBS.md), each read by one of the two functions below (lu.hip) and nowhere else.
 struct LuKnobs {  // read on every call: tests flip these inside one process
     bool fast = true;             // RMHIP_LU_FAST=0: the grid-wide pivot rule on the solve path too
@@ -569,6 +577,8 @@ int svd_solve_device(Context* c, const double* A, size_t m, size_t n, const doub
 // the same decomposition behind rank / cond / pinv (rank.rs, cond.rs, pinv.rs: nalgebra's SVD on the CPU)
 int svd_values_host(Context* c, const char* who, const double* A, size_t m, size_t n, std::vector<double>* values);
 double svd_default_tolerance(const std::vector<double>& values, size_t m, size_t n);
+// `singular_value_rcond` (common/linalg.rs:241-259): 0 for a non-finite value or s_max == 0, else s_min / s_max - rcond and linsolve's rcond
+double svd_rcond(const std::vector<double>& values);
 int svd_pinv_device(Context* c, const double* A, size_t m, size_t n, double tol, double* X);
 
 // The switches of the solve dispatch (docs/KNOBS.md), read by solve_knobs() (solve.cpp) and nowhere else.

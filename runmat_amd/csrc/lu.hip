@@ -3537,26 +3537,28 @@ int lu_pad_identity_device(Context* c, double* W, size_t ldw, size_t n, size_t n
     return launch_check(c);
 }
 
+// The substitutions alone, on X = P B (common.h).  RMHIP_SUBST_RETRY: X is clobbered, the caller gathers again and calls once more.
+int lu_substitute_device(Context* c, const double* LU, size_t n, size_t lda, double* X, size_t nrhs, size_t ldx) {
+    if (n == 0 || nrhs == 0) return RMHIP_OK;
+    if (nrhs <= (size_t)RU_MAX_RHS && !(lu_process_knobs().skip & 16)) return substitute_few_rhs(c, LU, n, lda, X, ldx, nrhs);
+    RMHIP_TRY(trsm_lower_rec(c, LU, lda, n, X, ldx, nrhs));
+    return trsm_upper_rec(c, LU, lda, n, X, ldx, nrhs);
+}
+
 // X = U^-1 L^-1 (P B) for square LU (n x n).
 int lu_solve_device(Context* c, const double* LU, size_t n, size_t lda, const int* perm_dev, const double* B,
                     size_t nrhs, size_t ldb, double* X, size_t ldx) {
     if (n == 0 || nrhs == 0) return RMHIP_OK;
     if (nrhs > 65535) return fail(RMHIP_ERR_UNSUPPORTED, "mldivide: more than 65535 right-hand sides");
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n + 255) / 256), (unsigned)nrhs), dim3(256), 0, c->stream, B, ldb,
-                       perm_dev, n, nrhs, X, ldx);
-    RMHIP_TRY(launch_check(c));
-    if (nrhs <= (size_t)RU_MAX_RHS && !(lu_process_knobs().skip & 16)) {
-        int rc = substitute_few_rhs(c, LU, n, lda, X, ldx, nrhs);
-        if (rc == RMHIP_SUBST_RETRY) {  // the chain kernel timed out (never seen; context flag now selects the pair form)
-            hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n + 255) / 256), (unsigned)nrhs), dim3(256), 0, c->stream, B, ldb,
-                               perm_dev, n, nrhs, X, ldx);
-            RMHIP_TRY(launch_check(c));
-            rc = substitute_few_rhs(c, LU, n, lda, X, ldx, nrhs);
-        }
-        return rc;
+    int rc = RMHIP_SUBST_RETRY;
+    // a second round only after the chain kernel timed out (never seen; the context flag then selects the pair form)
+    for (int round = 0; round < 2 && rc == RMHIP_SUBST_RETRY; ++round) {
+        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n + 255) / 256), (unsigned)nrhs), dim3(256), 0, c->stream, B, ldb,
+                           perm_dev, n, nrhs, X, ldx);
+        RMHIP_TRY(launch_check(c));
+        rc = lu_substitute_device(c, LU, n, lda, X, nrhs, ldx);
     }
-    RMHIP_TRY(trsm_lower_rec(c, LU, lda, n, X, ldx, nrhs));
-    return trsm_upper_rec(c, LU, lda, n, X, ldx, nrhs);
+    return rc;
 }
 
 // Split the packed factors into the five outputs of ProviderLuResult (host_lu.rs:72-118):

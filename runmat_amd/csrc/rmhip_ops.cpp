@@ -1078,13 +1078,7 @@ int rmhip_rcond(rmhip_ctx* ctx, rmhip_buf matrix, rmhip_buf* out) {
     if (rows == 0) return scalar_result(c, INFINITY, out);  // rcond.rs:311-313
     std::vector<double> sv;
     RMHIP_TRY(svd_values_host(c, "rcond", mb.data(), rows, cols, &sv));
-    double mn = INFINITY, mx = 0.0;  // singular_value_rcond, common/linalg.rs:241-259
-    for (double v : sv) {
-        const double a = std::fabs(v);
-        if (!std::isfinite(a)) return scalar_result(c, 0.0, out);
-        mn = a < mn ? a : mn, mx = a > mx ? a : mx;
-    }
-    return scalar_result(c, mx == 0.0 ? 0.0 : mn / mx, out);
+    return scalar_result(c, svd_rcond(sv), out);  // singular_value_rcond, common/linalg.rs:241-259
 }
 
 int rmhip_pinv(rmhip_ctx* ctx, rmhip_buf matrix, int has_tolerance, double tolerance, rmhip_buf* out) {

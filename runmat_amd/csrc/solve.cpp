@@ -28,8 +28,8 @@ SolveKnobs solve_knobs() {
 // Copy `src` (rows x cols, dense) into the padded workspace and factor it; when the persistent panel kernels
 // report that their workgroups were not co-resident the copy is refreshed and factored conservatively.
 // pad_n > rows (square systems on the solve path): factor [A 0; 0 I] of order pad_n instead - see lu_pad_rows
-static int lu_copy_and_factor(Context* c, const double* src, size_t rows, size_t cols, double* work, size_t ldw, int* perm,
-                              int* info, bool solve_path = false, size_t pad_n = 0) {
+int rmhip::lu_copy_and_factor(Context* c, const double* src, size_t rows, size_t cols, double* work, size_t ldw, int* perm, int* info,
+                              bool solve_path, size_t pad_n) {
     // solve_path: the caller only needs SOME stable factorisation (mldivide / linsolve / mrdivide: the pivots never leave the provider),
     // so the first attempt restricts pivoting to each panel's top block and checks the multipliers (lu.hip, k_rp_below); when that
     // check fails the copy is refreshed and factored with the reference's grid-wide rule.
@@ -59,7 +59,7 @@ static int lu_copy_and_factor(Context* c, const double* src, size_t rows, size_t
     return fail(RMHIP_ERR_HIP, "lu: factorisation failed on every panel path");
 }
 
-static size_t lu_padded_ld(size_t rows) { return rows >= 256 ? ((rows + 1) & ~(size_t)1) + 32 : ((rows + 1) & ~(size_t)1); }
+size_t rmhip::lu_padded_ld(size_t rows) { return rows >= 256 ? ((rows + 1) & ~(size_t)1) + 32 : ((rows + 1) & ~(size_t)1); }
 
 // Order the solves factor at.  The blocked driver's trailing updates are whole 128 x 128 x 16 tiles only when n is a multiple of
 // 128; otherwise EVERY update of the factorisation runs a guarded kernel (n = 10000: 37.0 ms against 31.7 at 10240, n = 13001: 55.6
@@ -446,8 +446,10 @@ int rmhip_mrdivide(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf* out) {
     return RMHIP_OK;
 }
 
+// serve_rcond: the call came through rmhip_linsolve_rcond - a general matrix with need_rcond / has_rcond, which rmhip_linsolve declines;
+// the solution is the one the sibling computes with both fields cleared, rcond comes from the Jacobi singular values
 static int linsolve_impl(rmhip_ctx* ctx, Context* c, rmhip_buf a, rmhip_buf b, const rmhip_linsolve_options_t* opts, rmhip_buf* out,
-                         double* reciprocal_condition) {
+                         double* reciprocal_condition, bool serve_rcond) {
     if (!out || !opts) return fail(RMHIP_ERR_INVALID, "linsolve: null argument");
     Buffer ab, bb;
     RMHIP_TRY(c->get(a, &ab));
@@ -475,9 +477,22 @@ static int linsolve_impl(rmhip_ctx* ctx, Context* c, rmhip_buf a, rmhip_buf b, c
     const size_t n = as[0], nrhs = bs[1];
     const bool triangular = lower || upper;
     if (triangular && as[0] != as[1]) return fail(RMHIP_ERR_SHAPE, "linsolve: triangular solves need a square matrix");
-    if (!triangular && (opts->need_rcond || opts->has_rcond))
+    if (serve_rcond && triangular)
+        return fail(RMHIP_ERR_UNSUPPORTED, "linsolve_rcond: the lower / upper hints are served by rmhip_linsolve");
+    if (serve_rcond && !opts->need_rcond && !opts->has_rcond)
+        return fail(RMHIP_ERR_UNSUPPORTED, "linsolve_rcond: no rcond asked for; rmhip_linsolve serves the plain solve");
+    if (!serve_rcond && !triangular && (opts->need_rcond || opts->has_rcond))
         return fail(RMHIP_ERR_UNSUPPORTED, "linsolve: rcond of a general matrix needs its singular values (CPU path)");
-    double rcond = std::numeric_limits<double>::quiet_NaN();  // stays NaN for a general matrix, whichever solver answered
+    double rcond = std::numeric_limits<double>::quiet_NaN();  // stays NaN for a general matrix unless serve_rcond, whichever solver answered
+    if (serve_rcond) {
+        if (as[0] == 0 || as[1] == 0 || nrhs == 0) return fail(RMHIP_ERR_UNSUPPORTED, "linsolve: empty system");
+        // linsolve.rs:933-944, 1000-1009: sigma_min / sigma_max of the (transposed) matrix, and the caller's threshold before any solve.
+        // Non-finite data and min(rows, cols) > svd_max_cols() are refused by the decomposition (RMHIP_ERR_UNSUPPORTED).
+        std::vector<double> sv;
+        RMHIP_TRY(svd_values_host(c, "linsolve", A, as[0], as[1], &sv));
+        rcond = svd_rcond(sv);
+        if (opts->has_rcond && rcond < opts->rcond) return fail(RMHIP_ERR_SINGULAR, "linsolve: matrix is singular to working precision.");
+    }
     rmhip_buf oid = 0;
     int rc = RMHIP_OK;
     if (as[0] != as[1]) {  // rectangular: least squares / minimum norm as rmhip_mldivide (linsolve.rs:933-970 is the SVD solve)
@@ -517,7 +532,14 @@ int rmhip_linsolve(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, const rmhip_linsolv
                    double* reciprocal_condition) {
     CTX_OR_FAIL(ctx);
     ScopedTimer timer(&c->tel.linsolve_count, &c->tel.linsolve_ns);
-    return count_fallback(c, linsolve_impl(ctx, c, a, b, opts, out, reciprocal_condition), "linsolve:unsupported", "linsolve:singular");
+    return count_fallback(c, linsolve_impl(ctx, c, a, b, opts, out, reciprocal_condition, false), "linsolve:unsupported", "linsolve:singular");
+}
+
+int rmhip_linsolve_rcond(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, const rmhip_linsolve_options_t* opts, rmhip_buf* out,
+                         double* reciprocal_condition) {
+    CTX_OR_FAIL(ctx);
+    ScopedTimer timer(&c->tel.linsolve_count, &c->tel.linsolve_ns);
+    return count_fallback(c, linsolve_impl(ctx, c, a, b, opts, out, reciprocal_condition, true), "linsolve:unsupported", "linsolve:singular");
 }
 
 // ---- block-level building blocks (views) ----------------------------------------------------------

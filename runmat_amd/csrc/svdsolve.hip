@@ -249,6 +249,17 @@ double svd_default_tolerance(const std::vector<double>& values, size_t m, size_t
     return (double)(m > n ? m : n) * eps_like(mx);
 }
 
+// `singular_value_rcond` (common/linalg.rs:241-259)
+double svd_rcond(const std::vector<double>& values) {
+    double mn = INFINITY, mx = 0.0;
+    for (double v : values) {
+        const double a = std::fabs(v);
+        if (!std::isfinite(a)) return 0.0;
+        mn = a < mn ? a : mn, mx = a > mx ? a : mx;
+    }
+    return mx == 0.0 ? 0.0 : mn / mx;
+}
+
 // X (n x m) = pinv(A) with the cutoff `tol` (< 0: the default rule)
 int svd_pinv_device(Context* c, const double* A, size_t m, size_t n, double tol, double* X) {
     JacobiSvd s;

@@ -1033,13 +1033,23 @@ class HipProvider:
     def linsolve(self, lhs: GpuTensorHandle, rhs: GpuTensorHandle,
                  options: Optional[ProviderLinsolveOptions] = None) -> ProviderLinsolveResult:
         """lib.rs:2422-2429; CPU semantics linsolve.rs:691-726."""
+        return self._linsolve(self._lib.rmhip_linsolve, lhs, rhs, options)
+
+    def linsolve_rcond(self, lhs: GpuTensorHandle, rhs: GpuTensorHandle,
+                       options: Optional[ProviderLinsolveOptions] = None) -> ProviderLinsolveResult:
+        """The hook's second entry point, for what `linsolve` declines: a general matrix with `need_rcond` or `rcond` set.  The solution is
+        `linsolve`'s with both cleared, bit for bit; reciprocal_condition = sigma_min / sigma_max (linsolve.rs:933-944), and a value below
+        `options.rcond` raises SINGULAR (linsolve.rs:1000-1009).  The triangular hints and a request without rcond raise UNSUPPORTED."""
+        return self._linsolve(self._lib.rmhip_linsolve_rcond, lhs, rhs, options)
+
+    def _linsolve(self, entry, lhs, rhs, options) -> ProviderLinsolveResult:
         o = options or ProviderLinsolveOptions()
         co = _lib.LinsolveOptions(int(o.lower), int(o.upper), int(o.rectangular), int(o.transposed), int(o.conjugate),
                                   int(o.symmetric), int(o.posdef), int(o.need_rcond), int(o.rcond is not None),
                                   float(o.rcond) if o.rcond is not None else 0.0)
         out = C.c_uint64()
         rc = C.c_double(float("nan"))
-        self._check(self._lib.rmhip_linsolve(self._ctx, self._id(lhs), self._id(rhs), C.byref(co), C.byref(out), C.byref(rc)))
+        self._check(entry(self._ctx, self._id(lhs), self._id(rhs), C.byref(co), C.byref(out), C.byref(rc)))
         return ProviderLinsolveResult(self._handle(out.value), rc.value)
 
     def transpose(self, a: GpuTensorHandle, *, entry: str = "rmhip_transpose") -> GpuTensorHandle:
@@ -1101,6 +1111,17 @@ class HipProvider:
             raise RmhipError(1, f"cond: norm {norm!r}")
         out = C.c_uint64()
         self._check(self._lib.rmhip_cond(self._ctx, self._id(matrix), codes[norm], C.byref(out)))
+        return self._handle(out.value)
+
+    def cond_norm(self, matrix, norm: str = "one") -> GpuTensorHandle:
+        """The hook's second entry point, for the norms `cond` declines: `one`, `inf`, `fro` (cond.rs:343-357, 384-414) -> [1, 1],
+        norm(A) * norm(inv(A)) with the LU inverse formed and folded into the norms slab by slab.  Inf for an exactly singular matrix;
+        raises UNSUPPORTED for non-finite data and for a nonzero pivot at the LU's cut-off, and for `two` (served by `cond`)."""
+        codes = {"two": 0, "one": 1, "inf": 2, "fro": 3}
+        if norm not in codes:
+            raise RmhipError(1, f"cond: norm {norm!r}")
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_cond_norm(self._ctx, self._id(matrix), codes[norm], C.byref(out)))
         return self._handle(out.value)
 
     def rcond(self, matrix) -> GpuTensorHandle:

@@ -541,7 +541,14 @@ impl AccelProvider for HipProvider {
                 posdef: o.posdef as c_int, need_rcond: o.need_rcond as c_int, has_rcond: o.rcond.is_some() as c_int,
                 rcond: o.rcond.unwrap_or(0.0) };
             let (mut out, mut rcond) = (0u64, f64::NAN);
-            check(unsafe { rmhip_linsolve(self.ctx, self.own(lhs)?, self.own(rhs)?, &c, &mut out, &mut rcond) })?;
+            // a general matrix whose rcond is asked for (`[x, r] = linsolve(A, b)`, opts.RCOND): the hook's second entry point, which
+            // adds sigma_min / sigma_max to the sibling's solution; everything else is the first entry point's
+            let triangular = o.lower || o.upper;
+            if !triangular && (o.need_rcond || o.rcond.is_some()) {
+                check(unsafe { rmhip_linsolve_rcond(self.ctx, self.own(lhs)?, self.own(rhs)?, &c, &mut out, &mut rcond) })?;
+            } else {
+                check(unsafe { rmhip_linsolve(self.ctx, self.own(lhs)?, self.own(rhs)?, &c, &mut out, &mut rcond) })?;
+            }
             Ok(ProviderLinsolveResult { solution: self.handle(out)?, reciprocal_condition: rcond })
         })
     }
@@ -600,7 +607,12 @@ impl AccelProvider for HipProvider {
         Box::pin(async move {
             let code = match norm { ProviderCondNorm::Two => 0, ProviderCondNorm::One => 1, ProviderCondNorm::Inf => 2, ProviderCondNorm::Fro => 3 };
             let mut out = 0u64;
-            check(unsafe { rmhip_cond(self.ctx, self.own(matrix)?, code, &mut out) })?;
+            // the 2-norm from the singular values; One / Inf / Fro through the hook's second entry point (the LU inverse folded into the norms)
+            if matches!(norm, ProviderCondNorm::Two) {
+                check(unsafe { rmhip_cond(self.ctx, self.own(matrix)?, code, &mut out) })?;
+            } else {
+                check(unsafe { rmhip_cond_norm(self.ctx, self.own(matrix)?, code, &mut out) })?;
+            }
             self.handle(out)
         })
     }
