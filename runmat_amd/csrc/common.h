@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/rmhip.h"
+#include "gemm_plan.h"
 
 namespace rmhip {
 
@@ -130,15 +131,6 @@ struct LaunchRecord {
 };
 static constexpr int kLaunchLog = 64;  // bounded log, newest overwrites oldest
 
-// What the last GEMM launcher call ran (rmhip_gemm_last_route): written by every launch site of launch_dgemm_impl, launch_pgemm_w8
-// and launch_sgemm_trans - a handful of host stores - so that a test can attest the route a shape took.  `kernel` is a literal.
-struct GemmRoute {
-    const char* kernel = "";  // small, w8, w8g, w8p, w4, pgemm, s_w8, s_w8g, s_w4
-    int guard = 0;            // GUARD (small, w8g, pgemm, s_w8g) / EDGE (w4, s_w4): the form that checks its bounds
-    int pre = 0, ta = 0, tb = 0, epi = 0, yield = 0;
-    unsigned splits = 0, k_chunk = 0;  // splits == 0: no product yet
-};
-
 struct FusedKernel;  // codegen.h
 struct Comm;         // comm.cpp
 
@@ -198,19 +190,7 @@ struct Context {
     // LU look-ahead (lu.hip getrf_blocked): extra dynamic LDS requested by launch_dgemm so that only ONE
     // dgemm block fits per CU and latency-bound kernels of the other stream find room beside it
     size_t gemm_lds_pad = 0;
-    GemmRoute gemm_route;  // the last GEMM launch of this context (any stream of the look-ahead LU included)
-    void note_gemm_route(const char* kernel, bool guard, bool pre, bool ta, bool tb, int epi, bool yield, unsigned splits, unsigned k_chunk) {
-        GemmRoute& r = gemm_route;
-        r.kernel = kernel;
-        r.guard = guard;
-        r.pre = pre;
-        r.ta = ta;
-        r.tb = tb;
-        r.epi = epi;
-        r.yield = yield;
-        r.splits = splits;
-        r.k_chunk = k_chunk;
-    }
+    GemmRoute gemm_route;  // the plan the last GEMM launch of this context executed (any stream of the look-ahead LU included)
     // look-ahead LU, late phase: the update stream's dgemm runs as a persistent kernel that stays off the panels' XCD
     unsigned* gemm_tile_counters = nullptr;  // device, zeroed by the driver; one per launch
     size_t gemm_counter_next = 0, gemm_counter_cap = 0;
@@ -427,6 +407,7 @@ int launch_sgemm_trans(Context* c, bool ta, bool tb, size_t m, size_t n, size_t 
                        size_t ldb, float* C, size_t ldc);
 int launch_dgemm_epilogue(Context* c, size_t m, size_t n, size_t k, const double* A, size_t lda, const double* B,
                           size_t ldb, double* C, size_t ldc, const GemmEpilogue& ep);
+const GemmKnobs& gemm_knobs();  // dgemm.hip: the RMHIP_GEMM_* / RMHIP_SGEMM_* / RMHIP_MFMA_ROWMAP switches, read once per process
 
 // Batched page products (pagefun.hip, dgemm.hip k_pgemm_w8): C page p = A page a(p) * B page b(p), C pages dense.  Page p is
 // decomposed column-major over dims[0..rank); an operand's page offset (in elements) is sum_d idx_d * s?[d], with s?[d] = 0 along a

@@ -28,6 +28,8 @@
 //     blocks co-resident on an XCD then share A rows / B columns through that XCD's 4 MiB L2.
 //   * Numerics: each MFMA is a k-ordered fma chain in f64; the CPU reference rounds the product and
 //     the sum separately (sum += a*b).  Results agree to ~k*eps*sum|a||b| (tests state the bound).
+#include <cstring>
+
 #include "common.h"
 
 namespace rmhip {
@@ -43,21 +45,10 @@ static constexpr int A_TILE = BK * SA;  // doubles
 static constexpr int B_TILE = BN * SB;
 // tile rows per group of the XCD-aware order; interleaved A/B at 8192^3 (scripts/dgemm_ab.py): 4 -> 68.7, 8 -> 68.6,
 // 16 -> 69.0, 32 -> 69.0 TFLOP/s
-#ifndef GEMM_GROUP_M
-#define GEMM_GROUP_M 16
-#endif
-static constexpr int GROUP_M = GEMM_GROUP_M;
-// after which of the four k-steps of a tile the next tile's registers go to LDS (3 = after the last MFMA;
-// measured at 8192^3: 3 -> 68.6, 2 -> 66.4, 1 -> 67.1 TFLOP/s; s_setprio around the MFMA section: no effect)
-#ifndef GEMM_PIPE_W8
-#define GEMM_PIPE_W8 1
-#endif
-#ifndef GEMM_PIPE
-#define GEMM_PIPE 1
-#endif
-#ifndef GEMM_STASH_KK
-#define GEMM_STASH_KK 3
-#endif
+static constexpr int GROUP_M = 16;
+// k_dgemm's plain k loop (its EDGE and PRE forms): after which of the four k-steps of a tile the next tile's registers go to LDS
+// (3 = after the last MFMA; measured at 8192^3: 3 -> 68.6, 2 -> 66.4, 1 -> 67.1 TFLOP/s; s_setprio around the MFMA section: no effect)
+static constexpr int STASH_KK = 3;
 static_assert(A_TILE == B_TILE, "the transposed-operand variants swap the two staging patterns between the tiles");
 
 struct GemmArgs {
@@ -266,7 +257,6 @@ __global__ void __launch_bounds__(256, 2) k_dgemm(const GemmArgs g) {
     constexpr int A_KSTEP = TA ? 4 : 4 * SA, A_ISTEP = TA ? 16 * SB : 16;
     constexpr int B_KSTEP = TB ? 4 * SA : 4, B_JSTEP = TB ? 16 : 16 * SB;
 
-#if GEMM_PIPE
     if (!EDGE && !PRE) {  // (the C-preloading variant has no registers to spare for the second prefetch set: 132 bytes of scratch)
         // Software-pipelined k loop (one barrier per tile, nothing exposed around it): the fragments of step kk+1 are read while
         // step kk multiplies; the next tile is stashed during step 2 from registers that were loaded a whole tile earlier (and
@@ -349,7 +339,6 @@ __global__ void __launch_bounds__(256, 2) k_dgemm(const GemmArgs g) {
             if (kt + 1 < ktiles) step(kt + 1, ra2, rb2);
         }
     } else
-#endif
     for (unsigned kt = 0; kt < ktiles; ++kt) {
         const int cur = kt & 1;
         if (kt + 1 < ktiles) fetch((kt + 1) * BK);
@@ -367,7 +356,7 @@ __global__ void __launch_bounds__(256, 2) k_dgemm(const GemmArgs g) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     acc[j][i] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[j], af[i], acc[j][i], 0, 0, 0);
-            if (kk == GEMM_STASH_KK && kt + 1 < ktiles) stash(cur ^ 1);
+            if (kk == STASH_KK && kt + 1 < ktiles) stash(cur ^ 1);
         }
         __syncthreads();
     }
@@ -673,7 +662,6 @@ __device__ __forceinline__ void w8_tile(const GemmArgs& g, const unsigned tm, co
     const int b_off = TB ? lq * SA + wn * 32 + l15 : (wn * 32 + l15) * SB + lq;
     constexpr int A_KSTEP = TA ? 4 : 4 * SA, A_ISTEP = TA ? 16 * SB : 16;
     constexpr int B_KSTEP = TB ? 4 * SA : 4, B_JSTEP = TB ? 16 : 16 * SB;
-#if GEMM_PIPE_W8
     {
         // the software-pipelined k loop of k_dgemm (there: two blocks per CU fill each other's bubbles and it is worth 1 %; here all
         // eight waves of the CU share ONE barrier, and what surrounds it - LDS write completion, the first reads of the next tile -
@@ -746,28 +734,6 @@ __device__ __forceinline__ void w8_tile(const GemmArgs& g, const unsigned tm, co
         }
         __syncthreads();  // the caller may reuse the LDS tiles (persistent form)
     }
-#else
-    for (unsigned kt = 0; kt < ktiles; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < ktiles) fetch((kt + 1) * BK);
-        const double* a = As + cur * A_TILE + a_off;
-        const double* b = Bs + cur * B_TILE + b_off;
-#pragma unroll
-        for (int kk = 0; kk < BK / 4; ++kk) {
-            double af[4], bf[2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = a[kk * A_KSTEP + i * A_ISTEP];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = b[j * B_JSTEP + kk * B_KSTEP];
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[j][i] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[j], af[i], acc[j][i], 0, 0, 0);
-        }
-        if (kt + 1 < ktiles) stash(cur ^ 1);
-        __syncthreads();
-    }
-#endif
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         double* dst[16];
@@ -889,7 +855,23 @@ __global__ void __launch_bounds__(512, 2) k_pgemm_w8(const GemmArgs g0, const Pa
     }
 }
 
-static int g_rowmap = -1;
+// The GEMM dispatch's switches, read once per process and nowhere else (docs/KNOBS.md "GEMM dispatch").  Each is on unless its value
+// starts with 0; RMHIP_MFMA_ROWMAP is 1 or off.
+const GemmKnobs& gemm_knobs() {
+    static const GemmKnobs knobs = [] {
+        GemmKnobs k;
+        auto on = [](const char* v) { return !(v && *v == '0'); };
+        k.small = on(std::getenv("RMHIP_GEMM_SMALL"));
+        k.w8 = on(std::getenv("RMHIP_GEMM_W8"));
+        k.preload = on(std::getenv("RMHIP_GEMM_PRELOAD"));
+        k.guard = on(std::getenv("RMHIP_GEMM_GUARD"));
+        k.sgemm_w8 = on(std::getenv("RMHIP_SGEMM_W8"));
+        const char* v = std::getenv("RMHIP_MFMA_ROWMAP");
+        k.rowmap = (v && *v == '1') ? 1 : 0;
+        return k;
+    }();
+    return knobs;
+}
 
 static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double alpha, const double* A, size_t lda,
                              const double* B, size_t ldb, double beta, double* C, size_t ldc, const GemmEpilogue* ep,
@@ -906,38 +888,74 @@ int launch_dgemm_epilogue(Context* c, size_t m, size_t n, size_t k, const double
 }
 
 // C (m x n) = alpha * op(A) * op(B) + beta * C with op(X) = X' when tX: A is then stored k x m (lda >= k),
-// B stored n x k (ldb >= n).  Both transposed at once is not instantiated (callers materialise one operand).
+// B stored n x k (ldb >= n).  Both transposed at once is not instantiated (callers materialise one operand): the plan says so.
 int launch_dgemm_trans(Context* c, bool ta, bool tb, size_t m, size_t n, size_t k, double alpha, const double* A, size_t lda,
                        const double* B, size_t ldb, double beta, double* C, size_t ldc) {
-    if (ta && tb) return fail(RMHIP_ERR_UNSUPPORTED, "dgemm: A' * B' is not instantiated");
     return launch_dgemm_impl(c, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, ta, tb);
 }
 
-template <bool EDGE, bool EPI, bool TA, bool TB, bool PRE = false>
-static void launch_variant(Context* c, unsigned blocks, unsigned splits, size_t lds_bytes, size_t max_lds, const GemmArgs& g) {
-    c->ensure_max_lds((const void*)k_dgemm<EDGE, EPI, TA, TB, PRE>, max_lds);
-    hipLaunchKernelGGL((k_dgemm<EDGE, EPI, TA, TB, PRE>), dim3(blocks, splits), dim3(256), lds_bytes, c->stream, g);
-    c->note_gemm_route("w4", EDGE, PRE, TA, TB, EPI ? ((g.ep.flags & EP_POW) ? 2 : 1) : 0, false, splits, g.k_chunk);
-}
+// One launch helper per kernel, and the table from a route (gemm_plan.h plan_dgemm) to its instantiation: `lds` is the tile buffers
+// plus the stream's pad, which the 128 x 128 kernels opt in to up to kMaxLds; the 64 x 64 tiles are static LDS.
+static constexpr size_t kMaxLds = 128 * 1024;  // room for the look-ahead pad
+using GemmLaunch = void (*)(Context* c, dim3 grid, size_t lds, const GemmArgs& g);
 
-// One helper per kernel: the launch and the route note (Context::note_gemm_route) take their flags from the same template arguments.
+template <bool EDGE, bool EPI, bool TA, bool TB, bool PRE = false>
+static void launch_variant(Context* c, dim3 grid, size_t lds, const GemmArgs& g) {
+    c->ensure_max_lds((const void*)k_dgemm<EDGE, EPI, TA, TB, PRE>, kMaxLds);
+    hipLaunchKernelGGL((k_dgemm<EDGE, EPI, TA, TB, PRE>), grid, dim3(256), lds, c->stream, g);
+}
 template <bool PRE, bool GUARD>
-static void launch_small(Context* c, dim3 grid, size_t lds_bytes, const GemmArgs& g) {
-    hipLaunchKernelGGL((k_dgemm_small<PRE, GUARD>), grid, dim3(256), lds_bytes, c->stream, g);
-    c->note_gemm_route("small", GUARD, PRE, false, false, 0, false, 1, g.k_chunk);
+static void launch_small(Context* c, dim3 grid, size_t, const GemmArgs& g) {
+    hipLaunchKernelGGL((k_dgemm_small<PRE, GUARD>), grid, dim3(256), 0, c->stream, g);
 }
 template <bool PRE, bool TA = false, bool TB = false, int EPI = 0, bool YIELD = false>
-static void launch_w8(Context* c, unsigned blocks, unsigned splits, size_t lds_bytes, size_t max_lds, const GemmArgs& g) {
-    c->ensure_max_lds((const void*)k_dgemm_w8<PRE, TA, TB, EPI, YIELD>, max_lds);
-    hipLaunchKernelGGL((k_dgemm_w8<PRE, TA, TB, EPI, YIELD>), dim3(blocks, splits), dim3(512), lds_bytes, c->stream, g);
-    c->note_gemm_route("w8", false, PRE, TA, TB, EPI, YIELD, splits, g.k_chunk);
+static void launch_w8(Context* c, dim3 grid, size_t lds, const GemmArgs& g) {
+    c->ensure_max_lds((const void*)k_dgemm_w8<PRE, TA, TB, EPI, YIELD>, kMaxLds);
+    hipLaunchKernelGGL((k_dgemm_w8<PRE, TA, TB, EPI, YIELD>), grid, dim3(512), lds, c->stream, g);
 }
 template <bool PRE, bool TA, int EPI>
-static void launch_w8g(Context* c, unsigned blocks, unsigned splits, size_t lds_bytes, size_t max_lds, const GemmArgs& g) {
-    c->ensure_max_lds((const void*)k_dgemm_w8g<PRE, TA, EPI>, max_lds);
-    hipLaunchKernelGGL((k_dgemm_w8g<PRE, TA, EPI>), dim3(blocks, splits), dim3(512), lds_bytes, c->stream, g);
-    c->note_gemm_route("w8g", true, PRE, TA, false, EPI, false, splits, g.k_chunk);
+static void launch_w8g(Context* c, dim3 grid, size_t lds, const GemmArgs& g) {
+    c->ensure_max_lds((const void*)k_dgemm_w8g<PRE, TA, EPI>, kMaxLds);
+    hipLaunchKernelGGL((k_dgemm_w8g<PRE, TA, EPI>), grid, dim3(512), lds, c->stream, g);
 }
+static void launch_w8p(Context* c, dim3 grid, size_t lds, const GemmArgs& g) {
+    c->ensure_max_lds((const void*)k_dgemm_w8p, kMaxLds);
+    hipLaunchKernelGGL(k_dgemm_w8p, grid, dim3(512), lds, c->stream, g);
+}
+
+struct GemmVariant {
+    const char* kernel;
+    int guard, pre, ta, tb, epi, yield;
+    GemmLaunch launch;
+};
+// (rows in the order the kernels have always been emitted in: the code object keeps its layout)
+static const GemmVariant kGemmVariants[] = {
+    {"small", 0, 1, 0, 0, 0, 0, launch_small<true, false>},
+    {"small", 0, 0, 0, 0, 0, 0, launch_small<false, false>},
+    {"small", 1, 1, 0, 0, 0, 0, launch_small<true, true>},
+    {"small", 1, 0, 0, 0, 0, 0, launch_small<false, true>},
+    {"w8p", 0, 0, 0, 0, 0, 0, launch_w8p},
+    {"w8", 0, 0, 0, 0, 2, 0, launch_w8<false, false, false, 2>},
+    {"w8", 0, 0, 0, 0, 1, 0, launch_w8<false, false, false, 1>},
+    {"w8", 0, 0, 1, 0, 0, 0, launch_w8<false, true, false>},
+    {"w8", 0, 0, 0, 0, 0, 0, launch_w8<false>},
+    {"w8", 0, 1, 0, 0, 0, 1, launch_w8<true, false, false, 0, true>},
+    {"w8", 0, 1, 0, 0, 0, 0, launch_w8<true>},
+    {"w8g", 1, 0, 0, 0, 2, 0, launch_w8g<false, false, 2>},
+    {"w8g", 1, 0, 0, 0, 1, 0, launch_w8g<false, false, 1>},
+    {"w8g", 1, 0, 1, 0, 0, 0, launch_w8g<false, true, 0>},
+    {"w8g", 1, 1, 0, 0, 0, 0, launch_w8g<true, false, 0>},
+    {"w8g", 1, 0, 0, 0, 0, 0, launch_w8g<false, false, 0>},
+    {"w4", 1, 0, 0, 0, 1, 0, launch_variant<true, true, false, false>},  // (the epilogue's pow is a run-time flag of this kernel)
+    {"w4", 1, 0, 0, 0, 2, 0, launch_variant<true, true, false, false>},
+    {"w4", 0, 0, 1, 0, 0, 0, launch_variant<false, false, true, false>},
+    {"w4", 1, 0, 1, 0, 0, 0, launch_variant<true, false, true, false>},
+    {"w4", 0, 0, 0, 1, 0, 0, launch_variant<false, false, false, true>},
+    {"w4", 1, 0, 0, 1, 0, 0, launch_variant<true, false, false, true>},
+    {"w4", 0, 1, 0, 0, 0, 0, launch_variant<false, false, false, false, true>},
+    {"w4", 0, 0, 0, 0, 0, 0, launch_variant<false, false, false, false>},
+    {"w4", 1, 0, 0, 0, 0, 0, launch_variant<true, false, false, false>},
+};
 
 // C = alpha * (P_0 + P_1 + ... + P_{S-1}) + beta * C, partials m x n dense (ld m), summed in split order
 __global__ void __launch_bounds__(256) k_reduce_splits(const double* __restrict__ P, size_t mn, size_t m, unsigned splits,
@@ -952,16 +970,42 @@ __global__ void __launch_bounds__(256) k_reduce_splits(const double* __restrict_
     }
 }
 
+// Every f64 product: plan_dgemm (gemm_plan.h) decides, this function executes the route and leaves it in c->gemm_route.
 static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double alpha, const double* A, size_t lda,
                              const double* B, size_t ldb, double beta, double* C, size_t ldc, const GemmEpilogue* ep,
                              bool ta, bool tb) {
+    const GemmKnobs& knobs = gemm_knobs();
+    GemmProblem p;
+    p.m = m, p.n = n, p.k = k, p.lda = lda, p.ldb = ldb;
+    p.a_aligned = ((uintptr_t)A & 15) == 0;
+    p.b_aligned = ((uintptr_t)B & 15) == 0;
+    p.ta = ta, p.tb = tb;
+    p.epi = ep ? ((ep->flags & EP_POW) ? 2 : 1) : 0;
+    p.alpha = alpha, p.beta = beta;
+    GemmSite s;
+    s.num_cus = c->num_cus;
+    s.in_lookahead = c->in_lookahead;
+    s.lds_pad = c->gemm_lds_pad != 0;
+    s.chain_prio = c->gemm_chain_prio;
+    s.counter = c->gemm_tile_counters && c->gemm_counter_next < c->gemm_counter_cap;
+    s.yield_word = c->gemm_yield_word != nullptr;
+    s.small_upd = lu_process_knobs().small_upd;
+    const GemmRoute r = plan_dgemm(p, s, knobs);
+    if (r.unsupported) return fail(RMHIP_ERR_UNSUPPORTED, "%s", r.unsupported);
     if (m == 0 || n == 0) return RMHIP_OK;
     if (m > 0xffffffffULL || n > 0xffffffffULL || k > 0xffffffffULL)
         return fail(RMHIP_ERR_UNSUPPORTED, "dgemm: dimension exceeds 2^32");
-    if (g_rowmap < 0) {
-        const char* v = std::getenv("RMHIP_MFMA_ROWMAP");
-        g_rowmap = (v && *v == '1') ? 1 : 0;
-    }
+    const size_t lds_bytes = (size_t)(2 * A_TILE + 2 * B_TILE) * sizeof(double) + c->gemm_lds_pad;
+    if (lds_bytes > kMaxLds) return fail(RMHIP_ERR_INVALID, "dgemm: LDS pad too large");
+    const GemmVariant* variant = nullptr;
+    for (const GemmVariant& v : kGemmVariants)
+        if (!std::strcmp(v.kernel, r.kernel) && v.guard == r.guard && v.pre == r.pre && v.ta == r.ta && v.tb == r.tb && v.epi == r.epi &&
+            v.yield == r.yield)
+            variant = &v;
+    if (!variant)
+        return fail(RMHIP_ERR_UNSUPPORTED, "dgemm: no instantiation for the route %s guard=%d pre=%d ta=%d tb=%d epi=%d yield=%d", r.kernel,
+                    r.guard, r.pre, r.ta, r.tb, r.epi, r.yield);
+
     GemmArgs g;
     g.A = A;
     g.B = B;
@@ -972,224 +1016,44 @@ static int launch_dgemm_impl(Context* c, size_t m, size_t n, size_t k, double al
     g.m = (unsigned)m;
     g.n = (unsigned)n;
     g.k = (unsigned)k;
-    g.tiles_m = (unsigned)((m + BM - 1) / BM);
-    g.tiles_n = (unsigned)((n + BN - 1) / BN);
+    g.tiles_m = r.tiles_m;
+    g.tiles_n = r.tiles_n;
     g.alpha = alpha;
     g.beta = beta;
-    g.rowmap = g_rowmap;
-    g.vec_a = ((((uintptr_t)A & 15) == 0) && (lda % 2 == 0)) ? 1 : 0;
-    g.vec_b = ((((uintptr_t)B & 15) == 0) && (ldb % 2 == 0)) ? 1 : 0;
+    g.rowmap = knobs.rowmap;
+    g.vec_a = (p.a_aligned && lda % 2 == 0) ? 1 : 0;
+    g.vec_b = (p.b_aligned && ldb % 2 == 0) ? 1 : 0;
     if (ep) g.ep = *ep;
     else g.ep = GemmEpilogue{0, 1.0, 0.0, nullptr, nullptr, 0.0, 0.0, 0.0, nullptr};
-    const size_t lds_base = (size_t)(2 * A_TILE + 2 * B_TILE) * sizeof(double);
-    static long dev_pad = -1;  // developer knob: extra dynamic LDS for every launch (blocks per CU experiments)
-    if (dev_pad < 0) {
-        const char* v = std::getenv("RMHIP_GEMM_LDS_PAD");
-        dev_pad = v ? std::atol(v) : 0;
-    }
-    const size_t lds_bytes = lds_base + (c->gemm_lds_pad ? c->gemm_lds_pad : (size_t)dev_pad);
-    const bool fast = (m % BM == 0) && (n % BN == 0) && (k % BK == 0) && k > 0 && (lda % 2 == 0) && (ldb % 2 == 0) &&
-                      (((uintptr_t)A & 15) == 0) && (((uintptr_t)B & 15) == 0);
-    const unsigned blocks = g.tiles_m * g.tiles_n;
-    const size_t kMaxLds = 128 * 1024;  // room for the look-ahead pad
-    if (lds_bytes > kMaxLds) return fail(RMHIP_ERR_INVALID, "dgemm: LDS pad too large");
-    // Split-K: few output tiles but a long k (A'*A of a tall matrix, dot-product-like shapes) would leave most CUs
-    // idle; give every CU about two blocks.  Chunks are multiples of 1024 so the unguarded kernel stays eligible.
-    unsigned splits = 1;
-    g.k_chunk = (unsigned)k;
+    g.k_chunk = r.k_chunk;
     g.c_split_stride = 0;
-    g.tile_counter = nullptr;
-    g.avoid_xcc = nullptr;
-    g.yield_word = (c->gemm_lds_pad != 0) ? c->gemm_yield_word : nullptr;  // update streams of the two-level LU only
-    g.prio = (c->in_lookahead && c->gemm_lds_pad == 0 && c->gemm_chain_prio) ? 1 : 0;  // the look-ahead LU's main stream
+    g.tile_counter = nullptr, g.avoid_xcc = nullptr;
+    g.yield_word = s.lds_pad ? c->gemm_yield_word : nullptr;  // update streams of the two-level LU only
+    g.prio = r.prio;
     std::shared_ptr<Allocation> partials;
-    // (round 3: from k = 1024 - slices of multiples of 128 - outside the LU.  A block walks its k range at about 1 us per 16 columns
-    // - one memory latency per tile with nothing else resident - so few blocks with a long k are latency bound whatever the tile:
-    // 4096 x 100 with k = 4096 (32 tiles) 547 -> 97 us, 32 x 512 with k = 8192 on one slice 1100 us.)
-    const size_t split_min_k = c->in_lookahead ? 8192 : 1024;
-    if (!ep && blocks * 4 <= (unsigned)c->num_cus && k >= split_min_k) {
-        const size_t want = (2 * (size_t)c->num_cus + blocks - 1) / blocks;
-        size_t chunk = (k + want - 1) / want;
-        const size_t gran = k >= 8192 ? 1024 : (k >= 2048 ? 256 : 128);
-        chunk = ((chunk + gran - 1) / gran) * gran;
-        splits = (unsigned)((k + chunk - 1) / chunk);
-        if (splits > 1) {
-            RMHIP_TRY(c->alloc_device((size_t)splits * m * n, &partials));
-            g.k_chunk = (unsigned)chunk;
-            g.C = partials->ptr;
-            g.ldc = m;
-            g.c_split_stride = (unsigned long long)m * n;
-            g.alpha = 1.0;
-            g.beta = 0.0;
-        } else {
-            splits = 1;
-        }
+    if (r.splits > 1) {  // the slices write their partial products; k_reduce_splits applies alpha and beta
+        RMHIP_TRY(c->alloc_device((size_t)r.splits * m * n, &partials));
+        g.C = partials->ptr;
+        g.ldc = m;
+        g.c_split_stride = (unsigned long long)m * n;
+        g.alpha = 1.0;
+        g.beta = 0.0;
     }
-    const bool fast_k = fast && (splits == 1 || k % g.k_chunk == 0);
-    // C <- C - A*B (the LU's updates): preload C into the accumulators (RMHIP_GEMM_PRELOAD=0 keeps the read at the end)
-    static int preload_on = -1;
-    if (preload_on < 0) {
-        const char* v = std::getenv("RMHIP_GEMM_PRELOAD");
-        preload_on = (v && *v == '0') ? 0 : 1;
-    }
-    const bool preload = preload_on && !ep && !ta && !tb && splits == 1 && alpha == -1.0 && beta == 1.0 && k > 0;
-    // small-tile kernel: the big tiles would cover at most half of the CUs and k is short (RMHIP_GEMM_SMALL=0 disables).  Not on
-    // the look-ahead update stream (gemm_lds_pad != 0): its blocks must stay too big to share a CU with a panel block.
-    static int small_on = -1;
-    if (small_on < 0) {
-        const char* v = std::getenv("RMHIP_GEMM_SMALL");
-        small_on = (v && *v == '0') ? 0 : 1;
-    }
-    static long small_force = -1, small_pad = 0;  // developer knobs: RMHIP_GEMM_SMALL_FORCE=1 (any size), RMHIP_GEMM_SMALL_PAD=<bytes of extra LDS>
-    if (small_force < 0) {
-        small_force = std::getenv("RMHIP_GEMM_SMALL_FORCE") ? std::atol(std::getenv("RMHIP_GEMM_SMALL_FORCE")) : 0;
-        small_pad = std::getenv("RMHIP_GEMM_SMALL_PAD") ? std::atol(std::getenv("RMHIP_GEMM_SMALL_PAD")) : 0;
-    }
-    // shapes that are not whole tiles - any m, n, k, leading dimensions, 8-byte aligned bases - run the same kernels with clamped
-    // operand loads, a zeroed k tail and checked stores (GUARD).  RMHIP_GEMM_GUARD=0 sends them to the element-checking k_dgemm as
-    // before (which keeps A * B' and the epilogue of a transposed product).
-    static const int guard_on = std::getenv("RMHIP_GEMM_GUARD") ? std::atoi(std::getenv("RMHIP_GEMM_GUARD")) : 1;
-    const bool vec_ok = (lda % 2 == 0) && (ldb % 2 == 0) && (((uintptr_t)A & 15) == 0) && (((uintptr_t)B & 15) == 0);
-    static const int guard_lu = std::getenv("RMHIP_GEMM_GUARD_LU") ? std::atoi(std::getenv("RMHIP_GEMM_GUARD_LU")) : 1;  // A/B: guarded tiles inside the look-ahead LU
-    const bool guard_ok = guard_on && !tb && k >= 1 && (guard_lu || (!c->in_lookahead && c->gemm_lds_pad == 0));
-    // (skinny products - at most 64 rows or columns of output - waste half of every 128 x 128 tile or more: 100000 x 50 x 50 52 -> 30 us,
-    // 200000 x 16 x 16 34 -> 20 us on the 64 x 64 tiles, whatever the block count)
-    const bool skinny = (m <= (size_t)SM || n <= (size_t)SN) && k < 1024 && !c->in_lookahead;  // (longer k: split-K above)
-    // The look-ahead LU's update streams run their few-tile products - the dgemm steps of the W-wide triangular solves, 14-112 tiles of
-    // 128 x 128 for 0.1-0.2 ms each - on the 64 x 64 tiles as well: four times the blocks, 16384 69.1 -> 67.6 ms, 8192 20.6 -> 20.2
-    // (RMHIP_LU_SMALL_UPD = largest k, 0 = off; at most kSmallUpdBlocks 128 x 128 tiles)
-    constexpr long kSmallUpdBlocks = 128;
-    const long small_upd = lu_process_knobs().small_upd;
-    const bool upd_small = small_upd > 0 && c->gemm_lds_pad != 0 && c->in_lookahead && (long)k <= small_upd && (long)blocks <= kSmallUpdBlocks;
-    const bool small_shape = !ep && !ta && !tb && splits == 1 && (c->gemm_lds_pad == 0 || small_force || upd_small) && k > 0 &&
-                             ((k <= 1024 && (size_t)blocks * 2 <= (size_t)c->num_cus) || skinny || small_force || upd_small);
-    const bool small_whole = (m % SM == 0) && (n % SN == 0) && (k % BK == 0) && vec_ok;
-    if (small_on && small_shape && (small_whole || guard_ok)) {
-        g.tiles_m = (unsigned)((m + SM - 1) / SM);
-        g.tiles_n = (unsigned)((n + SN - 1) / SN);
-        const dim3 sgrid(g.tiles_m * g.tiles_n);
-        if (small_whole) {
-            if (preload) launch_small<true, false>(c, sgrid, (size_t)small_pad, g);
-            else launch_small<false, false>(c, sgrid, (size_t)small_pad, g);
-        } else {
-            if (preload) launch_small<true, true>(c, sgrid, (size_t)small_pad, g);
-            else launch_small<false, true>(c, sgrid, (size_t)small_pad, g);
-        }
-        c->tel.kernel_launches++;
-        RMHIP_HIP_CHECK(hipGetLastError());
-        return RMHIP_OK;
-    }
-    // eight-wave tile: on the look-ahead's update stream (one padded block per CU), and for every plain unguarded product
-    // (scripts/gemm_w8_ab.py, TFLOP/s four-wave -> eight-wave, both with the pipelined k loop: 4096^3 68.6 -> 71.9, 8192^3 69.5 ->
-    // 72.3, 4096^2 x 16384 68.8 -> 72.5, 8192^2 x 1024 68.4 -> 70.7, 12288 x 4096 x 2048 68.5 -> 71.4; equal at 2048^3 and at
-    // 16384^2 x 128 / 256: four pipelined waves per SIMD leave the matrix pipe fewer gaps than two) - but not on the main stream
-    // inside the look-ahead LU, whose blocks must fit beside the update stream's.
-    // RMHIP_GEMM_W8: 0 never, 2 always (A/B).
-    static int w8_mode = -1;
-    if (w8_mode < 0) {
-        const char* v = std::getenv("RMHIP_GEMM_W8");
-        w8_mode = v ? std::atoi(v) : 1;
-    }
-    if (fast_k && splits == 1 && !ep && !ta && !tb && c->gemm_tile_counters && c->gemm_lds_pad != 0 && w8_mode != 0 &&
-        c->gemm_counter_next < c->gemm_counter_cap) {
-        // update stream of the look-ahead LU while the panels sit on one XCD: persistent eight-wave kernel that stays off it
+    const unsigned blocks = r.tiles_m * r.tiles_n;
+    dim3 grid(blocks, r.splits);
+    if (!std::strcmp(r.kernel, "w8p")) {  // at most one persistent workgroup per CU, fed by the next of the driver's tile counters
         g.tile_counter = c->gemm_tile_counters + c->gemm_counter_next++;
         g.avoid_xcc = c->gemm_avoid_xcc;
-        static const long grid_cap = std::getenv("RMHIP_GEMM_W8P_GRID") ? std::atol(std::getenv("RMHIP_GEMM_W8P_GRID")) : 0;  // A/B: fewer persistent workgroups than CUs
-        unsigned grid = (unsigned)c->num_cus < blocks ? (unsigned)c->num_cus : blocks;
-        if (grid_cap > 0 && grid > (unsigned)grid_cap) grid = (unsigned)grid_cap;
-        c->ensure_max_lds((const void*)k_dgemm_w8p, kMaxLds);
-        hipLaunchKernelGGL(k_dgemm_w8p, dim3(grid), dim3(512), lds_bytes, c->stream, g);
-        c->note_gemm_route("w8p", false, false, false, false, 0, false, 1, g.k_chunk);
-        c->tel.kernel_launches++;
-        RMHIP_HIP_CHECK(hipGetLastError());
-        return RMHIP_OK;
+        grid.x = (unsigned)c->num_cus < blocks ? (unsigned)c->num_cus : blocks;
     }
-    const bool w8_fast = fast && g.k_chunk % BK == 0;  // every k slice a whole number of tiles
-    auto reduce_splits = [&]() -> int {
-        if (splits > 1) {
-            const size_t mn = m * n;
-            const unsigned rgrid = (unsigned)((mn + 255) / 256 < (size_t)c->num_cus * 4 ? (mn + 255) / 256 : (size_t)c->num_cus * 4);
-            hipLaunchKernelGGL(k_reduce_splits, dim3(rgrid), dim3(256), 0, c->stream, (const double*)g.C, mn, m, splits, alpha, beta, C, ldc);
-            c->tel.kernel_launches++;
-            RMHIP_HIP_CHECK(hipGetLastError());
-        }
-        return RMHIP_OK;
-    };
-    if (w8_fast && ep && !ta && !tb && w8_mode != 0 && !c->in_lookahead && c->gemm_lds_pad == 0) {
-        // matmul_epilogue on the eight-wave tile (splits == 1 whenever there is an epilogue)
-        if (g.ep.flags & EP_POW) launch_w8<false, false, false, 2>(c, blocks, 1, lds_bytes, kMaxLds, g);
-        else launch_w8<false, false, false, 1>(c, blocks, 1, lds_bytes, kMaxLds, g);
-        c->tel.kernel_launches++;
-        RMHIP_HIP_CHECK(hipGetLastError());
-        return RMHIP_OK;
-    }
-    if (w8_fast && !ep && ta && !tb && w8_mode != 0 && !c->in_lookahead && c->gemm_lds_pad == 0) {
-        // A' * B (transpose views, syrk, the Gram matrices of covariance and least squares): 70.7 -> 72.5 TFLOP/s at 8192^3 as
-        // well.  (A * B' measured 69.8 against 70.2 in this form and stays on k_dgemm.)
-        // Split-K (tall A'*A: few output tiles, long k) runs the same kernel with blockIdx.y over the k slices.
-        launch_w8<false, true, false>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        c->tel.kernel_launches++;
-        RMHIP_HIP_CHECK(hipGetLastError());
-        return reduce_splits();
-    }
-    if (w8_fast && splits > 1 && !ep && !ta && !tb && w8_mode != 0 && !c->in_lookahead && c->gemm_lds_pad == 0) {
-        launch_w8<false>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        c->tel.kernel_launches++;
-        RMHIP_HIP_CHECK(hipGetLastError());
-        return reduce_splits();
-    }
-    if (fast_k && splits == 1 && !ep && !ta && !tb &&
-        ((w8_mode == 1 && (c->gemm_lds_pad != 0 || !c->in_lookahead)) || w8_mode == 2)) {
-        if (preload && g.yield_word) {  // the two-level LU's update streams: the variant that checks the yield word
-            launch_w8<true, false, false, 0, true>(c, blocks, 1, lds_bytes, kMaxLds, g);
-        } else if (preload) {
-            launch_w8<true>(c, blocks, 1, lds_bytes, kMaxLds, g);
-        } else {
-            launch_w8<false>(c, blocks, 1, lds_bytes, kMaxLds, g);
-        }
-        c->tel.kernel_launches++;
-        RMHIP_HIP_CHECK(hipGetLastError());
-        return RMHIP_OK;
-    }
-    // (inside the look-ahead LU only the update stream - the one with the LDS pad - runs eight-wave blocks, as for whole tiles)
-    if (!fast && guard_ok && w8_mode != 0 && (splits == 1 || g.k_chunk % BK == 0) && !(ep && ta) && (c->gemm_lds_pad != 0 || !c->in_lookahead)) {
-        // guarded eight-wave tile (plain or transposed A; plain, preloaded-C or epilogue store; split-K slices are whole tiles except the last)
-        if (ep) {
-            if (g.ep.flags & EP_POW) launch_w8g<false, false, 2>(c, blocks, splits, lds_bytes, kMaxLds, g);
-            else launch_w8g<false, false, 1>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        } else if (ta) {
-            launch_w8g<false, true, 0>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        } else if (preload) {
-            launch_w8g<true, false, 0>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        } else {
-            launch_w8g<false, false, 0>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        }
-        c->tel.kernel_launches++;
-        RMHIP_HIP_CHECK(hipGetLastError());
-        return reduce_splits();
-    }
-    if (ep) {
-        if (ta || tb) return fail(RMHIP_ERR_UNSUPPORTED, "dgemm: epilogue with transposed operands is not instantiated");
-        launch_variant<true, true, false, false>(c, blocks, splits, lds_bytes, kMaxLds, g);
-    } else if (ta) {
-        if (fast_k) launch_variant<false, false, true, false>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        else launch_variant<true, false, true, false>(c, blocks, splits, lds_bytes, kMaxLds, g);
-    } else if (tb) {
-        if (fast_k) launch_variant<false, false, false, true>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        else launch_variant<true, false, false, true>(c, blocks, splits, lds_bytes, kMaxLds, g);
-    } else {
-        if (fast_k && preload) launch_variant<false, false, false, false, true>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        else if (fast_k) launch_variant<false, false, false, false>(c, blocks, splits, lds_bytes, kMaxLds, g);
-        else launch_variant<true, false, false, false>(c, blocks, splits, lds_bytes, kMaxLds, g);
-    }
+    variant->launch(c, grid, lds_bytes, g);
+    c->gemm_route = r;
     c->tel.kernel_launches++;
     RMHIP_HIP_CHECK(hipGetLastError());
-    if (splits > 1) {
+    if (r.splits > 1) {
         const size_t mn = m * n;
         const unsigned rgrid = (unsigned)((mn + 255) / 256 < (size_t)c->num_cus * 4 ? (mn + 255) / 256 : (size_t)c->num_cus * 4);
-        hipLaunchKernelGGL(k_reduce_splits, dim3(rgrid), dim3(256), 0, c->stream, (const double*)g.C, mn, m, splits, alpha, beta, C,
-                           ldc);
+        hipLaunchKernelGGL(k_reduce_splits, dim3(rgrid), dim3(256), 0, c->stream, (const double*)g.C, mn, m, r.splits, alpha, beta, C, ldc);
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
     }
@@ -1219,7 +1083,7 @@ int launch_pgemm_w8(Context* c, const double* A, const double* B, double* C, uns
     const unsigned grid = (unsigned)(work < (1ull << 20) ? work : (1ull << 20));
     c->ensure_max_lds((const void*)k_pgemm_w8, lds_bytes);
     hipLaunchKernelGGL(k_pgemm_w8, dim3(grid), dim3(512), lds_bytes, c->stream, g, pm, pages);
-    c->note_gemm_route("pgemm", true, false, false, false, 0, false, 1, g.k_chunk);
+    c->gemm_route = GemmRoute{"pgemm", 1, 0, 0, 0, 0, 0, 1, k, g.tiles_m, g.tiles_n};  // the one route of this launcher: guarded, unsplit
     c->tel.kernel_launches++;
     RMHIP_HIP_CHECK(hipGetLastError());
     return RMHIP_OK;

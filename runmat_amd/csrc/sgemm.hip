@@ -14,6 +14,8 @@
 //   banks exactly once).  Staging moves 8-byte pairs.
 // Accumulation is f32 in the matrix core: the result differs from the f64 path (RMHIP_F32_MATMUL=f64: widen, dgemm,
 // round once -- the CPU's `single` semantics exactly) by at most ~k * eps32 * sum|a||b|; tests state the bound.
+#include <cstring>
+
 #include "common.h"
 
 namespace rmhip {
@@ -27,10 +29,7 @@ static constexpr int BM = 128, BN = 128, BK = 16;
 static constexpr int SA = BM + 16;  // pattern M row stride (floats)
 static constexpr int SB = BK + 4;   // pattern K row stride (floats)
 static constexpr int TILE = (BK * SA > BN * SB) ? BK * SA : BN * SB;  // floats; either pattern fits either buffer
-#ifndef SGEMM_GROUP_M
-#define SGEMM_GROUP_M 8
-#endif
-static constexpr int GROUP_M = SGEMM_GROUP_M;
+static constexpr int GROUP_M = 8;
 }  // namespace sg
 
 struct SgemmArgs {
@@ -63,14 +62,10 @@ __device__ __forceinline__ void sg_tile_of_block(const SgemmArgs& g, unsigned& t
     tn = in_group / gsz;
 }
 
-#ifndef SGEMM_BLOCKS_PER_CU
-#define SGEMM_BLOCKS_PER_CU 2
-#endif
-
 // EDGE = false: m % 128 == 0, n % 128 == 0, k % 16 == 0, even leading dimensions, 8-byte aligned bases.
 // TA / TB: the operand is stored transposed (RunMat's transpose views), exactly as in k_dgemm.
 template <bool EDGE, bool TA, bool TB>
-__global__ void __launch_bounds__(256, SGEMM_BLOCKS_PER_CU) k_sgemm(const SgemmArgs g) {
+__global__ void __launch_bounds__(256, 2) k_sgemm(const SgemmArgs g) {
     using namespace sg;
     __shared__ __attribute__((aligned(16))) float lds[4 * TILE];
     float* As = lds;             // [2][TILE]
@@ -376,22 +371,33 @@ __global__ void __launch_bounds__(512, 4) k_sgemm_w8g(const SgemmArgs g) {  // f
     sgemm_w8_body<TA, true>(g, lds);
 }
 
+// One launch helper per kernel, and the table from a route (gemm_plan.h plan_sgemm) to its instantiation
+using SgemmLaunch = void (*)(Context* c, dim3 grid, const SgemmArgs& g);
 template <bool EDGE, bool TA, bool TB>
-static void sg_launch(Context* c, unsigned blocks, unsigned splits, const SgemmArgs& g) {
-    hipLaunchKernelGGL((k_sgemm<EDGE, TA, TB>), dim3(blocks, splits), dim3(256), 0, c->stream, g);
-    c->note_gemm_route("s_w4", EDGE, false, TA, TB, 0, false, splits, g.k_chunk);
-}
-
-template <bool TA>
-static void sg_launch_w8(Context* c, unsigned blocks, const SgemmArgs& g) {
-    hipLaunchKernelGGL(k_sgemm_w8<TA>, dim3(blocks), dim3(512), 0, c->stream, g);
-    c->note_gemm_route("s_w8", false, false, TA, false, 0, false, 1, g.k_chunk);
+static void sg_launch(Context* c, dim3 grid, const SgemmArgs& g) {
+    hipLaunchKernelGGL((k_sgemm<EDGE, TA, TB>), grid, dim3(256), 0, c->stream, g);
 }
 template <bool TA>
-static void sg_launch_w8g(Context* c, unsigned blocks, const SgemmArgs& g) {
-    hipLaunchKernelGGL(k_sgemm_w8g<TA>, dim3(blocks), dim3(512), 0, c->stream, g);
-    c->note_gemm_route("s_w8g", true, false, TA, false, 0, false, 1, g.k_chunk);
+static void sg_launch_w8(Context* c, dim3 grid, const SgemmArgs& g) {
+    hipLaunchKernelGGL(k_sgemm_w8<TA>, grid, dim3(512), 0, c->stream, g);
 }
+template <bool TA>
+static void sg_launch_w8g(Context* c, dim3 grid, const SgemmArgs& g) {
+    hipLaunchKernelGGL(k_sgemm_w8g<TA>, grid, dim3(512), 0, c->stream, g);
+}
+struct SgemmVariant {
+    const char* kernel;
+    int guard, ta, tb;
+    SgemmLaunch launch;
+};
+// (rows in the order the kernels have always been emitted in: the code object keeps its layout)
+static const SgemmVariant kSgemmVariants[] = {
+    {"s_w8g", 1, 1, 0, sg_launch_w8g<true>},        {"s_w8g", 1, 0, 0, sg_launch_w8g<false>},
+    {"s_w8", 0, 1, 0, sg_launch_w8<true>},          {"s_w4", 0, 1, 0, sg_launch<false, true, false>},
+    {"s_w4", 1, 1, 0, sg_launch<true, true, false>}, {"s_w4", 0, 0, 1, sg_launch<false, false, true>},
+    {"s_w4", 1, 0, 1, sg_launch<true, false, true>}, {"s_w8", 0, 0, 0, sg_launch_w8<false>},
+    {"s_w4", 0, 0, 0, sg_launch<false, false, false>}, {"s_w4", 1, 0, 0, sg_launch<true, false, false>},
+};
 
 // C = P_0 + P_1 + ... + P_{S-1} (partials m x n dense, ld m), summed in split order in f64 and rounded once
 __global__ void __launch_bounds__(256) k_sreduce_splits(const float* __restrict__ P, size_t mn, size_t m, unsigned splits,
@@ -404,13 +410,28 @@ __global__ void __launch_bounds__(256) k_sreduce_splits(const float* __restrict_
 }
 
 // C (m x n, f32) = op(A) * op(B); op(X) = X' when tX (A then stored k x m, B stored n x k).  k == 0 gives zeros.
+// plan_sgemm (gemm_plan.h) decides, this function executes the route and leaves it in c->gemm_route.
 int launch_sgemm_trans(Context* c, bool ta, bool tb, size_t m, size_t n, size_t k, const float* A, size_t lda, const float* B,
                        size_t ldb, float* C, size_t ldc) {
-    using namespace sg;
     if (m == 0 || n == 0) return RMHIP_OK;
-    if (ta && tb) return fail(RMHIP_ERR_UNSUPPORTED, "sgemm: A' * B' is not instantiated");
+    GemmProblem p;
+    p.m = m, p.n = n, p.k = k, p.lda = lda, p.ldb = ldb;
+    p.a_aligned = ((uintptr_t)A & 7) == 0;
+    p.b_aligned = ((uintptr_t)B & 7) == 0;
+    p.ta = ta, p.tb = tb;
+    GemmSite s;
+    s.num_cus = c->num_cus;
+    const GemmRoute r = plan_sgemm(p, s, gemm_knobs());
+    if (r.unsupported) return fail(RMHIP_ERR_UNSUPPORTED, "%s", r.unsupported);
     if (m > 0xffffffffULL || n > 0xffffffffULL || k > 0xffffffffULL)
         return fail(RMHIP_ERR_UNSUPPORTED, "sgemm: dimension exceeds 2^32");
+    const SgemmVariant* variant = nullptr;
+    for (const SgemmVariant& v : kSgemmVariants)
+        if (!std::strcmp(v.kernel, r.kernel) && v.guard == r.guard && v.ta == r.ta && v.tb == r.tb) variant = &v;
+    if (!variant || r.pre || r.epi || r.yield)
+        return fail(RMHIP_ERR_UNSUPPORTED, "sgemm: no instantiation for the route %s guard=%d pre=%d ta=%d tb=%d epi=%d yield=%d", r.kernel,
+                    r.guard, r.pre, r.ta, r.tb, r.epi, r.yield);
+
     SgemmArgs g;
     g.A = A;
     g.B = B;
@@ -421,72 +442,33 @@ int launch_sgemm_trans(Context* c, bool ta, bool tb, size_t m, size_t n, size_t 
     g.m = (unsigned)m;
     g.n = (unsigned)n;
     g.k = (unsigned)k;
-    g.tiles_m = (unsigned)((m + BM - 1) / BM);
-    g.tiles_n = (unsigned)((n + BN - 1) / BN);
-    g.vec_a = ((((uintptr_t)A & 7) == 0) && (lda % 2 == 0)) ? 1 : 0;
-    g.vec_b = ((((uintptr_t)B & 7) == 0) && (ldb % 2 == 0)) ? 1 : 0;
-    const bool fast = (m % BM == 0) && (n % BN == 0) && (k % BK == 0) && k > 0 && g.vec_a && g.vec_b;
-    const unsigned blocks = g.tiles_m * g.tiles_n;
-    // Split-K as in dgemm.hip: few output tiles but a long k would leave most CUs idle; about two blocks per CU.
-    unsigned splits = 1;
-    g.k_chunk = (unsigned)k;
+    g.tiles_m = r.tiles_m;
+    g.tiles_n = r.tiles_n;
+    g.vec_a = (p.a_aligned && lda % 2 == 0) ? 1 : 0;
+    g.vec_b = (p.b_aligned && ldb % 2 == 0) ? 1 : 0;
+    g.k_chunk = r.k_chunk;
     g.c_split_stride = 0;
     std::shared_ptr<Allocation> partials;
-    if (blocks * 4 <= (unsigned)c->num_cus && k >= 1024) {  // (from k = 1024, as dgemm.hip: few blocks with a long k are latency bound)
-        const size_t want = (2 * (size_t)c->num_cus + blocks - 1) / blocks;
-        size_t chunk = (k + want - 1) / want;
-        const size_t gran = k >= 8192 ? 1024 : (k >= 2048 ? 256 : 128);  // multiples of the k tile keep the unguarded kernel eligible
-        chunk = ((chunk + gran - 1) / gran) * gran;
-        splits = (unsigned)((k + chunk - 1) / chunk);
-        if (splits > 1) {
-            RMHIP_TRY(c->alloc_device(((size_t)splits * m * n + 1) / 2, &partials));
-            g.k_chunk = (unsigned)chunk;
-            g.C = reinterpret_cast<float*>(partials->ptr);
-            g.ldc = m;
-            g.c_split_stride = (unsigned long long)m * n;
-        } else {
-            splits = 1;
-        }
+    if (r.splits > 1) {  // the slices write their partial products; k_sreduce_splits adds them
+        RMHIP_TRY(c->alloc_device(((size_t)r.splits * m * n + 1) / 2, &partials));
+        g.C = reinterpret_cast<float*>(partials->ptr);
+        g.ldc = m;
+        g.c_split_stride = (unsigned long long)m * n;
     }
-    const bool fast_k = fast && (splits == 1 || k % g.k_chunk == 0);
-    // shapes that are not whole tiles: the guarded eight-wave tile (RMHIP_GEMM_GUARD=0: the element-checking k_sgemm as before)
-    static const int guard_on = std::getenv("RMHIP_GEMM_GUARD") ? std::atoi(std::getenv("RMHIP_GEMM_GUARD")) : 1;
-    const bool w8_env_off = std::getenv("RMHIP_SGEMM_W8") && *std::getenv("RMHIP_SGEMM_W8") == '0';
-    if (!fast && guard_on && !w8_env_off && !tb && splits == 1 && k >= 1) {
-        if (ta) sg_launch_w8g<true>(c, blocks, g);
-        else sg_launch_w8g<false>(c, blocks, g);
-        c->tel.kernel_launches++;
-        RMHIP_HIP_CHECK(hipGetLastError());
-        return RMHIP_OK;
-    }
-    if (ta) {
-        if (fast_k && splits == 1 && !w8_env_off) sg_launch_w8<true>(c, blocks, g);  // A' * B (syrk, covariance, transpose views)
-        else if (fast_k) sg_launch<false, true, false>(c, blocks, splits, g);
-        else sg_launch<true, true, false>(c, blocks, splits, g);
-    } else if (tb) {
-        if (fast_k) sg_launch<false, false, true>(c, blocks, splits, g);
-        else sg_launch<true, false, true>(c, blocks, splits, g);
-    } else {
-        static int w8_mode = -1;  // RMHIP_SGEMM_W8=0: the four-wave kernel for everything (A/B)
-        if (w8_mode < 0) {
-            const char* v = std::getenv("RMHIP_SGEMM_W8");
-            w8_mode = (v && *v == '0') ? 0 : 1;
-        }
-        if (fast_k && splits == 1 && w8_mode) sg_launch_w8<false>(c, blocks, g);
-        else if (fast_k) sg_launch<false, false, false>(c, blocks, splits, g);
-        else sg_launch<true, false, false>(c, blocks, splits, g);
-    }
+    variant->launch(c, dim3(r.tiles_m * r.tiles_n, r.splits), g);
+    c->gemm_route = r;
     c->tel.kernel_launches++;
     RMHIP_HIP_CHECK(hipGetLastError());
-    if (splits > 1) {
+    if (r.splits > 1) {
         const size_t mn = m * n;
         const size_t want_blocks = (mn + 255) / 256, cap = (size_t)c->num_cus * 4;
         hipLaunchKernelGGL(k_sreduce_splits, dim3((unsigned)(want_blocks < cap ? want_blocks : cap)), dim3(256), 0, c->stream,
-                           reinterpret_cast<const float*>(partials->ptr), mn, m, splits, C, ldc);
+                           reinterpret_cast<const float*>(partials->ptr), mn, m, r.splits, C, ldc);
         c->tel.kernel_launches++;
         RMHIP_HIP_CHECK(hipGetLastError());
     }
     return RMHIP_OK;
 }
+
 
 }  // namespace rmhip

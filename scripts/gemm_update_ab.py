@@ -1,5 +1,5 @@
 """Developer tool: the rank-k update shapes of the blocked LU (m x n x k, k = 256 / 512) through rmhip_matmul under different
-kernel / LDS-pad knobs (set in the environment): TFLOP/s from HIP events."""
+kernel knobs (RMHIP_GEMM_*, set in the environment): TFLOP/s from HIP events."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from runmat_amd import HipProvider

@@ -1,4 +1,4 @@
-"""Developer tool: k_dgemm (four waves per block) against k_dgemm_w8 (RMHIP_GEMM_W8=2) over product sizes, TFLOP/s from HIP events."""
+"""Developer tool: k_dgemm (four waves per block, RMHIP_GEMM_W8=0) against the default k_dgemm_w8 over product sizes: run it once with each setting, TFLOP/s from HIP events."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from runmat_amd import HipProvider

@@ -475,6 +475,35 @@ def test_solve_knobs_are_read_in_one_place_and_match_the_knob_table():
     assert {k for k, v in table.items() if v == "per process"} == {"RMHIP_SVD_MAX_COLS"}
 
 
+def test_gemm_knobs_are_read_in_one_place_and_match_the_knob_table():
+    """The RMHIP_GEMM_*, RMHIP_SGEMM_* and RMHIP_MFMA_ROWMAP variables are read by gemm_knobs() (per process) in dgemm.hip and nowhere
+    else - the launchers and gemm_plan.h take the GemmKnobs value - and the "GEMM dispatch" table of docs/KNOBS.md names exactly
+    those variables, each as read per process."""
+    import re
+
+    pat = re.compile(r'getenv\("(RMHIP_S?GEMM_[A-Z0-9_]+|RMHIP_MFMA_ROWMAP)"\)')
+    src = ROOT / "runmat_amd" / "csrc"
+    everywhere = []
+    for f in sorted(list(src.glob("*.cpp")) + list(src.glob("*.hip")) + list(src.glob("*.h"))):
+        everywhere += pat.findall(f.read_text())
+    in_knobs = pat.findall(_function_body((src / "dgemm.hip").read_text(), "const GemmKnobs& gemm_knobs()"))
+    assert sorted(in_knobs) == ["RMHIP_GEMM_GUARD", "RMHIP_GEMM_PRELOAD", "RMHIP_GEMM_SMALL", "RMHIP_GEMM_W8", "RMHIP_MFMA_ROWMAP",
+                                "RMHIP_SGEMM_W8"]
+    assert sorted(everywhere) == sorted(in_knobs), "a GEMM knob is read outside gemm_knobs()"
+    assert "getenv" not in (src / "gemm_plan.h").read_text() and "getenv" not in (src / "sgemm.hip").read_text()
+
+    doc = (ROOT / "docs" / "KNOBS.md").read_text()
+    section = doc[doc.index("## GEMM dispatch"):]
+    section = section[:section.index("\n## ", 1)]
+    table = {}
+    for row in section.splitlines():
+        m = re.match(r"\| `(RMHIP_[A-Z0-9_]+)` \|[^|]*\| ([^|]*) \|", row)
+        if m:
+            assert m.group(1) not in table, f"{m.group(1)} has two rows"
+            table[m.group(1)] = m.group(2).strip()
+    assert set(table) == set(in_knobs) and set(table.values()) == {"per process"}, table
+
+
 def test_ctx_or_fail_is_defined_once():
     """The entry-point prologue CTX_OR_FAIL is one macro in common.h; no translation unit carries a copy of its own (the collectives'
     variant without a NarrowScope has a name of its own, next to it)."""

@@ -1,12 +1,13 @@
 """tests/gemm_ref.py on the host (CPU only): the integer reference is exact for the stated operand ranges in f64 and f32, in any
 association order; the frames are what they claim; and every row of the route tables has the divisibility and alignment properties
-its route name claims under the launchers' rules (dgemm.hip launch_dgemm_impl, sgemm.hip launch_sgemm_trans) at 256 compute units."""
+its route name claims under the launchers' own rule - gemm_plan.h plan_dgemm / plan_sgemm, run through tests/cpp/gemm_route_check.cpp -
+at 256 compute units; and the routes that only the look-ahead LU's sites select."""
 import numpy as np
 import pytest
 
 import gemm_ref as G
 
-TILE, SMALL_TILE, KT = 128, 64, 16
+TILE, SMALL_TILE = 128, 64
 
 
 # ---- the reference ------------------------------------------------------------------------------------------------------------------
@@ -96,64 +97,65 @@ def layout(c):
     return (k if ta else m), (n if tb else k), True, True  # whole buffers: allocations are at least 16-byte aligned
 
 
-def model(c, knobs=None, bits=64):
-    """The route the launchers' conditions give for a case at G.NUM_CUS compute units, outside the look-ahead LU.  This is a MIRROR of
-    launch_dgemm_impl / launch_sgemm_trans, kept in step with them by hand - a threshold that moves there moves here too - and not an
-    independent specification: it says why a row has its route (which divisibility, alignment or block-count rule), while what
-    actually runs is decided by tests/test_gpu_gemm_paths.py against the launcher's own record."""
-    knobs = knobs or {}
-    m, n, k, e = c["m"], c["n"], c["k"], c["entry"]
-    ta, tb, ep = e in ("matmul_ta", "syrk"), e == "matmul_tb", e == "epilogue"
-    epi = (2 if "pow" in c else 1) if ep else 0
-    if e == "pagefun":
-        assert m >= 256 and n >= 256 and max(m, n, k) > 32 and c["pages"] > 1  # rmhip_pagefun's tier 4
-        return G.route("pgemm guard", 1, k)
-    lda, ldb, a_even, b_even = layout(c)
-    vec_ok = lda % 2 == 0 and ldb % 2 == 0 and a_even and b_even  # f32: 8-byte alignment of 4-byte elements, the same parity rule
-    fast = m % TILE == 0 and n % TILE == 0 and k % KT == 0 and k > 0 and vec_ok
-    blocks = -(-m // TILE) * -(-n // TILE)
-    splits, chunk = 1, k
-    if not ep and blocks * 4 <= G.NUM_CUS and k >= 1024:
-        want = -(-2 * G.NUM_CUS // blocks)
-        gran = 1024 if k >= 8192 else 256 if k >= 2048 else 128
-        ch = -(--(-k // want) // gran) * gran
-        if -(-k // ch) > 1:
-            splits, chunk = -(-k // ch), ch
-    fast_k = fast and (splits == 1 or k % chunk == 0)
-    guard_on = knobs.get("RMHIP_GEMM_GUARD", "1") != "0"
-    if bits == 32:
-        w8 = knobs.get("RMHIP_SGEMM_W8", "1") != "0"
-        if not fast and guard_on and w8 and not tb and splits == 1 and k >= 1:
-            return G.route("s_w8g guard" + (" ta" if ta else ""), 1, k)
-        if fast_k and splits == 1 and w8 and not tb:
-            return G.route("s_w8" + (" ta" if ta else ""), 1, k)
-        return G.route("s_w4" + ("" if fast_k else " edge") + (" ta" if ta else "") + (" tb" if tb else ""), splits, chunk)
-    alpha, beta = c.get("alpha", 1.0), c.get("beta", 0.0)
-    preload = knobs.get("RMHIP_GEMM_PRELOAD", "1") != "0" and not (ep or ta or tb) and splits == 1 and alpha == -1.0 and beta == 1.0 and k > 0
-    w8_on = knobs.get("RMHIP_GEMM_W8", "1") != "0"
-    guard_ok = guard_on and not tb and k >= 1
-    skinny = (m <= SMALL_TILE or n <= SMALL_TILE) and k < 1024
-    small_shape = not (ep or ta or tb) and splits == 1 and k > 0 and ((k <= 1024 and blocks * 2 <= G.NUM_CUS) or skinny)
-    small_whole = m % SMALL_TILE == 0 and n % SMALL_TILE == 0 and k % KT == 0 and vec_ok
-    pre = " pre" if preload else ""
-    if knobs.get("RMHIP_GEMM_SMALL", "1") != "0" and small_shape and (small_whole or guard_ok):
-        return G.route("small" + ("" if small_whole else " guard") + pre, 1, k)
-    w8_fast = fast and chunk % KT == 0
-    if w8_fast and ep and w8_on:
-        return G.route(f"w8 epi{epi}", 1, k)
-    if w8_fast and ta and w8_on:
-        return G.route("w8 ta", splits, chunk)
-    if w8_fast and splits > 1 and not tb and w8_on:
-        return G.route("w8", splits, chunk)
-    if fast_k and splits == 1 and not (ep or ta or tb) and w8_on:
-        return G.route("w8" + pre, 1, k)
-    if not fast and guard_ok and w8_on and (splits == 1 or chunk % KT == 0):
-        return G.route("w8g guard" + (f" epi{epi}" if ep else " ta" if ta else pre), splits, chunk)
-    if ep:
-        return G.route(f"w4 edge epi{epi}", splits, chunk)
-    if ta or tb:
-        return G.route("w4" + ("" if fast_k else " edge") + (" ta" if ta else " tb"), splits, chunk)
-    return G.route("w4" + (pre if fast_k and preload else "" if fast_k else " edge"), splits, chunk)
+ABI = dict(num_cus=G.NUM_CUS, in_lookahead=0, lds_pad=0, chain_prio=0, counter=0, yield_word=0, small_upd=1024)
+KNOB_ORDER = ("RMHIP_GEMM_SMALL", "RMHIP_GEMM_W8", "RMHIP_GEMM_PRELOAD", "RMHIP_GEMM_GUARD", "RMHIP_SGEMM_W8")
+
+
+@pytest.fixture(scope="module")
+def plan(tmp_path_factory):
+    """The launchers' own rule: tests/cpp/gemm_route_check.cpp --table runs plan_dgemm / plan_sgemm (runmat_amd/csrc/gemm_plan.h), the
+    function launch_dgemm_impl and launch_sgemm_trans execute.  plan(rows) takes (case, knobs, bits, site) tuples and returns, per row,
+    the route as rmhip_gemm_last_route would report it plus tiles_m, tiles_n and prio, or {"unsupported": message}."""
+    import subprocess
+
+    from test_host_plan import compile_check
+
+    exe = compile_check(tmp_path_factory.mktemp("gemm_route_check"), "gemm_route_check")
+
+    def run(rows):
+        lines = []
+        for c, knobs, bits, site in rows:
+            e = c["entry"]
+            ta, tb = c.get("ta", e in ("matmul_ta", "syrk")), c.get("tb", e == "matmul_tb")
+            epi = c.get("epi", ((2 if "pow" in c else 1) if e == "epilogue" else 0))
+            lda, ldb, a_even, b_even = layout(c)  # f32: 8-byte alignment of 4-byte elements, the same parity rule
+            s = dict(ABI, **(site or {}))
+            on = [int((knobs or {}).get(k, "1") != "0") for k in KNOB_ORDER]
+            lines.append(" ".join(str(x) for x in [bits, c["m"], c["n"], c["k"], lda, ldb, int(a_even), int(b_even), int(ta), int(tb), epi,
+                                                   c.get("alpha", 1.0), c.get("beta", 0.0), *s.values(), *on]))
+        r = subprocess.run([str(exe), "--table"], input="\n".join(lines) + "\n", capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        out = []
+        for ln in r.stdout.splitlines():
+            if ln.startswith("unsupported: "):
+                out.append({"unsupported": ln[len("unsupported: "):]})
+                continue
+            w = ln.split()
+            keys = ("guard", "pre", "ta", "tb", "epi", "yield", "splits", "k_chunk", "tiles_m", "tiles_n", "prio")
+            out.append({"kernel": w[0], **{k: int(v) for k, v in zip(keys, w[1:])}})
+        assert len(out) == len(rows), r.stdout
+        return out
+
+    return run
+
+
+def reported(r):
+    """The fields rmhip_gemm_last_route reports (G.route's keys)."""
+    return {k: r[k] for k in ("kernel", "guard", "pre", "ta", "tb", "epi", "yield", "splits", "k_chunk")}
+
+
+def planned(plan, table, knobs=None, bits=64):
+    """Each case's planned route at G.NUM_CUS compute units, outside the look-ahead LU.  rmhip_pagefun's large-page tier has its own
+    launcher with the one route 'pgemm guard' and does not pass through the plan: those rows are checked for the tier's conditions."""
+    out = iter(plan([(c, knobs, bits, None) for c in table if c["entry"] != "pagefun"]))
+    routes = []
+    for c in table:
+        if c["entry"] == "pagefun":
+            assert c["m"] >= 256 and c["n"] >= 256 and max(c["m"], c["n"], c["k"]) > 32 and c["pages"] > 1  # rmhip_pagefun's tier 4
+            routes.append(G.route("pgemm guard", 1, c["k"]))
+        else:
+            routes.append(reported(next(out)))
+    return routes
 
 
 def test_case_ids_are_unique_and_k_stays_exact():
@@ -165,27 +167,94 @@ def test_case_ids_are_unique_and_k_stays_exact():
             assert 2.0 * c["m"] * c["n"] * c["k"] * c.get("pages", 1) <= 4e9, c["id"]  # a few GFLOP at most
 
 
+@pytest.fixture(scope="module")
+def default_routes(plan):
+    """id -> planned route of every row of every table, at the default knobs (planned once for the module)."""
+    out = {}
+    for bits, tables in ((64, [G.F64_CASES, *G.KNOB_CASES.values()]), (32, [G.F32_CASES, *G.F32_KNOB_CASES.values()])):
+        rows = [c for t in tables for c in t]
+        out.update({(bits, c["id"]): r for c, r in zip(rows, planned(plan, rows, bits=bits))})
+    return out
+
+
 @pytest.mark.parametrize("c", G.F64_CASES, ids=lambda c: c["id"])
-def test_f64_rows_have_the_properties_their_routes_claim(c):
-    assert model(c) == c["route"], (model(c), c["route"])
+def test_f64_rows_have_the_properties_their_routes_claim(default_routes, c):
+    assert default_routes[64, c["id"]] == c["route"], (default_routes[64, c["id"]], c["route"])
 
 
 @pytest.mark.parametrize("knob", sorted(G.KNOB_CASES))
-def test_knob_rows_have_the_properties_their_routes_claim(knob):
-    for c in G.KNOB_CASES[knob]:
-        assert model(c, {knob: "0"}) == c["route"], (c["id"], model(c, {knob: "0"}))
+def test_knob_rows_have_the_properties_their_routes_claim(plan, default_routes, knob):
+    for c, got in zip(G.KNOB_CASES[knob], planned(plan, G.KNOB_CASES[knob], {knob: "0"})):
+        assert got == c["route"], (c["id"], got)
     # and the setting is what selects them: all but the anchor rows of a table route elsewhere by default
-    assert sum(model(c) != c["route"] for c in G.KNOB_CASES[knob]) >= len(G.KNOB_CASES[knob]) - 2
+    assert sum(default_routes[64, c["id"]] != c["route"] for c in G.KNOB_CASES[knob]) >= len(G.KNOB_CASES[knob]) - 2
 
 
 @pytest.mark.parametrize("c", G.F32_CASES, ids=lambda c: c["id"])
-def test_f32_rows_have_the_properties_their_routes_claim(c):
-    assert model(c, bits=32) == c["route"], (model(c, bits=32), c["route"])
+def test_f32_rows_have_the_properties_their_routes_claim(default_routes, c):
+    assert default_routes[32, c["id"]] == c["route"], (default_routes[32, c["id"]], c["route"])
 
 
-def test_f32_knob_rows_have_the_properties_their_routes_claim():
-    for c in G.F32_KNOB_CASES["RMHIP_SGEMM_W8"]:
-        assert model(c, {"RMHIP_SGEMM_W8": "0"}, bits=32) == c["route"], c["id"]
+def test_f32_knob_rows_have_the_properties_their_routes_claim(plan, default_routes):
+    table = G.F32_KNOB_CASES["RMHIP_SGEMM_W8"]
+    for c, got in zip(table, planned(plan, table, {"RMHIP_SGEMM_W8": "0"}, bits=32)):
+        assert got == c["route"], (c["id"], got)
+    assert sum(default_routes[32, c["id"]] != c["route"] for c in table) >= len(table) - 2
+
+
+# ---- the rules only the look-ahead LU reaches (host-only rows: no entry point selects a site, so the GPU suite cannot iterate them) ----
+MAIN = dict(in_lookahead=1)                # the LU's main stream: four-wave blocks that fit beside the update streams'
+UPD = dict(in_lookahead=1, lds_pad=1)      # an update stream: one padded block per CU
+_big = dict(m=2048, n=1152)                # 144 tiles of 128 x 128: past the 128 tiles of the small-update rule
+
+
+def _lu(text, site, m, n, k, update=True, yield_=0, splits=1, k_chunk=None, **opts):
+    c = G.case("blk", m, n, k, text, splits, k_chunk, **(dict(alpha=-1.0, beta=1.0) if update else dict(alpha=1.0, beta=0.0)), **opts)
+    c["route"]["yield"] = yield_
+    return c, site
+
+
+LU_ROWS = [
+    # update stream with a tile counter left: the persistent kernel; without one, or for a ragged shape, the eight-wave tiles
+    _lu("w8p", dict(UPD, counter=1), k=128, **_big), _lu("w8p", dict(UPD, counter=1), k=128, update=False, **_big),
+    _lu("w8 pre", UPD, k=128, **_big), _lu("w8g guard pre", dict(UPD, counter=1), m=2049, n=1153, k=128),
+    # update stream with a yield word: the update C - A B watches it, any other product does not
+    _lu("w8 pre", dict(UPD, yield_word=1), k=128, yield_=1, **_big), _lu("w8", dict(UPD, yield_word=1), k=128, update=False, **_big),
+    _lu("w8p", dict(UPD, yield_word=1, counter=1), k=128, **_big),
+    # update stream, k <= small_upd and at most 128 tiles: the 64 x 64 tiles, before the persistent kernel; the boundaries
+    _lu("small pre", UPD, m=2048, n=1024, k=1024), _lu("small pre", dict(UPD, counter=1), m=2048, n=1024, k=1024),
+    _lu("small guard pre", UPD, m=2047, n=1024, k=1024),
+    _lu("w8 pre", UPD, m=128, n=16512, k=1024),                          # 129 tiles
+    _lu("w8g guard pre", UPD, m=2048, n=1024, k=1025),                   # k = small_upd + 1 (ragged, so the guarded tile)
+    _lu("w8 pre", UPD, m=2048, n=1024, k=1040),
+    _lu("w8 pre", dict(UPD, small_upd=0), m=2048, n=1024, k=1024), _lu("small pre", dict(UPD, small_upd=128), m=2048, n=1024, k=128),
+    _lu("w8 pre", dict(UPD, small_upd=128), m=2048, n=1024, k=144),
+    # main stream inside the look-ahead: four-wave tiles, whole and ragged; split-K only from k = 8192
+    _lu("w4", MAIN, k=128, update=False, **_big), _lu("w4 pre", MAIN, k=128, **_big), _lu("w4 edge", MAIN, m=2049, n=1153, k=128),
+    _lu("w4 pre", dict(MAIN, chain_prio=1), k=128, **_big),
+    _lu("w4", MAIN, m=128, n=128, k=2048, update=False), _lu("w4", MAIN, m=128, n=128, k=8192, update=False, splits=8, k_chunk=1024),
+]
+
+
+def test_the_rules_only_the_lookahead_lu_reaches(plan):
+    got = plan([(c, None, 64, site) for c, site in LU_ROWS])
+    for (c, site), r in zip(LU_ROWS, got):
+        assert reported(r) == c["route"], (c["id"], site, r)
+        assert r["prio"] == site.get("chain_prio", 0) and (r["tiles_m"], r["tiles_n"]) == tuple(
+            -(-x // (SMALL_TILE if r["kernel"] == "small" else TILE)) for x in (c["m"], c["n"])), (c["id"], r)
+    # every instantiation and rule the tables of gemm_ref.py cannot reach is in these rows
+    keys = {(c["route"]["kernel"], c["route"]["pre"], c["route"]["yield"]) for c, _ in LU_ROWS}
+    assert {("w8p", 0, 0), ("w8", 1, 1), ("small", 1, 0), ("w4", 0, 0), ("w4", 1, 0)} <= keys
+
+
+def test_requests_no_kernel_serves_are_refused_by_the_plan(plan):
+    base = dict(entry="blk", m=128, n=128, k=16)
+    got = plan([(dict(base, ta=True, tb=True), None, 64, None), (dict(base, ta=True, epi=1), None, 64, None),
+                (dict(base, tb=True, epi=2), None, 64, None), (dict(base, ta=True, tb=True), None, 32, None)])
+    assert got == [{"unsupported": "dgemm: A' * B' is not instantiated"},
+                   {"unsupported": "dgemm: epilogue with transposed operands is not instantiated"},
+                   {"unsupported": "dgemm: epilogue with transposed operands is not instantiated"},
+                   {"unsupported": "sgemm: A' * B' is not instantiated"}]
 
 
 def test_the_tables_cover_every_instantiation_reachable_from_the_abi():

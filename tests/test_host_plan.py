@@ -1,6 +1,6 @@
 """Host logic that needs no GPU, checked by small C++ programs over sweeps of shapes: the reduction launch geometry and the
-routing of a shape to its kernel and finalize (reduce_plan.h) and the broadcast stride preparation / dimension collapsing of the elementwise entry points
-(host_shape.h), including the in-place addressing of lazy repmat views."""
+routing of a shape to its kernel and finalize (reduce_plan.h), the broadcast stride preparation / dimension collapsing of the elementwise entry points
+(host_shape.h), including the in-place addressing of lazy repmat views, and the GEMM dispatch (gemm_plan.h)."""
 import subprocess
 from pathlib import Path
 
@@ -9,13 +9,34 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 
 
+def compile_check(out_dir, name):
+    """tests/cpp/<name>.cpp against the library's headers, with a plain host compiler and every warning an error."""
+    exe = Path(out_dir) / name
+    c = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", f"-I{ROOT / 'runmat_amd' / 'csrc'}",
+                        str(ROOT / "tests" / "cpp" / f"{name}.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert c.returncode == 0, c.stderr
+    return exe
+
+
 @pytest.mark.parametrize("name,needle", [("reduce_plan_check", "reduce plan ok"), ("reduce_route_check", "reduce route ok"),
                                          ("broadcast_prep_check", "broadcast prep ok"),
                                          ("repmat_view_check", "repmat view ok")])
 def test_host_logic(tmp_path, name, needle):
-    exe = tmp_path / name
-    c = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", f"-I{ROOT / 'runmat_amd' / 'csrc'}",
-                        str(ROOT / "tests" / "cpp" / f"{name}.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    assert c.returncode == 0, c.stderr
+    exe = compile_check(tmp_path, name)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0 and needle in r.stdout, r.stdout + r.stderr
+
+
+def test_gemm_plan_routes_the_sweep_as_the_launchers_ladders_did(tmp_path):
+    """plan_dgemm / plan_sgemm over the fixed sweep of gemm_route_check.cpp (shapes, layouts, operations, every site of the look-ahead
+    LU, three device sizes, each knob off): per group, the case count and the digest of the routes equal what the launchers' former
+    if-ladders gave (tests/golden/gemm_routes.txt, recorded from them).  `gemm_route_check --dump` prints the routes themselves."""
+    exe = compile_check(tmp_path, "gemm_route_check")
+    r = subprocess.run([str(exe), "--sweep"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    want = [ln for ln in (ROOT / "tests" / "golden" / "gemm_routes.txt").read_text().splitlines() if ln and not ln.startswith("#")]
+    got = r.stdout.splitlines()
+    assert len(want) == 108 and len({ln.rsplit(" ", 2)[0] for ln in want}) == 108  # 2 precisions x (13 sites + 5 knobs) x 3 device sizes
+    assert all(int(ln.split()[-2]) == 11 * 11 * 13 * 9 * (7 if ln.startswith("f64") else 3) for ln in want)
+    differing = [(g, w) for g, w in zip(got, want) if g != w]
+    assert len(got) == len(want) and not differing, differing[:5]
