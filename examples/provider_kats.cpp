@@ -181,6 +181,26 @@ int main() {
             }
         }
         {
+            // pagefun's second entry point on a hand-computed Gaussian-integer product: [1+i 2; -i 3+2i] * [1-i; 2+i] = [6+2i; 3+6i], and times
+            // the real column [1; 2] = [5+i; 6+3i]; pagefun itself declines a complex input
+            rmhip::PagefunRequest q;
+            auto za = p.complex_from_real_imag(p.upload({1, 0, 2, 3}, {2, 2}), p.upload({1, -1, 0, 2}, {2, 2}));
+            auto br = p.upload({1, 2}, {2, 1});
+            q.inputs = {za, p.complex_from_real_imag(br, p.upload({-1, 1}, {2, 1}))};
+            q.output_shape = {2, 1};
+            q.input_page_dims = {{}, {}};
+            try {
+                p.pagefun(q);
+                ok = false;
+            } catch (const rmhip::ProviderError& e) {
+                ok = ok && e.code == RMHIP_ERR_UNSUPPORTED;
+            }
+            auto zc = p.complex_pagefun(q);
+            ok = ok && zc.shape == std::vector<size_t>{2, 1} && p.is_complex(zc) && eq(p.download(zc).data, {6, 2, 3, 6});
+            q.inputs[1] = br;
+            ok = ok && eq(p.download(p.complex_pagefun(q)).data, {5, 1, 6, 3});
+        }
+        {
             // moving_window's second entry point: the 101-point median (shrinking at the ends) of the ramp 0 .. 199 with a spike at 100, which
             // moving_window itself declines; against the middle of each sorted window
             std::vector<double> ramp(200);

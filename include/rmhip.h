@@ -630,7 +630,7 @@ RMHIP_API int rmhip_window(rmhip_ctx* ctx, int kind, size_t len, int periodic, r
  * elementwise arithmetic `rmhip_complex_unary` / `rmhip_complex_binary` / `rmhip_complex_scalar` and the shape and indexing hooks
  * `rmhip_complex_reshape` / `_transpose` / `_permute` / `_repmat` / `_gather_linear` / `_scatter_linear` / `_circshift` / `_flip` /
  * `_cat`, and the calculus and filter hooks `rmhip_complex_gradient_dim` / `_trapz_dim` / `_polyint` / `_iir_filter` /
- * `_iir_filter_long` - and by the plumbing (download, shape, storage, isreal, free).  Every other entry point returns RMHIP_ERR_UNSUPPORTED for
+ * `_iir_filter_long`, and the batched page products `rmhip_complex_pagefun` - and by the plumbing (download, shape, storage, isreal, free).  Every other entry point returns RMHIP_ERR_UNSUPPORTED for
  * them (the caller gathers, as for any `Err`): fused elementwise, reductions, matmul, round_digits, pow, the comparisons, tril / triu
  * and read_scalar among them, and so do the real forms of the hooks just named (`rmhip_transpose`, `rmhip_permute`, ...): a caller
  * chooses the entry point by the operand's storage kind.  A precision-32 context rounds the values a complex result COMPUTES through
@@ -1176,12 +1176,27 @@ RMHIP_API int rmhip_eig(rmhip_ctx* ctx, rmhip_buf a, int compute_left, rmhip_buf
  * output_shape ([m, n, page_dims...]); a zero m, n or page extent gives an empty tensor, k == 0 zeros.  At most 2 launches, no
  * device -> host read.  RMHIP_ERR_INVALID: n_inputs != 2, a missing input_page_dims, an output_shape that is not [m, n, page_dims...],
  * an operand whose element count is not rows x cols x its page volume; RMHIP_ERR_SHAPE: inner dimensions or page extents (neither
- * equal nor 1) that disagree; RMHIP_ERR_UNSUPPORTED: complex operands, another op, more than 8 page dimensions that do not collapse.
- * The builtin takes its host path on any error. */
+ * equal nor 1) that disagree; RMHIP_ERR_UNSUPPORTED: a complex-interleaved operand (rmhip_complex_pagefun serves it), another op, more
+ * than 8 page dimensions that do not collapse.  The builtin takes its host path on any error. */
 enum rmhip_pagefun_op { RMHIP_PAGEFUN_MTIMES = 0 };
 /* @serves pagefun */
 RMHIP_API int rmhip_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inputs, const size_t* page_dims, size_t page_rank,
                             const size_t* input_page_dims, const size_t* output_shape, size_t out_rank, rmhip_buf* out);
+/* The same hook when at least one of the two operands is complex-interleaved (the builtin hands complex handles over unchecked,
+ * pagefun.rs:413-448, and its host loop answers with OutputKind::Complex): rmhip_pagefun's arguments, shape rules, page broadcasting and
+ * refusals in its order, extents counted in logical elements; the result is a complex-interleaved tensor of output_shape.  A real
+ * operand may be a transpose or repmat view, a lazy random_normal or f32 storage.  Arithmetic is the host loop's, one of three loops
+ * per page pair (common/linalg.rs:57-147): complex x complex re += ar*br - ai*bi, im += ar*bi + ai*br (the k-term formed first);
+ * complex x real re += ar*br, im += ai*br; real x complex re += ar*br, im += ar*bi - the mixed forms never multiply by an implied zero,
+ * so an Inf in the complex operand stays Inf.  Bit-exact for pages of at most 32 on a side; above, each part within
+ * 2k eps (S(|Ar|,|Br|) + S(|Ai|,|Bi|)) resp. 2k eps (S(|Ar|,|Bi|) + S(|Ai|,|Br|)) of the loop (k eps and the one surviving term for
+ * the mixed forms), S the product of absolute values.  k == 0 gives (+0, +0), a zero m, n or page extent an empty complex tensor.  A
+ * precision-32 context rounds each part through f32 once, on the final store.  At most 2 launches, no device -> host read, no
+ * synchronisation.  RMHIP_ERR_UNSUPPORTED also when both operands are real (rmhip_pagefun serves them).  A refused call leaves no
+ * buffer behind; inputs are never written. */
+/* @serves pagefun */
+RMHIP_API int rmhip_complex_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inputs, const size_t* page_dims, size_t page_rank,
+                                    const size_t* input_page_dims, const size_t* output_shape, size_t out_rank, rmhip_buf* out);
 /* `inv(matrix, options)` (lib.rs:2430-2436, ProviderInvOptions {} :716; CPU inv.rs:209-230, 258-280: nalgebra 0.32.6 `try_inverse`, an LU
  * with partial pivoting and substitutions on the identity - absent from /root/reference, parity by residual as for mldivide): X = A \ I on
  * the LU path.  Scalars, [n, n] and [n, n, 1, ...] operands (the shape is kept); a non-square or higher-rank operand is

@@ -706,8 +706,12 @@ public:
         out.perm_vector = with_shape(ids[3]);
         return out;
     }
-    // lib.rs:2386: batched page products (Mtimes); throws for what the host loop must answer (malformed request, complex input)
-    GpuTensorHandle pagefun(const PagefunRequest& request) const {
+    // lib.rs:2386: batched page products (Mtimes); throws for what the host loop must answer (malformed request) and for a complex
+    // input, which complex_pagefun serves
+    GpuTensorHandle pagefun(const PagefunRequest& request) const { return pagefun_entry(rmhip_pagefun, request); }
+    // the same request with at least one complex-interleaved input (the other may be real) -> a complex tensor; two real inputs throw
+    GpuTensorHandle complex_pagefun(const PagefunRequest& request) const { return pagefun_entry(rmhip_complex_pagefun, request); }
+    GpuTensorHandle pagefun_entry(decltype(&rmhip_pagefun) entry, const PagefunRequest& request) const {
         const size_t rank = request.page_dims.size();
         if (request.input_page_dims.size() != request.inputs.size())
             throw std::runtime_error("pagefun: input_page_dims must hold one row per input");
@@ -719,8 +723,8 @@ public:
             ipd.insert(ipd.end(), request.input_page_dims[i].begin(), request.input_page_dims[i].end());
         }
         uint64_t out = 0;
-        check(rmhip_pagefun(ctx_, RMHIP_PAGEFUN_MTIMES, ids.data(), ids.size(), request.page_dims.data(), rank, ipd.data(),
-                            request.output_shape.data(), request.output_shape.size(), &out));
+        check(entry(ctx_, RMHIP_PAGEFUN_MTIMES, ids.data(), ids.size(), request.page_dims.data(), rank, ipd.data(),
+                    request.output_shape.data(), request.output_shape.size(), &out));
         return with_shape(out);
     }
     // lib.rs:2491-2497: real, bitwise symmetric matrices of order <= 4096 - eigenvalues ascending, orthonormal right vectors, `left` a copy

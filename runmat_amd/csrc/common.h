@@ -441,6 +441,12 @@ int launch_pagefun_mfma(Context* c, const double* A, const double* B, double* C,
                         unsigned long long pages, const PageMap& pm);
 int launch_pgemm_w8(Context* c, const double* A, const double* B, double* C, unsigned m, unsigned n, unsigned k,
                     unsigned long long pages, const PageMap& pm);
+// the same products with an interleaved operand (complex_pagefun.hip): kind 0 complex x complex, 1 complex x real, 2 real x complex;
+// C is interleaved, an interleaved operand's PageMap offsets are doubled inside the kernels
+int launch_cpage_small(Context* c, int kind, const double* A, const double* B, double* C, unsigned m, unsigned n, unsigned k,
+                       unsigned long long pages, const PageMap& pm, bool a_dense, bool b_dense, unsigned* pages_per_block);
+int launch_cpage_mfma(Context* c, int kind, const double* A, const double* B, double* C, unsigned m, unsigned n, unsigned k,
+                      unsigned long long pages, const PageMap& pm);
 
 // rng (rng.hip)
 int launch_rng_uniform(Context* c, uint64_t state, double* out, size_t n);

@@ -1565,32 +1565,45 @@ int rmhip_stochastic_evolution_sharded(rmhip_ctx* ctx, rmhip_buf state, double d
     return rc;
 }
 
-// pagefun(@mtimes) (include/rmhip.h; kernels pagefun.hip and dgemm.hip k_pgemm_w8).  Validation restates
-// build_pagefun_request (pagefun.rs:450-530) so that a malformed request never reaches a kernel; the tier is chosen here from
-// (m, n, k, page count, broadcast pattern) and recorded as record_launch("pagefun", {m, n, k, pages}, {tier, ...}).
-int rmhip_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inputs, const size_t* page_dims, size_t page_rank,
-                  const size_t* input_page_dims, const size_t* output_shape, size_t out_rank, rmhip_buf* out) {
-    CTX_OR_FAIL(ctx);
-    if (!out) return fail(RMHIP_ERR_INVALID, "pagefun: null out");
-    *out = 0;
-    if (op != RMHIP_PAGEFUN_MTIMES) return fail(RMHIP_ERR_UNSUPPORTED, "pagefun: unknown op %d", op);
-    if (n_inputs != 2 || !inputs) return fail(RMHIP_ERR_INVALID, "pagefun: @mtimes takes exactly two inputs (got %zu)", n_inputs);
-    if (page_rank && (!page_dims || !input_page_dims)) return fail(RMHIP_ERR_INVALID, "pagefun: page dimensions missing");
-    if (!output_shape && out_rank) return fail(RMHIP_ERR_INVALID, "pagefun: null output shape");
-    Buffer raw[2];
-    size_t rows[2], cols[2], vol[2] = {1, 1};
+}  // extern "C"
+
+// pagefun(@mtimes) (include/rmhip.h; kernels pagefun.hip, complex_pagefun.hip and dgemm.hip k_pgemm_w8).
+namespace {
+
+// What rmhip_pagefun and rmhip_complex_pagefun share: the request's validation, which restates build_pagefun_request
+// (pagefun.rs:450-530) so that a malformed request never reaches a kernel, and the PageMap.  `who` heads the messages; `cplx_entry`:
+// the call came through rmhip_complex_pagefun, which takes interleaved operands (extents count logical elements) and refuses a pair of
+// real ones; the real entry point refuses an interleaved operand where it meets it.
+struct PagefunPlan {
+    Buffer raw[2];  // the table entries as they are (storage kind, shape): operands are settled by the caller
+    size_t m = 0, n = 0, k = 0, pages = 1, vol[2] = {1, 1};
+    PageMap pm{};
+    bool dense[2] = {false, false};  // not broadcast: the operand's page of output page p is page p
+};
+
+int pagefun_plan(Context* c, const char* who, bool cplx_entry, int op, const rmhip_buf* inputs, size_t n_inputs, const size_t* page_dims,
+                 size_t page_rank, const size_t* input_page_dims, const size_t* output_shape, size_t out_rank, PagefunPlan* plan) {
+    if (op != RMHIP_PAGEFUN_MTIMES) return fail(RMHIP_ERR_UNSUPPORTED, "%s: unknown op %d", who, op);
+    if (n_inputs != 2 || !inputs) return fail(RMHIP_ERR_INVALID, "%s: @mtimes takes exactly two inputs (got %zu)", who, n_inputs);
+    if (page_rank && (!page_dims || !input_page_dims)) return fail(RMHIP_ERR_INVALID, "%s: page dimensions missing", who);
+    if (!output_shape && out_rank) return fail(RMHIP_ERR_INVALID, "%s: null output shape", who);
+    Buffer* const raw = plan->raw;
+    size_t rows[2], cols[2];
+    size_t* const vol = plan->vol;
     for (int i = 0; i < 2; ++i) {
         RMHIP_TRY(c->lookup(inputs[i], &raw[i]));
-        if (raw[i].cplx) return fail(RMHIP_ERR_UNSUPPORTED, "pagefun: complex input; the host path answers");
+        if (raw[i].cplx && !cplx_entry) return fail(RMHIP_ERR_UNSUPPORTED, "%s: complex input; the host path answers", who);
         const std::vector<size_t>& s = raw[i].shape;  // canonical_matrix_shape (pagefun.rs:899-911)
         rows[i] = s.empty() ? 1 : (s.size() == 1 ? 1 : s[0]);
         cols[i] = s.empty() ? 1 : (s.size() == 1 ? s[0] : s[1]);
         for (size_t d = 0; d < page_rank; ++d) vol[i] *= input_page_dims[i * page_rank + d];
         if (raw[i].numel != rows[i] * cols[i] * vol[i])
-            return fail(RMHIP_ERR_INVALID, "pagefun: input %d holds %zu elements, not %zu x %zu x %zu", i, raw[i].numel, rows[i], cols[i], vol[i]);
+            return fail(RMHIP_ERR_INVALID, "%s: input %d holds %zu elements, not %zu x %zu x %zu", who, i, raw[i].numel, rows[i], cols[i], vol[i]);
     }
+    if (cplx_entry && !raw[0].cplx && !raw[1].cplx)
+        return fail(RMHIP_ERR_UNSUPPORTED, "%s: both operands are real (rmhip_pagefun serves them)", who);
     const size_t m = rows[0], k = cols[0], n = cols[1];
-    if (k != rows[1]) return fail(RMHIP_ERR_SHAPE, "pagefun: inner matrix dimensions must agree (%zux%zu * %zux%zu)", m, k, rows[1], n);
+    if (k != rows[1]) return fail(RMHIP_ERR_SHAPE, "%s: inner matrix dimensions must agree (%zux%zu * %zux%zu)", who, m, k, rows[1], n);
     size_t pages = 1;
     for (size_t d = 0; d < page_rank; ++d) {
         const size_t ea = input_page_dims[d], eb = input_page_dims[page_rank + d];
@@ -1598,19 +1611,18 @@ int rmhip_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inpu
         if (ea == 0 || eb == 0) want = 0;
         else if (ea == 1 || ea == eb) want = eb;
         else if (eb == 1) want = ea;
-        else return fail(RMHIP_ERR_SHAPE, "pagefun: page dimension %zu mismatch (%zu vs %zu)", d + 3, ea, eb);
-        if (page_dims[d] != want) return fail(RMHIP_ERR_INVALID, "pagefun: page_dims[%zu] = %zu, the inputs give %zu", d, page_dims[d], want);
+        else return fail(RMHIP_ERR_SHAPE, "%s: page dimension %zu mismatch (%zu vs %zu)", who, d + 3, ea, eb);
+        if (page_dims[d] != want) return fail(RMHIP_ERR_INVALID, "%s: page_dims[%zu] = %zu, the inputs give %zu", who, d, page_dims[d], want);
         pages *= want;
     }
     if (out_rank != page_rank + 2 || output_shape[0] != m || output_shape[1] != n)
-        return fail(RMHIP_ERR_INVALID, "pagefun: output shape must be [m, n, page_dims...]");
+        return fail(RMHIP_ERR_INVALID, "%s: output shape must be [m, n, page_dims...]", who);
     for (size_t d = 0; d < page_rank; ++d)
-        if (output_shape[2 + d] != page_dims[d]) return fail(RMHIP_ERR_INVALID, "pagefun: output shape must be [m, n, page_dims...]");
+        if (output_shape[2 + d] != page_dims[d]) return fail(RMHIP_ERR_INVALID, "%s: output shape must be [m, n, page_dims...]", who);
     if (m > 0xffffffffULL || n > 0xffffffffULL || k > 0xffffffffULL)
-        return fail(RMHIP_ERR_UNSUPPORTED, "pagefun: a page side exceeds 2^32");
+        return fail(RMHIP_ERR_UNSUPPORTED, "%s: a page side exceeds 2^32", who);
     // page strides in elements (0 along a broadcast dimension); dimensions of extent 1 dropped, neighbours whose strides continue each
     // other merged (a dense operand collapses to one dimension)
-    PageMap pm{};
     std::vector<unsigned long long> dims, sa, sb;
     unsigned long long cur[2] = {(unsigned long long)m * k, (unsigned long long)k * n};
     for (size_t d = 0; d < page_rank; ++d) {
@@ -1628,14 +1640,36 @@ int rmhip_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inpu
         sb.push_back(s1);
     }
     if (m != 0 && n != 0 && pages != 0 && dims.size() > (size_t)kPageRankMax)
-        return fail(RMHIP_ERR_UNSUPPORTED, "pagefun: %zu page dimensions after collapsing (at most %d)", dims.size(), kPageRankMax);
+        return fail(RMHIP_ERR_UNSUPPORTED, "%s: %zu page dimensions after collapsing (at most %d)", who, dims.size(), kPageRankMax);
+    PageMap& pm = plan->pm;
     pm.rank = (int)dims.size();
     for (size_t d = 0; d < dims.size() && d < (size_t)kPageRankMax; ++d) {
         pm.dims[d] = dims[d];
         pm.sa[d] = sa[d];
         pm.sb[d] = sb[d];
     }
-    const bool dense[2] = {vol[0] == pages, vol[1] == pages};  // not broadcast: the operand's page of output page p is page p
+    plan->m = m, plan->n = n, plan->k = k, plan->pages = pages;
+    plan->dense[0] = vol[0] == pages, plan->dense[1] = vol[1] == pages;
+    return RMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The tier is chosen here from (m, n, k, page count, broadcast pattern) and recorded as record_launch("pagefun", {m, n, k, pages},
+// {tier, ...}).
+int rmhip_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inputs, const size_t* page_dims, size_t page_rank,
+                  const size_t* input_page_dims, const size_t* output_shape, size_t out_rank, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "pagefun: null out");
+    *out = 0;
+    PagefunPlan pl;
+    RMHIP_TRY(pagefun_plan(c, "pagefun", false, op, inputs, n_inputs, page_dims, page_rank, input_page_dims, output_shape, out_rank, &pl));
+    const size_t m = pl.m, n = pl.n, k = pl.k, pages = pl.pages;
+    const size_t* const vol = pl.vol;
+    const bool* const dense = pl.dense;
+    const PageMap& pm = pl.pm;
     Buffer ob;
     RMHIP_TRY(c->new_buffer(output_shape, out_rank, out, &ob));
     if (ob.numel == 0) return RMHIP_OK;
@@ -1668,6 +1702,47 @@ int rmhip_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inpu
     }
     c->record_launch("pagefun", {{"m", m}, {"n", n}, {"k", k}, {"pages", pages}},
                      {{"tier", (uint64_t)tier}, {"page_rank", (uint64_t)pm.rank}, {"pages_per_block", tuning}});
+    return RMHIP_OK;
+}
+
+
+// The complex sibling: at least one operand interleaved, the result interleaved.  A real operand is settled to plain f64 (views, lazy
+// normals, f32 storage); record_launch("complex_pagefun", {m, n, k, pages}, {tier, kind, page_rank, pages_per_block}).
+int rmhip_complex_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_t n_inputs, const size_t* page_dims, size_t page_rank,
+                          const size_t* input_page_dims, const size_t* output_shape, size_t out_rank, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "complex_pagefun: null out");
+    *out = 0;
+    PagefunPlan pl;
+    RMHIP_TRY(pagefun_plan(c, "complex_pagefun", true, op, inputs, n_inputs, page_dims, page_rank, input_page_dims, output_shape, out_rank, &pl));
+    const size_t m = pl.m, n = pl.n, k = pl.k, pages = pl.pages;
+    const int kind = pl.raw[0].cplx && pl.raw[1].cplx ? 0 : (pl.raw[0].cplx ? 1 : 2);
+    Buffer ob;
+    RMHIP_TRY(c->new_buffer_complex(output_shape, out_rank, out, &ob));
+    if (ob.numel == 0) return RMHIP_OK;
+    Buffer ab, bb;
+    int rc = c->get_any(inputs[0], &ab);
+    if (!rc) rc = c->get_any(inputs[1], &bb);
+    int tier = 0;
+    unsigned tuning = 0;
+    if (rc) {
+    } else if (k == 0) {
+        rc = launch_fill(c, ob.data(), 2 * ob.numel, 0.0);  // the three loops' empty sums: (+0, +0)
+    } else if (m <= 32 && n <= 32 && k <= 32) {
+        tier = 2;
+        rc = launch_cpage_small(c, kind, ab.data(), bb.data(), ob.data(), (unsigned)m, (unsigned)n, (unsigned)k, pages, pl.pm, pl.dense[0], pl.dense[1],
+                                &tuning);
+    } else {
+        tier = 3;
+        rc = launch_cpage_mfma(c, kind, ab.data(), bb.data(), ob.data(), (unsigned)m, (unsigned)n, (unsigned)k, pages, pl.pm);
+    }
+    if (rc) {
+        rmhip_free(ctx, *out);
+        *out = 0;
+        return rc;
+    }
+    c->record_launch("complex_pagefun", {{"m", m}, {"n", n}, {"k", k}, {"pages", pages}},
+                     {{"tier", (uint64_t)tier}, {"kind", (uint64_t)kind}, {"page_rank", (uint64_t)pl.pm.rank}, {"pages_per_block", tuning}});
     return RMHIP_OK;
 }
 

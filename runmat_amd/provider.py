@@ -962,10 +962,10 @@ class HipProvider:
             return None
         return ProviderQrPowerIterResult(*[self._handle(outs[i]) for i in range(4)])
 
-    def pagefun(self, request: PagefunRequest) -> GpuTensorHandle:
+    def pagefun(self, request: PagefunRequest, entry: str = "rmhip_pagefun") -> GpuTensorHandle:
         """`pagefun(request)` (lib.rs:2386): for `PagefunOp.Mtimes` every output page is the product of the inputs' pages, an input of
         page extent 1 broadcasting along that dimension; the host loop's arithmetic (pagefun.rs:330-384 over matmul_real).  Malformed
-        requests raise INVALID / SHAPE, complex inputs UNSUPPORTED, and the builtin takes its host path."""
+        requests raise INVALID / SHAPE, complex inputs UNSUPPORTED (`complex_pagefun` serves them), and the builtin takes its host path."""
         if request.op != PagefunOp.Mtimes:
             raise ProviderError(_lib.ERR_UNSUPPORTED, f"pagefun: unsupported op {request.op!r}")
         rank = len(request.page_dims)
@@ -977,9 +977,15 @@ class HipProvider:
         osh = (C.c_size_t * max(len(request.output_shape), 1))(*[int(d) for d in request.output_shape])
         out = C.c_uint64()
         op = _lib.ENUMS["rmhip_pagefun_op"]["RMHIP_PAGEFUN_MTIMES"]
-        self._check(self._lib.rmhip_pagefun(self._ctx, op, ids, len(request.inputs), pd, rank, ipd, osh, len(request.output_shape),
-                                            C.byref(out)))
+        self._check(getattr(self._lib, entry)(self._ctx, op, ids, len(request.inputs), pd, rank, ipd, osh, len(request.output_shape),
+                                              C.byref(out)))
         return self._handle(out.value, request.output_shape)
+
+    def complex_pagefun(self, request: PagefunRequest) -> GpuTensorHandle:
+        """`pagefun(request)` with at least one complex-interleaved input (the other may be real) -> complex tensor of `output_shape`: the
+        request, the shape rules and the refusals of `pagefun`; the host loop's arithmetic over matmul_complex / matmul_complex_real /
+        matmul_real_complex (common/linalg.rs:57-147).  Two real inputs raise UNSUPPORTED (`pagefun` serves them)."""
+        return self.pagefun(request, entry="rmhip_complex_pagefun")
 
     def eig(self, a: GpuTensorHandle, compute_left: bool = False) -> ProviderEigResult:
         """`eig(a, compute_left)` (lib.rs:2491-2497) for real, bitwise symmetric matrices of order <= 4096: eigenvalues [n, 1] ascending,

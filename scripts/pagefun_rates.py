@@ -1,5 +1,6 @@
-"""Developer tool (GPU box): device pagefun(@mtimes) per tier against the per-page matmul loop, the host builtin's numpy restatement and torch.matmul - ms per call, launches, share of the tier's roofline.  Usage: pagefun_rates.py [--quick] [--torch]
-(--torch adds the vendor ceiling; leave it out under a kernel tracer)
+"""Developer tool (GPU box): device pagefun(@mtimes) per tier against the per-page matmul loop, the host builtin's numpy restatement and torch.matmul - ms per call, launches, share of the tier's roofline.  Usage: pagefun_rates.py [--quick] [--torch] | --complex
+(--torch adds the vendor ceiling; leave it out under a kernel tracer; --complex times rmhip_complex_pagefun per operand kind beside the real
+sibling at the same shapes and nothing else)
 
 Roofline: bytes = 8 (pages_A m k + pages_B k n + P m n), flops = 2 m n k P; the least time is the larger of bytes / 8.0 TB/s (HBM) and
 flops / 78.6 TFLOP/s (fp64 MFMA dense peak, MI355X_MICROARCH); the tiny tier's VALU bound (about 39e12 f64 lane ops/s, 2 per
@@ -44,7 +45,51 @@ def device_ms(prov, fn, reps):
     return prov.timer_end() / reps
 
 
+def complex_rates(prov):
+    """--complex: rmhip_complex_pagefun per operand kind beside the real sibling at the same shape.  A complex x complex product moves
+    2x the bytes (16 per element) and does 4x the real multiply-adds (8 m n k P flops); a mixed product moves (A or B doubled, C doubled)
+    and does 2x.  `x_real` is the ratio of the times."""
+    def operand(shape, cplx):
+        hr = prov.random_uniform(shape)
+        if not cplx:
+            return hr
+        hi = prov.random_uniform(shape)
+        z = prov.complex_from_real_imag(hr, hi)
+        prov.free(hr)
+        prov.free(hi)
+        return z
+
+    for m, k, n, P in [(4, 4, 4, 100000), (8, 8, 8, 100000), (16, 16, 16, 100000), (32, 32, 32, 20000), (40, 40, 40, 2000), (128, 128, 128, 200),
+                       (512, 512, 512, 16)]:
+        r = build_request([m, k, P], [k, n, P])
+        reps = 10
+        ha, hb = operand([m, k, P], False), operand([k, n, P], False)
+        req = PagefunRequest(PagefunOp.Mtimes, [ha, hb], r.output_shape, r.page_dims, r.input_page_dims)
+        real_ms = device_ms(prov, lambda: prov.free(prov.pagefun(req)), reps)
+        rec = {"shape": [m, k, n], "pages": P, "real_tier": tier_of(prov), "real_ms": round(real_ms, 4)}
+        prov.free(ha)
+        prov.free(hb)
+        for kind, name in ((0, "cc"), (1, "cr"), (2, "rc")):
+            ea, eb = (1 if kind == 2 else 2), (1 if kind == 1 else 2)
+            ha, hb = operand([m, k, P], ea == 2), operand([k, n, P], eb == 2)
+            req = PagefunRequest(PagefunOp.Mtimes, [ha, hb], r.output_shape, r.page_dims, r.input_page_dims)
+            ms = device_ms(prov, lambda: prov.free(prov.complex_pagefun(req)), reps)
+            log = [e for e in prov.telemetry_snapshot()["kernel_launches_log"] if e["kernel"] == "complex_pagefun"][-1]
+            nbytes = 8.0 * P * (ea * m * k + eb * k * n + 2 * m * n)
+            flops = (8.0 if kind == 0 else 4.0) * m * n * k * P
+            rec[name] = {"tier": log["tuning"]["tier"], "pages_per_block": log["tuning"]["pages_per_block"], "ms": round(ms, 4),
+                         "x_real": round(ms / real_ms, 2), "hbm_TBs": round(nbytes / ms / 1e9, 3), "TFLOPs": round(flops / ms / 1e9, 2),
+                         "roofline_frac": round(max(nbytes / HBM, flops / MFMA) * 1e3 / ms, 3)}
+            prov.free(ha)
+            prov.free(hb)
+        print(json.dumps(rec), flush=True)
+
+
 prov = HipProvider(0)
+if "--complex" in sys.argv:
+    complex_rates(prov)
+    prov.close()
+    sys.exit(0)
 for m, k, n, P, lhs_pages in SHAPES:
     pa = P if lhs_pages is None else lhs_pages
     ha = prov.random_uniform([m, k, pa])

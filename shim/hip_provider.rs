@@ -699,8 +699,9 @@ impl AccelProvider for HipProvider {
     }
     // The library keeps the transpose lazily (a view consumed in place by matmul / syrk); nothing to record on
     // the Rust side, so `handle_transpose_info` stays empty for these handles and callers treat them as plain.
-    // pagefun(@mtimes): batched page products on the device (rmhip_pagefun); Err (malformed request, complex input) -> the builtin's
-    // host loop, pagefun.rs:413-448.  `input_page_dims` goes over row by row (n_inputs x page_rank).
+    // pagefun(@mtimes): batched page products on the device, the entry point chosen by the inputs' storage - rmhip_pagefun for real
+    // pages, rmhip_complex_pagefun when either input is complex-interleaved (the result then is too); Err (malformed request) -> the
+    // builtin's host loop, pagefun.rs:413-448.  `input_page_dims` goes over row by row (n_inputs x page_rank).
     fn pagefun(&self, request: &PagefunRequest) -> Result<GpuTensorHandle> {
         let op = match request.op {
             PagefunOp::Mtimes => RMHIP_PAGEFUN_MTIMES,
@@ -712,11 +713,19 @@ impl AccelProvider for HipProvider {
         let ids = request.inputs.iter().map(|h| self.own(h)).collect::<Result<Vec<u64>>>()?;
         let ipd: Vec<usize> = request.input_page_dims.iter().flatten().copied().collect();
         let mut out = 0u64;
-        check(unsafe {
-            rmhip_pagefun(self.ctx, op, ids.as_ptr(), ids.len(), request.page_dims.as_ptr(), rank, ipd.as_ptr(),
-                request.output_shape.as_ptr(), request.output_shape.len(), &mut out)
-        })?;
-        self.handle(out)
+        if !request.inputs.iter().any(Self::is_complex) {
+            check(unsafe {
+                rmhip_pagefun(self.ctx, op, ids.as_ptr(), ids.len(), request.page_dims.as_ptr(), rank, ipd.as_ptr(),
+                    request.output_shape.as_ptr(), request.output_shape.len(), &mut out)
+            })?;
+            self.handle(out)
+        } else {
+            check(unsafe {
+                rmhip_complex_pagefun(self.ctx, op, ids.as_ptr(), ids.len(), request.page_dims.as_ptr(), rank, ipd.as_ptr(),
+                    request.output_shape.as_ptr(), request.output_shape.len(), &mut out)
+            })?;
+            self.complex_handle(out)
+        }
     }
     fn transpose(&self, a: &GpuTensorHandle) -> Result<GpuTensorHandle> {
         let mut out = 0u64;
