@@ -21,6 +21,7 @@
 
 #include "../../include/rmhip.h"
 #include "gemm_plan.h"
+#include "lu_plan.h"
 
 namespace rmhip {
 
@@ -524,35 +525,9 @@ int lu_substitute_device(Context* c, const double* LU, size_t n, size_t lda, dou
 size_t lu_padded_ld(size_t rows);
 int lu_copy_and_factor(Context* c, const double* src, size_t rows, size_t cols, double* work, size_t ldw, int* perm, int* info,
                        bool solve_path = false, size_t pad_n = 0);
-// The RMHIP_LU_* environment knobs (docs/KNOBS.md), each read by one of the two functions below (lu.hip) and nowhere else.
-struct LuKnobs {  // read on every call: tests flip these inside one process
-    bool fast = true;             // RMHIP_LU_FAST=0: the grid-wide pivot rule on the solve path too
-    double tau = 8.0;             // RMHIP_LU_TAU: the solve path's multiplier bound
-    bool pad = true;              // RMHIP_LU_PAD=0: the solves factor at the order they were given
-    int lookahead = -1;           // RMHIP_LU_LOOKAHEAD: 1 forces the look-ahead driver, 0 disables it, -1 (unset) by order
-    long nb = -1;                 // RMHIP_LU_NB: panel width of the one-level look-ahead driver (-1: by order)
-    bool panel_columns = false;   // RMHIP_LU_PANEL=columns: the one-launch-per-column panels
-    bool panel_debug = false;     // RMHIP_LU_PANEL_DEBUG=1: phase ticks of the panel kernels on stderr
-    bool subst_pair = false;      // RMHIP_LU_SUBST=pair: launch-per-block substitution instead of k_subst_chain
-    bool verbose = false;         // RMHIP_LU_VERBOSE
-    bool timeline = false;        // RMHIP_LU_TIMELINE
-    bool test_retry = false;      // RMHIP_LU_TEST_RETRY (test hook)
-    bool test_growth = false;     // RMHIP_LU_TEST_GROWTH (test hook)
-    bool test_subst_retry = false;  // RMHIP_LU_TEST_SUBST_RETRY (test hook)
-};
+// The RMHIP_LU_* environment knobs (docs/KNOBS.md; the structs are in lu_plan.h), each read by one of the two functions below (lu.hip) and
+// nowhere else.
 LuKnobs lu_knobs();
-struct LuProcessKnobs {  // read once per process: tests set these in a fresh subprocess
-    bool super = true;            // RMHIP_LU_SUPER=0: the one-level driver on the solve path
-    std::vector<std::pair<size_t, size_t>> super_seq;  // RMHIP_LU_SUPER_SEQ: super-panel plan (W, nb) (empty: by order)
-    std::pair<size_t, size_t> super_late{128, 128};    // RMHIP_LU_SUPER_LATE
-    long super_rows = -1;         // RMHIP_LU_SUPER_ROWS (-1: by order)
-    int iprep = -1;               // RMHIP_LU_IPREP (-1: by order)
-    bool iprep_split = true;      // RMHIP_LU_IPREP_SPLIT
-    long small_upd = 1024;        // RMHIP_LU_SMALL_UPD (dgemm.hip)
-    bool rb_mfma = true;          // RMHIP_LU_RB_MFMA
-    bool trsm_mfma = true;        // RMHIP_LU_TRSM_MFMA
-    int skip = 0;                 // RMHIP_LU_SKIP: phase bit mask (results are garbage)
-};
 const LuProcessKnobs& lu_process_knobs();
 
 // svdsolve.hip: minimum-norm least squares by a one-sided Jacobi SVD with the reference's tolerance rule (mldivide.rs:380-404) - what the

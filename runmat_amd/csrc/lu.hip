@@ -38,9 +38,9 @@ __device__ __forceinline__ unsigned cu_key() {
 __device__ __forceinline__ void chain_prio() { __builtin_amdgcn_s_setprio(3); }
 
 
+using namespace lu_plan;  // the geometry constants the rules and the kernels share (BASE_W, TRSM_W, P2_ROWS, ...: lu_plan.h)
+
 static constexpr double LU_EPS = 1.0e-12;  // host_lu.rs:3
-static constexpr int BASE_W = 64;          // base panel width (columns factored one launch each)
-static constexpr int TRSM_W = 128;         // base triangular solve size (one fused launch)
 
 struct LuState {
     Context* c;
@@ -61,13 +61,12 @@ struct LuState {
     unsigned long long* xrec;   // device [2][PK_MAXB][2]: candidate records (16-byte granules, see k_lu_panel2)
     unsigned long long* xvals;  // device [2][PK_MAXB][BASE_W][2]: candidate rows' panel values (tagged half words)
     unsigned xbase;       // host: panel columns factored so far (exchange step counter)
-    bool persistent;      // use k_lu_panel2 for base panels
     unsigned long long* xdbg;  // device [16] phase ticks (RMHIP_LU_PANEL_DEBUG=1) or nullptr
     long panel_pad_kb = -1;    // extra LDS a panel block asks for (-1: the default, see getrf_rec)
     int* panel_xcc = nullptr;  // device word: the XCD of the last one-XCD panel (-1 otherwise)
     // solve path (k_rp_top + k_rp_below): pivoting restricted to the panel's top block, multipliers checked against tau
-    bool fast = false;
-    double tau = 8.0;
+    LuRoute route;                        // plan_lu_factor's answer: driver, panel family (persistent / fast), tau
+    LuSite site;                          // what plan_base_panel / plan_blocked look at of the context
     double* ucomp = nullptr;              // device [BASE_W][BASE_W]: the pivot rows of the panel in flight
     unsigned long long* growth = nullptr; // device: bits of the largest multiplier below the top block so far
     bool screened = false;                // the first panel's multipliers were checked on the host (early way out)
@@ -91,11 +90,6 @@ static hipEvent_t lu_new_event(LuState& s) {
     return c->lu_events[s.ev_used++];
 }
 
-static constexpr int MAX_PANEL_BLOCKS = 1024;  // 64 rows per block => up to 65536 rows per panel
-static constexpr int PANEL_JT = 8;            // panel columns per thread (unrolled batch; keep the code small)
-static constexpr int PANEL_GROUPS = BASE_W / PANEL_JT;
-static constexpr int PANEL_ROWS = 64;          // rows per block (32 was measured slower: 278 vs 246 ms at n = 16384)
-static constexpr int PANEL_THREADS = PANEL_ROWS * PANEL_GROUPS;
 
 // ---- base panel: ONE launch per column, lazy pivoting ----------------------------------------------
 // Inside a base panel rows are NOT moved: a pivot row simply retires where it lies, and the position
@@ -270,7 +264,6 @@ __global__ void __launch_bounds__(PANEL_THREADS) k_lu_col(double* __restrict__ A
 //   * spins are bounded: if the blocks are not co-resident (device shared with another context) the
 //     kernel sets *xerr and the factorisation fails loudly instead of hanging.
 // Pivot rule, tie-break, singular cut-off and the lazy-pivoting bookkeeping are those of k_lu_col.
-static constexpr int PK_MAXB = 256;              // at most one block per CU
 static constexpr int PK_SPIN_LIMIT = 400000;
 typedef unsigned long long pk_u64;
 
@@ -413,12 +406,6 @@ __device__ __forceinline__ int quad_argmax_f64(double key, unsigned pos, double*
 //     final positions itself: the block then needed a whole CU and had to wait for one to drain under look-ahead; with
 //     18.5 KiB it starts beside the update stream's dgemm block.
 // Pivot rule, tie-break, cut-off, lazy bookkeeping and the arithmetic (division, unfused multiply-subtract) are unchanged.
-static constexpr int P2_ROWS = 256;
-static constexpr int P2_THREADS = P2_ROWS;
-static constexpr int P2_WAVES = P2_THREADS / 64;
-static constexpr int P2_ONEHOP_MAXB = 32;
-static constexpr int P2_RB = BASE_W + 16;  // row stride of the wave candidate buffer (the dump runs in groups of 16 slots and may overshoot by 12)
-static constexpr size_t P2_LDS_DOUBLES = (size_t)P2_ONEHOP_MAXB * BASE_W + (size_t)P2_WAVES * P2_RB;  // 18.5 KiB
 typedef unsigned int pk_v4u __attribute__((ext_vector_type(4)));
 
 struct P2Args {
@@ -857,7 +844,6 @@ __global__ void __launch_bounds__(P2_THREADS) k_lu_panel2(const P2Args g) {
 // the eight pivots at once - eight chained FMAs per element with the operands fetched from LDS in bulk, instead of 64 sweeps that
 // each wait for their own operands.  The loop over micro-panels is rolled and the window shifts by eight (static register
 // indices; straight-line code for 64 steps would be executed once per launch from cold instruction caches).
-static constexpr int RT_ROWS = 256;  // rows of the top block = threads of k_rp_top
 static constexpr int RT_VS = 10;     // doubles per 8-value LDS record: 80 bytes put the 16-byte accesses of consecutive records on distinct banks
 static constexpr int RT_TRAIL = BASE_W - 8;
 
@@ -1180,7 +1166,6 @@ __global__ void __launch_bounds__(RT_ROWS) k_rp_top(const RtArgs g, pk_u64* dbg)
 // (k = 4 s + lq at step s = r): no shuffles, no LDS round trip, the A operands (inverses and negated U blocks, row-major [k][i]) come
 // from LDS with conflict-free 64-lane reads.  Rounding differs from the substitution's (products with an inverted block: error
 // ~ cond(U_bb) eps per block instead of eps per step); the multiplier bound is checked exactly as before.
-static constexpr int RBM_JT = 2;  // 16-row tiles per wave (32 rows: 64 accumulator registers - the wave must fit beside an update block's two waves per SIMD)
 __global__ void __launch_bounds__(64) k_rp_below_mfma(double* __restrict__ A, const size_t lda, const size_t rows, const size_t r0, const int j0,
                                                       const double* __restrict__ ut, pk_u64* __restrict__ growth) {
     typedef double v4d __attribute__((ext_vector_type(4)));
@@ -1255,7 +1240,6 @@ __global__ void __launch_bounds__(64) k_rp_below_mfma(double* __restrict__ A, co
 // Rows below the top block: l = a U11^-1, one thread per row, U (transposed, as k_rp_top left it) staged in LDS.  One wave per
 // workgroup: every FMA takes an 8-byte operand from LDS, so a CU's LDS feeds about one wave at the rate its SIMD multiplies, and the
 // rows should spread over as many CUs as there are.
-static constexpr int RB_THREADS = 64;
 template <bool DBG>
 __global__ void __launch_bounds__(RB_THREADS) k_rp_below(double* __restrict__ A, const size_t lda, const size_t rows, const size_t r0,
                                                          const int j0, const int w, const double* __restrict__ ut,
@@ -1428,7 +1412,6 @@ __global__ void __launch_bounds__(2 * PLIST) k_laswp_lists(double* __restrict__ 
 //   MODE 0: lower, implicit unit diagonal (LU factors)        B <- L^-1 B
 //   MODE 1: lower, stored diagonal (`linsolve` LT, linsolve.rs:769-800)
 //   MODE 2: upper, stored diagonal                             B <- U^-1 B
-static constexpr int TRSM_SW = TRSM_W + 1;  // LDS row stride (doubles) of a 65..128-wide solve; 65 for <= 64
 
 // value of lane `lane` (wave-uniform index) in every lane: two v_readlane_b32, no LDS round trip
 __device__ __forceinline__ double bcast_lane(double v, int lane) {
@@ -1442,20 +1425,9 @@ __device__ __forceinline__ double bcast_lane(double v, int lane) {
 // TRSM_THREADS: 256 (one wave per SIMD: the substitution is VALU-issue bound) for few columns, 512 for many.
 template <int MODE, int TRSM_NC, int TRSM_THREADS>
 __global__ void __launch_bounds__(TRSM_THREADS) k_trsm_fused(const double* __restrict__ T, size_t ldt, int w,
-                                                             double* __restrict__ B, size_t ldb, size_t ncols, unsigned* counter,
-                                                             const int* avoid_xcc) {
+                                                             double* __restrict__ B, size_t ldb, size_t ncols) {
     extern __shared__ double Ts[];  // [w][sw]
-    if (!counter) chain_prio();
-    // counter != nullptr (update stream of the LU's late phase, see k_dgemm_w8p): column groups are handed out by a counter, wave
-    // by wave, and workgroups on XCD *avoid_xcc leave before they stage anything
-    if (counter && avoid_xcc && gridDim.x >= 16) {
-        __shared__ int s_avoid;  // one read per workgroup (see k_dgemm_w8p)
-        if (threadIdx.x == 0) s_avoid = __hip_atomic_load(avoid_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        if ((int)(xcc & 0xf) == s_avoid) return;
-    }
+    chain_prio();
     const int wr = w > 64 ? TRSM_W : 64;  // staged rows per column (64-wide solves keep a 33 KiB footprint)
     const int sw = wr + 1;                // LDS row stride (doubles)
     // stage the needed triangle: eight independent loads in flight per thread before the first LDS write
@@ -1493,14 +1465,7 @@ __global__ void __launch_bounds__(TRSM_THREADS) k_trsm_fused(const double* __res
     const bool recip_ok = MODE != 0 && !__any(!(fabs(r0) < 1.0e300 && fabs(r0) > 1.0e-300 && fabs(r1) < 1.0e300 && fabs(r1) > 1.0e-300));
     auto scale = [=](double x, double d, double r) { return recip_ok ? x * r : x / d; };
     for (size_t it = 0;; ++it) {
-        size_t c0;
-        if (counter) {
-            unsigned ch = 0;
-            if (i == 0) ch = atomicAdd(counter, 1u);
-            c0 = (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)ch) * TRSM_NC;
-        } else {
-            c0 = (wave + it * nwaves) * TRSM_NC;
-        }
+        const size_t c0 = (wave + it * nwaves) * TRSM_NC;
         if (c0 >= ncols) break;
         double x0[TRSM_NC], x1[TRSM_NC];
 #pragma unroll
@@ -1793,54 +1758,41 @@ __global__ void __launch_bounds__(64) k_trsm_lower_mfma(const double* __restrict
 }
 
 static int launch_check(Context* c);
+// the two_pass and fused rows of the table below: NC and TRSM_THREADS are the route's NC and threads
 template <int MODE, int NC, int TRSM_THREADS>
-static int launch_trsm_fused_nc(Context* c, const double* T, size_t ldt, size_t w, double* B, size_t ldb, size_t nc) {
-    // inside the look-ahead LU a 65..128-wide unit-lower solve takes the two-pass kernel (66 KiB: it shares CUs with the update
-    // stream's dgemm blocks, where the 132 KiB one-pass kernel waits for a whole CU)
-    if (MODE == 0 && w > 64 && c->in_lookahead) {
-        const size_t lds2 = (size_t)64 * TRSM_SW * sizeof(double);
-        c->ensure_max_lds((const void*)k_trsm_lower_2p<NC, TRSM_THREADS>, lds2);
-        const size_t per_block2 = (size_t)(TRSM_THREADS / 64) * NC;
-        size_t want2 = (nc + per_block2 - 1) / per_block2;
-        const size_t cap2 = (size_t)c->num_cus;
-        if (want2 < 1) want2 = 1;
-        hipLaunchKernelGGL((k_trsm_lower_2p<NC, TRSM_THREADS>), dim3((unsigned)(want2 < cap2 ? want2 : cap2)), dim3(TRSM_THREADS), lds2,
-                           c->stream, T, ldt, (int)w, B, ldb, nc);
+static int launch_trsm_fused_nc(Context* c, const TrsmRoute& r, const double* T, size_t ldt, size_t w, double* B, size_t ldb, size_t nc) {
+    if (r.kernel == TrsmKernel::two_pass) {
+        c->ensure_max_lds((const void*)k_trsm_lower_2p<NC, TRSM_THREADS>, r.lds_bytes);
+        hipLaunchKernelGGL((k_trsm_lower_2p<NC, TRSM_THREADS>), dim3(r.grid), dim3(TRSM_THREADS), r.lds_bytes, c->stream, T, ldt, (int)w, B, ldb, nc);
         return launch_check(c);
     }
-    const size_t lds_bytes = w * (w > 64 ? (size_t)TRSM_SW : (size_t)65) * sizeof(double);
     c->ensure_max_lds((const void*)k_trsm_fused<MODE, NC, TRSM_THREADS>, TRSM_W * TRSM_SW * sizeof(double));
-    const size_t per_block = (size_t)(TRSM_THREADS / 64) * NC;  // columns one block solves per pass
-    size_t want = (nc + per_block - 1) / per_block;
-    const size_t cap = (size_t)c->num_cus * (w <= 64 ? 2 : 1);
-    if (want < 1) want = 1;
-    const unsigned grid = (unsigned)(want < cap ? want : cap);
-    // (counter-driven column groups + leaving the panels' XCD, as k_laswp_lists does in the LU's late phase, measured WORSE for
-    // this kernel: 104.7 vs 103.5 ms at n = 16384 - the kernel arguments stay, the driver passes none)
-    unsigned* counter = nullptr;
-    hipLaunchKernelGGL((k_trsm_fused<MODE, NC, TRSM_THREADS>), dim3(grid), dim3(TRSM_THREADS), lds_bytes, c->stream, T, ldt, (int)w, B, ldb,
-                       nc, counter, (const int*)nullptr);
+    // (Tried: counter-driven column groups + leaving the panels' XCD, as k_laswp_lists does in the LU's late phase: 104.7 vs 103.5 ms
+    // at n = 16384.)
+    hipLaunchKernelGGL((k_trsm_fused<MODE, NC, TRSM_THREADS>), dim3(r.grid), dim3(TRSM_THREADS), r.lds_bytes, c->stream, T, ldt, (int)w, B, ldb, nc);
     return launch_check(c);
 }
+// One triangular solve of at most TRSM_W rows: plan_trsm (lu_plan.h) names the kernel, this maps the route to its instantiation.
 template <int MODE>
 static int launch_trsm_fused(Context* c, const double* T, size_t ldt, size_t w, double* B, size_t ldb, size_t nc) {
-    if (MODE == 0 && c->lu_linv && (w == 64 || w == 128) && ldt == c->lu_work_ld && T >= c->lu_work && ((uintptr_t)B & 15) == 0 && ldb % 2 == 0) {
-        // a diagonal block of the solve-path factorisation in flight: the matrix-core solve with k_rp_top's inverted 16 x 16 blocks
-        const size_t off = (size_t)(T - c->lu_work);
-        const size_t j = off / (ldt + 1);
-        bool have = j * (ldt + 1) == off && j % 16 == 0 && c->lu_linv_ok && (j + w) / 16 <= c->lu_linv_ok->size();
-        for (size_t q = j / 16; have && q < (j + w) / 16; ++q) have = (*c->lu_linv_ok)[q] != 0;
-        if (have) {
-            const double* linv = c->lu_linv + (j / 16) * 256;
-            const unsigned grid = (unsigned)((nc + 15) / 16);
-            if (w == 64) hipLaunchKernelGGL(k_trsm_lower_mfma<4>, dim3(grid), dim3(64), 0, c->stream, T, ldt, linv, B, ldb, nc);
-            else hipLaunchKernelGGL(k_trsm_lower_mfma<8>, dim3(grid), dim3(64), 0, c->stream, T, ldt, linv, B, ldb, nc);
+    // is T a diagonal block of the solve-path factorisation in flight, and do k_rp_top's inverted 16 x 16 blocks exist for all of it?
+    const bool aligned = MODE == 0 && c->lu_linv && ldt == c->lu_work_ld && T >= c->lu_work && ((uintptr_t)B & 15) == 0 && ldb % 2 == 0;
+    const size_t off = aligned ? (size_t)(T - c->lu_work) : 0, j = off / (ldt + 1);
+    bool have = aligned && j * (ldt + 1) == off && j % 16 == 0 && c->lu_linv_ok && (j + w) / 16 <= c->lu_linv_ok->size();
+    for (size_t q = j / 16; have && q < (j + w) / 16; ++q) have = (*c->lu_linv_ok)[q] != 0;
+    const TrsmRoute r = plan_trsm(MODE, w, nc, c->num_cus, c->in_lookahead, have, aligned);
+    switch (r.kernel) {
+        case TrsmKernel::mfma4:
+            hipLaunchKernelGGL(k_trsm_lower_mfma<4>, dim3(r.grid), dim3(64), 0, c->stream, T, ldt, c->lu_linv + (j / 16) * 256, B, ldb, nc);
             return launch_check(c);
-        }
+        case TrsmKernel::mfma8:
+            hipLaunchKernelGGL(k_trsm_lower_mfma<8>, dim3(r.grid), dim3(64), 0, c->stream, T, ldt, c->lu_linv + (j / 16) * 256, B, ldb, nc);
+            return launch_check(c);
+        case TrsmKernel::two_pass:
+        case TrsmKernel::fused:
+            break;
     }
-    const size_t waves_on_chip = (size_t)c->num_cus * 4;  // one wave per SIMD
-    return nc > 2 * waves_on_chip ? launch_trsm_fused_nc<MODE, 4, 512>(c, T, ldt, w, B, ldb, nc)
-                                  : launch_trsm_fused_nc<MODE, 1, 256>(c, T, ldt, w, B, ldb, nc);
+    return r.NC == 4 ? launch_trsm_fused_nc<MODE, 4, 512>(c, r, T, ldt, w, B, ldb, nc) : launch_trsm_fused_nc<MODE, 1, 256>(c, r, T, ldt, w, B, ldb, nc);
 }
 
 // ---- environment knobs (docs/KNOBS.md): every RMHIP_LU_* variable is read here and nowhere else -----------------------------------
@@ -1912,13 +1864,6 @@ static int launch_check(Context* c) {
     return RMHIP_OK;
 }
 
-// split point of a triangular solve wider than the base TRSM_W: whole base blocks on the left
-static size_t trsm_split(size_t w) {
-    size_t h = ((w / 2 + TRSM_W - 1) / TRSM_W) * TRSM_W;
-    if (h >= w) h = w / 2;
-    return h;
-}
-
 // B[w x nc] <- L^-1 B with L = unit-lower part of T[w x w]; recursive halving, dgemm in between.
 static int trsm_lower_rec(Context* c, const double* T, size_t ldt, size_t w, double* B, size_t ldb, size_t nc,
                           bool unit = true) {
@@ -1966,13 +1911,15 @@ static int laswp(LuState& s, size_t c0, size_t c1, size_t k0, size_t k1) {
     return launch_check(s.c);
 }
 
-// Most blocks a base panel may have and still sit on ONE XCD, one per CU (getrf_rec's placement rule; 0: never - after such a
-// panel timed out once, see lu_factor_device).
-// (Tried: twice as many - tall panels, two blocks per CU in a 256-register build of the kernel - so that the update stream's
-// persistent dgemm has the other seven XCDs to itself in the first half too: 124 ms against 102 at n = 16384.  A panel block
-// that needs a whole SIMD's registers waits for every small kernel of the other streams to leave its CU; the panels then
-// average 450 us instead of 210 and the main stream becomes the critical path from the start.)
-static size_t one_xcd_block_limit(const Context* c) { return c->one_xcd_ok ? (size_t)c->num_cus / 8 : 0; }
+// (Tried: twice as many blocks on one XCD as one_xcd_block_limit (lu_plan.h) allows - tall panels, two blocks per CU in a 256-register
+// build of the kernel - so that the update stream's persistent dgemm has the other seven XCDs to itself in the first half too: 124 ms
+// against 102 at n = 16384.  A panel block that needs a whole SIMD's registers waits for every small kernel of the other streams to
+// leave its CU; the panels then average 450 us instead of 210 and the main stream becomes the critical path from the start.)
+static LuSite lu_site(const Context* c) {
+    LuSite site;
+    site.num_cus = c->num_cus, site.one_xcd_ok = c->one_xcd_ok, site.conservative = c->lu_conservative;
+    return site;
+}
 
 // retarget the context's stream (and the LDS pad that goes with it) for a scope
 struct StreamScope {
@@ -1997,153 +1944,135 @@ struct StreamScope {
 // own_swaps_by_caller: a base panel leaves its own columns un-interchanged (k_lu_panel2 stores every row where it was
 // loaded from); the recursion step above it then widens the k_laswp_lists call that moves the sibling's columns anyway
 // to this panel's columns, instead of a launch of its own.  *deferred reports that this happened.
+// (tests/cpp/lu_route_check.cpp `Walk` models this recursion to name the kernels a table row reaches: change both together.)
 static int getrf_rec(LuState& s, size_t j0, size_t w, bool own_swaps_by_caller = false, bool* deferred = nullptr) {
     if (deferred) *deferred = false;
     if (w == 0 || j0 >= s.rows) return RMHIP_OK;
     if (w <= (size_t)BASE_W) {
         const size_t c1 = j0 + w;  // j0 + w <= min(rows, cols) always holds (see lu_factor_device)
-        const size_t nbp = (s.rows - j0 + P2_ROWS - 1) / P2_ROWS;
-        if (s.fast && !(lu_process_knobs().skip & 1)) {
-            // solve path: ONE workgroup factors the top P2_ROWS rows with partial pivoting (no exchange), k_rp_below turns every row
-            // below into multipliers and records the largest one
-            const size_t pid = s.panel_start->size();
-            RtArgs g;
-            g.A = s.A;
-            g.lda = s.lda;
-            g.rows = (s.rows - j0) > (size_t)RT_ROWS ? j0 + RT_ROWS : s.rows;
-            g.j0 = (int)j0;
-            g.w = (int)w;
-            g.prow_arr = s.prow;
-            g.ipiv = s.ipiv;
-            g.info = s.info;
-            g.plist = s.plist + pid * PLIST;
-            double* const ucomp = s.ucomp + (size_t)(s.ucomp_slot++ % kUcompSlots) * UCOMP_STRIDE;
-            g.ucomp = ucomp;
-            g.xcc_out = s.panel_xcc;
-            g.yield_word = s.yield_word;
-            const bool below_mfma = lu_process_knobs().rb_mfma && w == (size_t)BASE_W && !s.xdbg;
-            g.uinv_on = below_mfma ? 1 : 0;
-            g.linv = (below_mfma && s.linv) ? s.linv + (j0 / 16) * 256 : nullptr;
-            if (g.linv && s.c->lu_linv_ok)
-                for (size_t q = j0 / 16; q < (j0 + BASE_W) / 16 && q < s.c->lu_linv_ok->size(); ++q) (*s.c->lu_linv_ok)[q] = 1;
-            // like k_lu_panel2 the block ASKS for more LDS than it uses (48.6 KiB static) so that it does not share its CU with an
-            // update-stream dgemm block: every column step would run slower beside one (the phase-dependent values of the drivers apply)
-            constexpr long kTopPadKb = 96;  // (96: the workgroup has its CU to itself; 32: 78.3 -> 77.3 ms at n = 16384)
-            const size_t pad_bytes = (size_t)(s.panel_pad_kb >= 0 ? (s.panel_pad_kb > kTopPadKb ? kTopPadKb : s.panel_pad_kb) : kTopPadKb) * 1024;
-            if (pad_bytes) {
-                s.c->ensure_max_lds((const void*)k_rp_top<false>, 96 * 1024);
-                s.c->ensure_max_lds((const void*)k_rp_top<true>, 96 * 1024);
-            }
-            if (s.xdbg) hipLaunchKernelGGL(k_rp_top<true>, dim3(1), dim3(RT_ROWS), pad_bytes, s.c->stream, g, (pk_u64*)s.xdbg);
-            else hipLaunchKernelGGL(k_rp_top<false>, dim3(1), dim3(RT_ROWS), pad_bytes, s.c->stream, g, (pk_u64*)nullptr);
-            RMHIP_TRY(launch_check(s.c));
-            if (g.rows < s.rows) {
-                const size_t r0 = g.rows, nrows = s.rows - r0;
-                if (below_mfma)
-                    hipLaunchKernelGGL(k_rp_below_mfma, dim3((unsigned)((nrows + 16 * RBM_JT - 1) / (16 * RBM_JT))), dim3(64), 0, s.c->stream, s.A, s.lda,
-                                       s.rows, r0, (int)j0, (const double*)ucomp, (pk_u64*)s.growth);
-                else if (s.xdbg)
-                    hipLaunchKernelGGL(k_rp_below<true>, dim3((unsigned)((nrows + RB_THREADS - 1) / RB_THREADS)), dim3(RB_THREADS), 0,
-                                       s.c->stream, s.A, s.lda, s.rows, r0, (int)j0, (int)w, (const double*)ucomp, (pk_u64*)s.growth, s.tau, (pk_u64*)s.xdbg);
-                else
-                    hipLaunchKernelGGL(k_rp_below<false>, dim3((unsigned)((nrows + RB_THREADS - 1) / RB_THREADS)), dim3(RB_THREADS), 0,
-                                       s.c->stream, s.A, s.lda, s.rows, r0, (int)j0, (int)w, (const double*)ucomp, (pk_u64*)s.growth, s.tau, (pk_u64*)s.xdbg);
-                s.c->tel.kernel_launches++;
-                RMHIP_HIP_CHECK(hipGetLastError());
-            }
-            s.xbase += (unsigned)w;
-            s.panel_start->push_back(j0);
-            if (!s.screened) {
-                // Early way out: a matrix whose large entries lie outside the top block (a row-permuted diagonally dominant one, say)
-                // fails at its first panel; one small read here instead of a whole factorisation of wasted work.
-                s.screened = true;
-                unsigned long long bits = 0;
-                RMHIP_HIP_CHECK(hipMemcpyAsync(&bits, s.growth, sizeof(bits), hipMemcpyDeviceToHost, s.c->stream));
-                RMHIP_HIP_CHECK(hipStreamSynchronize(s.c->stream));
-                double gmax;
-                std::memcpy(&gmax, &bits, sizeof(gmax));
-                if (!(gmax <= s.tau)) {
-                    s.c->lu_last_growth = gmax;
-                    return RMHIP_LU_GROWTH;
-                }
-            }
-            if (own_swaps_by_caller && deferred) {
-                *deferred = true;
-                return RMHIP_OK;
-            }
-            return laswp(s, j0, c1, j0, c1);  // the panel's own interchange
-        }
-        if (s.persistent && nbp <= (size_t)PK_MAXB && nbp <= (size_t)s.c->num_cus && !(lu_process_knobs().skip & 1)) {
-            // one launch factors the panel, interchanges its own columns and leaves the row-move list for the others
-            const size_t pid = s.panel_start->size();
-            P2Args g;
-            g.A = s.A;
-            g.lda = s.lda;
-            g.rows = s.rows;
-            g.j0 = (int)j0;
-            g.w = (int)w;
-            g.nblocks = (int)nbp;
-            g.onehop_max = P2_ONEHOP_MAXB;
-            // One-XCD placement when every block finds a CU of its own on one XCD (<= num_cus / 8 blocks): the exchange hop
-            // drops from a write-through + a miss in another XCD's L2 to two accesses of one L2 (scripts/micro/
-            // xcd_exchange.hip: 2.1-2.5 -> 1.45 us per step).
-            g.bstride = nbp <= one_xcd_block_limit(s.c) ? 8 : 1;
-            if (g.bstride > 1) s.c->lu_used_one_xcd = true;
-            g.seq0 = s.xbase;
-            g.xerr = s.xerr;
-            g.xrec = s.xrec;
-            g.xvals = s.xvals;
-            g.prow_arr = s.prow;
-            g.ipiv = s.ipiv;
-            g.info = s.info;
-            g.plist = s.plist + pid * PLIST;
-            g.dbg = s.xdbg;
-            g.xcc_out = s.panel_xcc;
-            // The block needs 18.5 KiB of LDS but ASKS for 82.5: it then does not fit beside an update-stream dgemm block
-            // (84 KiB) and waits for a CU of its own.  Sharing a CU costs more than the wait: with the panel waves on the
-            // same SIMDs as a dgemm wave every column step slows down, and the column chain is the critical path
-            // (n = 16384: 135 ms sharing, 123 ms exclusive).
-            constexpr long kPanelPadKb = 64;
-            const size_t lds_bytes = P2_LDS_DOUBLES * sizeof(double) + (size_t)(s.panel_pad_kb >= 0 ? s.panel_pad_kb : kPanelPadKb) * 1024;
-            if (lds_bytes > 65536) {
-                s.c->ensure_max_lds((const void*)k_lu_panel2<false>, lds_bytes);
-                s.c->ensure_max_lds((const void*)k_lu_panel2<true>, lds_bytes);
-            }
-            const unsigned grid = (unsigned)nbp * (unsigned)g.bstride;
-            if (s.xdbg) hipLaunchKernelGGL((k_lu_panel2<true>), dim3(grid), dim3(P2_THREADS), lds_bytes, s.c->stream, g);
-            else hipLaunchKernelGGL((k_lu_panel2<false>), dim3(grid), dim3(P2_THREADS), lds_bytes, s.c->stream, g);
-            RMHIP_TRY(launch_check(s.c));
-            s.xbase += (unsigned)w;
-            s.panel_start->push_back(j0);
-            if (own_swaps_by_caller && deferred) {
-                *deferred = true;
-                return RMHIP_OK;
-            }
-            return laswp(s, j0, c1, j0, c1);  // the panel's own interchange
-        }
-        const size_t nb = (s.rows - j0 + PANEL_ROWS - 1) / PANEL_ROWS;  // one block per PANEL_ROWS rows
-        if (nb > (size_t)MAX_PANEL_BLOCKS)
-            return fail(RMHIP_ERR_UNSUPPORTED, "lu: more than %d rows per panel not supported yet", MAX_PANEL_BLOCKS * PANEL_ROWS);
-        // init launch: candidates for column j0; then one launch per column
-        hipLaunchKernelGGL(k_lu_col, dim3((unsigned)nb), dim3(PANEL_THREADS), 0, s.c->stream, s.A, s.lda, s.rows, (int)j0,
-                           (int)j0 - 1, (int)c1, 1, (int)nb, s.pos_of, s.row_at, s.prow, s.ipiv, s.info, s.cand_abs, s.cand_pos, s.cand_row);
-        RMHIP_TRY(launch_check(s.c));
-        for (size_t k = j0; k < c1 && !(lu_process_knobs().skip & 1); ++k) {
-            hipLaunchKernelGGL(k_lu_col, dim3((unsigned)nb), dim3(PANEL_THREADS), 0, s.c->stream, s.A, s.lda, s.rows,
-                               (int)j0, (int)k, (int)c1, 0, (int)nb, s.pos_of, s.row_at, s.prow, s.ipiv, s.info,
-                               s.cand_abs, s.cand_pos, s.cand_row);
-            RMHIP_TRY(launch_check(s.c));
-        }
-        // the panel's row moves as one gather list, then the physical interchange of the panel columns
+        const PanelRoute panel = plan_base_panel(s.rows, j0, w, s.route, s.site, s.panel_pad_kb, lu_process_knobs(), s.xdbg != nullptr);
+        if (panel.unsupported) return fail(RMHIP_ERR_UNSUPPORTED, "%s", panel.unsupported);
         const size_t pid = s.panel_start->size();
-        s.panel_start->push_back(j0);
-        hipLaunchKernelGGL(k_build_plist, dim3(1), dim3(PLIST), 0, s.c->stream, (int)j0, (int)c1, s.pos_of, s.prow,
-                           s.plist + pid * PLIST);
-        RMHIP_TRY(launch_check(s.c));
-        return laswp(s, j0, c1, j0, c1);
+        switch (panel.kind) {
+            case PanelKind::top: {
+                // solve path: ONE workgroup factors the top rows with partial pivoting (no exchange), k_rp_below* turns every row
+                // below into multipliers and records the largest one
+                RtArgs g;
+                g.A = s.A;
+                g.lda = s.lda;
+                g.rows = j0 + panel.top_rows;
+                g.j0 = (int)j0;
+                g.w = (int)w;
+                g.prow_arr = s.prow;
+                g.ipiv = s.ipiv;
+                g.info = s.info;
+                g.plist = s.plist + pid * PLIST;
+                double* const ucomp = s.ucomp + (size_t)(s.ucomp_slot++ % kUcompSlots) * UCOMP_STRIDE;
+                g.ucomp = ucomp;
+                g.xcc_out = s.panel_xcc;
+                g.yield_word = s.yield_word;
+                g.uinv_on = panel.inverses ? 1 : 0;
+                g.linv = (panel.inverses && s.linv) ? s.linv + (j0 / 16) * 256 : nullptr;
+                if (g.linv && s.c->lu_linv_ok)
+                    for (size_t q = j0 / 16; q < (j0 + BASE_W) / 16 && q < s.c->lu_linv_ok->size(); ++q) (*s.c->lu_linv_ok)[q] = 1;
+                if (panel.lds_bytes) {  // the pad (lu_plan.h kTopPadKb)
+                    s.c->ensure_max_lds((const void*)k_rp_top<false>, kTopPadKb * 1024);
+                    s.c->ensure_max_lds((const void*)k_rp_top<true>, kTopPadKb * 1024);
+                }
+                if (s.xdbg) hipLaunchKernelGGL(k_rp_top<true>, dim3(panel.grid), dim3(panel.threads), panel.lds_bytes, s.c->stream, g, (pk_u64*)s.xdbg);
+                else hipLaunchKernelGGL(k_rp_top<false>, dim3(panel.grid), dim3(panel.threads), panel.lds_bytes, s.c->stream, g, (pk_u64*)nullptr);
+                RMHIP_TRY(launch_check(s.c));
+                if (panel.below != PanelBelow::none) {
+                    const size_t r0 = g.rows;
+                    if (panel.below == PanelBelow::mfma)
+                        hipLaunchKernelGGL(k_rp_below_mfma, dim3(panel.below_grid), dim3(64), 0, s.c->stream, s.A, s.lda, s.rows, r0, (int)j0,
+                                           (const double*)ucomp, (pk_u64*)s.growth);
+                    else if (s.xdbg)
+                        hipLaunchKernelGGL(k_rp_below<true>, dim3(panel.below_grid), dim3(RB_THREADS), 0, s.c->stream, s.A, s.lda, s.rows, r0,
+                                           (int)j0, (int)w, (const double*)ucomp, (pk_u64*)s.growth, s.route.tau, (pk_u64*)s.xdbg);
+                    else
+                        hipLaunchKernelGGL(k_rp_below<false>, dim3(panel.below_grid), dim3(RB_THREADS), 0, s.c->stream, s.A, s.lda, s.rows, r0,
+                                           (int)j0, (int)w, (const double*)ucomp, (pk_u64*)s.growth, s.route.tau, (pk_u64*)s.xdbg);
+                    s.c->tel.kernel_launches++;
+                    RMHIP_HIP_CHECK(hipGetLastError());
+                }
+                s.xbase += (unsigned)w;
+                s.panel_start->push_back(j0);
+                if (!s.screened) {
+                    // Early way out: a matrix whose large entries lie outside the top block (a row-permuted diagonally dominant one, say)
+                    // fails at its first panel; one small read here instead of a whole factorisation of wasted work.
+                    s.screened = true;
+                    unsigned long long bits = 0;
+                    RMHIP_HIP_CHECK(hipMemcpyAsync(&bits, s.growth, sizeof(bits), hipMemcpyDeviceToHost, s.c->stream));
+                    RMHIP_HIP_CHECK(hipStreamSynchronize(s.c->stream));
+                    double gmax;
+                    std::memcpy(&gmax, &bits, sizeof(gmax));
+                    if (!(gmax <= s.route.tau)) {
+                        s.c->lu_last_growth = gmax;
+                        return RMHIP_LU_GROWTH;
+                    }
+                }
+                break;
+            }
+            case PanelKind::persistent: {
+                // one launch factors the panel, interchanges its own columns and leaves the row-move list for the others
+                P2Args g;
+                g.A = s.A;
+                g.lda = s.lda;
+                g.rows = s.rows;
+                g.j0 = (int)j0;
+                g.w = (int)w;
+                g.nblocks = (int)(panel.grid / (unsigned)panel.bstride);
+                g.onehop_max = P2_ONEHOP_MAXB;
+                g.bstride = panel.bstride;
+                if (g.bstride > 1) s.c->lu_used_one_xcd = true;
+                g.seq0 = s.xbase;
+                g.xerr = s.xerr;
+                g.xrec = s.xrec;
+                g.xvals = s.xvals;
+                g.prow_arr = s.prow;
+                g.ipiv = s.ipiv;
+                g.info = s.info;
+                g.plist = s.plist + pid * PLIST;
+                g.dbg = s.xdbg;
+                g.xcc_out = s.panel_xcc;
+                if (panel.lds_bytes > 65536) {  // beyond what a launch may ask for without the attribute
+                    s.c->ensure_max_lds((const void*)k_lu_panel2<false>, panel.lds_bytes);
+                    s.c->ensure_max_lds((const void*)k_lu_panel2<true>, panel.lds_bytes);
+                }
+                if (s.xdbg) hipLaunchKernelGGL((k_lu_panel2<true>), dim3(panel.grid), dim3(panel.threads), panel.lds_bytes, s.c->stream, g);
+                else hipLaunchKernelGGL((k_lu_panel2<false>), dim3(panel.grid), dim3(panel.threads), panel.lds_bytes, s.c->stream, g);
+                RMHIP_TRY(launch_check(s.c));
+                s.xbase += (unsigned)w;
+                s.panel_start->push_back(j0);
+                break;
+            }
+            case PanelKind::columns: {
+                const int nb = (int)panel.grid;
+                // init launch: candidates for column j0; then one launch per column
+                hipLaunchKernelGGL(k_lu_col, dim3(panel.grid), dim3(panel.threads), 0, s.c->stream, s.A, s.lda, s.rows, (int)j0, (int)j0 - 1, (int)c1, 1,
+                                   nb, s.pos_of, s.row_at, s.prow, s.ipiv, s.info, s.cand_abs, s.cand_pos, s.cand_row);
+                RMHIP_TRY(launch_check(s.c));
+                for (size_t k = j0; k < j0 + panel.steps; ++k) {
+                    hipLaunchKernelGGL(k_lu_col, dim3(panel.grid), dim3(panel.threads), 0, s.c->stream, s.A, s.lda, s.rows, (int)j0, (int)k, (int)c1, 0,
+                                       nb, s.pos_of, s.row_at, s.prow, s.ipiv, s.info, s.cand_abs, s.cand_pos, s.cand_row);
+                    RMHIP_TRY(launch_check(s.c));
+                }
+                // the panel's row moves as one gather list, then the physical interchange of the panel columns
+                s.panel_start->push_back(j0);
+                hipLaunchKernelGGL(k_build_plist, dim3(1), dim3(PLIST), 0, s.c->stream, (int)j0, (int)c1, s.pos_of, s.prow, s.plist + pid * PLIST);
+                RMHIP_TRY(launch_check(s.c));
+                return laswp(s, j0, c1, j0, c1);
+            }
+        }
+        // a base panel leaves its own columns un-interchanged when the recursion step above moves them with the sibling's
+        if (own_swaps_by_caller && deferred) {
+            *deferred = true;
+            return RMHIP_OK;
+        }
+        return laswp(s, j0, c1, j0, c1);  // the panel's own interchange
     }
-    size_t h = ((w / 2 + 15) / 16) * 16;
-    if (h >= w) h = w / 2;
+    const size_t h = rec_split(w);
     const size_t hk = (j0 + h <= s.rows) ? h : (s.rows - j0);  // pivots produced by the left half
     bool left_deferred = false, right_deferred = false;
     RMHIP_TRY(getrf_rec(s, j0, h, true, &left_deferred));
@@ -2204,11 +2133,10 @@ static int iprep_columns(LuState& s, size_t S0, size_t j, size_t w, size_t c0, s
     return trsm_lower_rec(s.c, s.A + j + j * s.lda, s.lda, w, A12, s.lda, c1 - c0);
 }
 
-// update-stream dgemm blocks ask for 84 KiB of LDS (73.7 needed): one per CU, leaving 76 KiB for a panel
-// block (66 KiB) or a main-stream dgemm block (73.7 KiB)
-static constexpr size_t kSidePad = 84 * 1024 - 73728;
-
-static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
+// One step per panel, planned up front (plan_blocked, lu_plan.h: widths by phase, the panels' LDS pad, the late phase, the split of the
+// trailing columns); what is left here is which stream does what after which event.
+// (tests/cpp/lu_route_check.cpp `Walk` models which panels and updates a step runs: change both together.)
+static int getrf_blocked(LuState& s, size_t kmin) {
     Context* c = s.c;
     hipStream_t main_stream = c->stream;
     int prio_low = 0, prio_high = 0;
@@ -2249,17 +2177,10 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
     } restore{c, &s};
     c->in_lookahead = true;
     int rc = RMHIP_OK;
-    // Late phase (the next panel fits one XCD, getrf_rec places it there): the update stream's dgemm runs as a persistent
-    // kernel whose workgroups leave the panel's XCD at once (k_dgemm_w8p), and the panel blocks drop their LDS pad so that
-    // such a placeholder can always be scheduled beside them.  The panel chain is the critical path there and everything
-    // the update stream does disturbs it (without ANY update work in that phase the solve takes 95.7 instead of 108.4 ms):
-    // this keeps the panel's CUs free (no drain before a panel or a 132 KiB triangular solve starts) and its L2 quiet.
-    // (Not on the solve path: its panel is one workgroup and k_rp_below's workgroups fit beside a dgemm block, so there is no XCD to
-    // keep free; n = 16384: 78.8 -> 76.4 ms without the persistent form.)
-    const bool late_xcd_on = !s.fast;
+    const BlockedPlan plan = plan_blocked(s.rows, s.cols, kmin, s.route.nb, s.route.fast, s.site);
     constexpr size_t kCounters = 4096;
     unsigned* late_counters = nullptr;
-    if (late_xcd_on && c->one_xcd_ok) {
+    if (plan.late_counters) {  // the late phase's persistent, XCD-avoiding update kernels (BlockedPlan)
         RMHIP_TRY(c->alloc_device(kCounters / 2 + 8, &late_ctl));
         late_counters = (unsigned*)late_ctl->ptr;
         s.panel_xcc = (int*)(late_counters + kCounters);
@@ -2269,59 +2190,21 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
         c->gemm_counter_cap = kCounters;
         c->gemm_avoid_xcc = s.panel_xcc;
     }
-    // Split update: on the update stream the interchanges and triangular solves are 14 % of the
-    // throughput-bound first half, and the matrix cores idle meanwhile.  While more than kSplitRows rows remain (6144: into the
-    // beginning of the late phase; 8192 measured 0.5 ms slower at n = 16384 and 8192) the trailing
-    // columns are cut at a fixed column csplit into A | B; a third stream prepares (interchange + solve) one part while the
-    // update stream's dgemm runs on the other:
+    // Split update (BlockedStep::split): the trailing columns are cut at a fixed column csplit into A | B; a third stream prepares
+    // (interchange + solve) one part while the update stream's dgemm runs on the other:
     //   prep:    wait(P_j, dgemm_{j-1}(A)) -> prep_j(A) -> wait(dgemm_{j-1}(B)) -> prep_j(B)
     //   update:  wait(prep_j(A)) -> dgemm_j(A) -> wait(prep_j(B)) -> dgemm_j(B) -> interchanges of the finished left columns
-    // csplit stays put (so A_j lies inside A_{j-1}) until A has shrunk below a fifth of the range, then it moves to the
-    // middle again (that one step waits for all of step j-1).  The main stream waits for dgemm_{j-1}(A) only - the next
+    // When csplit moves, that one step waits for all of step j-1.  The main stream waits for dgemm_{j-1}(A) only - the next
     // panel's columns are its first ones - in either mode.  Same kernels on the same columns: bit-identical factors.
-    constexpr size_t kSplitRows = 6144;
     if (!c->lu_prep_stream) RMHIP_HIP_CHECK(hipStreamCreateWithPriority(&c->lu_prep_stream, hipStreamNonBlocking, prio_low));
     hipStream_t prep = c->lu_prep_stream;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;  // dgemm of the previous step finished on [.., a_end) / everything of that step finished
-    size_t a_end = s.cols;                      // right edge of the previous step's part A
-    size_t csplit = 0;
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;  // dgemm of the previous step finished on [.., st.a_end) / everything of that step finished
     {
         hipEvent_t e0 = new_event();  // side starts after whatever main already has queued (the copy of A)
         (void)hipEventRecord(e0, main_stream);
         (void)hipStreamWaitEvent(side, e0, 0);
         (void)hipStreamWaitEvent(prep, e0, 0);
     }
-    // Panel width by phase.  While the trailing matrix is large the update stream is the bottleneck and the main stream
-    // idles a third of the time: wider panels there (fewer, deeper rank-k updates: the dgemm runs 53 instead of 47
-    // TFLOP/s at k = 512 with one block per CU).  Once the panel chain is the critical path (about the last 8192
-    // columns) the narrower panel wins.  n = 16384: 128.3 -> 125.2 ms (interleaved, scripts/lu_env_ab.sh); giving the
-    // main stream a share of the trailing columns as well (its dgemm blocks fit beside the update stream's) measured
-    // nothing (127.3 vs 127.9).
-    constexpr size_t kNbEarly = 512, kEarlyRows = 10240;  // (10240 since the update stream's eight-wave dgemm: 113.7 -> 112.7 ms; 8192 before)
-    const size_t nb_early = kNbEarly < nb ? nb : kNbEarly;
-    // third tier: once the panel chain is the critical path, a narrower panel moves more of each update from the main stream
-    // (look-ahead columns) to the idle update stream
-    // (n = 16384, interleaved: 123.1 / 124.2 ms without, 120.8 / 120.6 with 128 below 6144 rows; 64 below 3072: 122.9 / 121.6)
-    constexpr size_t kNbLate = 128, kLateRows = 8192;  // (8192 since the two-pass solve and the third stream: 98.4 vs 99.1 ms at n = 16384; 6144 before)
-    const size_t nb_late = kNbLate > nb ? nb : kNbLate;
-    // the very first panel is narrower (the update stream has nothing to do until it is factored: 128 columns instead of
-    // 512 start it 1.5 ms earlier; n = 16384: 108.9 -> 107.9 ms); the second one realigns to multiples of the wide width
-    constexpr size_t kNbFirst = 128;
-    auto width_at = [&](size_t j) {
-        if (kNbFirst < nb_early && kmin > kEarlyRows + nb_early) {
-            if (j == 0) return kNbFirst;
-            if (j == kNbFirst) return nb_early - kNbFirst;
-        }
-        if (kmin - j > kEarlyRows) return nb_early;
-        if (kmin - j <= kLateRows) return nb_late;
-        return nb;
-    };
-    // While the trailing matrix is large the machine is throughput bound on the update dgemm (one block per CU: ~50 TFLOP/s
-    // in place, 56 alone) and the main stream has slack, so the panel blocks drop their LDS pad there and start beside a
-    // dgemm block instead of waiting for a CU to drain (n = 16384: 119.9 -> 118.8 ms).  Letting the update stream drop ITS
-    // pad there as well (two dgemm blocks per CU) starves the main stream: a retiring block's slot goes to the next block
-    // of the same kernel, stream priority or not (138 ms).  In the late phase (panel on one XCD) the panel blocks drop their pad
-    // too, see above.
     // (Also tried: the interchanges of the finished left columns on a third low-priority stream - they only depend on their panel and
     // on the previous update - instead of behind the update: 109.25 vs 108.6 ms, 8192: 40.4 vs 39.7 ms.)
     // (Also tried: the first quarter / half of the trailing columns on a second update stream, so that its dgemm covers the
@@ -2335,50 +2218,30 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
     // Bit-identical pivots, correct factors - and slower at every far_c: 113.3 ms at 10240, 111.4 at 12288, 109.6 at 13312
     // against 108.5 without.  The update stream's idle time in the second half is not free: whatever runs there slows the
     // panel chain - exchange latency under load, CUs that must drain before a panel or a triangular solve starts.)
-    for (size_t j = 0; j < kmin && rc == RMHIP_OK;) {
-        const size_t nbj = width_at(j);
-        const bool early = kmin - j > kEarlyRows;
-        // this panel on one XCD?  (the condition getrf_rec applies to its first base panel)
-        const bool late_xcd = late_counters && (s.rows - j + P2_ROWS - 1) / P2_ROWS <= one_xcd_block_limit(c);
-        s.panel_pad_kb = (late_xcd || early) ? 0 : -1;  // unpadded panel blocks in the early and the late phase (-1: getrf_rec's default)
-        const size_t w = (kmin - j) < nbj ? (kmin - j) : nbj;
+    for (const BlockedStep& st : plan.steps) {
+        if (rc != RMHIP_OK) break;
+        const size_t j = st.j, w = st.w, next = j + w, la_w = st.la_w, t0 = st.t0, csplit = st.csplit;
+        s.panel_pad_kb = st.panel_pad_kb;
         rc = getrf_rec(s, j, w);  // P_j on main
         if (rc != RMHIP_OK) break;
         hipEvent_t panel_done = new_event();
         (void)hipEventRecord(panel_done, main_stream);
-        const size_t next = j + w;
-        size_t la_w = 0;
-        if (next < kmin) {  // there is a next panel: the main stream updates its columns right away
-            const size_t nbn = width_at(next);
-            la_w = (kmin - next) < nbn ? (kmin - next) : nbn;
-        }
-        const size_t t0 = next + la_w;  // trailing columns [t0, cols)
-        const bool next_late = late_counters && next < s.rows && (s.rows - next + P2_ROWS - 1) / P2_ROWS <= one_xcd_block_limit(c);
-        bool split = kmin - j > kSplitRows && s.cols > t0 && s.cols - t0 >= 2048;
-        bool moved = false;
-        if (split) {
-            if (csplit < t0 + 256 || csplit >= s.cols || (csplit - t0) * 5 < (s.cols - t0)) {
-                csplit = t0 + (((s.cols - t0) / 2 + 127) / 128) * 128;
-                moved = true;
-            }
-            if (csplit >= s.cols) split = false;
-        }
         // (Tried: while the update stream is the bottleneck, hand it the next panel's columns as well - first in line, prepared by
         // the third stream - so that the main stream only factors panels: 101.9-103.9 ms against 101.3, worse the longer it is kept up.)
         if (la_w) {
             if (ev_a) (void)hipStreamWaitEvent(main_stream, ev_a, 0);
-            if (ev_b && next + la_w > a_end) (void)hipStreamWaitEvent(main_stream, ev_b, 0);
+            if (ev_b && next + la_w > st.a_end) (void)hipStreamWaitEvent(main_stream, ev_b, 0);
             rc = update_columns(s, j, w, next, next + la_w);
             if (rc != RMHIP_OK) break;
         }
-        if (split) {
-            c->gemm_tile_counters = next_late ? late_counters : nullptr;  // persistent, XCD-avoiding kernels if the next panel sits on one XCD
+        if (st.split) {
+            c->gemm_tile_counters = st.next_late ? late_counters : nullptr;  // persistent, XCD-avoiding kernels if the next panel sits on one XCD
             hipEvent_t ra = new_event(), rb = new_event();
             (void)hipStreamWaitEvent(prep, panel_done, 0);
             {
                 StreamScope scope(c, prep, 0);  // unpadded small blocks: they run beside the update stream's dgemm
                 if (ev_a) (void)hipStreamWaitEvent(prep, ev_a, 0);
-                if (ev_b && (moved || csplit > a_end)) (void)hipStreamWaitEvent(prep, ev_b, 0);
+                if (ev_b && (st.moved || csplit > st.a_end)) (void)hipStreamWaitEvent(prep, ev_b, 0);
                 rc = prep_columns(s, j, w, t0, csplit);
                 (void)hipEventRecord(ra, prep);
                 if (ev_b) (void)hipStreamWaitEvent(prep, ev_b, 0);
@@ -2394,12 +2257,11 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
             if (rc == RMHIP_OK) rc = gemm_columns(s, j, w, csplit, s.cols);
             if (rc == RMHIP_OK && j > 0) rc = laswp(s, 0, j, j, j + w);  // finished left columns
             c->gemm_tile_counters = nullptr;
-            a_end = csplit;
         } else {
             (void)hipStreamWaitEvent(side, panel_done, 0);
             StreamScope scope(c, side, kSidePad);
             // S_j overlaps panel j+1: persistent, XCD-avoiding dgemm if that panel sits on one XCD
-            c->gemm_tile_counters = next_late ? late_counters : nullptr;
+            c->gemm_tile_counters = st.next_late ? late_counters : nullptr;
             // (Attribution, n = 16384 at 100.9 ms: dropping the update stream's work of this phase altogether - knob below, results
             // are garbage - gives 100.3: with the XCD partition it no longer disturbs the chain.  But the phase has no room to
             // spare either: repeating its dgemm into a scratch copy k more times, on this stream before or behind the event the main
@@ -2411,11 +2273,9 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
             (void)hipEventRecord(ev_a, side);
             if (rc == RMHIP_OK && j > 0) rc = laswp(s, 0, j, j, j + w);  // finished left columns
             c->gemm_tile_counters = nullptr;
-            a_end = s.cols;
         }
         ev_b = new_event();
         (void)hipEventRecord(ev_b, side);
-        j = next;
     }
     s.panel_pad_kb = -1;
     if (ev_b) (void)hipStreamWaitEvent(main_stream, ev_b, 0);
@@ -2445,10 +2305,7 @@ static int getrf_blocked(LuState& s, size_t kmin, size_t nb) {
 // row block by row block on the mid stream while the inner panels are factored - twice the flops of the substitution, all at the
 // deep-product rate, with a guard on the inverse's largest entry: measured slower.  Also tried: the main stream's dgemm blocks,
 // k_rp_below_mfma and k_trsm_lower_mfma counting themselves into the yield table as k_rp_top does: neutral.  docs/EXPERIMENTS.md R6.)
-struct SuperPanel {
-    size_t s0, s1, nb;
-};
-
+// (tests/cpp/lu_route_check.cpp `Walk` models which panels, solves and updates a super-panel runs: change both together.)
 static int getrf_super(LuState& s, size_t kmin) {
     Context* c = s.c;
     hipStream_t main_stream = c->stream;
@@ -2480,30 +2337,7 @@ static int getrf_super(LuState& s, size_t kmin) {
     c->gemm_chain_prio = true;  // the main stream's dgemm launches raise their wave priority (GemmArgs::prio)
     const LuKnobs knobs = lu_knobs();
     const LuProcessKnobs& pknobs = lu_process_knobs();
-    // ---- the plan: super-panels (W, nb) while more than super_rows rows remain, single panels afterwards
-    // (defaults by order, interleaved runs of scripts/lu_super_ab.sh: n = 16384 69.7-69.9 ms with 256 / 1024 / 2048-column super-panels of
-    // 256-column panels down to 4096 remaining rows against 71.6-72.7 with the plan below; 12288 41.0-41.5 against 40.9, 8192 22.1 against 20.8:
-    // the shorter plan stays below 14336)
-    const bool large = kmin >= 14336;
-    const std::vector<std::pair<size_t, size_t>> seq =
-        !pknobs.super_seq.empty() ? pknobs.super_seq
-                                  : (large ? std::vector<std::pair<size_t, size_t>>{{256, 256}, {1024, 256}, {2048, 256}}
-                                           : std::vector<std::pair<size_t, size_t>>{{512, 512}, {1024, 512}, {2048, 512}});
-    const std::pair<size_t, size_t> late = pknobs.super_late;
-    const size_t super_rows = pknobs.super_rows >= 0 ? (size_t)pknobs.super_rows : (large ? 4096 : 6144);
-    std::vector<SuperPanel> plan;
-    for (size_t s0 = 0, i = 0; s0 < kmin;) {
-        const size_t rem = kmin - s0;
-        std::pair<size_t, size_t> e = late;
-        if (rem > super_rows) {
-            e = seq[i < seq.size() ? i : seq.size() - 1];
-            ++i;
-            if (e.first > rem - super_rows && rem - super_rows >= e.second) e.first = ((rem - super_rows + e.second - 1) / e.second) * e.second;  // do not overshoot the switch point by much
-        }
-        const size_t s1 = s0 + e.first < kmin ? s0 + e.first : kmin;
-        plan.push_back({s0, s1, e.second < e.first ? e.second : e.first});
-        s0 = s1;
-    }
+    const SuperPlan plan = plan_super(kmin, pknobs);  // the super-panels, their panel widths and whether U's block rows go out incrementally
     // the mid and far streams' dgemm blocks ask for kSidePad of LDS like the update stream of getrf_blocked: one eight-wave block per CU
     // with room beside it
     // cooperative yield of the update blocks on k_rp_top's CU: k_rp_top names its CU in the table, the update streams' eight-wave dgemm
@@ -2529,10 +2363,7 @@ static int getrf_super(LuState& s, size_t kmin) {
     hipEvent_t ev_far_next = nullptr;  // far finished the columns of the super-panel after the one in flight
     hipEvent_t ev_far_all = nullptr;
     hipEvent_t ev_iprep = nullptr;     // the mid stream's last incremental block row of U for the next super-panel's columns
-    // incremental block rows of U for the next super-panel's columns (iprep_columns): 12288 40.4-40.8 -> 39.3-39.9 ms with the 512-column
-    // plan; with the large-order plan the far stream delivers those columns too late - the mid stream stalls behind the wait and
-    // 16384 goes 69.4 -> 73 ms (docs/EXPERIMENTS.md R5 22)
-    const bool iprep = pknobs.iprep >= 0 ? pknobs.iprep != 0 : !large;
+    const bool iprep = plan.iprep;
     int rc = RMHIP_OK;
     // developer aid (RMHIP_LU_TIMELINE=1): timed events on the main stream around every super-panel boundary, printed after the factorisation
     const bool tl_on = knobs.timeline;
@@ -2547,26 +2378,19 @@ static int getrf_super(LuState& s, size_t kmin) {
     tl_mark("start");
     const auto host_t0 = std::chrono::steady_clock::now();
     auto host_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count(); };
-    for (size_t J = 0; J < plan.size() && rc == RMHIP_OK; ++J) {
-        const size_t S0 = plan[J].s0, S1 = plan[J].s1, nbJ = plan[J].nb, W = S1 - S0;
-        if (knobs.verbose && (W > nbJ || J + 1 == plan.size())) std::fprintf(stderr, "[lu] host %.2f ms: super-panel %zu [%zu, %zu) nb %zu queued so far %llu launches\n", host_ms(), J, S0, S1, nbJ, (unsigned long long)c->tel.kernel_launches);
-        const size_t S1n = J + 1 < plan.size() ? plan[J + 1].s1 : S1;
-        const size_t S1nn = J + 2 < plan.size() ? plan[J + 2].s1 : S1n;
-        const bool multi = W > nbJ;
-        for (size_t j = S0; j < S1 && rc == RMHIP_OK;) {
-            const size_t w = (S1 - j) < nbJ ? (S1 - j) : nbJ;
+    for (size_t J = 0; J < plan.panels.size() && rc == RMHIP_OK; ++J) {
+        const size_t S0 = plan.panels[J].s0, S1 = plan.panels[J].s1, nbJ = plan.panels[J].nb, W = S1 - S0;
+        const bool multi = plan.multi(J);
+        if (knobs.verbose && (multi || J + 1 == plan.panels.size())) std::fprintf(stderr, "[lu] host %.2f ms: super-panel %zu [%zu, %zu) nb %zu queued so far %llu launches\n", host_ms(), J, S0, S1, nbJ, (unsigned long long)c->tel.kernel_launches);
+        const size_t S1n = plan.s1_after(J, 1);
+        for (const SuperStep& st : plan.steps(J, kmin)) {
+            if (rc != RMHIP_OK) break;
+            const size_t j = st.j, w = st.w, next = j + w, la_w = st.la_w, t0 = st.t0;
+            const bool boundary = st.boundary;
             rc = getrf_rec(s, j, w);  // P_j on main
             if (rc != RMHIP_OK) break;
-            if (tl_on && W > nbJ) tl_mark("J" + std::to_string(J) + " panel " + std::to_string(j) + " done");
+            if (tl_on && multi) tl_mark("J" + std::to_string(J) + " panel " + std::to_string(j) + " done");
             hipEvent_t panel_done = record(main_stream);
-            const size_t next = j + w;
-            const bool boundary = next == S1;
-            size_t la_w = 0;
-            if (next < kmin) {
-                if (!boundary) la_w = (S1 - next) < nbJ ? (S1 - next) : nbJ;
-                else la_w = (plan[J + 1].s1 - next) < plan[J + 1].nb ? (plan[J + 1].s1 - next) : plan[J + 1].nb;
-            }
-            const size_t t0 = next + la_w;
             if (!boundary) {
                 if (ev_mid) (void)hipStreamWaitEvent(main_stream, ev_mid, 0);
                 rc = update_columns(s, j, w, next, t0);  // LA_j on main
@@ -2632,7 +2456,7 @@ static int getrf_super(LuState& s, size_t kmin) {
                         if (iprep && multi) {
                             rc = iprep_columns(s, S0, j, w, t0, S1n);
                             // the second panel's columns first: the main stream's next look-ahead update waits for these only
-                            const size_t nbn = plan[J + 1].nb, t1 = (pknobs.iprep_split && t0 + nbn < S1n) ? t0 + nbn : S1n;
+                            const size_t t1 = plan.iprep_cut(J, t0);
                             if (rc == RMHIP_OK) rc = gemm_columns(s, S0, W, t0, t1);
                             if (rc == RMHIP_OK && t1 < S1n) {
                                 ev_mid = record(mid);
@@ -2659,7 +2483,7 @@ static int getrf_super(LuState& s, size_t kmin) {
                     StreamScope scope(c, far, kSidePad);
                     ev_far_next = nullptr;
                     if (S1n < s.cols) {
-                        const size_t cn = S1nn < s.cols ? S1nn : s.cols;
+                        const size_t cn = plan.far_cut(J, s.cols);
                         // (tried: interchange + solve + update of the next super-panel's columns first, then the rest's - a second
                         // 31-launch solve per boundary on this stream: 69.4 -> 73.8 ms; the far stream is the bottleneck of the first phase)
                         rc = prep_columns(s, S0, W, S1n, s.cols);
@@ -2673,7 +2497,6 @@ static int getrf_super(LuState& s, size_t kmin) {
                 }
                 ev_far_all = record(far);
             }
-            j = next;
         }
     }
     s.panel_pad_kb = -1;
@@ -2721,9 +2544,13 @@ __global__ void k_lu_fold_status(const int* __restrict__ info, const unsigned lo
 int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda, int* perm_dev, int* info_host,
                      std::vector<int>* ipiv_host, int mode, double* ipiv_dev_f64, double* deferred_guard) {
     const size_t kmin = rows < cols ? rows : cols;
-    if (rows > 0x7fffffffULL || cols > 0x7fffffffULL) return fail(RMHIP_ERR_UNSUPPORTED, "lu: dimension exceeds 2^31");
-    c->lu_used_one_xcd = false;
     const LuKnobs knobs = lu_knobs();
+    LuProblem problem;
+    problem.rows = rows, problem.cols = cols, problem.mode = mode, problem.deferred_guard = deferred_guard != nullptr;
+    const LuSite site = lu_site(c);
+    const LuRoute route = plan_lu_factor(problem, site, knobs, lu_process_knobs());  // which driver, which panels: lu_plan.h
+    if (route.unsupported) return fail(RMHIP_ERR_UNSUPPORTED, "%s", route.unsupported);
+    c->lu_used_one_xcd = false;
     // one device block: ipiv[rows] | info | pos_of | row_at | prow | panel lists | cand_abs[2*MAXB] | cand_pos | cand_row
     const size_t n_int = rows + 4;
     const size_t isz = (rows * sizeof(int) + 15) & ~(size_t)15;
@@ -2753,27 +2580,19 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
     panel_start.reserve(max_panels);
     LuState s{c, A, rows, cols, lda, ipiv, info, (int*)(blk + off_posof), (int*)(blk + off_rowat), (int*)(blk + off_prow),
               (int2*)(blk + off_plist), &panel_start, (double*)(blk + off_abs), (int*)(blk + off_pos), (int*)(blk + off_row),
-              (int*)(blk + off_xctl + 16), (unsigned long long*)(blk + off_xa), (unsigned long long*)(blk + off_xvals), 0u, true,
-              nullptr};
-    {
-        // persistent panels need all their blocks co-resident (18.5 KiB of LDS and 270 VGPRs per 4-wave block: at most one
-        // per CU beside a dgemm block, so up to num_cus blocks)
-        if (knobs.panel_columns || c->lu_conservative) s.persistent = false;  // RMHIP_LU_PANEL=columns: the one-launch-per-column kernels
-        if (knobs.panel_debug) s.xdbg = (unsigned long long*)(blk + off_xctl + 64);
-        // solve path: RMHIP_LU_FAST=0 keeps the grid-wide pivot rule everywhere; RMHIP_LU_TAU sets the multiplier bound
-        s.fast = mode == 1 && knobs.fast && s.persistent;
-        c->lu_last_fast = s.fast;  // the caller counts solve-path factorisations on what actually ran (rmhip_lu_stats)
-        s.tau = knobs.tau;
-        c->lu_tau = s.tau;
-        s.ucomp = (double*)(blk + off_ucomp);
-        s.growth = (unsigned long long*)(blk + off_xctl + 32);
-        if (deferred_guard) s.screened = true;  // no early read of the first panel's multipliers: the caller's guard sees them at the end
-        // a driver that runs updates on a stream of its own beside this factorisation (csrc/sharded.cpp) lends its yield table: k_rp_top
-        // counts itself in and that stream's eight-wave blocks on its CU pause (the two-level driver below installs its own)
-        if (c->ext_yield_tab) s.yield_word = c->ext_yield_tab;
-        // matrix-core triangular solves with k_rp_top's inverted diagonal blocks: every base panel must be 64 columns wide
-        if (s.fast && lu_process_knobs().trsm_mfma && !s.xdbg) s.linv = (double*)(blk + off_linv);
-    }
+              (int*)(blk + off_xctl + 16), (unsigned long long*)(blk + off_xa), (unsigned long long*)(blk + off_xvals), 0u, nullptr};
+    s.route = route;
+    s.site = site;
+    if (knobs.panel_debug) s.xdbg = (unsigned long long*)(blk + off_xctl + 64);
+    c->lu_last_fast = route.fast;  // the caller counts solve-path factorisations on what actually ran (rmhip_lu_stats)
+    c->lu_tau = route.tau;
+    s.ucomp = (double*)(blk + off_ucomp);
+    s.growth = (unsigned long long*)(blk + off_xctl + 32);
+    s.screened = !route.screen;  // deferred guard: no early read of the first panel's multipliers, the caller's guard sees them at the end
+    // a driver that runs updates on a stream of its own beside this factorisation (csrc/sharded.cpp) lends its yield table: k_rp_top
+    // counts itself in and that stream's eight-wave blocks on its CU pause (the two-level driver installs its own)
+    if (c->ext_yield_tab) s.yield_word = c->ext_yield_tab;
+    if (route.use_linv) s.linv = (double*)(blk + off_linv);
     std::vector<unsigned char> linv_ok(rows / 16 + 8, 0);
     struct LinvScope {  // the solves find the inverses through the context while this factorisation runs
         Context* c;
@@ -2790,35 +2609,23 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
         c->lu_work = A;
         c->lu_work_ld = lda;
     }
-    // Panel width of the look-ahead driver and its threshold, from an interleaved sweep (scripts/lu_knobs.py, ms for
-    // x = A\b): n = 6144: 38.7 without look-ahead, 33.6 with nb 128, 34.9 with 256, 36.8 with 512; 8192: 51.2 (nb 512)
-    // / 48.4 (256) / 47.2 (128); 10240: 67.3 / 63.4 / 62.2; 12288: 84.7 / 80.6 / 81.2; 16384: 130.8 / 130.7 / -;
-    // 5120: 31.6 without, 27.9 with; 4096: 22.2 without, 22.6-24 with.
-    size_t nb = knobs.nb >= 0 ? (size_t)knobs.nb : (kmin < 12288 ? 128 : 256);
-    nb = nb < 64 ? 64 : (nb / 64) * 64;
-    // Look-ahead (second stream): default from kmin = 5120; RMHIP_LU_LOOKAHEAD=1 forces it for every kmin > nb, =0
-    // disables it.  It needs the persistent panels: with one launch per column the panel kernels wait behind the
-    // update's dgemm blocks.
-    // Solve path (one-workgroup panels: nothing has to be co-resident, and the chain is all there is at these sizes): from 1152 -
-    // n = 1280 3.30 -> 2.52 ms, 1536 3.63 -> 2.95, 2048 4.30 -> 3.91, 3072 8.06 -> 5.98, 4096 9.92 -> 8.17 (5120: 16.9 without,
-    // 10.6 with; 1024: 2.03 / 2.00).
-    bool blocked = kmin >= (s.fast ? 1152u : 5120u) && kmin > nb;
-    if (knobs.lookahead >= 0) blocked = kmin > nb && knobs.lookahead == 1;
-    if (!s.persistent) blocked = false;
     // Under look-ahead the panels keep 256-row blocks (132 KiB of LDS: a whole CU).  The update stream's dgemm runs one
     // block per CU (84 KiB) at low priority, so a CU is empty whenever its dgemm block retires and the waiting panel
     // block (main stream, higher priority) takes it: all blocks are resident after about one dgemm-block time
     // (~55 us) and the bounded spins absorb that.  128-row blocks (66 KiB) fit BESIDE a dgemm block and start at
     // once, but twice as many blocks make every exchange slower: measured 145.8 ms against 129.0 ms at n = 16384.
-    // two-level driver (super-panels) on the solve path from kmin = 8192 (RMHIP_LU_SUPER=0: the one-level driver)
-    constexpr size_t kSuperMin = 8192;
-    const bool super = blocked && s.fast && lu_process_knobs().super && kmin >= kSuperMin;
-    int rc = super ? getrf_super(s, kmin) : (blocked ? getrf_blocked(s, kmin, nb) : getrf_rec(s, 0, kmin));
+    int rc = RMHIP_OK;
+    switch (route.driver) {
+        case LuDriver::super: rc = getrf_super(s, kmin); break;
+        case LuDriver::blocked: rc = getrf_blocked(s, kmin); break;
+        case LuDriver::rec: rc = getrf_rec(s, 0, kmin); break;
+    }
+    const bool blocked = route.driver != LuDriver::rec;
     if (rc == RMHIP_OK && cols > rows && !blocked) {  // wide: finish U's right block (the blocked driver covers it)
         rc = laswp(s, rows, cols, 0, rows);
         if (rc == RMHIP_OK) rc = trsm_lower_rec(c, A, lda, rows, A + rows * lda, lda, cols - rows);
     }
-    if (rc == RMHIP_OK && deferred_guard && s.fast && !s.xdbg) {
+    if (rc == RMHIP_OK && deferred_guard && s.route.fast && !s.xdbg) {
         // Deferred checks (a panel of a larger factorisation whose driver has a guard of its own - csrc/sharded.cpp): nothing is read
         // back; the interchange vector goes out as a device tensor, the status words into the caller's guard value.  Everything above
         // and these two launches are queued on the context's stream: the workspace block goes back to the pool stream-ordered.
@@ -2837,22 +2644,22 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
         unsigned long long h_growth = 0;
         e = hipMemcpyAsync(h_ipiv.data(), ipiv, sizeof(int) * (rows + 1), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&h_xerr, s.xerr, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && s.fast) e = hipMemcpyAsync(&h_growth, s.growth, sizeof(h_growth), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && s.route.fast) e = hipMemcpyAsync(&h_growth, s.growth, sizeof(h_growth), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(RMHIP_ERR_HIP, "lu: reading pivots: %s", hipGetErrorString(e));
-        if (e == hipSuccess && s.fast) {
+        if (e == hipSuccess && s.route.fast) {
             double gmax;
             std::memcpy(&gmax, &h_growth, sizeof(gmax));
             c->lu_last_growth = gmax;
             // a multiplier beyond tau, a NaN, or a pivot at the singular cut-off inside a top block (a larger entry may lie below it)
-            if (!(gmax <= s.tau) || h_ipiv[rows] > 0 || knobs.test_growth) {
+            if (!(gmax <= s.route.tau) || h_ipiv[rows] > 0 || knobs.test_growth) {
                 if (knobs.verbose)
                     std::fprintf(stderr, "[lu] solve path: max multiplier %.3g (tau %.3g), %d small pivot(s): refactoring with the grid-wide rule\n", gmax,
-                                 s.tau, h_ipiv[rows]);
+                                 s.route.tau, h_ipiv[rows]);
                 return RMHIP_LU_GROWTH;
             }
         }
-        if (!h_xerr && s.persistent && knobs.test_retry) h_xerr = 1;  // test hook for the retry path
+        if (!h_xerr && s.route.persistent && knobs.test_retry) h_xerr = 1;  // test hook for the retry path
         if (e == hipSuccess && h_xerr) {
             c->lu_exchange_timeouts++;
             // bounded spins expired: the panel workgroups were not co-resident (device shared with another
@@ -2877,7 +2684,7 @@ int lu_factor_device(Context* c, double* A, size_t rows, size_t cols, size_t lda
                 static const char* names_top[16] = {"load", "candidate", "barrier", "winner+window", "park", "barrier", "g solve", "rank-8",
                                                     "store+shift", "below: stage U", "below: load", "below: triangle", "below: stores", "below: rank-8",
                                                     "below: tail", "-"};
-                const char* const* names = s.fast ? names_top : names_grid;
+                const char* const* names = s.route.fast ? names_top : names_grid;
                 for (int i = 0; i < 15; ++i)
                     std::fprintf(stderr, "[lu panel] %-12s %10.1f us total  %7.3f us/column\n", names[i], h[i] * 0.01,
                                  kmin ? h[i] * 0.01 / (double)kmin : 0.0);
@@ -3170,7 +2977,6 @@ __global__ void __launch_bounds__(256) k_gather_rows(const double* __restrict__ 
 // one or two columns; at n = 16384 that substitution cost ~25 ms for 2 n^2 flop (measured).  Here every
 // 128-row diagonal block is one k_trsm_fused launch followed by one k_rhs_update launch that streams the
 // block column below (lower) / above (upper) it once: X[rest, :] -= T[rest, blk] * X[blk, :].
-static constexpr int RU_MAX_RHS = 8;
 static constexpr int RU_ROWS = 64;   // rows per block
 static constexpr int RU_KG = 4;      // k groups per row (partial sums meet in LDS)
 template <int NRHS>
@@ -3470,20 +3276,18 @@ static int launch_subst_chain(Context* c, const double* LU, size_t lda, size_t n
     return launch_check(c);
 }
 
-static int substitute_few_rhs(Context* c, const double* LU, size_t n, size_t lda, double* X, size_t ldx, size_t nrhs) {
-    // One launch per direction (k_subst_chain) when the system is big enough for the launches to matter and the chain's
-    // workgroups (one per 128 rows) fit the chip; RMHIP_LU_SUBST=pair keeps the launch-per-block form.
-    const LuKnobs knobs = lu_knobs();
-    const int chain = knobs.subst_pair ? 0 : 1;
-    const size_t nblk_chain = (n + TRSM_W - 1) / TRSM_W;
-    if (chain && nblk_chain >= 4 && nblk_chain <= (size_t)c->num_cus && !c->subst_chain_failed) {
+// at most RU_MAX_RHS right-hand sides: one launch per direction (SubstForm::chain) or one pair of launches per block (pair)
+static int substitute_few_rhs(Context* c, const SubstRoute& route, const LuKnobs& knobs, const double* LU, size_t n, size_t lda, double* X, size_t ldx,
+                              size_t nrhs) {
+    const size_t nblk_chain = route.nblk;
+    if (route.form == SubstForm::chain) {
         std::shared_ptr<Allocation> ctl;  // flags of both directions + the error word, pooled
         RMHIP_TRY(c->alloc_device(nblk_chain + 2, &ctl));
         unsigned* flags = (unsigned*)ctl->ptr;
         int* err = (int*)(flags + 2 * nblk_chain);
         RMHIP_HIP_CHECK(hipMemsetAsync(flags, 0, (2 * nblk_chain + 1) * sizeof(unsigned), c->stream));
-        for (size_t q0 = 0; q0 < nrhs; q0 += 4) {
-            const size_t nq = nrhs - q0 < 4 ? nrhs - q0 : 4;
+        for (size_t q0 = 0; q0 < nrhs; q0 += route.group) {
+            const size_t nq = nrhs - q0 < route.group ? nrhs - q0 : route.group;
             if (q0) RMHIP_HIP_CHECK(hipMemsetAsync(flags, 0, 2 * nblk_chain * sizeof(unsigned), c->stream));
             RMHIP_TRY(launch_subst_chain<0>(c, LU, lda, n, X + q0 * ldx, ldx, nq, flags, err));
             RMHIP_TRY(launch_subst_chain<2>(c, LU, lda, n, X + q0 * ldx, ldx, nq, flags + nblk_chain, err));
@@ -3504,8 +3308,7 @@ static int substitute_few_rhs(Context* c, const double* LU, size_t n, size_t lda
         RMHIP_TRY(launch_rhs_update(c, LU + (ib + w) + ib * lda, lda, n - ib - w, w, X + ib, X + ib + w, ldx, nrhs));
     }
     // backward: upper, last block first (blocks aligned to multiples of TRSM_W from the top)
-    const size_t nblk = (n + TRSM_W - 1) / TRSM_W;
-    for (size_t bi = nblk; bi-- > 0;) {
+    for (size_t bi = route.nblk; bi-- > 0;) {
         const size_t ib = bi * TRSM_W;
         const size_t w = (n - ib) < (size_t)TRSM_W ? (n - ib) : (size_t)TRSM_W;
         RMHIP_TRY(launch_trsm_fused<2>(c, LU + ib + ib * lda, lda, w, X + ib, ldx, nrhs));
@@ -3516,7 +3319,7 @@ static int substitute_few_rhs(Context* c, const double* LU, size_t n, size_t lda
 
 // W (np x np, ld ldw) holds an n x n matrix in its top-left corner: make the rest [0; 0 I] - the padded system [A 0; 0 I] has the
 // factors of A in its leading block, the padded rows are never chosen as pivots for A's columns (zeros there) and the padded
-// unknowns come out zero.  Used by the solves for n that is not a multiple of 128 (solve.cpp: lu_pad_rows).
+// unknowns come out zero.  Used by the solves for n that is not a multiple of 128 (lu_plan.h: lu_pad_rows).
 __global__ void __launch_bounds__(256) k_lu_pad_identity(double* __restrict__ W, size_t ldw, size_t n, size_t np) {
     const size_t pad = np - n;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;  // row 0 .. np-1
@@ -3530,7 +3333,7 @@ __global__ void __launch_bounds__(256) k_lu_pad_identity(double* __restrict__ W,
 }
 int lu_pad_identity_device(Context* c, double* W, size_t ldw, size_t n, size_t np) {
     if (np <= n) return RMHIP_OK;
-    if (np > 65535) {  // blockIdx.y
+    if (np > kPadMaxOrder) {  // blockIdx.y
         return fail(RMHIP_ERR_UNSUPPORTED, "lu padding: dimension %zu too large", np);
     }
     hipLaunchKernelGGL(k_lu_pad_identity, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, c->stream, W, ldw, n, np);
@@ -3540,7 +3343,15 @@ int lu_pad_identity_device(Context* c, double* W, size_t ldw, size_t n, size_t n
 // The substitutions alone, on X = P B (common.h).  RMHIP_SUBST_RETRY: X is clobbered, the caller gathers again and calls once more.
 int lu_substitute_device(Context* c, const double* LU, size_t n, size_t lda, double* X, size_t nrhs, size_t ldx) {
     if (n == 0 || nrhs == 0) return RMHIP_OK;
-    if (nrhs <= (size_t)RU_MAX_RHS && !(lu_process_knobs().skip & 16)) return substitute_few_rhs(c, LU, n, lda, X, ldx, nrhs);
+    // (the per-call knobs are read only where the few-column kernels can serve: subst_pair and the test hook matter nowhere else)
+    const bool few = nrhs <= (size_t)RU_MAX_RHS && !(lu_process_knobs().skip & 16);
+    const LuKnobs knobs = few ? lu_knobs() : LuKnobs{};
+    const SubstRoute route = plan_substitute(n, nrhs, c->num_cus, knobs.subst_pair, c->subst_chain_failed, !few);
+    switch (route.form) {
+        case SubstForm::chain:
+        case SubstForm::pair: return substitute_few_rhs(c, route, knobs, LU, n, lda, X, ldx, nrhs);
+        case SubstForm::rec: break;
+    }
     RMHIP_TRY(trsm_lower_rec(c, LU, lda, n, X, ldx, nrhs));
     return trsm_upper_rec(c, LU, lda, n, X, ldx, nrhs);
 }

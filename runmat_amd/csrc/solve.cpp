@@ -61,17 +61,6 @@ int rmhip::lu_copy_and_factor(Context* c, const double* src, size_t rows, size_t
 
 size_t rmhip::lu_padded_ld(size_t rows) { return rows >= 256 ? ((rows + 1) & ~(size_t)1) + 32 : ((rows + 1) & ~(size_t)1); }
 
-// Order the solves factor at.  The blocked driver's trailing updates are whole 128 x 128 x 16 tiles only when n is a multiple of
-// 128; otherwise EVERY update of the factorisation runs a guarded kernel (n = 10000: 37.0 ms against 31.7 at 10240, n = 13001: 55.6
-// against 47.2 at 13056).  The solves therefore factor [A 0; 0 I] at the next multiple of 128 - 2-4 % more flops, all of them on
-// the fast kernels - and drop the padded unknowns (zero).  `lu` itself returns factors of the order it was given.
-// RMHIP_LU_PAD=0 disables (read per call: the tests compare both forms).
-static size_t lu_pad_rows(size_t n) {
-    constexpr size_t kPadMin = 2048;
-    if (!lu_knobs().pad || n < kPadMin || n % 128 == 0) return n;
-    const size_t np = (n + 127) / 128 * 128;
-    return np <= 65535 ? np : n;
-}
 // X (n x nrhs, ld n) = A^-1 B from factors of order np >= n (np > n: the padded system)
 static int lu_solve_padded(Context* c, const double* LU, size_t n, size_t np, size_t ldw, const int* perm, const double* B, size_t nrhs, double* X) {
     if (nrhs == 0) return RMHIP_OK;  // (a zero-height hipMemcpy2DAsync is hipErrorInvalidValue)
@@ -264,7 +253,7 @@ static int solve_square_general(rmhip_ctx* ctx, Context* c, SolvePolicy p, const
     // Factorisation workspace with a PADDED leading dimension: with lda a large power of two every
     // element of a row maps to the same HBM channel / L2 slice, and the panel kernels (one lane per
     // row, walking across columns) serialise on it; +32 doubles rotates the channel per column.
-    const size_t np = lu_pad_rows(n);  // order of the factorisation (the next multiple of 128 for a large ragged n)
+    const size_t np = lu_pad_rows(n, lu_knobs().pad);  // order of the factorisation (the next multiple of 128 for a large ragged n)
     const size_t ldw = lu_padded_ld(np);
     std::shared_ptr<Allocation> work, perm_mem;  // pooled, released in stream order
     RMHIP_TRY(c->alloc_device(ldw * np, &work));

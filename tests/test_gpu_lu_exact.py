@@ -4,43 +4,48 @@ a skipped update, a wrong entry of an inverted block, two mis-ordered rows or a 
 a residual below a tolerance.  No U(-1,1) data, no tolerances, no residuals here; the comparisons are `lu_exact_ref.mismatches`
 (uint64 views; only the sign of a computed zero is free, see that module).
 
-THE TABLE.  One row per case: what it runs, the path it is meant to reach and the dispatch condition that sends it there
-(lu.hip / solve.cpp / small_solve.hip line numbers as of this change).  `lu_stats` cannot tell which kernel ran; the cited conditions
-are the evidence.  Kernels named as reached:
-  k_lu_panel2        rows rec-*, lookahead-*, rect-*, perm-* of LU_TABLE (lu.hip:2076: persistent panels, the default of `lu`)
-  k_lu_col           rows columns-* and perm-*-columns (lu.hip:2761 RMHIP_LU_PANEL=columns -> !persistent -> lu.hip:2124-2136)
-  k_build_plist      the same rows (lu.hip:2140)
-  k_rp_top           every blocked solve: the rows of SOLVE_TABLE with n > 64 or nrhs > 16 (lu.hip:2006 s.fast, set at lu.hip:2764 for mode 1)
-  k_rp_below         solves with rows below a top block and a base panel that is not 64 wide - 300, 513, 1151, 1153 - and every panel
-                     under RMHIP_LU_RB_MFMA=0 (lu.hip:2024 below_mfma = rb_mfma && w == 64, lu.hip:2040-2050)
-  k_rp_below_mfma    solves of order 1152, 1280, 2100 (padded to 2176), 2176, 8192: 64-wide base panels with rows below (lu.hip:2042)
-  k_laswp_lists      every `lu` and blocked solve (lu.hip:1964); empty lists under the identity permutation, full ones under the reversal
-  k_trsm_fused       MODE 0: `lu` of order > 64 outside the look-ahead driver, and ragged blocks (lu.hip:1811-1823); MODE 1 / 2: linsolve's
-                     triangular hints (lu.hip:3063-3070) and the substitution in pairs (lu.hip:3500-3513: n < 385, RMHIP_LU_SUBST=pair)
+THE TABLE.  One row per case: what it runs and the path it is meant to reach, named by the rule of runmat_amd/csrc/lu_plan.h that sends it
+there.  `lu_stats` cannot tell which kernel ran; the rules are the evidence, and tests/test_lu_exact_host.py checks every claim of the
+tables below against them (tests/cpp/lu_route_check.cpp --table plans each row as the drivers do).  Kernels named as reached:
+  k_lu_panel2        rows rec-*, lookahead-*, rect-*, perm-* of LU_TABLE (plan_base_panel: PanelKind::persistent, the default of `lu`)
+  k_lu_col           rows columns-* and perm-*-columns (plan_lu_factor: RMHIP_LU_PANEL=columns -> !persistent -> PanelKind::columns)
+  k_build_plist      the same rows
+  k_rp_top           every blocked solve: the rows of SOLVE_TABLE with n > 64 or nrhs > 16 (plan_lu_factor: fast for mode 1 ->
+                     PanelKind::top)
+  k_rp_below         solves with rows below a top block under a base panel that is not 64 wide - 300, 1151 - and every panel with rows
+                     below under RMHIP_LU_RB_MFMA=0 (plan_base_panel: inverses = rb_mfma && w == 64, PanelBelow::valu); SOLVE_REACH
+  k_rp_below_mfma    solves of order 257, 513, 1151, 1152, 1153, 1280, 2100 (padded to 2176), 2176, 8192: 64-wide base panels with rows
+                     below (PanelBelow::mfma); SOLVE_REACH
+  k_laswp_lists      every `lu` and blocked solve; empty lists under the identity permutation, full ones under the reversal
+  k_trsm_fused       MODE 0: `lu` of order > 64, and ragged blocks (plan_trsm: TrsmKernel::fused); MODE 1 / 2: linsolve's triangular
+                     hints and the substitution in pairs (plan_substitute: SubstForm::pair - n < 385, RMHIP_LU_SUBST=pair)
   k_trsm_lower_2p    the look-ahead driver without inverses, 65..128-wide blocks: rows lookahead-* with RMHIP_LU_NB >= 128, and
-                     RMHIP_LU_TRSM_MFMA=0 behind a solve of order >= 1152 (lu.hip:1800)
-  k_trsm_lower_mfma  solves of order 1152, 1280, 2176, 8192: <4> inside a 128-wide panel's recursion, <8> in the drivers (lu.hip:1827-1838)
-  k_gather_rows      every blocked solve (lu.hip:3556)
-  k_rhs_update       substitution in pairs (lu.hip:3504, 3512)
-  k_subst_chain<0/2> n >= 385 with nrhs <= 8 (lu.hip:3479: four or more 128-row blocks; lu.hip:3485: groups of four columns - nrhs 5 is
-                     4 + 1, nrhs 8 is 4 + 4); nrhs > 8 takes trsm_lower_rec / trsm_upper_rec with a dgemm in between (lu.hip:3543-3545)
-  k_lu_pad_identity  order 2100 (solve.cpp:69-73: n >= 2048 and not a multiple of 128 factors at 2176; RMHIP_LU_PAD=0 does not)
-  k_lu_extract       every `lu` (solve.cpp:354)
-  small_solve.hip    2 <= n <= 64 with nrhs <= 16 (small_solve.hip:202, solve.cpp:249)
-  getrf_super        order 8192 on the solve path (lu.hip:2814-2815), one child process per plan
-Not reachable from these entry points: k_permute_rows, k_permute_rows_dev and k_compose_swaps serve rmhip_blk_swap_rows only
-(solve.cpp:708-731), a building block of the row-partitioned driver, which is out of scope here.
+                     RMHIP_LU_TRSM_MFMA=0 behind a solve of order >= 1152 (plan_trsm: TrsmKernel::two_pass)
+  k_trsm_lower_mfma  solves from order 129: <4> inside a 128-wide panel's recursion, <8> on 128-wide diagonal blocks (plan_trsm:
+                     mfma4 / mfma8 once the inverses of the block are queued); SOLVE_REACH
+  k_gather_rows      every blocked solve
+  k_rhs_update       substitution in pairs
+  k_subst_chain<0/2> n >= 385 with nrhs <= 8 (plan_substitute: four or more 128-row blocks, in groups of four columns - nrhs 5 is
+                     4 + 1, nrhs 8 is 4 + 4); nrhs > 8 takes trsm_lower_rec / trsm_upper_rec with a dgemm in between (SubstForm::rec)
+  k_lu_pad_identity  order 2100 (lu_pad_rows: n >= 2048 and not a multiple of 128 factors at 2176; RMHIP_LU_PAD=0 does not)
+  k_lu_extract       every `lu` (solve.cpp)
+  small_solve.hip    2 <= n <= 64 with nrhs <= 16 (small_solve_applies)
+  getrf_super        order 8192 on the solve path (plan_lu_factor: kSuperMin), one child process per plan
+Not reachable from these entry points: k_permute_rows, k_permute_rows_dev and k_compose_swaps serve rmhip_blk_swap_rows only, a building
+block of the row-partitioned driver, which is out of scope here.
 
-Shapes the dispatch sends elsewhere than one might expect:
-  * RMHIP_LU_NB=256 below 8192 + 128 remaining columns runs 128-wide panels (lu.hip:2306, 2316: nb_late = min(nb, 128)); what NB=256
-    changes at these orders is only the `kmin > nb` test of lu.hip:2806.
-  * 64 x 700 and 700 x 64 have kmin = 64 = the smallest nb, so a forced look-ahead still takes getrf_rec (lu.hip:2806) and the wide
-    one its laswp + trsm_lower_rec tail (lu.hip:2817-2820); 200 x 330 and 330 x 200 do reach getrf_blocked with RMHIP_LU_NB=64.
-  * linsolve refuses 1 x 1 operands (solve.cpp:459: the CPU path), so the triangular hints start at n = 2 and n = 1 is asserted to raise.
-  * mrdivide(B', A') transposes both operands back (solve.cpp:431-436): it factors A itself, so the transposed system U' L' P never
+Shapes the dispatch sends elsewhere than one might expect (the first three and the last are asserted against the plan by
+tests/test_lu_exact_host.py):
+  * RMHIP_LU_NB=256 below 8192 + 128 remaining columns runs 128-wide panels (plan_blocked: nb_late = min(nb, kNbLate)); what NB=256
+    changes at these orders is only the `kmin > nb` test of plan_lu_factor.
+  * 64 x 700 and 700 x 64 have kmin = 64 = the smallest nb, so a forced look-ahead still takes getrf_rec (plan_lu_factor) and the wide
+    one its laswp + trsm_lower_rec tail (lu_factor_device).
+  * 200 x 330 and 330 x 200 do reach getrf_blocked with RMHIP_LU_NB=64.
+  * linsolve refuses 1 x 1 operands (solve.cpp: the CPU path), so the triangular hints start at n = 2 and n = 1 is asserted to raise.
+  * mrdivide(B', A') transposes both operands back (solve.cpp): it factors A itself, so the transposed system U' L' P never
     has to be exact; linsolve with `transposed` is fed A' for the same reason.
   * RMHIP_LU_FAST=0 behind a solve runs the grid-wide rule, which the statistics do not count as a solve-path factorisation
-    (solve.cpp:56); n <= 64 then takes the blocked kernels too (solve.cpp:249).
+    (lu_copy_and_factor); n <= 64 then takes the blocked kernels too (solve.cpp).
 
 Order 8192 (operands built on the device, three plans, one child each).  Bit budget from the construction's parameters alone
 (lu_exact_ref.bit_budget_worst_case(8192, 2, 3): every entry at its largest magnitude): form 1 30 bits, form 2 30 bits, form 3 45 bits.
@@ -73,41 +78,51 @@ NB = "RMHIP_LU_NB"
 # ---- 3a: `lu` (grid-wide rule).  (id, rows, cols, per-call environment, permutation, path) ------------------------------------------------
 LU_TABLE = []
 for _n in (1, 2, 17, 63, 64, 65, 130, 255, 256, 257, 513, 700, 1153):
-    # getrf_rec (lu.hip:2816: `lu` is mode 0, look-ahead only from 5120) -> k_lu_panel2; 1..64 one base panel, 65 / 130 ragged halves
-    # (lu.hip:2145: h = w/2 rounded up to 16), 255..257 one / two 256-row panel blocks (lu.hip:2005), 1153 recursion depth 5
+    # getrf_rec (plan_lu_factor: `lu` is mode 0, look-ahead only from kBlockedMin) -> k_lu_panel2; 1..64 one base panel, 65 / 130 ragged
+    # halves (rec_split: h = w/2 rounded up to 16), 255..257 one / two 256-row panel blocks (plan_base_panel), 1153 recursion depth 5
     LU_TABLE.append((f"rec-{_n}", _n, _n, {}, "random", "getrf_rec + k_lu_panel2"))
 for _n in (17, 65, 257, 700):
     LU_TABLE.append((f"columns-{_n}", _n, _n, {"RMHIP_LU_PANEL": "columns"}, "random", "getrf_rec + k_lu_col + k_build_plist"))
 for _n, _nb in ((200, 64), (300, 64), (300, 128), (700, 128), (700, 256), (1153, 64), (1153, 256)):
-    # getrf_blocked forced (lu.hip:2806); 200 with 64-wide panels ends in an 8-column panel; nb >= 128: k_trsm_lower_2p (lu.hip:1800)
-    LU_TABLE.append((f"lookahead-{_n}-nb{_nb}", _n, _n, {LA: "1", NB: str(_nb)}, "random", "getrf_blocked"))
+    # getrf_blocked forced (plan_lu_factor: lookahead); 200 with 64-wide panels ends in an 8-column panel; nb >= 128: k_trsm_lower_2p
+    # (plan_trsm)
+    LU_TABLE.append((f"lookahead-{_n}-nb{_nb}", _n, _n, {LA: "1", NB: str(_nb)}, "random",
+                     "getrf_blocked" + (" + k_trsm_lower_2p" if _nb >= 128 else "")))
 for _r, _c in ((200, 330), (330, 200), (64, 700), (700, 64)):
-    LU_TABLE.append((f"rect-{_r}x{_c}-rec", _r, _c, {}, "random", "getrf_rec" + (" + wide tail lu.hip:2817" if _c > _r else "")))
+    LU_TABLE.append((f"rect-{_r}x{_c}-rec", _r, _c, {}, "random", "getrf_rec" + (" + wide tail" if _c > _r else "")))
     LU_TABLE.append((f"rect-{_r}x{_c}-la", _r, _c, {LA: "1", NB: "64"}, "random",
-                     "getrf_blocked" if min(_r, _c) > 64 else "getrf_rec (kmin = nb)"))
+                     "getrf_blocked" if min(_r, _c) > 64 else "getrf_rec" + (" + wide tail" if _c > _r else "")))  # 64: kmin = nb
 for _kind in ("identity", "reverse"):
     # empty row-move lists / full 64-entry lists in k_laswp_lists (and k_build_plist under columns)
     LU_TABLE.append((f"perm-{_kind}-300", 300, 300, {}, _kind, "getrf_rec"))
     LU_TABLE.append((f"perm-{_kind}-300-columns", 300, 300, {"RMHIP_LU_PANEL": "columns"}, _kind, "k_lu_col + k_build_plist"))
-    LU_TABLE.append((f"perm-{_kind}-700-la", 700, 700, {LA: "1", NB: "128"}, _kind, "getrf_blocked"))
+    LU_TABLE.append((f"perm-{_kind}-700-la", 700, 700, {LA: "1", NB: "128"}, _kind, "getrf_blocked + k_trsm_lower_2p"))
 
 # ---- 3b: the solves.  (n, nrhs) ----------------------------------------------------------------------------------------------------------------
-# 2..64: small_solve.hip; 65..1151: getrf_rec on the solve path (lu.hip:2805); 1152..: getrf_blocked; 2100: padded to 2176; nrhs 1, 3:
-# one chain / pair group, 5: 4 + 1, 8: 4 + 4, 16 / 17: trsm_*_rec (lu.hip:3543) and, at n <= 64, 16 the small solver's last width and 17
-# the first that leaves it (small_solve.hip:202)
+# 2..64: small_solve.hip; 65..1151: getrf_rec on the solve path (plan_lu_factor: kBlockedMinFast); 1152..: getrf_blocked; 2100: padded to
+# 2176; nrhs 1, 3: one chain / pair group, 5: 4 + 1, 8: 4 + 4, 16 / 17: trsm_*_rec (plan_substitute) and, at n <= 64, 16 the small
+# solver's last width and 17 the first that leaves it (small_solve_applies)
 SOLVE_ORDERS = (2, 17, 33, 64, 65, 129, 255, 257, 300, 513, 1151, 1152, 1153, 1280, 2100, 2176)
 SOLVE_TABLE = [(n, 1) for n in SOLVE_ORDERS] + [(17, 3), (33, 16), (33, 17), (64, 5), (64, 16), (64, 17), (65, 5), (300, 3), (300, 5),
                                                 (300, 8), (300, 17), (513, 5), (513, 8), (513, 16), (1153, 3), (1153, 5), (1153, 17),
                                                 (1280, 5), (1280, 8), (2100, 5), (2176, 17)]
+# which orders of SOLVE_ORDERS above 64 reach which kernel under the default knobs - these and no others
+SOLVE_REACH = {
+    "k_rp_below": (300, 1151),
+    "k_rp_below_mfma": (257, 513, 1151, 1152, 1153, 1280, 2100, 2176),
+    "k_trsm_lower_mfma<4>": (129, 255, 257, 513, 1151, 1152, 1153, 1280, 2100, 2176),
+    "k_trsm_lower_mfma<8>": (255, 257, 513, 1152, 1153, 1280, 2100, 2176),
+    "k_trsm_lower_2p": (),
+}
 # per-call knobs (lu_knobs(), solve_knobs(): read at every call).  (knob, [(n, nrhs)])
 KNOB_TABLE = [
-    ({"RMHIP_LU_FAST": "0"}, [(17, 1), (64, 3), (300, 5), (1153, 1), (2100, 5)]),         # grid-wide rule behind a solve (lu.hip:2764)
-    ({"RMHIP_NO_SMALL_SOLVE": "1"}, [(2, 1), (17, 3), (33, 16), (64, 1), (64, 5)]),       # blocked kernels at n <= 64 (solve.cpp:249)
-    ({"RMHIP_LU_SUBST": "pair"}, [(513, 1), (513, 5), (1153, 3), (1280, 8), (2100, 5)]),   # k_trsm_fused + k_rhs_update (lu.hip:3477)
+    ({"RMHIP_LU_FAST": "0"}, [(17, 1), (64, 3), (300, 5), (1153, 1), (2100, 5)]),         # grid-wide rule behind a solve (plan_lu_factor: fast)
+    ({"RMHIP_NO_SMALL_SOLVE": "1"}, [(2, 1), (17, 3), (33, 16), (64, 1), (64, 5)]),       # blocked kernels at n <= 64 (solve.cpp)
+    ({"RMHIP_LU_SUBST": "pair"}, [(513, 1), (513, 5), (1153, 3), (1280, 8), (2100, 5)]),   # k_trsm_fused + k_rhs_update (plan_substitute: pair)
     ({"RMHIP_LU_LOOKAHEAD": "0"}, [(1152, 1), (1153, 5), (1280, 3), (2100, 1)]),         # getrf_rec where the default is getrf_blocked
     ({"RMHIP_LU_LOOKAHEAD": "1"}, [(129, 1), (300, 5), (513, 3), (700, 1)]),             # getrf_blocked where the default is getrf_rec
-    ({"RMHIP_LU_PAD": "0"}, [(2100, 1), (2100, 5)]),                                     # ragged order unpadded (solve.cpp:71)
-    ({"RMHIP_LU_TEST_GROWTH": "1"}, [(65, 1), (300, 5), (1153, 3), (2100, 1)]),          # forced refactorisation (lu.hip:2848)
+    ({"RMHIP_LU_PAD": "0"}, [(2100, 1), (2100, 5)]),                                     # ragged order unpadded (lu_pad_rows)
+    ({"RMHIP_LU_TEST_GROWTH": "1"}, [(65, 1), (300, 5), (1153, 3), (2100, 1)]),          # forced refactorisation (lu_factor_device)
 ]
 TRI_ORDERS = (2, 17, 64, 65, 300, 1153)
 TRI_NRHS = (1, 3, 17)
@@ -248,8 +263,8 @@ def test_per_call_knobs_return_the_same_bits(prov, knobs, cases):
 
 @pytest.mark.parametrize("n", TRI_ORDERS)
 def test_linsolve_triangular_hints_return_the_integer_solution(prov, n):
-    """`lower` on the constructed unit-lower L, `upper` on U, and both `transposed` forms (solve.cpp:464-469 swaps the hint): one
-    k_trsm_fused launch up to 128, the recursive halving with dgemm above (lu.hip:1923-1946)."""
+    """`lower` on the constructed unit-lower L, `upper` on U, and both `transposed` forms (solve.cpp swaps the hint): one
+    k_trsm_fused launch up to 128, the recursive halving with dgemm above (trsm_split, trsm_lower_rec / trsm_upper_rec)."""
     from runmat_amd import ProviderLinsolveOptions as Opt
 
     c = lu_case(n, n)
@@ -355,7 +370,7 @@ def test_per_process_switches_return_the_same_bits(built, switches):
 
 @pytest.mark.parametrize("plan", SUPER_PLANS, ids=["default", "super-0", "alternative-plan"])
 def test_two_level_driver_returns_the_integer_solution(built, plan):
-    """n = 8192 (kSuperMin is a constexpr, lu.hip:2814: no smaller order reaches getrf_super), operands built on the device; only the
+    """n = 8192 (kSuperMin is a constexpr of lu_plan.h: no smaller order reaches getrf_super), operands built on the device; only the
     n x 2 solution crosses the bus.  The bit budget holds for every matrix the construction can produce (45 of 53 bits)."""
     budget = ref.bit_budget_worst_case(SUPER_N, SUPER_NRHS, SUPER_XMAX)
     assert max(budget.values()) <= ref.BIT_CAP, budget

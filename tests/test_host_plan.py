@@ -1,6 +1,6 @@
 """Host logic that needs no GPU, checked by small C++ programs over sweeps of shapes: the reduction launch geometry and the
 routing of a shape to its kernel and finalize (reduce_plan.h), the broadcast stride preparation / dimension collapsing of the elementwise entry points
-(host_shape.h), including the in-place addressing of lazy repmat views, and the GEMM dispatch (gemm_plan.h)."""
+(host_shape.h), including the in-place addressing of lazy repmat views, the GEMM dispatch (gemm_plan.h) and the LU dispatch (lu_plan.h)."""
 import subprocess
 from pathlib import Path
 
@@ -38,5 +38,24 @@ def test_gemm_plan_routes_the_sweep_as_the_launchers_ladders_did(tmp_path):
     got = r.stdout.splitlines()
     assert len(want) == 108 and len({ln.rsplit(" ", 2)[0] for ln in want}) == 108  # 2 precisions x (13 sites + 5 knobs) x 3 device sizes
     assert all(int(ln.split()[-2]) == 11 * 11 * 13 * 9 * (7 if ln.startswith("f64") else 3) for ln in want)
+    differing = [(g, w) for g, w in zip(got, want) if g != w]
+    assert len(got) == len(want) and not differing, differing[:5]
+
+
+def test_lu_plan_routes_the_sweep_as_the_drivers_conditions_did(tmp_path):
+    """lu_plan.h over the fixed sweep of lu_route_check.cpp (factor routes around every threshold under each knob, base panels, triangular
+    solves, the step lists of the one-level and the two-level driver, substitution, padding; three device sizes): per group, the case
+    count and the digest of the routes equal what the drivers' former conditions gave (tests/golden/lu_routes.txt, recorded from them).
+    `lu_route_check --dump` prints the routes themselves."""
+    exe = compile_check(tmp_path, "lu_route_check")
+    r = subprocess.run([str(exe), "--sweep"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    want = [ln for ln in (ROOT / "tests" / "golden" / "lu_routes.txt").read_text().splitlines() if ln and not ln.startswith("#")]
+    got = r.stdout.splitlines()
+    # 16 settings x 3 device sizes; 3 panel families x one-XCD on / off x 3; 3; fast on / off x one-XCD on / off x 3; 6 plans; 3; padding
+    groups = {"factor": 48, "panel": 18, "trsm": 3, "blocked": 12, "super": 6, "subst": 3, "pad": 1}
+    assert len(want) == sum(groups.values()) == 91 and len({ln.rsplit(" ", 2)[0] for ln in want}) == 91
+    assert {k: sum(ln.split()[0] == k for ln in want) for k in groups} == groups
+    assert all(int(ln.split()[-2]) > 0 for ln in want)
     differing = [(g, w) for g, w in zip(got, want) if g != w]
     assert len(got) == len(want) and not differing, differing[:5]
