@@ -11,14 +11,15 @@
 // split re / im arrays with one pad slot per 32, runs in-place decimation-in-frequency passes of radix 8 (then 4 or 2) with ONE
 // barrier per pass, and leaves through a digit-reversed LDS read, so both the loads and the stores are coalesced: along the points
 // when the line is contiguous, across neighbouring lines otherwise (lines along a trailing dimension).  Lengths above the tile take
-// two such passes (n = m1 * m2: strided length-m1 transforms, the step twiddle, length-m2 transforms); lengths that are not powers of
-// two go through Bluestein's chirp convolution on the same kernel.
+// two or three such passes, lengths that are not powers of two go through Bluestein's chirp convolution on the same kernel.
+// Which passes, tiles, work buffers and tables a shape gets is decided in fft_plan.h; the drivers here execute it through launch_pass.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "common.h"
+#include "fft_plan.h"
 
 // parity here is by tolerance against the exact transform (the reference's rustfft has its own operation order): fused
 // multiply-adds are allowed in this file - fewer instructions and one rounding less per complex product
@@ -29,18 +30,10 @@ using namespace rmhip;
 namespace rmhip {
 namespace {
 
-typedef unsigned long long u64;
-constexpr int FT = 256;         // threads per workgroup of the small elementwise kernels
-constexpr int TILE = 4096;      // complex points per workgroup (512 threads, two workgroups per CU) ...
-constexpr int TILE_SMALL = 2048;  // ... half of that for lines of up to 2048 points (256 threads, four per CU) ...
-constexpr int TILE_BIG = 8192;  // ... or a whole 8192-point line (1024 threads, one workgroup per CU: 132 KiB of LDS)
-constexpr int MAXB = 256;       // lines per workgroup
-constexpr u64 NOLINE = ~0ull;
-constexpr int STEP_LO = 12;     // step twiddle w_n^t = lo[t & 4095] * hi[t >> 12]
+using namespace fft_plan;  // u64, Side, the tile constants, the routes
 
-struct Side {  // where point p of line (i, q, o) lives: element offset i*si + q*sq + o*so + p*sp
-    u64 si, sq, so, sp;
-};
+constexpr int FT = 256;         // threads per workgroup of the small elementwise kernels
+constexpr u64 NOLINE = ~0ull;
 
 struct FftPass {
     u64 nlines, inner, qcnt;  // line l = i + inner * (q + qcnt * o)
@@ -423,169 +416,76 @@ int fft_table(Context* c, int kind, u64 n, u64 count, Table* out) {
     return RMHIP_OK;
 }
 
-inline int ilog2(u64 v) {
-    int l = 0;
-    while ((1ull << l) < v) ++l;
-    return l;
-}
-inline bool is_pow2(u64 v) { return v && !(v & (v - 1)); }
+// What launch_pass needs beside a pass's geometry: the buffers their roles name, and what the first and the last pass carry.
+struct PassIo {
+    const double* in;
+    int in_complex;
+    double* work;
+    double* out;            // complex
+    bool conj_in, conj_out;
+    double scale;
+    bool round32;
+    const double2* mul_in;  // a factor per input point (Bluestein's chirp), or null
+    const double* win;      // a REAL factor per input point (the spectral estimate's window): k_fft_tile<NT, true>, or null
+};
 
-void set_radices(FftPass& P) {
-    int rem = P.log2m;
-    P.nrad = 0;
-    if (rem % 3 == 2) P.rad[P.nrad++] = 4, rem -= 2;  // the odd radix first: that pass has no twiddles
-    if (rem % 3 == 1) P.rad[P.nrad++] = 2, rem -= 1;
-    while (rem >= 3) P.rad[P.nrad++] = 8, rem -= 3;
+typedef void (*TileKernel)(const FftPass);
+TileKernel tile_kernel(int threads, bool win) {
+    static const TileKernel kernels[3][2] = {{k_fft_tile<256, false>, k_fft_tile<256, true>},
+                                             {k_fft_tile<512, false>, k_fft_tile<512, true>},
+                                             {k_fft_tile<1024, false>, k_fft_tile<1024, true>}};
+    return kernels[threads == 256 ? 0 : (threads == 512 ? 1 : 2)][win ? 1 : 0];
 }
 
-int launch_pass(Context* c, FftPass& P) {
-    set_radices(P);
-    const int m = 1 << P.log2m;
-    int lb = 0;
-    // lines of up to 2048 points take half-size tiles (256 threads, 37 KiB: four workgroups per CU instead of two - the same threads per CU
-    // in more independent phases: 3-7 % on every shape measured), unless that would leave fewer than eight neighbouring lines to a tile
-    const size_t cap = (size_t)m <= (size_t)TILE_SMALL && (P.mode == 0 || (size_t)m * 8 <= (size_t)TILE_SMALL) ? (size_t)TILE_SMALL : (size_t)TILE;
-    while (((size_t)m << (lb + 1)) <= cap && (1 << (lb + 1)) <= MAXB && (1ull << lb) < P.nlines) ++lb;
-    P.log2b = lb;
+// The one launcher: a pass's geometry (fft_plan.h), the buffers and the route's step tables (STEP_N's lo, hi, then STEP_N1's) become
+// an FftPass; plan_tile gives its tile.
+int launch_pass(Context* c, const PassGeom& g, const PassIo& io, const Table* steps = nullptr) {
+    FftPass P{};
+    P.nlines = g.nlines, P.inner = g.inner, P.qcnt = g.qcnt;
+    P.in = g.src == FROM_INPUT ? io.in : io.work, P.in_complex = g.src == FROM_INPUT ? io.in_complex : 1;
+    P.out = g.dst == TO_WORK ? io.work : io.out;
+    P.a = g.a, P.b = g.b;
+    P.in_pk = g.in_pk, P.in_qk = g.in_qk, P.in_len = g.in_len;
+    P.log2m = g.log2m, P.mode = g.mode, P.step_by_i = g.step_by_i;
+    if (g.step != STEP_NONE) {
+        const Table* t = steps + (g.step == STEP_N ? 0 : 2);
+        P.step_lo = tptr(t[0]), P.step_hi = tptr(t[1]);
+    }
+    P.scale = 1.0;
+    if (g.first) P.conj_in = io.conj_in, P.mul_in = io.mul_in, P.win = io.win;
+    if (g.last) P.conj_out = io.conj_out, P.scale = io.scale, P.round32 = io.round32;
+    const TilePlan t = plan_tile(g.log2m, g.mode, g.nlines);
+    P.log2b = t.log2b, P.nrad = t.nrad;
+    std::copy(t.rad, t.rad + t.nrad, P.rad);
+    const u64 m = 1ull << g.log2m;
     Table tw;
-    RMHIP_TRY(fft_table(c, 0, (u64)m, (u64)m, &tw));
+    RMHIP_TRY(fft_table(c, 0, m, m, &tw));
     P.tw = tptr(tw);
-    const u64 blocks = (P.nlines + (1ull << lb) - 1) >> lb;
-    if (blocks > 0x7fffffffull) return fail(RMHIP_ERR_UNSUPPORTED, "fft: %llu lines", P.nlines);
-    const size_t tile = (size_t)m << lb, lds = (2 * (tile + (tile >> 3) + 1) + 2 * ((size_t)1 << lb)) * sizeof(double) + 2 * ((size_t)1 << lb) * sizeof(unsigned);
-    if (P.win) {
-        if (tile > (size_t)TILE) hipLaunchKernelGGL((k_fft_tile<1024, true>), dim3((unsigned)blocks), dim3(1024), lds, c->stream, P);
-        else if (tile <= (size_t)TILE_SMALL) hipLaunchKernelGGL((k_fft_tile<256, true>), dim3((unsigned)blocks), dim3(256), lds, c->stream, P);
-        else hipLaunchKernelGGL((k_fft_tile<512, true>), dim3((unsigned)blocks), dim3(512), lds, c->stream, P);
-    } else if (tile > (size_t)TILE) hipLaunchKernelGGL(k_fft_tile<1024>, dim3((unsigned)blocks), dim3(1024), lds, c->stream, P);
-    else if (tile <= (size_t)TILE_SMALL) hipLaunchKernelGGL(k_fft_tile<256>, dim3((unsigned)blocks), dim3(256), lds, c->stream, P);
-    else hipLaunchKernelGGL(k_fft_tile<512>, dim3((unsigned)blocks), dim3(512), lds, c->stream, P);
+    if (t.refused) return fail(RMHIP_ERR_UNSUPPORTED, "fft: %llu lines", P.nlines);
+    hipLaunchKernelGGL(tile_kernel(t.threads, P.win != nullptr), dim3((unsigned)t.blocks), dim3(t.threads), t.lds, c->stream, P);
     c->tel.kernel_launches++;
     RMHIP_HIP_CHECK(hipGetLastError());
     return RMHIP_OK;
 }
 
-// A set of lines in tensor layout: point k of line (i, o) at element i + inner * (k + len * o).
-struct Lines {
+struct Lines {  // a LineShape with its buffers
     const double* in;
     int in_complex;
-    u64 inner, outer, len_in;  // len_in: points the input holds per line
-    double* out;               // complex, n points per line, same layout
+    LineShape shape;
+    double* out;  // complex, n points per line, same layout
 };
 
 // forward transform of conj^a(x), conjugated b times (a = b = 1: the unscaled inverse) - power-of-two length n along the lines; `scale` multiplies the result.
 // `mul_in` (or null): a factor per input point k (Bluestein's chirp); points from `valid` on read as zero whatever the input holds.
 int fft_pow2(Context* c, const Lines& L, u64 n, bool conj_in, bool conj_out, double scale, bool round32, const double2* mul_in = nullptr, u64 valid = ~0ull) {
-    const int lg = ilog2(n);
-    const u64 in_len = std::min<u64>(std::min<u64>(L.len_in, n), valid);
-    const u64 lines = L.inner * L.outer;
-    // a line along a trailing dimension is read across neighbouring lines: short transforms, many lines per tile
-    const bool single = L.inner == 1 ? n <= (u64)TILE_BIG : lg <= 8;
-    if (single) {
-        FftPass P{};
-        P.nlines = lines, P.inner = L.inner, P.qcnt = 1;
-        P.in = L.in, P.out = L.out, P.in_complex = L.in_complex;
-        P.a = Side{1, 0, L.len_in * L.inner, L.inner};
-        P.b = Side{1, 0, n * L.inner, L.inner};
-        P.in_pk = 1, P.in_qk = 0, P.in_len = in_len;
-        P.mul_in = mul_in;
-        P.scale = scale, P.log2m = lg;
-        P.mode = L.inner > 1 ? 1 : 0;
-        P.conj_in = conj_in, P.conj_out = conj_out;
-        P.round32 = round32;
-        return launch_pass(c, P);
-    }
-    if (lg > (L.inner == 1 ? 27 : 24)) return fail(RMHIP_ERR_UNSUPPORTED, "fft: length %llu", n);
-    if (L.inner == 1 && lg >= 23) {  // measured crossover (scripts/fft_long_ab.py): 2^22 equal, 2^23 0.33 -> 0.22 ms, 2^24 0.78 -> 0.49 ms
-        // Two factors of a very long line pass 2048 and a tile holds one or two lines: the strided side of each pass moves 16- or 32-byte
-        // pieces (a 2^24-point vector: 0.80 ms).  Three passes instead, n = m1 m2 m3, k = k1 m2 m3 + k2 m3 + k3,
-        // j = j1 + m1 j2 + m1 m2 j3, every one reading and writing neighbouring lines:
-        //   (A) over k1 (stride m2 m3), lines (k', o), k' = k2 m3 + k3, times w_n^(j1 k')          -> T[o][j1][k']
-        //   (B) over k2 (stride m3),   lines (k3, j1, o),            times w_{m2 m3}^(j2 k3)       -> T[o][j1][j2][k3]   (in place)
-        //   (C) over k3 (contiguous),  lines (j1, j2, o)                                           -> y[o][j1 + m1 j2 + m1 m2 j3]
-        const int l1 = lg / 3, l2 = (lg - l1) / 2, l3 = lg - l1 - l2;
-        const u64 m1 = 1ull << l1, m2 = 1ull << l2, m3 = 1ull << l3, N1 = m2 * m3;
-        std::shared_ptr<Allocation> t;
-        RMHIP_TRY(c->alloc_device(2 * n * lines, &t));
-        Table slo, shi, rlo, rhi;
-        RMHIP_TRY(fft_table(c, 0, n, std::min<u64>(n, 1ull << STEP_LO), &slo));
-        RMHIP_TRY(fft_table(c, 1, n, std::max<u64>(1, n >> STEP_LO), &shi));
-        RMHIP_TRY(fft_table(c, 0, N1, std::min<u64>(N1, 1ull << STEP_LO), &rlo));
-        RMHIP_TRY(fft_table(c, 1, N1, std::max<u64>(1, N1 >> STEP_LO), &rhi));
-        {
-            FftPass P{};
-            P.nlines = lines * N1, P.inner = 1, P.qcnt = N1;
-            P.in = L.in, P.out = t->ptr, P.in_complex = L.in_complex;
-            P.a = Side{0, 1, L.len_in, N1};
-            P.b = Side{0, 1, n, N1};
-            P.in_pk = N1, P.in_qk = 1, P.in_len = in_len;
-            P.mul_in = mul_in;
-            P.step_lo = tptr(slo), P.step_hi = tptr(shi);
-            P.scale = 1.0, P.log2m = l1, P.mode = 1;
-            P.conj_in = conj_in;
-            RMHIP_TRY(launch_pass(c, P));
-        }
-        {
-            FftPass P{};
-            P.nlines = lines * m1 * m3, P.inner = m3, P.qcnt = m1;
-            P.in = t->ptr, P.out = t->ptr, P.in_complex = 1;
-            P.a = Side{1, N1, n, m3};
-            P.b = Side{1, N1, n, m3};
-            P.in_pk = 1, P.in_qk = 0, P.in_len = m2;
-            P.step_lo = tptr(rlo), P.step_hi = tptr(rhi), P.step_by_i = 1;
-            P.scale = 1.0, P.log2m = l2, P.mode = 1;
-            RMHIP_TRY(launch_pass(c, P));
-        }
-        {
-            FftPass P{};
-            P.nlines = lines * m1 * m2, P.inner = m1, P.qcnt = m2;
-            P.in = t->ptr, P.out = L.out, P.in_complex = 1;
-            P.a = Side{N1, m3, n, 1};
-            P.b = Side{1, m1, n, m1 * m2};
-            P.in_pk = 1, P.in_qk = 0, P.in_len = m3;
-            P.scale = scale, P.log2m = l3, P.mode = 2;
-            P.conj_out = conj_out;
-            P.round32 = round32;
-            RMHIP_TRY(launch_pass(c, P));
-        }
-        return RMHIP_OK;
-    }
-    // n = m1 * m2: (1) length-m1 transforms over k1 of x[k1 * m2 + k2], times w_n^(j1 k2), into T[j1 * m2 + k2];
-    //              (2) length-m2 transforms over k2 of T[j1 * m2 + k2] into y[j1 + m1 * j2]
-    const int l1 = lg / 2, l2 = lg - l1;
-    const u64 m1 = 1ull << l1, m2 = 1ull << l2;
-    std::shared_ptr<Allocation> tmp;
-    RMHIP_TRY(c->alloc_device(2 * n * lines, &tmp));
-    Table slo, shi;
-    RMHIP_TRY(fft_table(c, 0, n, std::min<u64>(n, 1ull << STEP_LO), &slo));
-    RMHIP_TRY(fft_table(c, 1, n, std::max<u64>(1, n >> STEP_LO), &shi));
-    {
-        FftPass P{};
-        P.nlines = lines * m2, P.inner = L.inner, P.qcnt = m2;
-        P.in = L.in, P.out = tmp->ptr, P.in_complex = L.in_complex;
-        P.a = Side{1, L.inner, L.len_in * L.inner, m2 * L.inner};
-        P.b = Side{1, L.inner, n * L.inner, m2 * L.inner};
-        P.in_pk = m2, P.in_qk = 1, P.in_len = in_len;
-        P.mul_in = mul_in;
-        P.step_lo = tptr(slo), P.step_hi = tptr(shi);
-        P.scale = 1.0, P.log2m = l1;
-        P.mode = 1;  // neighbouring lines (i, then k2) are neighbours in memory
-        P.conj_in = conj_in;
-        RMHIP_TRY(launch_pass(c, P));
-    }
-    {
-        FftPass P{};
-        P.nlines = lines * m1, P.inner = L.inner, P.qcnt = m1;
-        P.in = tmp->ptr, P.out = L.out, P.in_complex = 1;
-        P.a = Side{1, L.inner * m2, n * L.inner, L.inner};
-        P.b = Side{1, L.inner, n * L.inner, m1 * L.inner};
-        P.in_pk = 1, P.in_qk = 0, P.in_len = m2;
-        P.scale = scale, P.log2m = l2;
-        P.mode = L.inner > 1 ? 1 : 2;
-        P.conj_out = conj_out;
-        P.round32 = round32;
-        RMHIP_TRY(launch_pass(c, P));
-    }
+    const Pow2Route r = plan_pow2(L.shape, n, valid);
+    if (r.npass == 0) return fail(RMHIP_ERR_UNSUPPORTED, "fft: length %llu", n);
+    std::shared_ptr<Allocation> work;
+    if (r.work) RMHIP_TRY(c->alloc_device(2 * r.work, &work));
+    Table steps[4];
+    for (int k = 0; k < r.ntables; ++k) RMHIP_TRY(fft_table(c, r.tables[k].kind, r.tables[k].n, r.tables[k].count, &steps[k]));
+    const PassIo io{L.in, L.in_complex, work ? work->ptr : nullptr, L.out, conj_in, conj_out, scale, round32, mul_in, nullptr};
+    for (int k = 0; k < r.npass; ++k) RMHIP_TRY(launch_pass(c, r.pass[k], io, steps));
     return RMHIP_OK;
 }
 
@@ -627,9 +527,9 @@ __global__ void __launch_bounds__(FT) k_bluestein_finish(const double2* __restri
 }
 
 int fft_bluestein(Context* c, const Lines& L, u64 n, bool inverse, double scale, bool round32) {
-    u64 M = 1;
-    while (M < 2 * n - 1) M <<= 1;
-    if (M > (1ull << 24)) return fail(RMHIP_ERR_UNSUPPORTED, "fft: length %llu", n);
+    const ChirpPlan p = plan_chirp(L.shape, n);
+    const u64 M = p.M, inner = L.shape.inner, len_in = L.shape.len_in;
+    if (p.refused == CHIRP_LENGTH) return fail(RMHIP_ERR_UNSUPPORTED, "fft: length %llu", n);
     Table chirp;
     RMHIP_TRY(fft_table(c, 2, n, n, &chirp));
     // G = FFT_M of the wrapped conjugate chirp, kept beside the tables (kind 3)
@@ -644,34 +544,42 @@ int fft_bluestein(Context* c, const Lines& L, u64 n, bool inverse, double scale,
         RMHIP_TRY(c->alloc_device(2 * M, &G));
         hipLaunchKernelGGL(k_bluestein_kernel, dim3((unsigned)((M + FT - 1) / FT)), dim3(FT), 0, c->stream, tptr(chirp), n, M, reinterpret_cast<double2*>(g->ptr));
         c->tel.kernel_launches++;
-        Lines gl{g->ptr, 1, 1, 1, M, G->ptr};
+        Lines gl{g->ptr, 1, {1, 1, M}, G->ptr};
         RMHIP_TRY(fft_pow2(c, gl, M, false, false, 1.0, false));
         c->fft_tables[gkey] = G;
     }
-    // the two work tensors [inner, M, outer'] stay below ~1 GiB each: whole outer slabs at a time
-    const u64 slab = L.inner * M;
-    if (slab > (1ull << 27)) return fail(RMHIP_ERR_UNSUPPORTED, "fft: %llu lines of chirp length %llu along a trailing dimension", L.inner, M);
-    const u64 outer_per = std::min<u64>(L.outer, std::max<u64>(1, (1ull << 26) / slab));
-    Table A, Y;
-    RMHIP_TRY(c->alloc_device(2 * slab * outer_per, &A));
-    RMHIP_TRY(c->alloc_device(2 * slab * outer_per, &Y));
-    const u64 valid = std::min<u64>(L.len_in, n);
-    for (u64 o0 = 0; o0 < L.outer; o0 += outer_per) {
-        const u64 oc = std::min<u64>(outer_per, L.outer - o0), total = oc * slab;
-        const double* in = L.in + (L.in_complex ? 2 : 1) * (o0 * L.len_in * L.inner);
-        double* out = L.out + 2 * (o0 * n * L.inner);
-        Lines f{in, L.in_complex, L.inner, oc, L.len_in, A->ptr};  // a = op(x) .* chirp, zero-extended to M, transformed
-        RMHIP_TRY(fft_pow2(c, f, M, inverse, false, 1.0, false, tptr(chirp), valid));
-        hipLaunchKernelGGL(k_line_mul, dim3((unsigned)((total + FT - 1) / FT)), dim3(FT), 0, c->stream, reinterpret_cast<double2*>(A->ptr), tptr(G), L.inner, M, total);
-        Lines b{A->ptr, 1, L.inner, oc, M, Y->ptr};
+    if (p.refused == CHIRP_SLAB) return fail(RMHIP_ERR_UNSUPPORTED, "fft: %llu lines of chirp length %llu along a trailing dimension", inner, M);
+    Table A, Y;  // the two work tensors [inner, M, outer_per]
+    RMHIP_TRY(c->alloc_device(2 * p.slab * p.outer_per, &A));
+    RMHIP_TRY(c->alloc_device(2 * p.slab * p.outer_per, &Y));
+    for (u64 k = 0; k < p.nslabs; ++k) {
+        const Slab s = chirp_slab(p, L.shape.outer, k);
+        const u64 total = s.oc * p.slab;
+        const double* in = L.in + (L.in_complex ? 2 : 1) * (s.o0 * len_in * inner);
+        double* out = L.out + 2 * (s.o0 * n * inner);
+        Lines f{in, L.in_complex, {inner, s.oc, len_in}, A->ptr};  // a = op(x) .* chirp, zero-extended to M, transformed
+        RMHIP_TRY(fft_pow2(c, f, M, inverse, false, 1.0, false, tptr(chirp), p.valid));
+        hipLaunchKernelGGL(k_line_mul, dim3((unsigned)((total + FT - 1) / FT)), dim3(FT), 0, c->stream, reinterpret_cast<double2*>(A->ptr), tptr(G), inner, M, total);
+        Lines b{A->ptr, 1, {inner, s.oc, M}, Y->ptr};
         RMHIP_TRY(fft_pow2(c, b, M, true, true, 1.0 / (double)M, false));
-        const u64 ototal = oc * L.inner * n;
+        const u64 ototal = s.oc * inner * n;
         hipLaunchKernelGGL(k_bluestein_finish, dim3((unsigned)((ototal + FT - 1) / FT)), dim3(FT), 0, c->stream, reinterpret_cast<const double2*>(Y->ptr), tptr(chirp),
-                           L.inner, n, M, ototal, scale, inverse ? 1 : 0, round32 ? 1 : 0, reinterpret_cast<double2*>(out));
+                           inner, n, M, ototal, scale, inverse ? 1 : 0, round32 ? 1 : 0, reinterpret_cast<double2*>(out));
         c->tel.kernel_launches += 2;
         RMHIP_HIP_CHECK(hipGetLastError());
     }
     return RMHIP_OK;
+}
+
+// a failed entry hands back no handle: the results it had made leave the table and their ids read 0
+void drop_outputs(Context* c, std::initializer_list<rmhip_buf*> ids) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (rmhip_buf* id : ids) {
+        Buffer victim;
+        auto it = c->table.find(*id);
+        if (*id && it != c->table.end()) victim = std::move(it->second), c->table.erase(it);
+        *id = 0;
+    }
 }
 
 int fft_entry(Context* c, rmhip_buf a, long long len_or_neg, int dim, bool inverse, rmhip_buf* out) {
@@ -699,36 +607,16 @@ int fft_entry(Context* c, rmhip_buf a, long long len_or_neg, int dim, bool inver
     RMHIP_TRY(c->new_buffer_complex(oshape.data(), oshape.size(), out, &ob));
     if (ob.numel == 0) return RMHIP_OK;
     const bool r32 = c->precision == 32;
-    Lines L{ab.data(), ab.cplx ? 1 : 0, inner, outer, cur, ob.data()};
+    const Lines L{ab.data(), ab.cplx ? 1 : 0, {inner, outer, cur}, ob.data()};
     const double scale = inverse ? 1.0 / (double)n : 1.0;
-    int rc;
-    if (n == 1 || cur == 0) {
-        // a one-point transform is the point itself (or zero where the input has none): the tile kernel with m = 1 has no pass to run
-        FftPass P{};
-        P.nlines = inner * outer, P.inner = inner, P.qcnt = 1;
-        P.in = L.in, P.out = L.out, P.in_complex = L.in_complex;
-        P.a = Side{1, 0, cur * inner, inner};
-        P.b = Side{1, 0, n * inner, inner};
-        P.in_pk = 1, P.in_qk = 0, P.in_len = std::min<u64>(cur, n);
-        P.scale = scale, P.log2m = 0, P.round32 = r32;
-        P.mode = 1;
-        if (n == 1) rc = launch_pass(c, P);
-        else {
-            RMHIP_HIP_CHECK(hipMemsetAsync(ob.data(), 0, 2 * ob.numel * sizeof(double), c->stream));
-            rc = RMHIP_OK;
-        }
-    } else if (is_pow2(n)) {
-        rc = fft_pow2(c, L, n, inverse, inverse, scale, r32);
-    } else {
-        rc = fft_bluestein(c, L, n, inverse, scale, r32);
+    int rc = RMHIP_OK;
+    switch (plan_entry(cur, n)) {
+        case ENTRY_ZERO_FILL: RMHIP_HIP_CHECK(hipMemsetAsync(ob.data(), 0, 2 * ob.numel * sizeof(double), c->stream)); break;
+        case ENTRY_ONE_POINT: rc = launch_pass(c, one_point_pass(L.shape), PassIo{L.in, L.in_complex, nullptr, L.out, false, false, scale, r32, nullptr, nullptr}); break;
+        case ENTRY_POW2: rc = fft_pow2(c, L, n, inverse, inverse, scale, r32); break;
+        case ENTRY_CHIRP: rc = fft_bluestein(c, L, n, inverse, scale, r32); break;
     }
-    if (rc != RMHIP_OK) {
-        Buffer victim;
-        std::lock_guard<std::mutex> lk(c->mu);
-        auto it = c->table.find(*out);
-        if (it != c->table.end()) victim = std::move(it->second), c->table.erase(it);
-        *out = 0;
-    }
+    if (rc != RMHIP_OK) drop_outputs(c, {out});
     return rc;
 }
 
@@ -830,14 +718,12 @@ int spectral_entry(Context* c, rmhip_buf input, const SpectralArgs& a, rmhip_buf
     if (a.input_len > xb.numel) return fail(RMHIP_ERR_INVALID, "uniform_spectral_estimate: input_len %zu exceeds the tensor's %zu elements", a.input_len, xb.numel);
     if ((a.input_complex != 0) != xb.cplx) return fail(RMHIP_ERR_INVALID, "uniform_spectral_estimate: input_complex disagrees with the handle's storage");
     const u64 nfft = a.nfft, fc = a.frame_count;
-    // what fft_pow2 / fft_bluestein transform along dimension 0
-    const bool pow2 = is_pow2(nfft);
-    if (pow2 ? nfft > (1ull << 27) : nfft > (1ull << 23)) return fail(RMHIP_ERR_UNSUPPORTED, "uniform_spectral_estimate: nfft %zu", a.nfft);
+    if (!length_served(nfft, 1)) return fail(RMHIP_ERR_UNSUPPORTED, "uniform_spectral_estimate: nfft %zu", a.nfft);
     u64 total = 0, bytes = 0, top = 0;
     if (mul_ovf(nfft, fc, &total) || mul_ovf(total, 2 * sizeof(double), &bytes) || (total + FT - 1) / FT > 0x7fffffffull)
         return fail(RMHIP_ERR_UNSUPPORTED, "uniform_spectral_estimate: %zu frames of %zu points", a.frame_count, a.nfft);
     // `top`: one past the largest source index any frame forms - the coverage rule above only looks at the last frame
-    const u64 wl = a.mode == 2 ? a.window_len : std::min<u64>(a.window_len, nfft);  // window points a frame reads
+    const u64 wl = spectral_window_points(a.mode, a.window_len, nfft);
     bool ovf = false;
     if (a.mode == 0) ovf = mul_ovf(fc - 1, a.hop, &top);
     else if (a.mode == 2) ovf = mul_ovf(fc - 1, a.input_rows, &top);
@@ -851,63 +737,47 @@ int spectral_entry(Context* c, rmhip_buf input, const SpectralArgs& a, rmhip_buf
         }
     }
     if (ovf || add_ovf(top, wl, &top)) return fail(RMHIP_ERR_UNSUPPORTED, "uniform_spectral_estimate: index overflow");
-    const bool fused = pow2 && nfft >= 2 && nfft <= (u64)TILE_BIG && a.mode != 2 && top <= a.input_len;
-    const u64 rows = a.range == 0 ? nfft / 2 + 1 : nfft;
-    const u64 shift = nfft % 2 == 0 ? nfft / 2 + 1 : (nfft + 1) / 2;  // common.rs:221-227
-    const bool r32 = c->precision == 32;
-    const bool direct = a.range == 1;  // two-sided: the transform's output IS `s`
+    const SpectralPlan sp = plan_spectral(a.mode, a.range, nfft, top, a.input_len);
+    const u64 rows = sp.rows;
+    const bool r32 = c->precision == 32, direct = sp.direct;
 
     Table win, frames, spec;
     RMHIP_TRY(c->alloc_device(a.window_len, &win));
     RMHIP_HIP_CHECK(hipMemcpyAsync(win->ptr, a.window, a.window_len * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const bool own_spectrum = nfft == 1 && !fused;  // a one-point frame is its own spectrum: the frame kernel writes what the finish kernel reads
-    if (!fused && !(own_spectrum && direct)) RMHIP_TRY(c->alloc_device(2 * total, &frames));
-    if (!direct && !own_spectrum) RMHIP_TRY(c->alloc_device(2 * total, &spec));
+    if (sp.alloc_frames) RMHIP_TRY(c->alloc_device(2 * total, &frames));
+    if (sp.alloc_spec) RMHIP_TRY(c->alloc_device(2 * total, &spec));
     const size_t oshape[2] = {(size_t)rows, (size_t)fc};
     Buffer sb, pb;
     RMHIP_TRY(c->new_buffer_complex(oshape, 2, s, &sb));
     int rc = c->new_buffer(oshape, 2, ps, &pb);
     double* const spec_ptr = direct ? sb.data() : (spec ? spec->ptr : frames->ptr);
-    if (rc == RMHIP_OK && fused) {
-        FftPass P{};
-        P.nlines = fc, P.inner = 1, P.qcnt = a.mode == 1 ? a.fpc : 1;
-        P.in = xb.data(), P.out = spec_ptr, P.in_complex = xb.cplx ? 1 : 0;
-        P.a = a.mode == 1 ? Side{0, a.hop, a.input_rows, 1} : Side{0, 0, a.hop, 1};
-        P.b = Side{0, nfft, nfft * P.qcnt, 1};
-        P.in_pk = 1, P.in_qk = 0, P.in_len = wl;
-        P.win = win->ptr;
-        P.scale = 1.0, P.log2m = ilog2(nfft), P.mode = 0;
-        rc = launch_pass(c, P);
+    if (rc == RMHIP_OK && sp.fused) {
+        const PassIo io{xb.data(), xb.cplx ? 1 : 0, nullptr, spec_ptr, false, false, 1.0, false, nullptr, win->ptr};
+        rc = launch_pass(c, spectral_frame_pass(a.mode, fc, a.fpc, a.hop, a.input_rows, nfft, wl), io);
     } else if (rc == RMHIP_OK) {
         const SpectralFrames F{a.input_len, a.window_len, nfft, a.hop, a.input_rows, a.fpc ? a.fpc : 1, a.mode, xb.cplx ? 1 : 0};
-        double* const fout = nfft == 1 ? spec_ptr : frames->ptr;
+        double* const fout = sp.own_spectrum ? spec_ptr : frames->ptr;
         hipLaunchKernelGGL(k_spectral_frame, dim3((unsigned)((total + FT - 1) / FT)), dim3(FT), 0, c->stream, xb.data(), win->ptr, F, total, reinterpret_cast<double2*>(fout));
         c->tel.kernel_launches++;
         if (hipGetLastError() != hipSuccess) rc = fail(RMHIP_ERR_HIP, "uniform_spectral_estimate: launch failed");
-        if (rc == RMHIP_OK && nfft > 1) {
-            const Lines L{frames->ptr, 1, 1, fc, nfft, spec_ptr};
-            rc = pow2 ? fft_pow2(c, L, nfft, false, false, 1.0, false) : fft_bluestein(c, L, nfft, false, 1.0, false);
+        if (rc == RMHIP_OK && !sp.own_spectrum) {
+            const Lines L{frames->ptr, 1, {1, fc, nfft}, spec_ptr};
+            rc = is_pow2(nfft) ? fft_pow2(c, L, nfft, false, false, 1.0, false) : fft_bluestein(c, L, nfft, false, 1.0, false);
         }
     }
     if (rc == RMHIP_OK) {
         const u64 otot = rows * fc;
         double2* const s_out = direct ? (r32 ? reinterpret_cast<double2*>(sb.data()) : nullptr) : reinterpret_cast<double2*>(sb.data());
         hipLaunchKernelGGL(k_spectral_finish, dim3((unsigned)((otot + FT - 1) / FT)), dim3(FT), 0, c->stream, reinterpret_cast<const double2*>(spec_ptr), nfft, rows, otot,
-                           a.range, shift, a.denominator, r32 ? 1 : 0, s_out, pb.data());
+                           a.range, sp.shift, a.denominator, r32 ? 1 : 0, s_out, pb.data());
         c->tel.kernel_launches++;
         if (hipGetLastError() != hipSuccess) rc = fail(RMHIP_ERR_HIP, "uniform_spectral_estimate: launch failed");
     }
     if (rc != RMHIP_OK) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        for (rmhip_buf* id : {s, ps}) {
-            Buffer victim;
-            auto it = c->table.find(*id);
-            if (*id && it != c->table.end()) victim = std::move(it->second), c->table.erase(it);
-            *id = 0;
-        }
+        drop_outputs(c, {s, ps});
         return rc;
     }
-    if (fused) c->record_launch("spectral", {{"rows", rows}, {"frames", fc}}, {{"fused", 1}});
+    if (sp.fused) c->record_launch("spectral", {{"rows", rows}, {"frames", fc}}, {{"fused", 1}});
     else c->record_launch("spectral", {{"rows", rows}, {"frames", fc}}, {{"framed", 1}});
     *rows_out = rows, *cols_out = fc;
     return RMHIP_OK;

@@ -4,17 +4,18 @@ One case table, CASES, names every path the launchers can take; each case states
 and the test asserts it from the telemetry, so a case that stops exercising its path (a moved threshold, say) fails.  With
 lg = log2(n), `inner` = the product of the dimensions before the transformed one, M = the chirp convolution's length:
 
-  path     selected by                            launches   what runs
-  tile0    inner == 1, lg <= 13                   1          one tile, points contiguous (mode 0); 256 / 512 / 1024 threads
-  tile1    inner > 1, lg <= 8                     1          one tile, lines contiguous (mode 1)
-  two0     inner == 1, lg 14..22                  2          m1 = 2^(lg // 2) strided, step twiddle, then mode 2
-  two1     inner > 1, lg 9..24                    2          both passes mode 1
-  three    inner == 1, lg 23..27                  3          splits lg 23: 7, 8, 8; 24: 8, 8, 8; 26: 8, 9, 9
-  chirp    n not a power of two                   2 p + 2    p = the passes of the length-M transform at that inner
-  chirp3   n > 2^22, not a power of two           8          M = 2^24 in three passes: mul_in and valid through pass A
-  slabs    chirp with inner M outer > 2^26        per slab   the outer dimension in pieces (o0 > 0 offsets)
+  path     selected by (fft_plan.h)                                launches   what runs
+  tile0    pow2_passes = 1 -> one_pass: inner == 1, lg <= 13       1          one tile, points contiguous (mode 0); plan_tile: 256 / 512 / 1024 threads
+  tile1    pow2_passes = 1 -> one_pass: inner > 1, lg <= 8         1          one tile, lines contiguous (mode 1)
+  two0     pow2_passes = 2 -> two_pass: inner == 1, lg 14..22      2          m1 = 2^(lg // 2) strided, step twiddle, then mode 2
+  two1     pow2_passes = 2 -> two_pass: inner > 1, lg 9..24        2          both passes mode 1
+  three    pow2_passes = 3 -> three_pass: inner == 1, lg 23..27    3          splits lg 23: 7, 8, 8; 24: 8, 8, 8; 26: 8, 9, 9
+  chirp    plan_entry: n not a power of two -> plan_chirp          2 p + 2    p = pow2_passes of the length-M transform at that inner
+  chirp3   plan_chirp with M = 2^24 (n > 2^22)                     8          M = 2^24 in three passes: mul_in and valid through pass A
+  slabs    plan_chirp: nslabs > 1 (inner M outer > 2^26)           per slab   the outer dimension in pieces (chirp_slab: o0 > 0 offsets)
 and test_table_cache_eviction re-checks results after fft_tables has been cleared (more than 64 entries).  These are the counts the
-launchers make; none differed from what the paths' descriptions in fft.hip promise.
+drivers make when they walk the plan; tests/test_fft_paths_host.py asserts every case's family and count against fft_plan.h on the
+CPU, and none differed.
 
 Tolerance: the project's own (fft_ref.bound, shared with test_gpu_fft.py): per bin C eps log2(work length) ||line||_2, C = 4 for
 powers of two and 8 for the chirp path, / n for the inverse.  On an impulse line that is a bound relative to |a|.  Every line of
@@ -53,7 +54,7 @@ def case(cid, path, launches, shape, dim=0, length=None, variants=VARIANTS_ALL, 
 
 
 def tile0_lines(lg):
-    """B + 1, B = the lines per tile launch_pass gives a mode-0 tile of 2^lg points: one full tile and a tile of one line."""
+    """B + 1, B = the lines per tile plan_tile (fft_plan.h) gives a mode-0 tile of 2^lg points: one full tile and a tile of one line."""
     m = 1 << lg
     cap = 2048 if m <= 2048 else 4096
     return max(1, min(256, cap // m)) + 1

@@ -1,6 +1,7 @@
 """Host logic that needs no GPU, checked by small C++ programs over sweeps of shapes: the reduction launch geometry and the
 routing of a shape to its kernel and finalize (reduce_plan.h), the broadcast stride preparation / dimension collapsing of the elementwise entry points
-(host_shape.h), including the in-place addressing of lazy repmat views, the GEMM dispatch (gemm_plan.h) and the LU dispatch (lu_plan.h)."""
+(host_shape.h), including the in-place addressing of lazy repmat views, the GEMM dispatch (gemm_plan.h), the LU dispatch (lu_plan.h) and the
+transforms' dispatch and pass addressing (fft_plan.h)."""
 import subprocess
 from pathlib import Path
 
@@ -59,3 +60,42 @@ def test_lu_plan_routes_the_sweep_as_the_drivers_conditions_did(tmp_path):
     assert all(int(ln.split()[-2]) > 0 for ln in want)
     differing = [(g, w) for g, w in zip(got, want) if g != w]
     assert len(got) == len(want) and not differing, differing[:5]
+
+
+@pytest.fixture(scope="module")
+def fft_route_check(tmp_path_factory):
+    return compile_check(tmp_path_factory.mktemp("fft_route_check"), "fft_route_check")
+
+
+def test_fft_plan_routes_the_sweep_as_the_drivers_conditions_did(fft_route_check):
+    """fft_plan.h over the fixed sweep of fft_route_check.cpp (every power-of-two length lg 0..28 at five inners, two outers, four input
+    lengths; tiles at every line-count boundary; the entry's routes; Bluestein's sizes around every boundary of M, both refusals, the
+    slab and work-tensor limits; the length predicate; the spectral decision): per group, the case count and the digest of the routes
+    equal what the drivers' former conditions gave (tests/golden/fft_routes.txt, recorded from them).  `fft_route_check --dump` prints
+    the routes themselves."""
+    r = subprocess.run([str(fft_route_check), "--sweep"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    want = [ln for ln in (ROOT / "tests" / "golden" / "fft_routes.txt").read_text().splitlines() if ln and not ln.startswith("#")]
+    got = r.stdout.splitlines()
+    # 5 inners x 2 outers; 3 modes; 1; 4 outers; 1; 3 frame modes x 3 ranges
+    groups = {"pow2": 10, "tile": 3, "entry": 1, "chirp": 4, "served": 1, "spectral": 9}
+    assert len(want) == sum(groups.values()) == 28 and len({ln.rsplit(" ", 2)[0] for ln in want}) == 28
+    assert {k: sum(ln.split()[0] == k for ln in want) for k in groups} == groups
+    assert all(int(ln.split()[-2]) > 0 for ln in want)
+    differing = [(g, w) for g, w in zip(got, want) if g != w]
+    assert len(got) == len(want) and not differing, differing[:5]
+
+
+def test_fft_tiles_fit_the_kernel(fft_route_check):
+    """Every tile of that sweep: at most 8 points per thread, at most 160 KiB of LDS, enough workgroups for the lines, radices that
+    multiply to the line length with the twiddle-free one first."""
+    r = subprocess.run([str(fft_route_check), "--invariants"], capture_output=True, text=True)
+    assert r.returncode == 0 and "fft tile invariants ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_fft_pass_addressing_is_the_transform(fft_route_check):
+    """The exact model: every pass of the one-, two- and three-pass routes, the one-point pass and the fused spectral frames, run on
+    the host on impulses held as exponents of w_n, gives the transform's definition exponent for exponent, writes every element once,
+    reads only what the pass before wrote and stays inside its buffers (fft_route_check.cpp states the cases)."""
+    r = subprocess.run([str(fft_route_check), "--model"], capture_output=True, text=True)
+    assert r.returncode == 0 and "fft model ok" in r.stdout, r.stdout + r.stderr
