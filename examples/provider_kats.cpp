@@ -186,7 +186,8 @@ int main() {
             rmhip::PagefunRequest q;
             auto za = p.complex_from_real_imag(p.upload({1, 0, 2, 3}, {2, 2}), p.upload({1, -1, 0, 2}, {2, 2}));
             auto br = p.upload({1, 2}, {2, 1});
-            q.inputs = {za, p.complex_from_real_imag(br, p.upload({-1, 1}, {2, 1}))};
+            auto zb = p.complex_from_real_imag(br, p.upload({-1, 1}, {2, 1}));
+            q.inputs = {za, zb};
             q.output_shape = {2, 1};
             q.input_page_dims = {{}, {}};
             try {
@@ -199,6 +200,18 @@ int main() {
             ok = ok && zc.shape == std::vector<size_t>{2, 1} && p.is_complex(zc) && eq(p.download(zc).data, {6, 2, 3, 6});
             q.inputs[1] = br;
             ok = ok && eq(p.download(p.complex_pagefun(q)).data, {5, 1, 6, 3});
+            // matmul's second entry point on the same operands, and the real column on the left of the complex row [1+i 2]
+            try {
+                p.matmul(za, br);
+                ok = false;
+            } catch (const rmhip::ProviderError& e) {
+                ok = ok && e.code == RMHIP_ERR_UNSUPPORTED;
+            }
+            auto zm = p.complex_matmul(za, zb);
+            ok = ok && zm.shape == std::vector<size_t>{2, 1} && p.is_complex(zm) && eq(p.download(zm).data, {6, 2, 3, 6});
+            ok = ok && eq(p.download(p.complex_matmul(za, br)).data, {5, 1, 6, 3});
+            auto zrow = p.complex_from_real_imag(p.upload({1, 2}, {1, 2}), p.upload({1, 0}, {1, 2}));
+            ok = ok && eq(p.download(p.complex_matmul(br, zrow)).data, {1, 1, 2, 2, 2, 0, 4, 0});
         }
         {
             // moving_window's second entry point: the 101-point median (shrinking at the ends) of the ramp 0 .. 199 with a spike at 100, which

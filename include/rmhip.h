@@ -630,7 +630,7 @@ RMHIP_API int rmhip_window(rmhip_ctx* ctx, int kind, size_t len, int periodic, r
  * elementwise arithmetic `rmhip_complex_unary` / `rmhip_complex_binary` / `rmhip_complex_scalar` and the shape and indexing hooks
  * `rmhip_complex_reshape` / `_transpose` / `_permute` / `_repmat` / `_gather_linear` / `_scatter_linear` / `_circshift` / `_flip` /
  * `_cat`, and the calculus and filter hooks `rmhip_complex_gradient_dim` / `_trapz_dim` / `_polyint` / `_iir_filter` /
- * `_iir_filter_long`, and the batched page products `rmhip_complex_pagefun` - and by the plumbing (download, shape, storage, isreal, free).  Every other entry point returns RMHIP_ERR_UNSUPPORTED for
+ * `_iir_filter_long`, the batched page products `rmhip_complex_pagefun` and the plain product `rmhip_complex_matmul` - and by the plumbing (download, shape, storage, isreal, free).  Every other entry point returns RMHIP_ERR_UNSUPPORTED for
  * them (the caller gathers, as for any `Err`): fused elementwise, reductions, matmul, round_digits, pow, the comparisons, tril / triu
  * and read_scalar among them, and so do the real forms of the hooks just named (`rmhip_transpose`, `rmhip_permute`, ...): a caller
  * chooses the entry point by the operand's storage kind.  A precision-32 context rounds the values a complex result COMPUTES through
@@ -920,6 +920,25 @@ RMHIP_API int rmhip_bandwidth(rmhip_ctx* ctx, rmhip_buf a, unsigned* lower, unsi
  * (simple_provider.rs:7698-7741). fp64 MFMA kernel. */
 /* @serves matmul */
 RMHIP_API int rmhip_matmul(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf* out);
+/* The same hook when at least one operand is complex-interleaved (the builtin hands complex handles over unchecked, mtimes.rs:173-218,
+ * and on the provider's error gathers and runs matmul_complex / matmul_complex_real / matmul_real_complex on the host): C = A*B, 2-D,
+ * column-major, rmhip_matmul's shape rule and wording, extents counted in logical elements; the result is a complex-interleaved [m, n]
+ * tensor.  The real operand of a mixed product may be a transpose or repmat view, a lazy random_normal or f32 storage (it is
+ * materialised to plain f64).  Checks in this order: a null `out` RMHIP_ERR_INVALID; unknown ids RMHIP_ERR_NOT_FOUND; both operands
+ * real RMHIP_ERR_UNSUPPORTED (rmhip_matmul serves them); more than 2-D RMHIP_ERR_UNSUPPORTED; inner extents that disagree
+ * RMHIP_ERR_SHAPE; an embedded extent (2m, 2n, k) of 2^32 or more RMHIP_ERR_UNSUPPORTED.  A product of at most 32 on every side runs
+ * the host loops' arithmetic (common/linalg.rs:57-147, as rmhip_complex_pagefun's small tier): bit-exact.  A larger one is ONE real
+ * product on the fp64 matrix cores: the interleaved A read as the real 2m x k matrix of its rows, B as the planes [B_re | B_im], then
+ * re = Ar Br - Ai Bi and im = Ar Bi + Ai Br from the product's four blocks, each with one rounding (a mixed product has no such step
+ * and never multiplies by an implied zero, so an Inf in the complex operand stays Inf).  Each part is within
+ * 2k eps (S(|Ar|,|Br|) + S(|Ai|,|Bi|)) resp. 2k eps (S(|Ar|,|Bi|) + S(|Ai|,|Br|)) of the host loop (k eps and the one surviving
+ * term for the mixed kinds), S the product of absolute values; bit-exact on Gaussian integers whose partial sums stay below 2^53.
+ * k == 0 gives (+0, +0), m == 0 or n == 0 an empty complex tensor.  A precision-32 context rounds each part through f32 once, on the
+ * final store (storage stays 2 x f64).  Workspace beyond the result: at most 2kn + 4mn doubles, returned to the pool by the call.
+ * No device -> host read, no synchronisation.  A refused call - a failed workspace allocation included - leaves no buffer behind;
+ * inputs are never written.  rmhip_matmul keeps refusing complex storage. */
+/* @serves matmul */
+RMHIP_API int rmhip_complex_matmul(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf* out);
 /* `matmul_epilogue` (lib.rs:2394-2405, descriptor `MatmulEpilogue` lib.rs:3498-3560): the epilogue is
  * folded into the dgemm store.  Order (simple_provider.rs:7800-7836): v = acc*alpha + beta; row scale;
  * column scale; clamp_min (max); clamp_max (min); pow; then the diagonal copy.  Buffer ids of 0 mean

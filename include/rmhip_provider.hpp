@@ -639,6 +639,12 @@ public:
         check(rmhip_matmul(ctx_, own(a), own(b), &out));
         return with_shape(out);
     }
+    // the same product with at least one complex-interleaved operand (the other may be real) -> a complex tensor; two real operands throw
+    GpuTensorHandle complex_matmul(const GpuTensorHandle& a, const GpuTensorHandle& b) const {
+        uint64_t out = 0;
+        check(rmhip_complex_matmul(ctx_, own(a), own(b), &out));
+        return with_shape(out);
+    }
     GpuTensorHandle matmul_epilogue(const GpuTensorHandle& a, const GpuTensorHandle& b, const rmhip_matmul_epilogue_t& ep) const {  // lib.rs:2394
         uint64_t id = 0;
         check(rmhip_matmul_epilogue(ctx_, own(a), own(b), &ep, &id));

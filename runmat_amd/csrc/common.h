@@ -448,6 +448,10 @@ int launch_cpage_small(Context* c, int kind, const double* A, const double* B, d
                        unsigned long long pages, const PageMap& pm, bool a_dense, bool b_dense, unsigned* pages_per_block);
 int launch_cpage_mfma(Context* c, int kind, const double* A, const double* B, double* C, unsigned m, unsigned n, unsigned k,
                       unsigned long long pages, const PageMap& pm);
+// the streaming passes around the real product that serves a 2-D product with an interleaved operand (cgemm.hip; gemm_plan.h plan_cgemm):
+// B (kn interleaved elements) -> the planes [B_re | B_im]; T, the real product, -> the interleaved result of mn elements
+int launch_cgemm_split_b(Context* c, const double* B, double* planes, size_t kn);
+int launch_cgemm_join(Context* c, int kind, const double* T, double* C, size_t mn);
 
 // rng (rng.hip)
 int launch_rng_uniform(Context* c, uint64_t state, double* out, size_t n);

@@ -3,7 +3,8 @@
 // decision, the launch follows it, and rmhip_gemm_last_route reports it.  No HIP header and no Context: tests/cpp/gemm_route_check.cpp
 // compiles this file with a plain host compiler and checks the rules (the tables of tests/gemm_ref.py and a sweep whose expected
 // digests, tests/golden/gemm_routes.txt, were taken from the launchers' former if-ladders).  A plan consumes nothing: the tile counter
-// of the persistent kernel is taken by the launcher, and only when the route says w8p.
+// of the persistent kernel is taken by the launcher, and only when the route says w8p.  plan_cgemm (at the end) says how a product with
+// a complex-interleaved operand is embedded in one real product; tests/cpp/cgemm_route_check.cpp checks it the same way.
 #pragma once
 #include <cstddef>
 
@@ -170,6 +171,44 @@ inline GemmRoute plan_sgemm(const GemmProblem& p, const GemmSite& s, const GemmK
     r.kernel = "s_w4";
     r.guard = !fast_k;
     return r;
+}
+
+// A product with a complex-interleaved operand (rmhip_complex_matmul, rmhip_ops.cpp; kernels cgemm.hip): kind 0 complex x complex,
+// 1 complex x real, 2 real x complex, as in complex_pagefun.hip.  An interleaved column-major A (m x k) is, read as doubles, the real
+// matrix A~ (2m x k, ld 2m) whose even rows are A_re and odd rows A_im, so every kind is ONE real product through launch_dgemm, which
+// plan_dgemm routes like any other:
+//   kind 1  A~ (2m x k) * B (k x n)                      is the interleaved result itself
+//   kind 2  T (m x 2n)  = A * [B_re | B_im]              join: C(i, j) = (T[i, j], T[i, n + j])
+//   kind 0  T (2m x 2n) = A~ * [B_re | B_im]             join: re = T[2i, j] - T[2i+1, n+j], im = T[2i, n+j] + T[2i+1, j]
+// `split_b`: B is first split into the planes [B_re | B_im] (k x 2n, ld k).  `join`: the product goes to T and a streaming pass forms
+// the result - kinds 0 and 2 always, kind 1 only in a precision-32 context, whose rounding is that pass.  `workspace` counts doubles:
+// 2kn for the planes (laid first) plus MN for T, so beyond the 2mn doubles of the result a call holds at most 2kn + 4mn doubles.
+// Products of at most kPageSmall on every side take the bit-exact small tier of complex pagefun as one page (`small`, nothing embedded).
+// The caller answers m == 0, n == 0 and k == 0 before it plans.
+namespace gemm_plan {
+constexpr size_t kPageSmall = 32;
+}
+struct CgemmPlan {
+    const char* route = "";  // small, embed
+    size_t M = 0, N = 0, K = 0, lda = 0, ldb = 0;  // the embedded real product (ldc = M)
+    bool split_b = false, join = false;
+    size_t workspace = 0;
+    const char* unsupported = nullptr;  // set: an embedded extent does not fit the launcher's 32-bit sides
+};
+inline CgemmPlan plan_cgemm(int kind, size_t m, size_t n, size_t k, bool r32) {
+    CgemmPlan p;
+    if (m <= gemm_plan::kPageSmall && n <= gemm_plan::kPageSmall && k <= gemm_plan::kPageSmall) return p.route = "small", p;
+    p.route = "embed";
+    p.M = kind == 2 ? m : 2 * m;
+    p.N = kind == 1 ? n : 2 * n;
+    p.K = k;
+    p.lda = p.M;
+    p.ldb = k;
+    p.split_b = kind != 1;
+    p.join = kind != 1 || r32;
+    p.workspace = (p.split_b ? 2 * k * n : 0) + (p.join ? p.M * p.N : 0);
+    if (p.M > 0xffffffffULL || p.N > 0xffffffffULL || p.K > 0xffffffffULL) p.unsupported = "complex_matmul: an embedded extent exceeds 2^32";
+    return p;
 }
 
 }  // namespace rmhip

@@ -1746,6 +1746,61 @@ int rmhip_complex_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inputs, size_
     return RMHIP_OK;
 }
 
+// matmul's second entry point: a 2-D product with at least one complex-interleaved operand, the result interleaved (include/rmhip.h;
+// kernels cgemm.hip).  plan_cgemm (gemm_plan.h) decides: a product of at most 32 on every side is one page of the complex
+// pagefun's bit-exact small tier; anything larger is ONE real product through launch_dgemm over the interleaved rows, between a split
+// of B into its planes and a join of the product's halves.  A real operand is settled to plain f64 as for complex pagefun.
+// record_launch("complex_matmul", {m, n, k}, {kind, route}), route 2 small and 4 embed (numbered after the pagefun tiers).
+int rmhip_complex_matmul(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "complex_matmul: null out");
+    *out = 0;
+    Buffer ra, rb;
+    RMHIP_TRY(c->lookup(a, &ra));
+    RMHIP_TRY(c->lookup(b, &rb));
+    if (!ra.cplx && !rb.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_matmul: both operands are real (rmhip_matmul serves them)");
+    if (ra.shape.size() != 2 || rb.shape.size() != 2) return fail(RMHIP_ERR_UNSUPPORTED, "matmul: only 2D supported");
+    const size_t m = ra.shape[0], k = ra.shape[1], kb = rb.shape[0], n = rb.shape[1];
+    if (k != kb) return fail(RMHIP_ERR_SHAPE, "matmul: inner dims must agree (%zux%zu * %zux%zu)", m, k, kb, n);
+    const int kind = ra.cplx && rb.cplx ? 0 : (ra.cplx ? 1 : 2);
+    const CgemmPlan pl = plan_cgemm(kind, m, n, k, c->precision == 32);
+    if (pl.unsupported) return fail(RMHIP_ERR_UNSUPPORTED, "%s", pl.unsupported);
+    const size_t oshape[2] = {m, n};
+    Buffer ob;
+    RMHIP_TRY(c->new_buffer_complex(oshape, 2, out, &ob));
+    if (ob.numel == 0) return RMHIP_OK;
+    Buffer ab, bb;
+    int rc = c->get_any(a, &ab);
+    if (!rc) rc = c->get_any(b, &bb);
+    int route = 0;
+    if (rc) {
+    } else if (k == 0) {
+        rc = launch_fill(c, ob.data(), 2 * ob.numel, 0.0);  // the three loops' empty sums: (+0, +0)
+    } else if (!std::strcmp(pl.route, "small")) {
+        route = 2;
+        PageMap pm{};  // one page of each operand: rank 0, offsets 0
+        rc = launch_cpage_small(c, kind, ab.data(), bb.data(), ob.data(), (unsigned)m, (unsigned)n, (unsigned)k, 1, pm, true, true, nullptr);
+    } else {
+        route = 4;
+        std::shared_ptr<Allocation> ws;  // [planes: 2kn][T: MN]; back in the pool on return, stream order keeps it until the kernels are done
+        if (pl.workspace) rc = c->alloc_device(pl.workspace, &ws);
+        double* const planes = ws ? ws->ptr : nullptr;
+        double* const T = ws ? ws->ptr + (pl.split_b ? 2 * k * n : 0) : nullptr;
+        if (!rc && pl.split_b) rc = launch_cgemm_split_b(c, bb.data(), planes, k * n);
+        if (!rc)
+            rc = launch_dgemm(c, pl.M, pl.N, pl.K, 1.0, ab.data(), pl.lda, pl.split_b ? planes : bb.data(), pl.ldb, 0.0,
+                              pl.join ? T : ob.data(), pl.M);
+        if (!rc && pl.join) rc = launch_cgemm_join(c, kind, T, ob.data(), m * n);
+    }
+    if (rc) {
+        rmhip_free(ctx, *out);
+        *out = 0;
+        return rc;
+    }
+    c->record_launch("complex_matmul", {{"m", m}, {"n", n}, {"k", k}}, {{"kind", (uint64_t)kind}, {"route", (uint64_t)route}});
+    return RMHIP_OK;
+}
+
 }  // extern "C"
 
 // ---- modulation (comms_ops.hip) ---------------------------------------------------------------------------------------------------------

@@ -904,6 +904,15 @@ class HipProvider:
         self._check(self._lib.rmhip_matmul(self._ctx, self._id(a), self._id(b), C.byref(out)))
         return self._handle(out.value, (a.shape[0], b.shape[1]))
 
+    def complex_matmul(self, a: GpuTensorHandle, b: GpuTensorHandle) -> GpuTensorHandle:
+        """`matmul(a, b)` with at least one complex-interleaved operand (the other may be real: a transpose or repmat view, a lazy
+        normal or f32 storage) -> complex [m, n] tensor.  `matmul`'s shape rule; the host loops' arithmetic (matmul_complex /
+        matmul_complex_real / matmul_real_complex, common/linalg.rs:57-147): bit-exact up to 32 on every side, above it one real product
+        over the interleaved rows within the contract of `rmhip.h`.  Two real operands raise UNSUPPORTED (`matmul` serves them)."""
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_complex_matmul(self._ctx, self._id(a), self._id(b), C.byref(out)))
+        return self._handle(out.value, (a.shape[0], b.shape[1]))
+
     def matmul_epilogue(self, a: GpuTensorHandle, b: GpuTensorHandle, alpha: float = 1.0, beta: float = 0.0,
                         row_scale: Optional[GpuTensorHandle] = None, col_scale: Optional[GpuTensorHandle] = None,
                         row_op: str = "multiply", col_op: str = "multiply", clamp_min: Optional[float] = None,

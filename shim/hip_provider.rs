@@ -494,11 +494,18 @@ impl AccelProvider for HipProvider {
             Ok(ProviderMoments2 { mean: self.handle(mean)?, ex2: self.handle(ex2)? })
         })
     }
+    // matmul: the entry point chosen by the operands' storage - rmhip_matmul for real operands, rmhip_complex_matmul when either is
+    // complex-interleaved (the result then is too); Err -> the builtin gathers and multiplies on the host, mtimes.rs:173-218.
     fn matmul<'a>(&'a self, a: &'a GpuTensorHandle, b: &'a GpuTensorHandle) -> AccelProviderFuture<'a, GpuTensorHandle> {
         Box::pin(async move {
             let mut out = 0u64;
-            check(unsafe { rmhip_matmul(self.ctx, self.own(a)?, self.own(b)?, &mut out) })?;
-            self.handle(out)
+            if !Self::is_complex(a) && !Self::is_complex(b) {
+                check(unsafe { rmhip_matmul(self.ctx, self.own(a)?, self.own(b)?, &mut out) })?;
+                self.handle(out)
+            } else {
+                check(unsafe { rmhip_complex_matmul(self.ctx, self.own(a)?, self.own(b)?, &mut out) })?;
+                self.complex_handle(out)
+            }
         })
     }
     fn mldivide<'a>(&'a self, lhs: &'a GpuTensorHandle, rhs: &'a GpuTensorHandle) -> AccelProviderFuture<'a, GpuTensorHandle> {
