@@ -212,6 +212,20 @@ int main() {
             ok = ok && eq(p.download(p.complex_matmul(za, br)).data, {5, 1, 6, 3});
             auto zrow = p.complex_from_real_imag(p.upload({1, 2}, {1, 2}), p.upload({1, 0}, {1, 2}));
             ok = ok && eq(p.download(p.complex_matmul(br, zrow)).data, {1, 1, 2, 2, 2, 0, 4, 0});
+            // the solves' second entry points undo the product: A \ (A * b) = b, inv(A) * (A * b) = b, and (b.' * A.') / A.' = b.'
+            try {
+                p.mldivide(za, zm);
+                ok = false;
+            } catch (const rmhip::ProviderError& e) {
+                ok = ok && e.code == RMHIP_ERR_UNSUPPORTED;
+            }
+            auto zs = p.complex_mldivide(za, zm);
+            ok = ok && zs.shape == std::vector<size_t>{2, 1} && p.is_complex(zs) && near(p.download(zs).data, {1, -1, 2, 1}, 1e-12);
+            ok = ok && near(p.download(p.complex_matmul(p.complex_inv(za), zm)).data, {1, -1, 2, 1}, 1e-12);
+            auto zat = p.complex_from_real_imag(p.upload({1, 2, 0, 3}, {2, 2}), p.upload({1, 0, -1, 2}, {2, 2}));  // A.'
+            auto zmt = p.complex_from_real_imag(p.upload({6, 3}, {1, 2}), p.upload({2, 6}, {1, 2}));                // (A * b).'
+            auto zr = p.complex_mrdivide(zmt, zat);
+            ok = ok && zr.shape == std::vector<size_t>{1, 2} && near(p.download(zr).data, {1, -1, 2, 1}, 1e-12);
         }
         {
             // moving_window's second entry point: the 101-point median (shrinking at the ends) of the ramp 0 .. 199 with a spike at 100, which

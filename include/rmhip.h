@@ -630,7 +630,8 @@ RMHIP_API int rmhip_window(rmhip_ctx* ctx, int kind, size_t len, int periodic, r
  * elementwise arithmetic `rmhip_complex_unary` / `rmhip_complex_binary` / `rmhip_complex_scalar` and the shape and indexing hooks
  * `rmhip_complex_reshape` / `_transpose` / `_permute` / `_repmat` / `_gather_linear` / `_scatter_linear` / `_circshift` / `_flip` /
  * `_cat`, and the calculus and filter hooks `rmhip_complex_gradient_dim` / `_trapz_dim` / `_polyint` / `_iir_filter` /
- * `_iir_filter_long`, the batched page products `rmhip_complex_pagefun` and the plain product `rmhip_complex_matmul` - and by the plumbing (download, shape, storage, isreal, free).  Every other entry point returns RMHIP_ERR_UNSUPPORTED for
+ * `_iir_filter_long`, the batched page products `rmhip_complex_pagefun`, the plain product `rmhip_complex_matmul` and the dense solves
+ * `rmhip_complex_mldivide` / `rmhip_complex_mrdivide` / `rmhip_complex_inv` - and by the plumbing (download, shape, storage, isreal, free).  Every other entry point returns RMHIP_ERR_UNSUPPORTED for
  * them (the caller gathers, as for any `Err`): fused elementwise, reductions, matmul, round_digits, pow, the comparisons, tril / triu
  * and read_scalar among them, and so do the real forms of the hooks just named (`rmhip_transpose`, `rmhip_permute`, ...): a caller
  * chooses the entry point by the operand's storage kind.  A precision-32 context rounds the values a complex result COMPUTES through
@@ -1109,6 +1110,37 @@ RMHIP_API int rmhip_mldivide(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf
  * back); here the same transposition around the LU solve, with the same soft failures as rmhip_mldivide. */
 /* @serves mrdivide */
 RMHIP_API int rmhip_mrdivide(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf* out);
+/* The same hook when at least one operand is complex-interleaved (try_gpu_mldivide screens only host `Value::Complex*`,
+ * mldivide.rs:201, so resident complex operands reach the provider; on its error the builtin gathers and runs mldivide_complex,
+ * mldivide.rs:343-395: the minimum-norm least-squares solution from an SVD with tol = eps * max(rows, cols) * max(s_max, 1)).  x = A\b,
+ * the result a complex-interleaved [n, k] tensor.  Operand kinds as rmhip_complex_matmul: complex \ complex, complex \ real, real \
+ * complex.  A complex system is the real system of twice the order [Ar -Ai; Ai Ar] [xr; xi] = [br; bi]: A -> E(A) preserves products,
+ * inverses, pseudo-inverses, least-squares and minimum-norm solutions, and E(A)'s singular values are A's, each twice.  So ONE real
+ * solve answers, with the policies of rmhip_mldivide: a complex A (m x n) is written out as E(A) (2m x 2n) and solved against [Br; Bi]
+ * (or [Br; 0]) - square by the small solver or the padded blocked LU, full-rank rectangular by the Gram route, what those refuse by the
+ * Jacobi SVD; a real A is solved as it is against the 2k columns [Br | Bi].  Bit for bit what rmhip_mldivide returns for the embedded
+ * system, re-joined.  The SVD's rank tolerance counts with the COMPLEX max(m, n) as the reference does; the pivot-ratio proxy
+ * (1e3 * order * eps), a routing heuristic, keeps the embedded order 2n.  Checks in this order, nothing allocated or left behind by a
+ * refused call: a null `out` RMHIP_ERR_INVALID; unknown ids RMHIP_ERR_NOT_FOUND; both operands real RMHIP_ERR_UNSUPPORTED
+ * (rmhip_mldivide serves them); more than 2-D RMHIP_ERR_UNSUPPORTED; a 1 x 1 divisor RMHIP_ERR_UNSUPPORTED (the reference's scalar form
+ * is an elementwise complex reciprocal and product: the CPU path); row counts that disagree RMHIP_ERR_SHAPE; an embedded extent beyond
+ * 2^31 - 1 or more than 65535 embedded right-hand sides RMHIP_ERR_UNSUPPORTED; an empty system RMHIP_ERR_UNSUPPORTED.  Status codes,
+ * messages, telemetry.solve_fallbacks[] names and the mldivide timer are rmhip_mldivide's.  A real operand may be a transpose or repmat
+ * view, a lazy random_normal or f32 storage (settled as rmhip_mldivide settles it).  A precision-32 context solves in f64 and rounds
+ * each part of the result through f32 once, on the final store.  Workspace beyond the real solve's own: 4mn + 2mk doubles (2mk for a
+ * real A) and the real 2n x k solution until it is joined.  No device -> host read beyond those of the real solve.  Cost: the real
+ * solve of order 2n - twice the flops and twice the matrix memory of a native complex LU.  rmhip_mldivide keeps refusing complex
+ * storage. */
+/* @serves mldivide */
+RMHIP_API int rmhip_complex_mldivide(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf* out);
+/* `mrdivide` with at least one complex-interleaved operand (mrdivide_complex, mrdivide.rs:343-402): X = B / A = (A.' \ B.').' with
+ * PLAIN transposes, not conjugate ones.  rmhip_complex_mldivide's solve on E(A.') - written by the embed pass itself, which then reads A
+ * with a stride of one stored column (contiguous stores, uncoalesced 16-byte loads: not a streaming read) - and the stacked
+ * B.', the join writing X; a real A is transposed into a temporary (mn + 2mk doubles of workspace in that case).  rmhip_mrdivide's shape
+ * rule, wording, solve_fallbacks names and timer (column counts must agree: RMHIP_ERR_SHAPE); otherwise the checks above in the same
+ * order.  The result is a complex-interleaved [rows(B), rows(A)] tensor. */
+/* @serves mrdivide */
+RMHIP_API int rmhip_complex_mrdivide(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf* out);
 /* `chol(a, lower)` (lib.rs:2502-2508 -> ProviderCholResult { factor, info } :658-662; host algorithm chol.rs:374-433: the reference's own
  * Cholesky-Crout with a symmetry check of every pair to 1e-12 relative): the upper factor R (A = R'R) or, lower != 0, L = R'.  The SUCCESS
  * path only - a recursive blocked factorisation (deep MFMA products, 64 x 64 leaves in LDS), *info = 0, forward error ~ cond * eps against
@@ -1223,6 +1255,17 @@ RMHIP_API int rmhip_complex_pagefun(rmhip_ctx* ctx, int op, const rmhip_buf* inp
  * "matrix is singular to working precision" or returns nalgebra's answer for a pivot in (0, 1e-12]).  [0, 0] gives [0, 0]. */
 /* @serves inv */
 RMHIP_API int rmhip_inv(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf* out);
+/* `inv` of a complex-interleaved matrix (inv_gpu hands resident complex handles over; inv_complex_tensor_impl, inv.rs:231-256, is
+ * nalgebra's `try_inverse`): ONE embedded solve E(A) \ [I; 0] (2n x 2n against 2n x n, not inv(E(A))) on rmhip_complex_mldivide's path
+ * with the SVD answer switched off - a pivot at the solver's cut-off or a pivot ratio below the proxy is RMHIP_ERR_SINGULAR and
+ * telemetry.solve_fallbacks[] counts "inv:singular", as in rmhip_inv.  rmhip_inv's shape rules and wording: [n, n] and [n, n, 1, ...]
+ * operands, the shape kept; non-square or higher-rank RMHIP_ERR_INVALID; [0, 0] gives an empty complex [0, 0].  Checks in this order:
+ * a null `out` RMHIP_ERR_INVALID; an unknown id RMHIP_ERR_NOT_FOUND; a real operand RMHIP_ERR_UNSUPPORTED (rmhip_inv serves it); the
+ * shape rules; a 1 x 1 operand RMHIP_ERR_UNSUPPORTED (a complex reciprocal: the CPU path); an embedded order beyond 2^31 - 1 or more
+ * than 65535 columns RMHIP_ERR_UNSUPPORTED.  Workspace beyond the real solve's own: 6 n^2 doubles and the real 2n x n solution until it
+ * is joined.  Precision 32 as rmhip_complex_mldivide.  A refused call leaves no buffer behind; the input is never written. */
+/* @serves inv */
+RMHIP_API int rmhip_complex_inv(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf* out);
 /* `linsolve` + ProviderLinsolveOptions / ProviderLinsolveResult (lib.rs:2422-2429, 679-697); CPU
  * semantics crates/runmat-runtime/src/builtins/math/linalg/solve/linsolve.rs:691-726 (option order:
  * TRANSA transposes A and swaps LT<->UT), 769-833 (substitution; a zero diagonal entry is the

@@ -655,6 +655,12 @@ public:
         check(rmhip_mldivide(ctx_, own(lhs), own(rhs), &out));
         return with_shape(out);
     }
+    // the same solve with at least one complex-interleaved operand (the other may be real) -> a complex tensor; two real operands throw
+    GpuTensorHandle complex_mldivide(const GpuTensorHandle& lhs, const GpuTensorHandle& rhs) const {
+        uint64_t out = 0;
+        check(rmhip_complex_mldivide(ctx_, own(lhs), own(rhs), &out));
+        return with_shape(out);
+    }
     // lib.rs:2502-2508 -> ProviderCholResult { factor, info } (lib.rs:658-662); throws for a matrix the host path must judge
     struct CholResult {
         GpuTensorHandle factor;
@@ -752,6 +758,17 @@ public:
     GpuTensorHandle mrdivide(const GpuTensorHandle& lhs, const GpuTensorHandle& rhs) const {
         uint64_t out = 0;
         check(rmhip_mrdivide(ctx_, own(lhs), own(rhs), &out));
+        return with_shape(out);
+    }
+    // inv / mrdivide on complex-interleaved operands (mrdivide: either operand may be real): one real solve of the embedded system
+    GpuTensorHandle complex_inv(const GpuTensorHandle& matrix) const {
+        uint64_t out = 0;
+        check(rmhip_complex_inv(ctx_, own(matrix), &out));
+        return with_shape(out);
+    }
+    GpuTensorHandle complex_mrdivide(const GpuTensorHandle& lhs, const GpuTensorHandle& rhs) const {
+        uint64_t out = 0;
+        check(rmhip_complex_mrdivide(ctx_, own(lhs), own(rhs), &out));
         return with_shape(out);
     }
     // ProviderLinsolveOptions / ProviderLinsolveResult (lib.rs:679-697, 2422-2429)

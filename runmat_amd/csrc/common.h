@@ -452,6 +452,15 @@ int launch_cpage_mfma(Context* c, int kind, const double* A, const double* B, do
 // B (kn interleaved elements) -> the planes [B_re | B_im]; T, the real product, -> the interleaved result of mn elements
 int launch_cgemm_split_b(Context* c, const double* B, double* planes, size_t kn);
 int launch_cgemm_join(Context* c, int kind, const double* T, double* C, size_t mn);
+// the streaming passes around the real solve that serves a system with a complex-interleaved operand (csolve.hip; csolve_plan.h):
+//   embed  A (m x n interleaved, ld m) -> E(A) = [Ar -Ai; Ai Ar] (2m x 2n real, ld 2m), or E(A.') (2n x 2m, ld 2n) when `transposed`
+//   stack  the right-hand side of the m-row system with k columns -> [Br; Bi] (2m x k; kind 0), [Br; 0] (kind 1), [Br | Bi] (m x 2k;
+//          kind 2) or [I; 0] (2m x k, kind 3: B is not read); `transposed`: B is stored k x m (ld k) and B.' is stacked
+//   join   T, the real solution (2n x k for kinds 0 and 1, n x 2k for kind 2), -> the interleaved X (n x k, ld n; `transposed`: X.' k x n,
+//          ld k), each part rounded through f32 at precision 32
+int launch_csolve_embed(Context* c, const double* A, size_t m, size_t n, bool transposed, double* E);
+int launch_csolve_stack(Context* c, int kind, const double* B, size_t m, size_t k, bool transposed, double* T);
+int launch_csolve_join(Context* c, int kind, const double* T, size_t n, size_t k, bool transposed, double* X);
 
 // rng (rng.hip)
 int launch_rng_uniform(Context* c, uint64_t state, double* out, size_t n);
@@ -539,7 +548,9 @@ const LuProcessKnobs& lu_process_knobs();
 static constexpr int kSvdMaxColsDefault = 4096;  // 0.15 s at 512, 0.45 s at 1024, 1.7 s at 2048, 9.6 s at 4096 (scripts/svd_sizes.py)
 int svd_max_cols();
 static constexpr int kSvdProxyMaxCols = 1024;  // up to here an LU with a tiny pivot RATIO (no pivot below the cut-off) is re-answered by the SVD
-int svd_solve_device(Context* c, const double* A, size_t m, size_t n, const double* B, size_t nrhs, double* X, int* rank_out);
+// tol_dim: the dimension in the rank tolerance eps * dim * max(s_max, 1); 0 = max(m, n) (a complex system solved through its real embedding
+// passes its complex max(rows, cols))
+int svd_solve_device(Context* c, const double* A, size_t m, size_t n, const double* B, size_t nrhs, double* X, int* rank_out, size_t tol_dim = 0);
 // the same decomposition behind rank / cond / pinv (rank.rs, cond.rs, pinv.rs: nalgebra's SVD on the CPU)
 int svd_values_host(Context* c, const char* who, const double* A, size_t m, size_t n, std::vector<double>* values);
 double svd_default_tolerance(const std::vector<double>& values, size_t m, size_t n);

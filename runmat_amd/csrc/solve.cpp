@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "csolve_plan.h"
 #include "host_shape.h"
 
 using namespace rmhip;
@@ -176,16 +177,16 @@ static int lstsq_full_rank(rmhip_ctx* ctx, Context* c, const double* A, size_t m
 // What the LU / Gram paths refuse - singular, rank-deficient or ill-conditioned systems - answered the way the reference answers every
 // system: minimum-norm least squares from an SVD with its tolerance rule (svdsolve.hip), as long as min(rows, cols) <= svd_max_cols().
 // `refused` is the status of the path that gave up, returned unchanged when the entry point does not allow an SVD answer (`allowed`),
-// the system is too large for the SVD path or RMHIP_NO_SVD_PATH is set.
+// the system is too large for the SVD path or RMHIP_NO_SVD_PATH is set.  `tol_dim` is handed through to svd_solve_device (0: max(m, n)).
 static int svd_fallback(rmhip_ctx* ctx, Context* c, bool allowed, int refused, const double* A, size_t m, size_t n, const double* B, size_t nrhs,
-                        rmhip_buf* out) {
+                        rmhip_buf* out, size_t tol_dim = 0) {
     if (!allowed || (m < n ? m : n) > (size_t)svd_max_cols() || !solve_knobs().svd_path) return refused;
     Buffer ob;
     rmhip_buf oid = 0;
     const size_t oshape[2] = {n, nrhs};
     RMHIP_TRY(c->new_buffer(oshape, 2, &oid, &ob));
     int rank = 0;
-    const int rc = svd_solve_device(c, A, m, n, B, nrhs, ob.data(), &rank);
+    const int rc = svd_solve_device(c, A, m, n, B, nrhs, ob.data(), &rank, tol_dim);
     if (rc) {
         rmhip_free(ctx, oid);
         return rc;
@@ -197,10 +198,10 @@ static int svd_fallback(rmhip_ctx* ctx, Context* c, bool allowed, int refused, c
 
 // A rectangular system: the Gram route, then the SVD for what it refuses (an empty system is refused by both)
 static int solve_rectangular(rmhip_ctx* ctx, Context* c, bool allow_svd, const double* A, size_t m, size_t n, const double* B, size_t nrhs,
-                             rmhip_buf* out) {
+                             rmhip_buf* out, size_t tol_dim = 0) {
     const int rc = lstsq_full_rank(ctx, c, A, m, n, B, nrhs, out);
     if (rc != RMHIP_ERR_UNSUPPORTED || !m || !n || !nrhs) return rc;
-    return svd_fallback(ctx, c, allow_svd, rc, A, m, n, B, nrhs, out);
+    return svd_fallback(ctx, c, allow_svd, rc, A, m, n, B, nrhs, out, tol_dim);
 }
 
 // How an entry point wants its general square system answered
@@ -213,12 +214,13 @@ struct SolvePolicy {
 
 // X = A \ B for a general square A of order n >= 1: the one-launch small solver where it applies, otherwise the blocked LU in the padded
 // workspace; a pivot at the cut-off (or, under `ratio_proxy`, a tiny pivot ratio) sets the SINGULAR message and the SVD answers if it may.
+// `tol_dim` only reaches the SVD's rank tolerance (0: n); the ratio proxy below is a routing heuristic and counts with the order it is given.
 static int solve_square_general(rmhip_ctx* ctx, Context* c, SolvePolicy p, const double* A, size_t n, const double* B, size_t nrhs,
-                                rmhip_buf* out) {
+                                rmhip_buf* out, size_t tol_dim = 0) {
     const SolveKnobs knobs = solve_knobs();
     auto at_cutoff = [&](size_t pivots) {
         const int refused = fail(RMHIP_ERR_SINGULAR, "%s: %zu pivot(s) <= 1e-12; %s", p.who, pivots, p.singular_hint);
-        return nrhs ? svd_fallback(ctx, c, p.allow_svd, refused, A, n, n, B, nrhs, out) : refused;  // no right-hand side: nothing for the SVD to answer
+        return nrhs ? svd_fallback(ctx, c, p.allow_svd, refused, A, n, n, B, nrhs, out, tol_dim) : refused;  // no right-hand side: nothing for the SVD to answer
     };
     // A nearly singular matrix need not produce a pivot below the cut-off, yet the reference would DROP its small singular values
     // (s_i <= eps * n * max(s_max, 1), mldivide.rs:396-404) where an LU divides by them.  Pivot ratio as the (cheap, rough) proxy of
@@ -227,7 +229,7 @@ static int solve_square_general(rmhip_ctx* ctx, Context* c, SolvePolicy p, const
     const double ratio_floor = 1.0e3 * (double)n * 2.220446049250313e-16;
     auto tiny_ratio = [&](double mn, double mx) {
         const int refused = fail(RMHIP_ERR_SINGULAR, "%s: pivot ratio %.2e: numerically singular", p.who, mx > 0 ? mn / mx : 0.0);
-        return svd_fallback(ctx, c, p.allow_svd, refused, A, n, n, B, nrhs, out);
+        return svd_fallback(ctx, c, p.allow_svd, refused, A, n, n, B, nrhs, out, tol_dim);
     };
     Buffer ob;
     rmhip_buf oid = 0;
@@ -308,7 +310,124 @@ static int mldivide_impl(rmhip_ctx* ctx, Context* c, rmhip_buf a, rmhip_buf b, b
     return solve_square_general(ctx, c, policy, ab.data(), as[0], bb.data(), bs[1], out);
 }
 
+// ---- the dense solves on complex-interleaved operands (csolve_plan.h, csolve.hip) ------------------------------------------------------
+// One real solve of the embedded system through the cores above, between an embed / stack pass and a join.  The system is m x n with nrhs
+// right-hand sides in COMPLEX extents; `transposed` (mrdivide): A is stored n x m and B nrhs x m, the system is A.' X.' = B.' with PLAIN
+// transposes, and the join writes X (nrhs x n).  `kind` is complex_matmul's (0 both complex, 1 A complex and B real, 2 A real and B
+// complex); inv passes kind 0 with B == nullptr, its right-hand side is [I; 0].  Both operands as Context::get_any hands them over.
+// The result is a complex buffer of shape `oshape`; the real solution the cores register is freed before returning.  `pl` is the
+// caller's plan_csolve(entry, kind, m, n, nrhs), already found servable; m and n are not zero.  The messages of the cores name mldivide
+// for all three entry points, as mldivide_impl's do for the real ones.
+static int complex_solve(rmhip_ctx* ctx, Context* c, const CsolvePlan& pl, int entry, int kind, const double* A, const double* B, size_t m,
+                         size_t n, size_t nrhs, bool allow_svd, const size_t* oshape, size_t orank, rmhip_buf* out) {
+    const bool transposed = pl.transpose_a;
+    std::shared_ptr<Allocation> ws;  // [E(A) or the transposed real A][stacked right-hand side]; back in the pool on return, in stream order
+    RMHIP_TRY(c->alloc_device(pl.workspace ? pl.workspace : 1, &ws));
+    double* const T = ws->ptr + pl.a_workspace;
+    const double* Areal = A;
+    if (pl.embed_a) {
+        RMHIP_TRY(launch_csolve_embed(c, A, transposed ? n : m, transposed ? m : n, transposed, ws->ptr));
+        Areal = ws->ptr;
+    } else if (transposed) {
+        RMHIP_TRY(transpose_device(c, A, n, n, m, ws->ptr, m));
+        Areal = ws->ptr;
+    }
+    RMHIP_TRY(launch_csolve_stack(c, B ? kind : 3, B, m, nrhs, transposed, T));
+    rmhip_buf xid = 0;
+    if (pl.M != pl.N) {
+        RMHIP_TRY(solve_rectangular(ctx, c, allow_svd, Areal, pl.M, pl.N, T, pl.NRHS, &xid, pl.tol_dim));
+    } else {
+        const SolvePolicy policy{"mldivide", "matrix is numerically singular, use the CPU SVD path", true, allow_svd};
+        RMHIP_TRY(solve_square_general(ctx, c, policy, Areal, pl.M, T, pl.NRHS, &xid, pl.tol_dim));
+    }
+    Buffer xb, ob;
+    int rc = c->lookup(xid, &xb);
+    if (!rc) rc = c->new_buffer_complex(oshape, orank, out, &ob);
+    if (!rc) {
+        rc = launch_csolve_join(c, kind, xb.data(), n, nrhs, transposed, ob.data());
+        if (rc) {
+            rmhip_free(ctx, *out);
+            *out = 0;
+        }
+    }
+    rmhip_free(ctx, xid);
+    if (rc) return rc;
+    c->record_launch("complex_solve", {{"m", m}, {"n", n}, {"nrhs", nrhs}}, {{"kind", (uint64_t)kind}, {"entry", (uint64_t)entry}});
+    return RMHIP_OK;
+}
+
+// A \ B or (divide_right) B / A with at least one complex-interleaved operand; `who` is "mldivide" or "mrdivide"
+static int complex_divide_impl(rmhip_ctx* ctx, Context* c, bool divide_right, rmhip_buf a, rmhip_buf b, rmhip_buf* out) {
+    const char* who = divide_right ? "mrdivide" : "mldivide";
+    if (!out) return fail(RMHIP_ERR_INVALID, "null out");
+    *out = 0;
+    Buffer ra, rb;
+    RMHIP_TRY(c->lookup(a, &ra));
+    RMHIP_TRY(c->lookup(b, &rb));
+    if (!ra.cplx && !rb.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_%s: both operands are real (rmhip_%s serves them)", who, who);
+    if (ra.shape.size() > 2 || rb.shape.size() > 2) return fail(RMHIP_ERR_UNSUPPORTED, "%s: only 2D supported", who);
+    const std::vector<size_t> as = normalize_matrix_shape(ra.shape), bs = normalize_matrix_shape(rb.shape);
+    // the reference's scalar form is an elementwise complex reciprocal and product: it stays with the host
+    if (ra.numel == 1) return fail(RMHIP_ERR_UNSUPPORTED, "complex_%s: scalar operands use the CPU path", who);
+    if (!divide_right && as[0] != bs[0]) return fail(RMHIP_ERR_SHAPE, "mldivide: row mismatch (%zu vs %zu)", as[0], bs[0]);
+    if (divide_right && bs[1] != as[1]) return fail(RMHIP_ERR_SHAPE, "mrdivide: column mismatch (%zu vs %zu)", bs[1], as[1]);
+    const int kind = ra.cplx && rb.cplx ? 0 : (ra.cplx ? 1 : 2);
+    // the system the solve sees: A (m x n) X = B, or A.' (m x n) X.' = B.'
+    const size_t m = divide_right ? as[1] : as[0], n = divide_right ? as[0] : as[1], nrhs = divide_right ? bs[0] : bs[1];
+    const CsolvePlan pl = plan_csolve(divide_right ? CSOLVE_MRDIVIDE : CSOLVE_MLDIVIDE, kind, m, n, nrhs);
+    if (pl.unsupported) return fail(RMHIP_ERR_UNSUPPORTED, "%s", pl.unsupported);
+    if (m == 0 || n == 0) return fail(RMHIP_ERR_UNSUPPORTED, "mldivide: empty system");
+    Buffer ab, bb;
+    RMHIP_TRY(c->get_any(a, &ab));
+    RMHIP_TRY(c->get_any(b, &bb));
+    const size_t oshape[2] = {divide_right ? nrhs : n, divide_right ? n : nrhs};
+    return complex_solve(ctx, c, pl, divide_right ? CSOLVE_MRDIVIDE : CSOLVE_MLDIVIDE, kind, ab.data(), bb.data(), m, n, nrhs, true, oshape, 2,
+                         out);
+}
+
 extern "C" {
+
+int rmhip_complex_mldivide(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf b, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    ScopedTimer timer(&c->tel.mldivide_count, &c->tel.mldivide_ns);
+    return count_fallback(c, complex_divide_impl(ctx, c, false, a, b, out), "mldivide:unsupported", "mldivide:singular");
+}
+
+int rmhip_complex_mrdivide(rmhip_ctx* ctx, rmhip_buf b, rmhip_buf a, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    ScopedTimer timer(&c->tel.mrdivide_count, &c->tel.mrdivide_ns);
+    return count_fallback(c, complex_divide_impl(ctx, c, true, a, b, out), "mrdivide:unsupported", "mrdivide:singular");
+}
+
+int rmhip_complex_inv(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf* out) {
+    CTX_OR_FAIL(ctx);
+    if (!out) return fail(RMHIP_ERR_INVALID, "null out");
+    *out = 0;
+    Buffer ab;
+    RMHIP_TRY(c->lookup(a, &ab));
+    if (!ab.cplx) return fail(RMHIP_ERR_UNSUPPORTED, "complex_inv: the operand is real (rmhip_inv serves it)");
+    // rmhip_inv's shape rules and wording (matrix_dimensions, inv.rs:209-230)
+    const std::vector<size_t>& s = ab.shape;
+    size_t rows = 1, cols = 1;
+    if (s.size() == 1) {
+        if (s[0] != 1) return fail(RMHIP_ERR_INVALID, "inv: input must be a square matrix.");
+    } else if (s.size() >= 2) {
+        for (size_t d = 2; d < s.size(); ++d)
+            if (s[d] != 1) return fail(RMHIP_ERR_INVALID, "inv: inputs must be 2-D matrices.");
+        rows = s[0];
+        cols = s[1];
+    }
+    if (rows != cols) return fail(RMHIP_ERR_INVALID, "inv: input must be a square matrix.");
+    if (rows == 1) return fail(RMHIP_ERR_UNSUPPORTED, "complex_inv: scalar operands use the CPU path");
+    if (rows == 0) return c->new_buffer_complex(s.data(), s.size(), out);
+    // (an order the real solve cannot take is refused in mldivide's words, as rmhip_inv refuses it through mldivide_impl)
+    const CsolvePlan pl = plan_csolve(CSOLVE_INV, 0, rows, rows, rows);
+    if (pl.unsupported) return count_fallback(c, fail(RMHIP_ERR_UNSUPPORTED, "%s", pl.unsupported), "inv:unsupported", "inv:singular");
+    // ONE embedded solve E(A) \ [I; 0], not inv(E(A)); a singular matrix is RMHIP_ERR_SINGULAR as in rmhip_inv - the minimum-norm
+    // solution mldivide would return is no inverse
+    return count_fallback(c, complex_solve(ctx, c, pl, CSOLVE_INV, 0, ab.data(), nullptr, rows, rows, rows, false, s.data(), s.size(), out),
+                          "inv:unsupported", "inv:singular");
+}
 
 int rmhip_lu(rmhip_ctx* ctx, rmhip_buf a, rmhip_buf out5[5]) {
     CTX_OR_FAIL(ctx);

@@ -210,11 +210,13 @@ static int svd_apply(Context* c, const JacobiSvd& s, size_t m, size_t n, const d
     return RMHIP_OK;
 }
 
-int svd_solve_device(Context* c, const double* A, size_t m, size_t n, const double* B, size_t nrhs, double* X, int* rank_out) {
+// tol_dim: the dimension the rank tolerance counts with; 0 = max(m, n), the rule for a real system.  The complex entry points (solve.cpp)
+// hand over the real embedding of a complex system and the COMPLEX max(rows, cols) the reference's rule is stated in.
+int svd_solve_device(Context* c, const double* A, size_t m, size_t n, const double* B, size_t nrhs, double* X, int* rank_out, size_t tol_dim) {
     if (m == 0 || n == 0 || nrhs == 0) return fail(RMHIP_ERR_UNSUPPORTED, "mldivide: empty system");
     JacobiSvd s;
     RMHIP_TRY(jacobi_svd(c, "mldivide", A, m, n, &s));
-    const double maxdim = (double)(m > n ? m : n);
+    const double maxdim = (double)(tol_dim ? tol_dim : (m > n ? m : n));
     const double tol = 2.220446049250313e-16 * maxdim * (s.smax > 1.0 ? s.smax : 1.0);  // mldivide.rs:396-404
     return svd_apply(c, s, m, n, B, nrhs, tol, X, rank_out);
 }

@@ -1016,6 +1016,30 @@ class HipProvider:
         self._check(self._lib.rmhip_mrdivide(self._ctx, self._id(lhs), self._id(rhs), C.byref(out)))
         return self._handle(out.value)
 
+    def complex_mldivide(self, lhs: GpuTensorHandle, rhs: GpuTensorHandle) -> GpuTensorHandle:
+        """`mldivide(lhs, rhs)` with at least one complex-interleaved operand (the other may be real: a view, a lazy normal or f32
+        storage) -> complex [n, k] tensor.  The contract is mldivide_complex (mldivide.rs:343-395); served as ONE real solve of the
+        embedded system [Ar -Ai; Ai Ar] [xr; xi] = [br; bi] with `mldivide`'s policies (LU, Gram route, Jacobi SVD with the tolerance
+        counted in complex dimensions), bit for bit what `mldivide` gives on that system.  Two real operands, a 1 x 1 divisor and more
+        than 2-D raise UNSUPPORTED."""
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_complex_mldivide(self._ctx, self._id(lhs), self._id(rhs), C.byref(out)))
+        return self._handle(out.value)
+
+    def complex_mrdivide(self, lhs: GpuTensorHandle, rhs: GpuTensorHandle) -> GpuTensorHandle:
+        """`mrdivide(lhs, rhs)` with at least one complex-interleaved operand: X = lhs / rhs = (rhs.' \\ lhs.').' with plain transposes
+        (mrdivide_complex, mrdivide.rs:343-402), through `complex_mldivide`'s solve -> complex [rows(lhs), rows(rhs)] tensor."""
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_complex_mrdivide(self._ctx, self._id(lhs), self._id(rhs), C.byref(out)))
+        return self._handle(out.value)
+
+    def complex_inv(self, matrix: GpuTensorHandle) -> GpuTensorHandle:
+        """`inv` of a complex-interleaved matrix: one embedded solve against [I; 0]; a singular matrix raises SINGULAR as `inv` does
+        (no minimum-norm answer), a real operand UNSUPPORTED.  [n, n, 1] keeps its shape, [0, 0] gives an empty complex tensor."""
+        out = C.c_uint64()
+        self._check(self._lib.rmhip_complex_inv(self._ctx, self._id(matrix), C.byref(out)))
+        return self._handle(out.value)
+
     def chol(self, a: GpuTensorHandle, lower: bool = False) -> "ProviderCholResult":
         """`chol` (lib.rs:2502-2508) -> `ProviderCholResult{factor, info}` (:658-662): the success path only (info == 0); a matrix that is
         not symmetric / positive definite raises (UNSUPPORTED) and chol.rs:331-342 takes its host path."""

@@ -508,11 +508,19 @@ impl AccelProvider for HipProvider {
             }
         })
     }
+    // mldivide / mrdivide / inv: the entry point chosen by the operands' storage - the real one when no operand is complex-interleaved,
+    // rmhip_complex_* when either is (the result then is too: one real solve of the embedded system of twice the order); Err -> the
+    // builtins gather and run mldivide_complex / mrdivide_complex / inv_complex_tensor_impl on the host.
     fn mldivide<'a>(&'a self, lhs: &'a GpuTensorHandle, rhs: &'a GpuTensorHandle) -> AccelProviderFuture<'a, GpuTensorHandle> {
         Box::pin(async move {
             let mut out = 0u64;
-            check(unsafe { rmhip_mldivide(self.ctx, self.own(lhs)?, self.own(rhs)?, &mut out) })?;
-            self.handle(out)
+            if !Self::is_complex(lhs) && !Self::is_complex(rhs) {
+                check(unsafe { rmhip_mldivide(self.ctx, self.own(lhs)?, self.own(rhs)?, &mut out) })?;
+                self.handle(out)
+            } else {
+                check(unsafe { rmhip_complex_mldivide(self.ctx, self.own(lhs)?, self.own(rhs)?, &mut out) })?;
+                self.complex_handle(out)
+            }
         })
     }
     // chol: the hook's second entry point ALONE.  It answers everything the first one answers, bit for bit, and the failure forms too (info
@@ -529,15 +537,25 @@ impl AccelProvider for HipProvider {
     fn inv<'a>(&'a self, matrix: &'a GpuTensorHandle, _options: ProviderInvOptions) -> AccelProviderFuture<'a, GpuTensorHandle> {
         Box::pin(async move {
             let mut out = 0u64;
-            check(unsafe { rmhip_inv(self.ctx, self.own(matrix)?, &mut out) })?;
-            self.handle(out)
+            if !Self::is_complex(matrix) {
+                check(unsafe { rmhip_inv(self.ctx, self.own(matrix)?, &mut out) })?;
+                self.handle(out)
+            } else {
+                check(unsafe { rmhip_complex_inv(self.ctx, self.own(matrix)?, &mut out) })?;
+                self.complex_handle(out)
+            }
         })
     }
     fn mrdivide<'a>(&'a self, lhs: &'a GpuTensorHandle, rhs: &'a GpuTensorHandle) -> AccelProviderFuture<'a, GpuTensorHandle> {
         Box::pin(async move {
             let mut out = 0u64;
-            check(unsafe { rmhip_mrdivide(self.ctx, self.own(lhs)?, self.own(rhs)?, &mut out) })?;
-            self.handle(out)
+            if !Self::is_complex(lhs) && !Self::is_complex(rhs) {
+                check(unsafe { rmhip_mrdivide(self.ctx, self.own(lhs)?, self.own(rhs)?, &mut out) })?;
+                self.handle(out)
+            } else {
+                check(unsafe { rmhip_complex_mrdivide(self.ctx, self.own(lhs)?, self.own(rhs)?, &mut out) })?;
+                self.complex_handle(out)
+            }
         })
     }
     fn linsolve<'a>(&'a self, lhs: &'a GpuTensorHandle, rhs: &'a GpuTensorHandle, o: &'a ProviderLinsolveOptions)
