@@ -1590,7 +1590,9 @@ RMHIP_API int rmhip_telemetry_solve_fallback(rmhip_ctx* ctx, size_t index, char*
 /* `ProviderTelemetry::kernel_launches` (lib.rs:1355-1356, `KernelLaunchTelemetry` :1372-1378): bounded log of recent
  * dispatches, oldest first (index 0); same kernel names and attribute keys as the reference's wgpu provider records
  * (ops/telemetry.rs:26-34,140-146, helpers.rs:36-50): "fused_elementwise" {len, inputs, rank}, "fused_elementwise_multi"
- * {.., num_outputs}, "fused_reduction" {reduce_len, slices, rank} / {wg, flavor}, "matmul" {m, n, k}. */
+ * {.., num_outputs}, "fused_reduction" {reduce_len, slices, rank} / {wg, flavor}, "matmul" {m, n, k}.  The tuning attributes of
+ * the two fused elementwise records name what ran: {wg, form, grid, unroll} - form 0 = the 16-byte streaming kernel, 1 = the
+ * element-sized one (an operand off a 16-byte boundary), 2 = the broadcast kernel, 3 = its flat form; grid = blocks launched. */
 typedef struct rmhip_kernel_attr {
     char key[16];
     uint64_t value;

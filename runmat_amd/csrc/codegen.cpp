@@ -489,8 +489,11 @@ int get_elementwise_kernel(Context* c, const ElementwiseProgram& p, unsigned mas
     // f32 storage: 4-byte accesses in the broadcast kernel, so twice the elements per thread keep the same bytes in flight
     // (interleaved A/B at 8192^2, `A - row`: 4051 -> 4244 GB/s)
     if (f32 && !std::getenv("RMHIP_EW_BCAST_ELEMS")) t.bcast_elems = 8;
-    char tun[96];
-    std::snprintf(tun, sizeof tun, "|u%d|b%d|bb%dx%d|nt%d%d|c%d|m%x", t.unroll, t.block, t.bcast_block, t.bcast_elems, t.nt_load, t.nt_store, t.chunked, mask);
+    // every field of `t` that the launch reads from the cached kernel is part of the key, blocks_per_cu (the grid cap) included: it does
+    // not change the source, but a kernel cached under another value would launch with that value's cap
+    char tun[112];
+    std::snprintf(tun, sizeof tun, "|u%d|b%d|g%d|bb%dx%d|nt%d%d|c%d|m%x", t.unroll, t.block, t.blocks_per_cu, t.bcast_block, t.bcast_elems, t.nt_load,
+                  t.nt_store, t.chunked, mask);
     const std::string key_text = p.canonical + tun + (f32 ? "|f32" : "") + (rng_mask ? "|rng" + std::to_string(rng_mask) : "");
     const uint64_t key = fnv1a(key_text);
     {

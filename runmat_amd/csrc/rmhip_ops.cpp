@@ -276,6 +276,8 @@ int rmhip_fused_elementwise(rmhip_ctx* ctx, const char* shader, const rmhip_buf*
 
     const EwTuning& t = kern->tuning;
     hipError_t e;
+    hipFunction_t fn = nullptr;          // the form launched, by the function itself: the record below names what ran
+    uint64_t grid_blocks = 0, unroll = 1;
     if (fast) {
         bool vec_ok = true;
         for (size_t k = 0; k < n_in; ++k)
@@ -287,7 +289,8 @@ int rmhip_fused_elementwise(rmhip_ctx* ctx, const char* shader, const rmhip_buf*
         const size_t work = vec_ok ? len / (f32 ? 4 : 2) : len;
         int n_stream = 0;
         for (size_t k = 0; k < n_in; ++k) n_stream += ((mask >> k) & 1u) ? 0 : 1;
-        const size_t per_block = (size_t)t.block * t.unroll_for(n_stream, program_is_heavy(prog));
+        unroll = (uint64_t)t.unroll_for(n_stream, program_is_heavy(prog));
+        const size_t per_block = (size_t)t.block * unroll;
         size_t want = (work + per_block - 1) / per_block;
         // a kernel that generates normals is VALU-bound and pays a skip-ahead + 10 KiB of table staging per block: one resident set of
         // blocks (2048 threads per CU) walks the tensor instead of blocks_per_cu waves of them
@@ -305,8 +308,9 @@ int rmhip_fused_elementwise(rmhip_ctx* ctx, const char* shader, const rmhip_buf*
             args.push_back(&rng_jp);
             for (size_t k = 0; k < n_in; ++k) c->lazy_randn_fused += (rng_mask >> k) & 1u;
         }
-        e = hipModuleLaunchKernel(vec_ok ? kern->fn_fast : kern->fn_fast1, grid, 1, 1, t.block, 1, 1, 0, c->stream,
-                                  args.data(), nullptr);
+        fn = vec_ok ? kern->fn_fast : kern->fn_fast1;
+        grid_blocks = grid;
+        e = hipModuleLaunchKernel(fn, grid, 1, 1, t.block, 1, 1, 0, c->stream, args.data(), nullptr);
     } else {
         std::vector<unsigned long long> p(11 + 8 * n_in, 0);
         const unsigned long long d0 = oshape[0];
@@ -325,7 +329,9 @@ int rmhip_fused_elementwise(rmhip_ctx* ctx, const char* shader, const rmhip_buf*
             unsigned n32 = (unsigned)len;
             args.push_back(&n32);
             const unsigned long long want = (len + 255) / 256, cap = (unsigned long long)c->num_cus * 16;
-            e = hipModuleLaunchKernel(kern->fn_bcast_flat, (unsigned)std::min(want, cap), 1, 1, 256, 1, 1, 0, c->stream, args.data(), nullptr);
+            fn = kern->fn_bcast_flat;
+            grid_blocks = std::min(want, cap);
+            e = hipModuleLaunchKernel(fn, (unsigned)grid_blocks, 1, 1, 256, 1, 1, 0, c->stream, args.data(), nullptr);
         } else {
             const unsigned long long blocks = nchunks * outer;
             const unsigned long long gx = std::min<unsigned long long>(blocks, 1048576ULL);
@@ -334,8 +340,9 @@ int rmhip_fused_elementwise(rmhip_ctx* ctx, const char* shader, const rmhip_buf*
                 for (size_t k = 0; k < n_out; ++k) rmhip_free(ctx, ids[k]);
                 return fail(RMHIP_ERR_UNSUPPORTED, "fused_elementwise: broadcast grid too large");
             }
-            e = hipModuleLaunchKernel(kern->fn_bcast, (unsigned)gx, (unsigned)gy, 1, t.bcast_block, 1, 1, 0, c->stream, args.data(),
-                                      nullptr);
+            fn = kern->fn_bcast;
+            grid_blocks = gx * gy;
+            e = hipModuleLaunchKernel(fn, (unsigned)gx, (unsigned)gy, 1, t.bcast_block, 1, 1, 0, c->stream, args.data(), nullptr);
         }
     }
     if (e != hipSuccess) {
@@ -343,9 +350,16 @@ int rmhip_fused_elementwise(rmhip_ctx* ctx, const char* shader, const rmhip_buf*
         return fail(RMHIP_ERR_HIP, "fused_elementwise launch: %s", hipGetErrorString(e));
     }
     c->tel.kernel_launches++;
-    if (n_out == 1) c->record_launch("fused_elementwise", {{"len", len}, {"inputs", n_in}, {"rank", rank}}, {{"wg", (uint64_t)(fast ? t.block : t.bcast_block)}});
-    else c->record_launch("fused_elementwise_multi", {{"len", len}, {"inputs", n_in}, {"rank", rank}, {"num_outputs", n_out}},
-                          {{"wg", (uint64_t)(fast ? t.block : t.bcast_block)}});
+    // form: 0 rm_ew_fast, 1 rm_ew_fast1, 2 rm_ew_bcast, 3 rm_ew_bcast_flat; grid: blocks launched (gx * gy for rm_ew_bcast);
+    // unroll: the streaming forms' vectors per thread and trip
+    const uint64_t form = fn == kern->fn_fast ? 0 : fn == kern->fn_fast1 ? 1 : fn == kern->fn_bcast ? 2 : 3;
+    const uint64_t wg = fast ? t.block : fn == kern->fn_bcast ? t.bcast_block : 256;
+    if (n_out == 1)
+        c->record_launch("fused_elementwise", {{"len", len}, {"inputs", n_in}, {"rank", rank}},
+                         {{"wg", wg}, {"form", form}, {"grid", grid_blocks}, {"unroll", unroll}});
+    else
+        c->record_launch("fused_elementwise_multi", {{"len", len}, {"inputs", n_in}, {"rank", rank}, {"num_outputs", n_out}},
+                         {{"wg", wg}, {"form", form}, {"grid", grid_blocks}, {"unroll", unroll}});
     for (size_t k = 0; k < n_out; ++k) out_ids[k] = ids[k];
     RMHIP_TRACEF("fused_elementwise: launched");
     return RMHIP_OK;
