@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "mode_runs.h"
+#include "reduce_plan.h"
 #include "row_keys.h"
 
 using namespace rmhip;
@@ -95,6 +96,7 @@ struct ExtSum {  // chunk summaries / carries
 // mapped monotonically (inverted for max, both zeros on one key), 0 = "fixed at a NaN" (beats everything, the earlier one on a tie)
 // and ~0 = "nothing yet" (loses to everything) - combine is `right key < left key ? right : left`, three shuffles per step.
 constexpr int WE = 4;
+static_assert(64 * WE == CUMEXT_WAVE_TRIP, "route_cumextreme rounds a wave's chunk to whole trips");
 constexpr u64 KEY_ZERO = 0x8000000000000000ull;
 template <bool MAX>
 __device__ __forceinline__ u64 ext_key(double x, int omit) {
@@ -293,22 +295,14 @@ __global__ void __launch_bounds__(256) k_cumext_carries(ExtSum sum, u64 nlines, 
     }
 }
 
+// wave or thread form, chunks per line, grid and launch count: reduce_plan.h route_cumextreme
 template <bool MAX>
 int launch_cumextreme(Context* c, const double* x, Lines g, int reverse, int omit, double* vals, double* idxs) {
-    const u64 nlines = g.pre * g.post;
-    if (nlines == 0 || g.len == 0) return RMHIP_OK;
-    if (g.len >= 0xffffffffull) return fail(RMHIP_ERR_UNSUPPORTED, "cummin / cummax: a dimension of %llu elements", g.len);
-    const bool wave = g.pre == 1;
-    // enough independent pieces for the device (two waves per SIMD of threads, or eight waves per CU of wave-pieces), pieces of >= 256
-    const u64 want = wave ? (u64)c->num_cus * 8 : (u64)c->num_cus * 512;
-    u64 nchunks = 1;
-    if (nlines < want && g.len >= 512) {
-        nchunks = std::min<u64>((want + nlines - 1) / nlines, g.len / 256);
-        nchunks = std::min<u64>(nchunks, 8192);
-    }
-    u64 chunk_len = (g.len + nchunks - 1) / nchunks;
-    if (wave) chunk_len = (chunk_len + 64 * WE - 1) / (64 * WE) * (64 * WE);
-    nchunks = (g.len + chunk_len - 1) / chunk_len;
+    if (g.pre * g.post == 0 || g.len == 0) return RMHIP_OK;
+    const CumextRoute r = route_cumextreme(g.pre, g.len, g.post, c->num_cus);
+    if (!r.valid) return fail(RMHIP_ERR_UNSUPPORTED, "cummin / cummax: a dimension of %llu elements", g.len);
+    const u64 nlines = r.nlines, nchunks = r.nchunks, chunk_len = r.chunk_len;
+    const dim3 grid(r.grid), block(r.block);
     ExtSum sum{nullptr, nullptr, nullptr};
     std::shared_ptr<Allocation> ws;
     if (nchunks > 1) {
@@ -317,18 +311,13 @@ int launch_cumextreme(Context* c, const double* x, Lines g, int reverse, int omi
         sum.v = ws->ptr;
         sum.pos = (u32*)(ws->ptr + slots);
         sum.kind = (int*)(sum.pos + slots);
-    }
-    const u64 pieces = nlines * nchunks;
-    const unsigned grid = (unsigned)(wave ? (pieces + 3) / 4 : (pieces + 255) / 256);
-    if (nchunks > 1) {
-        if (wave) hipLaunchKernelGGL((k_cumext_wave<MAX, 0>), dim3(grid), dim3(256), 0, c->stream, x, vals, idxs, g.len, nlines, chunk_len, nchunks, reverse, omit, sum);
-        else hipLaunchKernelGGL((k_cumext_thread<MAX, 0>), dim3(grid), dim3(256), 0, c->stream, x, vals, idxs, g, chunk_len, nchunks, reverse, omit, sum);
+        if (r.wave) hipLaunchKernelGGL((k_cumext_wave<MAX, 0>), grid, block, 0, c->stream, x, vals, idxs, g.len, nlines, chunk_len, nchunks, reverse, omit, sum);
+        else hipLaunchKernelGGL((k_cumext_thread<MAX, 0>), grid, block, 0, c->stream, x, vals, idxs, g, chunk_len, nchunks, reverse, omit, sum);
         hipLaunchKernelGGL(k_cumext_carries<MAX>, dim3((unsigned)nlines), dim3(256), 0, c->stream, sum, nlines, nchunks);
-        c->tel.kernel_launches += 2;
     }
-    if (wave) hipLaunchKernelGGL((k_cumext_wave<MAX, 1>), dim3(grid), dim3(256), 0, c->stream, x, vals, idxs, g.len, nlines, chunk_len, nchunks, reverse, omit, sum);
-    else hipLaunchKernelGGL((k_cumext_thread<MAX, 1>), dim3(grid), dim3(256), 0, c->stream, x, vals, idxs, g, chunk_len, nchunks, reverse, omit, sum);
-    c->tel.kernel_launches++;
+    if (r.wave) hipLaunchKernelGGL((k_cumext_wave<MAX, 1>), grid, block, 0, c->stream, x, vals, idxs, g.len, nlines, chunk_len, nchunks, reverse, omit, sum);
+    else hipLaunchKernelGGL((k_cumext_thread<MAX, 1>), grid, block, 0, c->stream, x, vals, idxs, g, chunk_len, nchunks, reverse, omit, sum);
+    c->tel.kernel_launches += r.launches;
     RMHIP_HIP_CHECK(hipGetLastError());
     return RMHIP_OK;
 }

@@ -697,7 +697,7 @@ __global__ void __launch_bounds__(BLOCK) k_scan_lines(const double* __restrict__
 // CPU's - then all waves write the tile out and drop the fetched one into the cells they just emptied (no barrier in between: a thread
 // stores and refills exactly its own cells).
 // LINES = 64, or 32 when 64 would leave CUs without a block (8192 lines: 128 blocks on 256 CUs).
-static constexpr int ST_STEPS = 64, ST_THREADS = 512;
+static constexpr int ST_STEPS = SCAN_STAGED_STEPS, ST_THREADS = SCAN_STAGED_THREADS;  // (reduce_plan.h: route_scan cuts chunks in whole tiles)
 // Few LONG lines (512 lines of 65536 steps: 16 workgroups, each a chain of 65536 - 3 ms) are cut into chunks along the line
 // (blockIdx.z): a first launch (TOT) only forms every chunk's total, k_scan_carries turns the totals of a line into the value carried
 // into each chunk, and the second launch scans every chunk from its carry - the scheme of the contiguous path below.  chunk_steps is
@@ -764,7 +764,7 @@ __global__ void __launch_bounds__(ST_THREADS) k_scan_lines_staged(const double* 
 // line between lanes.  A block stages a tile of consecutive lines - one contiguous piece of memory - in LDS with coalesced loads
 // (padded: the per-thread walks fall on distinct banks), thread t scans line t in place - the CPU's own sequence - and the tile goes
 // back the same way.
-static constexpr int SS_TILE = 4096;
+static constexpr int SS_TILE = SCAN_SHORT_TILE;
 __device__ __forceinline__ int ss_pad(int i) { return i + (i >> 5); }
 template <bool PROD>
 __global__ void __launch_bounds__(R2_BLOCK) k_scan_short(const double* __restrict__ x, double* __restrict__ y, u64 len, u64 nlines, unsigned per_block,
@@ -800,7 +800,8 @@ __global__ void __launch_bounds__(R2_BLOCK) k_scan_short(const double* __restric
 // 2^53).
 static constexpr int SCAN_PER_THREAD = 8;
 static constexpr int SCAN_TILE = R2_BLOCK * SCAN_PER_THREAD;
-static constexpr u64 SCAN_CHUNK = 8 * SCAN_TILE;  // 16384 elements: a 6.7e7-element vector gives 4096 blocks (with 32 tiles per block, 1024 blocks, that vector took 508 us against 332)
+// SCAN_CHUNK (reduce_plan.h) is 16384 elements: a 6.7e7-element vector gives 4096 blocks (with 32 tiles per block, 1024 blocks, that vector took 508 us against 332)
+static_assert(SCAN_CHUNK == 8 * SCAN_TILE && SCAN_BLOCK == R2_BLOCK, "route_scan's chunk is eight tiles of the scan block");
 static constexpr int SCAN_LDS = SCAN_TILE + SCAN_TILE / 8;  // one pad per eight: the transposed accesses spread over the banks
 __device__ __forceinline__ int scan_pad(int i) { return i + (i >> 3); }
 static_assert(R2_BLOCK == 256, "the scan kernels assume four waves per block");
@@ -936,96 +937,64 @@ __global__ void __launch_bounds__(R2_BLOCK) k_scan_chunks(const double* __restri
     }
 }
 
+// the launches of one route (reduce_plan.h route_scan); `totals`: lines x nchunks doubles, needed with more than one chunk per line
+template <bool PROD>
+static void launch_scan_route(Context* c, const ScanRoute& r, int reverse, int omit, const double* x, u64 pre, u64 len, u64 post, double* y,
+                              double* totals) {
+    const dim3 grid(r.gx, r.gy, r.gz), block(r.block), line_grid((unsigned)r.nlines), line_block(R2_BLOCK);
+    const u64 nchunks = r.nchunks, lines = r.nlines;
+    const double* carries = nchunks > 1 ? totals : nullptr;
+    switch (r.kernel) {
+        case ScanKernel::LINES_64x32:
+            hipLaunchKernelGGL((k_scan_lines<PROD, 64, 32>), grid, block, 0, c->stream, x, y, pre, len, post, reverse, omit);
+            break;
+        case ScanKernel::LINES_256x8:
+            hipLaunchKernelGGL((k_scan_lines<PROD, 256, 8>), grid, block, 0, c->stream, x, y, pre, len, post, reverse, omit);
+            break;
+        case ScanKernel::STAGED:
+            if (carries) {  // chunked: always 32 lines per block
+                hipLaunchKernelGGL((k_scan_lines_staged<PROD, 32, true>), grid, block, 0, c->stream, x, y, pre, len, post, reverse, omit, r.chunk_steps,
+                                   nchunks, (const double*)nullptr, totals);
+                hipLaunchKernelGGL(k_scan_carries<PROD>, line_grid, line_block, 0, c->stream, totals, nchunks, lines);
+            }
+            if (r.lines_per_block == 32)
+                hipLaunchKernelGGL((k_scan_lines_staged<PROD, 32, false>), grid, block, 0, c->stream, x, y, pre, len, post, reverse, omit, r.chunk_steps,
+                                   nchunks, carries, (double*)nullptr);
+            else
+                hipLaunchKernelGGL((k_scan_lines_staged<PROD, 64, false>), grid, block, 0, c->stream, x, y, pre, len, post, reverse, omit, r.chunk_steps,
+                                   nchunks, carries, (double*)nullptr);
+            break;
+        case ScanKernel::SHORT:
+            hipLaunchKernelGGL(k_scan_short<PROD>, grid, block, 0, c->stream, x, y, len, lines, r.per_block, reverse, omit);
+            break;
+        case ScanKernel::CHUNKS:
+            if (carries) {
+                hipLaunchKernelGGL(k_scan_chunk_totals<PROD>, grid, block, 0, c->stream, x, len, nchunks, lines, reverse, omit, totals);
+                hipLaunchKernelGGL(k_scan_carries<PROD>, line_grid, line_block, 0, c->stream, totals, nchunks, lines);
+            }
+            hipLaunchKernelGGL(k_scan_chunks<PROD>, grid, block, 0, c->stream, x, y, len, nchunks, lines, reverse, omit, carries);
+            break;
+    }
+}
+
+// Which kernel on which grid, how many chunks per line, how many launches: reduce_plan.h route_scan.  Every strided line is the CPU's
+// own chain - except the chunked STAGED form (few lines of >= 4096 steps: chunk totals carried forward, equal to rounding;
+// include/rmhip.h states the contract and the overflow caveat).
 int launch_cumulative(Context* c, int prod, int reverse, int omit, const double* x, size_t pre, size_t len, size_t post, double* y) {
     if (pre == 0 || len == 0 || post == 0) return RMHIP_OK;
-    const size_t lines = pre * post;
-    if (pre > 1) {  // lines along a strided dimension: every line is the CPU's own chain - except the chunked form below (few lines of >= 4096 steps:
-                    // chunk totals carried forward, equal to rounding; include/rmhip.h states the contract and the overflow caveat)
-        if (pre >= 8 && len >= 256 && lines < (size_t)c->num_cus * 256 && post <= 65535) {  // few long lines: staged tiles
-            const bool half = pre < 64 || ceil_div_u64(pre, 64) * post < (u64)c->num_cus;   // 64 lines per block would leave CUs (or lanes) idle
-            const u64 line_blocks = ceil_div_u64(pre, half ? 32 : 64) * post;
-            u64 nchunks = 1, chunk_steps = ceil_div_u64(len, ST_STEPS) * ST_STEPS;
-            if (line_blocks * 4 <= (u64)c->num_cus && len >= 4096) {  // a quarter of the CUs or fewer would run chains of len steps: chunks along the line
-                u64 want = ceil_div_u64((u64)c->num_cus * 4, line_blocks), most = len / 1024;  // chunks of >= 1024 steps
-                if (want > most) want = most;
-                if (want > 65535) want = 65535;
-                if (want > 1) {
-                    chunk_steps = ceil_div_u64(ceil_div_u64(len, want), ST_STEPS) * ST_STEPS;
-                    nchunks = ceil_div_u64(len, chunk_steps);
-                }
-            }
-            double* totals = nullptr;
-            if (nchunks > 1) {
-                RMHIP_TRY(c->ensure_scratch(sizeof(double) * lines * nchunks));
-                totals = c->scratch;
-            }
-            const dim3 sgrid((unsigned)ceil_div_u64(pre, half ? 32 : 64), (unsigned)post, (unsigned)nchunks);
-#define RMHIP_STAGED(P, L, T, CAR, TOTP)                                                                                                       \
-    hipLaunchKernelGGL((k_scan_lines_staged<P, L, T>), sgrid, dim3(ST_THREADS), 0, c->stream, x, y, (u64)pre, (u64)len, (u64)post, reverse, omit, \
-                       chunk_steps, nchunks, (const double*)(CAR), (double*)(TOTP))
-#define RMHIP_STAGED_PL(T, CAR, TOTP)                    \
-    do {                                                 \
-        if (prod && half) RMHIP_STAGED(true, 32, T, CAR, TOTP);   \
-        else if (prod) RMHIP_STAGED(true, 64, T, CAR, TOTP);      \
-        else if (half) RMHIP_STAGED(false, 32, T, CAR, TOTP);     \
-        else RMHIP_STAGED(false, 64, T, CAR, TOTP);               \
-    } while (0)
-            if (nchunks > 1) {
-                RMHIP_STAGED_PL(true, nullptr, totals);
-                if (prod) hipLaunchKernelGGL(k_scan_carries<true>, dim3((unsigned)lines), dim3(R2_BLOCK), 0, c->stream, totals, nchunks, (u64)lines);
-                else hipLaunchKernelGGL(k_scan_carries<false>, dim3((unsigned)lines), dim3(R2_BLOCK), 0, c->stream, totals, nchunks, (u64)lines);
-                c->tel.kernel_launches += 2;
-            }
-            RMHIP_STAGED_PL(false, totals, nullptr);
-#undef RMHIP_STAGED_PL
-#undef RMHIP_STAGED
-        } else if (lines >= (size_t)c->num_cus * 1024) {  // plenty of lines: four waves per block, eight loads deep
-            const unsigned grid = (unsigned)ceil_div_u64(lines, 256);
-            if (prod) hipLaunchKernelGGL((k_scan_lines<true, 256, 8>), dim3(grid), dim3(256), 0, c->stream, x, y, (u64)pre, (u64)len, (u64)post, reverse, omit);
-            else hipLaunchKernelGGL((k_scan_lines<false, 256, 8>), dim3(grid), dim3(256), 0, c->stream, x, y, (u64)pre, (u64)len, (u64)post, reverse, omit);
-        } else {
-            const unsigned grid = (unsigned)ceil_div_u64(lines, 64);
-            if (prod) hipLaunchKernelGGL((k_scan_lines<true, 64, 32>), dim3(grid), dim3(64), 0, c->stream, x, y, (u64)pre, (u64)len, (u64)post, reverse, omit);
-            else hipLaunchKernelGGL((k_scan_lines<false, 64, 32>), dim3(grid), dim3(64), 0, c->stream, x, y, (u64)pre, (u64)len, (u64)post, reverse, omit);
-        }
-        RMHIP_HIP_CHECK(hipGetLastError());
-        c->tel.kernel_launches++;
-        return RMHIP_OK;
+    const ScanRoute r = route_scan(pre, len, post, c->num_cus);
+    if (!r.valid) return fail(RMHIP_ERR_UNSUPPORTED, "cumulative scan: %llu contiguous lines exceed the launch limits", (u64)r.nlines);
+    double* totals = nullptr;
+    if (r.kernel == ScanKernel::CHUNKS || r.nchunks > 1) {
+        RMHIP_TRY(c->ensure_scratch(sizeof(double) * r.nlines * r.nchunks));
+        totals = c->scratch;
     }
-    if (len < 256) {  // short contiguous lines: a tile of lines per block, a thread per line
-        unsigned per_block = (unsigned)(SS_TILE / len);
-        if (per_block > R2_BLOCK) per_block = R2_BLOCK;
-        const unsigned grid = (unsigned)ceil_div_u64(lines, per_block);
-        if (prod) hipLaunchKernelGGL(k_scan_short<true>, dim3(grid), dim3(R2_BLOCK), 0, c->stream, x, y, (u64)len, (u64)lines, per_block, reverse, omit);
-        else hipLaunchKernelGGL(k_scan_short<false>, dim3(grid), dim3(R2_BLOCK), 0, c->stream, x, y, (u64)len, (u64)lines, per_block, reverse, omit);
-        RMHIP_HIP_CHECK(hipGetLastError());
-        c->tel.kernel_launches++;
-        return RMHIP_OK;
-    }
-    // long contiguous lines: blocked scans over chunks (a line of one chunk: the last pass only)
-    const u64 gy = lines < 65535 ? lines : 65535, gz = ceil_div_u64(lines, gy);
-    if (gz > 65535) return fail(RMHIP_ERR_UNSUPPORTED, "cumulative scan: %zu contiguous lines exceed the launch limits", lines);
-    const u64 nchunks = ceil_div_u64(len, SCAN_CHUNK);
-    RMHIP_TRY(c->ensure_scratch(lines * nchunks * sizeof(double)));
-    double* totals = c->scratch;
-    const dim3 grid((unsigned)nchunks, (unsigned)gy, (unsigned)gz);
-    const double* carries = nchunks > 1 ? totals : nullptr;
-    if (prod) {
-        if (carries) {
-            hipLaunchKernelGGL(k_scan_chunk_totals<true>, grid, dim3(R2_BLOCK), 0, c->stream, x, (u64)len, nchunks, (u64)lines, reverse, omit, totals);
-            hipLaunchKernelGGL(k_scan_carries<true>, dim3((unsigned)lines), dim3(R2_BLOCK), 0, c->stream, totals, nchunks, (u64)lines);
-        }
-        hipLaunchKernelGGL(k_scan_chunks<true>, grid, dim3(R2_BLOCK), 0, c->stream, x, y, (u64)len, nchunks, (u64)lines, reverse, omit, carries);
-    } else {
-        if (carries) {
-            hipLaunchKernelGGL(k_scan_chunk_totals<false>, grid, dim3(R2_BLOCK), 0, c->stream, x, (u64)len, nchunks, (u64)lines, reverse, omit, totals);
-            hipLaunchKernelGGL(k_scan_carries<false>, dim3((unsigned)lines), dim3(R2_BLOCK), 0, c->stream, totals, nchunks, (u64)lines);
-        }
-        hipLaunchKernelGGL(k_scan_chunks<false>, grid, dim3(R2_BLOCK), 0, c->stream, x, y, (u64)len, nchunks, (u64)lines, reverse, omit, carries);
-    }
+    if (prod) launch_scan_route<true>(c, r, reverse, omit, x, pre, len, post, y, totals);
+    else launch_scan_route<false>(c, r, reverse, omit, x, pre, len, post, y, totals);
     RMHIP_HIP_CHECK(hipGetLastError());
-    c->tel.kernel_launches += carries ? 3 : 1;
+    c->tel.kernel_launches += r.launches;
     return RMHIP_OK;
 }
 
 }  // namespace rmhip
+

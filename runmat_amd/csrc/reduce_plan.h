@@ -1,5 +1,6 @@
 // reduce_plan.h -- launch geometry for the [pre, red, post] reduction skeletons (skel_reduce.h).
-// Shared by the ahead-of-time reductions and the hipRTC fused reductions.
+// Shared by the ahead-of-time reductions and the hipRTC fused reductions.  The cumulative scans along a dimension choose here as
+// well: route_scan (cumsum / cumprod, reduce2.hip) and route_cumextreme (cummin / cummax, order_ops.hip) at the end of this file.
 //
 // Contrast with the reference: its generated reduction runs ONE workgroup per slice
 // (crates/runmat-accelerate/src/fusion.rs:1983-2030), i.e. a single CU for `sum(x,'all')`.
@@ -222,6 +223,141 @@ inline ReduceRoute route_reduction(uint64_t pre, uint64_t red, uint64_t post, in
         }
     }
     r.flat_final = reduce_flat_final(r.nsplit, r.nslices, fam);
+    return r;
+}
+
+// ---- which kernel serves a cumulative sum / product over [pre, len, post], in how many chunks, on which grid, in how many launches ----
+// launch_cumulative (reduce2.hip) switches over this and launches what it says; tests/cpp/scan_route_check.cpp pins it without a GPU.
+//   LINES_64x32 / LINES_256x8  one thread per strided line (blocks of 64 threads with 32 loads in flight, or 256 with 8)
+//   STAGED   few long strided lines: a block walks `lines_per_block` adjacent lines in LDS tiles of SCAN_STAGED_STEPS steps; lines of
+//            4096 steps and more on a quarter of the CUs or fewer are cut into `nchunks` chunks of `chunk_steps` (grid z) and take
+//            three launches: chunk totals, k_scan_carries, the scan from the carries
+//   SHORT    contiguous lines below 256 elements: `per_block` lines per block in an LDS tile
+//   CHUNKS   contiguous lines from 256 elements on: chunks of SCAN_CHUNK elements (grid x), lines over grid (y, z); three launches
+//            when a line has more than one chunk
+// A chunked STAGED scan always has 32 lines per block: 64 lines per block need ceil(pre / 64) * post >= num_cus line blocks, chunks
+// need four times the line blocks to be at most num_cus.
+enum class ScanKernel { LINES_64x32, LINES_256x8, STAGED, SHORT, CHUNKS };
+inline const char* scan_kernel_name(ScanKernel k) {
+    switch (k) {
+        case ScanKernel::LINES_64x32: return "lines_64x32";
+        case ScanKernel::LINES_256x8: return "lines_256x8";
+        case ScanKernel::STAGED: return "staged";
+        case ScanKernel::SHORT: return "short";
+        case ScanKernel::CHUNKS: return "chunks";
+    }
+    return "?";
+}
+static constexpr unsigned SCAN_STAGED_STEPS = 64, SCAN_STAGED_THREADS = 512;  // a STAGED tile's steps, its block
+static constexpr unsigned SCAN_SHORT_TILE = 4096;                             // elements of a SHORT block's LDS tile
+static constexpr unsigned SCAN_BLOCK = 256;                                   // SHORT, CHUNKS and the carry kernel
+static constexpr uint64_t SCAN_CHUNK = 8 * SCAN_BLOCK * 8;                    // 16384: eight tiles of 256 threads x 8 elements
+struct ScanRoute {
+    bool valid;  // false: no lines, or the contiguous lines exceed the grid limits (the caller reports UNSUPPORTED)
+    ScanKernel kernel;
+    unsigned lines_per_block;  // STAGED: 32 or 64
+    uint64_t nlines;           // pre * post (the carry kernel's grid)
+    uint64_t nchunks;          // STAGED, CHUNKS: chunks per line (1 elsewhere)
+    uint64_t chunk_steps;      // STAGED: steps per chunk, a multiple of SCAN_STAGED_STEPS; CHUNKS: SCAN_CHUNK
+    unsigned per_block;        // SHORT: lines per block
+    unsigned gx, gy, gz, block;
+    unsigned launches;         // 1, or 3 with more than one chunk per line
+};
+inline ScanRoute route_scan(uint64_t pre, uint64_t len, uint64_t post, int num_cus) {
+    ScanRoute r{};
+    if (pre == 0 || len == 0 || post == 0) return r;
+    const uint64_t cus = (uint64_t)num_cus;
+    r.valid = true;
+    r.nlines = pre * post;
+    r.nchunks = 1;
+    r.launches = 1;
+    r.gx = r.gy = r.gz = 1;
+    if (pre > 1) {
+        if (pre >= 8 && len >= 256 && r.nlines < cus * 256 && post <= 65535) {  // few long lines: staged tiles
+            const bool half = pre < 64 || ceil_div_u64(pre, 64) * post < cus;   // 64 lines per block would leave CUs (or lanes) idle
+            r.kernel = ScanKernel::STAGED;
+            r.lines_per_block = half ? 32 : 64;
+            const uint64_t line_blocks = ceil_div_u64(pre, r.lines_per_block) * post;
+            r.chunk_steps = ceil_div_u64(len, SCAN_STAGED_STEPS) * SCAN_STAGED_STEPS;
+            // a quarter of the CUs or fewer would run chains of len steps: chunks along the line (never with 64 lines per block)
+            if (half && line_blocks * 4 <= cus && len >= 4096) {
+                uint64_t want = ceil_div_u64(cus * 4, line_blocks), most = len / 1024;  // chunks of >= 1024 steps
+                if (want > most) want = most;
+                if (want > 65535) want = 65535;
+                if (want > 1) {
+                    r.chunk_steps = ceil_div_u64(ceil_div_u64(len, want), SCAN_STAGED_STEPS) * SCAN_STAGED_STEPS;
+                    r.nchunks = ceil_div_u64(len, r.chunk_steps);
+                }
+            }
+            r.gx = (unsigned)ceil_div_u64(pre, r.lines_per_block);
+            r.gy = (unsigned)post;
+            r.gz = (unsigned)r.nchunks;
+            r.block = SCAN_STAGED_THREADS;
+        } else if (r.nlines >= cus * 1024) {  // plenty of lines: four waves per block, eight loads deep
+            r.kernel = ScanKernel::LINES_256x8;
+            r.gx = (unsigned)ceil_div_u64(r.nlines, 256);
+            r.block = 256;
+        } else {
+            r.kernel = ScanKernel::LINES_64x32;
+            r.gx = (unsigned)ceil_div_u64(r.nlines, 64);
+            r.block = 64;
+        }
+    } else if (len < 256) {  // short contiguous lines: a tile of lines per block, a thread per line
+        r.kernel = ScanKernel::SHORT;
+        r.per_block = (unsigned)(SCAN_SHORT_TILE / len);
+        if (r.per_block > SCAN_BLOCK) r.per_block = SCAN_BLOCK;
+        r.gx = (unsigned)ceil_div_u64(r.nlines, r.per_block);
+        r.block = SCAN_BLOCK;
+    } else {  // long contiguous lines: blocked scans over chunks (a line of one chunk: the last pass only)
+        r.kernel = ScanKernel::CHUNKS;
+        const uint64_t gy = r.nlines < 65535 ? r.nlines : 65535, gz = ceil_div_u64(r.nlines, gy);
+        if (gz > 65535) {
+            r.valid = false;
+            return r;
+        }
+        r.chunk_steps = SCAN_CHUNK;
+        r.nchunks = ceil_div_u64(len, SCAN_CHUNK);
+        r.gx = (unsigned)r.nchunks;
+        r.gy = (unsigned)gy;
+        r.gz = (unsigned)gz;
+        r.block = SCAN_BLOCK;
+    }
+    if (r.nchunks > 1) r.launches = 3;
+    return r;
+}
+
+// ---- cummin / cummax (order_ops.hip launch_cumextreme): one wave (pre == 1) or one thread per (line, chunk) ----
+// Enough independent pieces for the device - eight waves per CU of wave pieces, two waves per SIMD of thread pieces - in chunks of
+// 256 elements and more; a wave's chunk is a multiple of its trip of CUMEXT_WAVE_TRIP elements.  More than one chunk per line: three
+// launches (chunk summaries, k_cumext_carries, the scan from the carries).
+static constexpr unsigned CUMEXT_WAVE_TRIP = 64 * 4;
+struct CumextRoute {
+    bool valid;  // false: no lines, or a dimension whose positions do not fit 32 bits (the caller reports UNSUPPORTED)
+    bool wave;
+    uint64_t nlines, nchunks, chunk_len;
+    unsigned grid, block;
+    unsigned launches;
+};
+inline CumextRoute route_cumextreme(uint64_t pre, uint64_t len, uint64_t post, int num_cus) {
+    CumextRoute r{};
+    r.nlines = pre * post;
+    if (r.nlines == 0 || len == 0 || len >= 0xffffffffull) return r;
+    r.valid = true;
+    r.wave = pre == 1;
+    const uint64_t want = r.wave ? (uint64_t)num_cus * 8 : (uint64_t)num_cus * 512;
+    r.nchunks = 1;
+    if (r.nlines < want && len >= 512) {
+        r.nchunks = ceil_div_u64(want, r.nlines);
+        if (r.nchunks > len / 256) r.nchunks = len / 256;
+        if (r.nchunks > 8192) r.nchunks = 8192;
+    }
+    r.chunk_len = ceil_div_u64(len, r.nchunks);
+    if (r.wave) r.chunk_len = ceil_div_u64(r.chunk_len, CUMEXT_WAVE_TRIP) * CUMEXT_WAVE_TRIP;
+    r.nchunks = ceil_div_u64(len, r.chunk_len);
+    const uint64_t pieces = r.nlines * r.nchunks;
+    r.grid = (unsigned)(r.wave ? ceil_div_u64(pieces, 4) : ceil_div_u64(pieces, 256));
+    r.block = 256;
+    r.launches = r.nchunks > 1 ? 3 : 1;
     return r;
 }
 
